@@ -12,8 +12,13 @@ fp32 MFMA peak.  --dtype f16: the 16-bit throughput mode of the transformer (fp1
 reference's harness requests with torch.autocast(fp16), demo_sample.py:66-68), priced against the 2.5 PF dense fp16 MFMA peak.
 --dtype bf16: the same mode with bfloat16 storage (the reference's other 16-bit option, utils/arg_util.py `fp16: int  # 1: using fp16, 2: bf16`).
 
+A plain run sets up, warms up, times exactly --steps steps and prints the line; --dump-outputs DIR then also writes the images the last timed
+step returned as DIR/images.npy (float32; a fixed, seeded sample of whole images if they exceed 64 MB).  The inputs (weights, labels, seeds)
+depend on the arguments only, so two builds of the project can be compared output for output.  --full adds the measurements beyond the
+headline figure: modes.f16, modes.bf16 and cpu_baseline below.
+
 Extra objects in the JSON line:
-  modes.f16    (default run, after the f32 timed region, same process / weights / workload) the 16-bit throughput mode: 2 warmup + >= 10 timed
+  modes.f16    (--full, after the f32 timed region, same process / weights / workload) the 16-bit throughput mode: 2 warmup + >= 10 timed
                steps between barriers, `value`, `ms_per_step`, its own measured dominant kernel with `roofline` and `whole_path`.  The
                headline `value` / `dtype` stay f32.
   modes.bf16   the same for the bfloat16 flavour of that mode.
@@ -26,7 +31,7 @@ Extra objects in the JSON line:
   whole_path   FLOPs per image as the reference computes them and as the kernels execute them (the decoder's Upsample2x convs run
                in a folded 4-tap form), both as a fraction of the MFMA peak of the mode; mfma_time_weighted: FLOPs / time summed over
                every GEMM / conv / attention launch of the profiled warmup step.
-  cpu_baseline the CPU oracle (oracle/, a scalar C port of the reference algorithm; kind "port") timed on this box's host
+  cpu_baseline (--full) the CPU oracle (oracle/, a scalar C port of the reference algorithm; kind "port") timed on the host
                cores on a bounded sample: eight images through all 10 scales + decode (rank 0, N=1 only).
 """
 import argparse
@@ -55,6 +60,7 @@ FAMILY_PEAK = {'gemm': PEAK_F32_MFMA_TFLOPS, 'gemm_small': PEAK_F32_MFMA_TFLOPS,
 DOMINANT = {'f32': {'gemm': 'k_dma_gemm<4,4,false,2,false>', 'conv3x3': 'k_dma_gemm<4,5,true,2,false>', 'attn': 'k_attn_cached<NW>'},
             'f16': {'gemm16': 'k_gemm16p', 'conv16h': 'k_conv16h<5,32,true>', 'attn16': 'k_attn16<NW>'}}
 DOMINANT['bf16'] = DOMINANT['f16']          # the same kernels compiled with the bf16 MFMA opcodes (namespace vh_bf16 in the symbol)
+DUMP_MAX_BYTES = 64 * 10 ** 6                # --dump-outputs: at most this many bytes of images, header included
 
 
 _STREAMS = []
@@ -67,8 +73,9 @@ def _two_streams(torch):
     return _STREAMS
 
 
-def run_mode(var, dtype, steps, warmup, args, world, step_fn, dist, hip, torch, in_flight2=False):
-    """warm up and time `steps` calls in one precision mode; returns the raw measurements of this rank (dt already MAX-reduced over ranks)"""
+def run_mode(var, dtype, steps, warmup, args, world, step_fn, dist, hip, torch, in_flight2=False, keep_output=False):
+    """warm up and time `steps` calls in one precision mode; returns the raw measurements of this rank (dt already MAX-reduced over ranks)
+    and, with keep_output, the images the last timed step returned (`img`)"""
     var.set_hip_precision(dtype)
     prepass = None
     for i in range(warmup):
@@ -103,6 +110,8 @@ def run_mode(var, dtype, steps, warmup, args, world, step_fn, dist, hip, torch, 
         rs = rank_stats(dt, dt_own, gather_ms, steps, img.shape, img.device)
         dt, ranks = rs['dt_max'], rs['ranks']
     res = dict(dt=dt, tt=tt, prepass=prepass, dominant=dominant, ranks=ranks, steps=steps, warmup=warmup, dtype=dtype)
+    if keep_output:
+        res['img'] = img
     if in_flight2:
         # the same K calls again, issued alternately on two HIP streams (a call's buffers are per stream): two calls in flight, so that the
         # latency-bound small scales and ragged last rounds of one call run beside the other's full-chip kernels.  Same barriers, same clock.
@@ -122,6 +131,19 @@ def run_mode(var, dtype, steps, warmup, args, world, step_fn, dist, hip, torch, 
             dt2 = float(t.item())
         res['dt_in_flight2'] = dt2
     return res
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: the images the last timed step returned (every image of every rank) as out_dir/images.npy, float32; above DUMP_MAX_BYTES
+    a fixed, seeded sample of whole images, kept in batch order"""
+    import numpy as np
+    import torch
+    keep = max(1, (DUMP_MAX_BYTES - 4096) // (img[0].numel() * 4))
+    if img.shape[0] > keep:
+        pick = torch.randperm(img.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        img = img[pick.to(img.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'images.npy'), img.float().cpu().numpy())
 
 
 def describe_mode(m, args, world, var, pns):
@@ -187,8 +209,13 @@ def main():
     ap.add_argument('--batch', type=int, default=64, help='images per GPU (weak scaling)')
     ap.add_argument('--depth', type=int, default=16)
     ap.add_argument('--dtype', default='f32', choices=['f32', 'f16', 'bf16'], help='the mode of the headline value (default f32: the parity contract)')
-    ap.add_argument('--no-modes', action='store_true', help='skip the extra 16-bit-mode measurements that follow the f32 timed region (modes.f16, modes.bf16)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the 16-bit modes after the f32 timed region (modes.f16, modes.bf16) '
+                         'and the CPU oracle baseline (cpu_baseline); a plain run times the headline mode only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the images the last timed step returned as DIR/images.npy (float32, at most 64 MB: a fixed, seeded sample of whole images beyond that)')
+    ap.add_argument('--no-modes', action='store_true', help='with --full: skip the extra 16-bit-mode measurements that follow the f32 timed region (modes.f16, modes.bf16)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip cpu_baseline')
     ap.add_argument('--in-flight', action='store_true',
                     help='N > 1 only: also run the informational two-calls-in-flight leg of modes.* (at N = 1 it always runs); it issues the all-gathers '
                          'alternately from two side streams, a pattern no multi-GPU run has exercised, so a scaling run leaves it out by default')
@@ -198,6 +225,8 @@ def main():
     ap.add_argument('--kernel-breakdown', action='store_true',
                     help='time every kernel family with HIP events in the timed region too (adds ~2 %% to a step); default: only the dominant kernel')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # `python bench.py --gpus N` outside a torchrun environment: start the N ranks ourselves.  Nothing above or below this point in
     # THIS process touches a GPU — the ranks are children (python -m torch.distributed.run), rank 0 prints the JSON line.
@@ -235,13 +264,17 @@ def main():
         return sample_sharded(var, B_total, labels, g_seed=i, cfg=1.5, top_k=900, top_p=0.96, rng_mode=args.rng_mode, gather=True, gather_events=gather_ev)
 
     # the headline mode: W warmup steps (the last one with every family timed: it names the dominant kernel), then exactly K timed steps
-    head = run_mode(var, args.dtype, args.steps, args.warmup, args, world, step, dist, hip, torch)
-    # then, in the same process, the 16-bit throughput mode (what the reference's harness runs under torch.autocast(fp16)): its own warmup,
+    head = run_mode(var, args.dtype, args.steps, args.warmup, args, world, step, dist, hip, torch, keep_output=True)
+    img = head.pop('img')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, img)
+    del img
+    # --full: then, in the same process, the 16-bit throughput mode (what the reference's harness runs under torch.autocast(fp16)): its own warmup,
     # >= 10 timed steps, its own dominant kernel and roofline.  The headline value / dtype stay those of the parity mode.
     # N > 1: one stream, one all-gather per step as in the headline region (the two-stream leg only with --in-flight), and a failure here is
     # reported inside `modes` instead of costing the headline line (every rank runs the same code, so a raise is a raise on all of them).
     others, mode_errors = {}, {}
-    if args.dtype == 'f32' and not args.no_modes:
+    if args.full and args.dtype == 'f32' and not args.no_modes:
         for dt16 in ('f16', 'bf16'):
             try:
                 others[dt16] = run_mode(var, dt16, max(10, args.steps), 2, args, world, step, dist, hip, torch, in_flight2=(world == 1 or args.in_flight))
@@ -285,7 +318,7 @@ def main():
                     'how': 'the same calls issued alternately on two HIP streams of one process and model (per-stream workspaces); `value` above is one call at a time'}
         for dt16, err in mode_errors.items():
             out.setdefault('modes', {})[dt16] = {'error': err}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args.depth, pns)
         print(json.dumps(out), flush=True)
     dist.barrier()

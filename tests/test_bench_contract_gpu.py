@@ -1,5 +1,5 @@
-"""bench.py's output contract on a real GPU: one JSON line with the driver's keys plus the `roofline` object (and `cpu_baseline`
-when not switched off).  Runs the real script as a child process on a small batch so it stays within half a minute."""
+"""bench.py's output contract on a real GPU: one JSON line with the driver's keys plus the `roofline` object (with --full: the 16-bit
+`modes` and `cpu_baseline` when not switched off).  Runs the real script as a child process on a small batch so it stays within half a minute."""
 import json
 import os
 import subprocess
@@ -22,7 +22,7 @@ def _run(*extra):
 
 
 def test_bench_line_has_the_contract_keys():
-    j = _run('--no-cpu-baseline')
+    j = _run('--full', '--no-cpu-baseline')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data', 'config', 'roofline'):
         assert k in j, k
     assert j['metric'].startswith('256x256 images/sec (CFG=1.5) VAR-d16') and j['unit'] == 'images/sec'
@@ -48,10 +48,26 @@ def test_bench_line_has_the_contract_keys():
 
 
 def test_bench_line_f16_headline_and_no_modes():
-    j = _run('--no-cpu-baseline', '--dtype', 'f16')
+    j = _run('--full', '--no-cpu-baseline', '--dtype', 'f16')
     assert j['dtype'] == 'f16' and 'modes' not in j and j['roofline']['peak'] == 2500.0
-    j = _run('--no-cpu-baseline', '--no-modes')
+    j = _run('--full', '--no-cpu-baseline', '--no-modes')
     assert j['dtype'] == 'f32' and 'modes' not in j
+
+
+def test_plain_bench_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """without --full the line is the headline mode alone (no modes.*, no cpu_baseline); --dump-outputs writes the images of the last timed step,
+    and two runs with the same arguments write the same images (f32: bit for bit)"""
+    import numpy as np
+    got = []
+    for run in ('a', 'b'):
+        j = _run('--steps', '2', '--dump-outputs', str(tmp_path / run))
+        assert j['steps'] == 2 and j['dtype'] == 'f32' and j['ms_per_step'] > 0 and abs(j['value'] - 2 / (j['ms_per_step'] * 1e-3)) < 1e-2 * j['value']
+        assert 'modes' not in j and 'cpu_baseline' not in j and 'roofline' in j
+        assert sorted(os.listdir(tmp_path / run)) == ['images.npy']
+        got.append(np.load(tmp_path / run / 'images.npy'))
+    a, b = got
+    assert a.dtype == np.float32 and a.shape == (2, 3, 256, 256) and np.isfinite(a).all() and 0 <= a.min() and a.max() <= 1 and a.std() > 0
+    assert np.array_equal(a, b)
 
 
 _RCCL_CHILD = r'''
@@ -94,7 +110,8 @@ def test_bench_two_ranks_on_one_card_through_the_launcher():
     """bench.py's own world > 1 branches executed as a whole before the driver's 8-GPU run does: `bench.py --gpus 2` outside torchrun starts two ranks
     through var_amd/launch.py; with the rehearsal backend (gloo: RCCL refuses two ranks on one device) both share this card.  Closing barriers,
     rank_stats, the all-gather of the decoded images and the modes.* legs (one stream, no two-stream collectives) all run; one JSON line comes out."""
-    cmd = [sys.executable, os.path.join(util.ROOT, 'bench.py'), '--gpus', '2', '--batch', '2', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--backend', 'gloo']
+    cmd = [sys.executable, os.path.join(util.ROOT, 'bench.py'), '--gpus', '2', '--batch', '2', '--steps', '1', '--warmup', '0', '--full', '--no-cpu-baseline',
+           '--backend', 'gloo']
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     out = subprocess.run(cmd, cwd=util.ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -1,6 +1,6 @@
 """CPU-side checks: the C ABI surface, the drop-in `models` boundary, host-side tables, and the multi-rank sharding logic
-(gloo, world_size 2).  No GPU compute happens here; the reference (if present in this container) is only used to pin the
-boundary (state-dict layout, teacher-forced forward) — these tests skip that part where /root/reference is absent."""
+(gloo, world_size 2).  No GPU compute happens here; the boundary (state-dict layout, teacher-forced forward) is pinned by
+tests/golden/boundary_d2_pn1234.npz, recorded from the reference by tools/gen_golden.py."""
 import contextlib
 import ctypes
 import io
@@ -16,7 +16,6 @@ import torch
 from tests import util
 
 ROOT = util.ROOT
-REF = '/root/reference'
 
 
 def _quiet_build(**kw):
@@ -96,54 +95,51 @@ def test_state_dict_layout_matches_the_documented_one(kw):
     assert dist.get_device() is not None and dist.initialized() is False
 
 
-def _import_reference():
-    """the reference's `models` package under a private name (it must not shadow ours)"""
-    if not os.path.isdir(REF):
-        pytest.skip('reference not present on this machine')
-    import importlib
-    import typing
-    torch.Optional = typing.Optional
-    saved = {k: sys.modules.pop(k) for k in list(sys.modules) if k == 'models' or k.startswith('models.') or k == 'dist'}
-    sys.path.insert(0, REF)
-    try:
-        ref_models = importlib.import_module('models')
-        ref_mods = {k: v for k, v in sys.modules.items() if k == 'models' or k.startswith('models.') or k == 'dist'}
-    finally:
-        sys.path.remove(REF)
-        for k in list(sys.modules):
-            if k == 'models' or k.startswith('models.') or k == 'dist':
-                del sys.modules[k]
-        sys.modules.update(saved)
-    return ref_models, ref_mods
-
-
-def test_against_reference_statedict_and_teacher_forced_forward():
-    ref_models, _ = _import_reference()
+def test_against_reference_statedict_and_teacher_forced_forward(golden_dir):
+    """the reference's state-dict layout (every key and shape, the detinit checksum of every tensor) and its CPU forward passes
+    (encode, teacher-forced logits, fhat_to_img, embed_to_fhat) on VAR-d2 / ch 32 / patch_nums (1, 2, 3, 4).  The fixture holds the input of
+    the reference's output projection instead of its 245 760 logits: they are rebuilt here with that nn.Linear and pinned to the reference's
+    own values by float64 checksums and a sample of raw logits."""
+    import json
     from var_amd.detinit import fill_module_
-    kw = dict(depth=2, ch=32, patch_nums=(1, 2, 3, 4))
-    with contextlib.redirect_stdout(io.StringIO()):
-        rvae, rvar = ref_models.build_vae_var(device='cpu', **kw)
-    vae, var = _quiet_build(**kw)
-    fill_module_(rvar, 2, 0, 'var.'); fill_module_(rvae, 2, 0, 'vae.')
-    var.load_state_dict(rvar.state_dict(), strict=True)           # their checkpoint into our module
-    vae.load_state_dict(rvae.state_dict(), strict=True)
-    rvar.load_state_dict(var.state_dict(), strict=True)           # and back
-    rvar.eval(); var.eval(); rvae.eval(); vae.eval()
-    rvar.cond_drop_rate = var.cond_drop_rate = 0.0
-    g = torch.Generator().manual_seed(3)
+    z = np.load(os.path.join(golden_dir, 'boundary_d2_pn1234.npz'))
+    meta = json.loads(str(z['meta']))
+    pns = tuple(meta['patch_nums'])
+    vae, var = _quiet_build(depth=meta['depth'], ch=meta['ch'], patch_nums=pns)
+    fill_module_(var, 2, 0, 'var.'); fill_module_(vae, 2, 0, 'vae.')
+    for pre, mod in (('var', var), ('vae', vae)):                 # what load_state_dict(strict=True) checks in both directions, and the values
+        sd = mod.state_dict()
+        assert list(sd.keys()) == meta[f'{pre}_keys'], pre
+        assert [list(v.shape) for v in sd.values()] == meta[f'{pre}_shapes'], pre
+        sums = np.array([float(v.double().sum()) for v in sd.values()])
+        assert np.allclose(sums, z[f'{pre}_sums'], rtol=1e-9, atol=1e-9), [k for k, a, b in zip(sd, sums, z[f'{pre}_sums']) if not np.isclose(a, b, rtol=1e-9, atol=1e-9)]
+    var.eval(); vae.eval()
+    var.cond_drop_rate = 0.0
+    g = torch.Generator().manual_seed(3)                           # the reference's inputs, from the same CPU generator stream
     img = torch.rand(2, 3, 64, 64, generator=g) * 2 - 1
+    f = torch.randn(2, 32, 4, 4, generator=g)
+    assert np.array_equal(img.reshape(-1)[:8].numpy(), z['img_head']) and abs(img.double().sum().item() - float(z['img_sum'])) <= 1e-9 * img.numel()
+    assert np.array_equal(f.numpy(), z['f']), 'torch CPU RNG stream differs from the fixture'
+    head = var.state_dict()
+    want_logits = torch.nn.functional.linear(torch.from_numpy(z['head_input']), head['head.weight'], head['head.bias'])
+    pick = torch.from_numpy(z['logits_pick']).long()
+    assert torch.allclose(want_logits.reshape(-1)[pick], torch.from_numpy(z['logits_at_pick']), atol=1e-6, rtol=0)
+    assert abs(want_logits.double().sum().item() - float(z['logits_sum'])) <= 1e-6 * float(z['logits_abs_sum'])
+    assert abs(want_logits.double().abs().sum().item() - float(z['logits_abs_sum'])) <= 1e-6 * float(z['logits_abs_sum'])
     with torch.no_grad():
-        ridx, idx = rvae.img_to_idxBl(img), vae.img_to_idxBl(img)                       # encode side (PyTorch, API kept)
-        for a, b in zip(ridx, idx):
-            assert torch.equal(a, b)
+        idx = vae.img_to_idxBl(img)                                                       # encode side (PyTorch, API kept)
+        assert len(idx) == len(pns)
+        for si, b in enumerate(idx):
+            assert np.array_equal(b.numpy(), z[f'idx_s{si}']), si
         x_in = vae.quantize.idxBl_to_var_input(idx)
-        assert torch.allclose(x_in, rvae.quantize.idxBl_to_var_input(ridx), atol=1e-6)
-        lab = torch.tensor([3, 999])
-        assert torch.allclose(var(lab, x_in), rvar(lab, x_in), atol=2e-5, rtol=1e-5)   # teacher-forced logits
-        f = torch.randn(2, 32, 4, 4, generator=g)
-        assert torch.allclose(vae.fhat_to_img(f), rvae.fhat_to_img(f), atol=1e-5)       # CPU tensors take the PyTorch modules
-        ms = [vae.quantize.embedding(i).transpose(1, 2).reshape(2, 32, pn, pn) for i, pn in zip(idx, kw['patch_nums'])]
-        assert torch.allclose(vae.quantize.embed_to_fhat(ms, last_one=True), rvae.quantize.embed_to_fhat(ms, last_one=True), atol=1e-6)
+        assert torch.allclose(x_in, torch.from_numpy(z['var_input']), atol=1e-6)
+        lab = torch.from_numpy(z['labels'])
+        got = var(lab, x_in)
+        assert torch.allclose(got, want_logits, atol=2e-5, rtol=1e-5)                   # teacher-forced logits, every one of them
+        assert torch.allclose(got.reshape(-1)[pick], torch.from_numpy(z['logits_at_pick']), atol=2e-5, rtol=1e-5)
+        assert torch.allclose(vae.fhat_to_img(f), torch.from_numpy(z['fhat_to_img']), atol=1e-5)     # CPU tensors take the PyTorch modules
+        ms = [vae.quantize.embedding(i).transpose(1, 2).reshape(2, 32, pn, pn) for i, pn in zip(idx, pns)]
+        assert torch.allclose(vae.quantize.embed_to_fhat(ms, last_one=True), torch.from_numpy(z['embed_to_fhat']), atol=1e-6)
 
 
 def test_encode_side_against_golden_fixture(golden_dir):
@@ -367,6 +363,14 @@ def test_bench_self_launches_when_asked_for_more_gpus_than_ranks(monkeypatch):
                          capture_output=True, text=True, timeout=240, env=env)
     if torch.cuda.device_count() < 2:
         assert out.returncode == 2 and 'ranks requested' in out.stderr and not any(ln.startswith('{') for ln in out.stdout.splitlines())
+
+
+def test_bench_options_and_step_count_are_checked_before_any_work():
+    """--full and --dump-outputs exist; --steps below 1 is refused by the argument parser (no timed step, no ms_per_step)"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and '--full' in out.stdout and '--dump-outputs' in out.stdout
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 2 and '--steps must be at least 1' in out.stderr and not out.stdout.strip()
 
 
 def test_device_side_detinit_matches_numpy():

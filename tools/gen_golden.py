@@ -333,6 +333,47 @@ def run_encode():
     print(f'[gen_golden] encode_t_pn12345: f std {f.std():.3f}, logits std {logits.std():.3f}', flush=True)
 
 
+def run_boundary():
+    """the drop-in `models` boundary (tests/test_host_cpu.py): the reference's state-dict layout (key -> shape, float64 checksum of every tensor
+    after detinit) and its CPU forward passes on VAR-d2 / ch 32 / patch_nums (1, 2, 3, 4): encode (img_to_idxBl, idxBl_to_var_input), teacher-forced
+    logits (VAR.forward, cond_drop_rate 0), fhat_to_img and embed_to_fhat(last_one=True).
+    Kept small: the input image is regenerated by the test from its seeded generator (head + checksum recorded here); the logits are recorded as
+    the input of the reference's `head` (nn.Linear, models/var.py:124), from which the test rebuilds all of them, plus float64 checksums and a
+    seeded sample of raw logits that pin the rebuild to the reference's own values."""
+    cfg = dict(depth=2, ch=32, patch_nums=(1, 2, 3, 4), attn_l2_norm=True, shared_aln=False)
+    vae, var = build_reference(cfg)
+    var.cond_drop_rate = 0.0
+    rec, meta = {}, dict(cfg)
+    for pre, mod in (('var', var), ('vae', vae)):
+        sd = mod.state_dict()
+        meta[f'{pre}_keys'] = list(sd.keys())
+        meta[f'{pre}_shapes'] = [list(v.shape) for v in sd.values()]
+        rec[f'{pre}_sums'] = np.array([float(v.double().sum()) for v in sd.values()], dtype=np.float64)
+    g = torch.Generator().manual_seed(3)
+    img = torch.rand(2, 3, 64, 64, generator=g) * 2 - 1
+    f = torch.randn(2, 32, 4, 4, generator=g)
+    lab = torch.tensor([3, 999])
+    head_in = []
+    hook = var.head.register_forward_hook(lambda mod, inp, out: head_in.append(inp[0].detach().clone()))
+    with torch.no_grad():
+        idx = vae.img_to_idxBl(img)
+        x_in = vae.quantize.idxBl_to_var_input(idx)
+        logits = var(lab, x_in)
+        f_img = vae.fhat_to_img(f)
+        ms = [vae.quantize.embedding(i).transpose(1, 2).reshape(2, 32, pn, pn) for i, pn in zip(idx, cfg['patch_nums'])]
+        fhat = vae.quantize.embed_to_fhat(ms, last_one=True)
+    hook.remove()
+    assert len(head_in) == 1 and torch.equal(torch.nn.functional.linear(head_in[0], var.head.weight, var.head.bias), logits)
+    pick = torch.randperm(logits.numel(), generator=torch.Generator().manual_seed(4))[:2048].sort().values
+    rec.update(img_head=img.reshape(-1)[:8].numpy(), img_sum=np.float64(img.double().sum()), f=f.numpy(), labels=lab.numpy(), var_input=x_in.numpy(),
+               head_input=head_in[0].numpy(), logits_sum=np.float64(logits.double().sum()), logits_abs_sum=np.float64(logits.double().abs().sum()),
+               logits_pick=pick.numpy().astype(np.int32), logits_at_pick=logits.reshape(-1)[pick].numpy(),
+               fhat_to_img=f_img.numpy(), embed_to_fhat=fhat.numpy(), meta=np.array(json.dumps(meta)))
+    for si, i in enumerate(idx): rec[f'idx_s{si}'] = i.numpy().astype(np.int32)
+    np.savez_compressed(os.path.join(GOLD, 'boundary_d2_pn1234.npz'), **rec)
+    print(f'[gen_golden] boundary_d2_pn1234: {len(meta["var_keys"])} + {len(meta["vae_keys"])} state-dict entries, logits std {logits.std():.3f}', flush=True)
+
+
 def run_nearest_code():
     """A17 fixture: VectorQuantizer2.f_to_idxBl_or_fhat (reference models/quant.py:135-166) on a random feature map."""
     cfg = CASES['t_pn12345']
@@ -398,6 +439,7 @@ def main():
     if not args.only or 'encode' in args.only: run_encode()
     if not args.only or 'nearest_code' in args.only: run_nearest_code()
     if not args.only or 'sampler' in args.only: run_sampler_vectors()
+    if not args.only or 'boundary' in args.only: run_boundary()
 
 
 if __name__ == '__main__':
