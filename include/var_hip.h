@@ -261,6 +261,16 @@ int varhip_smooth_select_f32(const float* logits, const int64_t* gt, const int32
                              int cand_count, int use_thr, float thr, float ratio, int B, int l, int V, double t_cfg,
                              int64_t* idx_out, float* maxval_out, float* distlp_out, float* cfg_out, varhip_stream_t stream);
 
+/* ---- teacher-forced class scoring (fork eval_prob.py:441-463 bayesian mode, var_analysis.py:322-349 guided likelihood) ----------------
+ * log_softmax(logits).gather(gt) of one scale of one pass, without the (rows, V) log_softmax tensor.  logits: the head's fp32 output of the
+ * pass, rows image-major, then class, then token: row (i * classes + c) * l + t; with_uncond != 0: the images' unconditional rows follow,
+ * row (images * classes + i) * l + t, and z = ca * cond - cb * uncond (each product and the difference rounded to fp32; the caller passes
+ * ca = fl32(1 + t), cb = t, t = fl32(fl32(cfg) * fl32(si / (S-1)))), else z = logits.  gt: the pass's tokens at the scale's offset,
+ * gt[i * ld_gt + t] (a token outside [0, V) scores NaN and is never read); out[i * ld_out_img + c * ld_out_cls + t] = (z_gt - max z) - log(sum exp(z - max z)).
+ * Not bit-identical to torch.log_softmax (another summation order): within a few ulps of the log-sum-exp of a float64 evaluation. */
+int varhip_token_loglik_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V,
+                            int with_uncond, float ca, float cb, float* out, int64_t ld_out_img, int64_t ld_out_cls, varhip_stream_t stream);
+
 /* ---- nearest-codebook lookup (encode side; quant.py:150-157) --------------------------------------------
  * idx[n] = argmin_v ( |z_n|^2 + |e_v|^2 - 2 z_n.e_v ), first index on ties; z: [N][Cv], codebook: [V][Cv] */
 int varhip_nearest_code_f32(const float* z, const float* codebook, int64_t* idx_out, int N, int V, int Cv, varhip_stream_t stream);

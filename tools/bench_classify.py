@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""Timing of VAR as a zero-shot classifier (fork eval_prob.py --mode bayesian, var_analysis.py --cfg) on one MI355X, random-init weights
+(detinit seed 0), N images of 256x256, d16:
+
+    new route  VAR.token_log_likelihood(gt_tokens, classes, cfg)                   (N x K rows packed into passes of <= --max-rows rows)
+    old route  per image: x = idxBl_to_var_input, VAR.forward(classes, x.expand(K, ...)) [+ one unconditional forward and the CFG combine],
+               log_softmax, gather                                                   (what a caller of this library writes today)
+
+both in the same process, alternated, the old one on a stream of its own (each route keeps its own workspace).
+
+    python tools/bench_classify.py [--images 16] [--k-large 100] [--cfg 0] [--dtype f32|f16|bf16] [--iters 3]
+
+Prints one JSON object: encode ms per image; per K: ms per image and images per second of both routes, their peak allocation increase,
+max |delta| of the per-token values; the scoring kernel's time from the library's timing table (family 'sampler', which no other kernel of
+the new route uses) and its bytes/s against the 8 TB/s HBM peak."""
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from var_amd import detinit, hip      # noqa: E402
+
+HBM_PEAK = 8.0e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--images', type=int, default=16)
+    ap.add_argument('--k-large', type=int, default=100)
+    ap.add_argument('--cfg', type=float, default=0.0)
+    ap.add_argument('--max-rows', type=int, default=64)
+    ap.add_argument('--iters', type=int, default=3)
+    ap.add_argument('--dtype', default='f32', choices=['f32', 'f16', 'bf16'])
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    dev = torch.device('cuda', 0)
+    from models import build_vae_var
+    pns = (1, 2, 3, 4, 5, 6, 8, 10, 13, 16)
+    with contextlib.redirect_stdout(io.StringIO()):
+        vae, var = build_vae_var(device=dev, patch_nums=pns, depth=16, ch=160)
+    detinit.fill_module_device_(var, 16, 0, 'var.'); detinit.fill_module_device_(vae, 16, 0, 'vae.')
+    var.eval(); vae.eval(); var.cond_drop_rate = 0.0
+    var.set_hip_precision(a.dtype)
+    N, S = a.images, len(pns)
+    g = torch.Generator(device=dev).manual_seed(0)
+    img = torch.rand(N, 3, 256, 256, device=dev, generator=g) * 2 - 1
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    side = torch.cuda.Stream()
+
+    with torch.inference_mode():
+        enc = []
+        for it in range(a.iters + 1):
+            e0, e1 = ev(), ev()
+            e0.record()
+            idx = vae.img_to_idxBl(img)
+            e1.record(); torch.cuda.synchronize()
+            if it: enc.append(e0.elapsed_time(e1))
+        gt = torch.cat(idx, 1)
+        ratio = torch.tensor([si / (S - 1) for si, pn in enumerate(pns) for _ in range(pn * pn)], device=dev)
+        t = a.cfg * ratio.unsqueeze(0).unsqueeze(-1)
+
+        def new_route(classes):
+            return var.token_log_likelihood(gt, classes, cfg=a.cfg, max_rows=a.max_rows)
+
+        def old_route(classes):
+            lab = torch.tensor(classes, device=dev)
+            out = []
+            for i in range(N):
+                x = vae.quantize.idxBl_to_var_input([j[i:i + 1] for j in idx])
+                logits = var(lab, x.expand(len(classes), -1, -1).contiguous())
+                if a.cfg > 0:
+                    logits = (1 + t) * logits - t * var(torch.tensor([var.num_classes], device=dev), x)
+                lp = torch.nn.functional.log_softmax(logits, dim=-1)
+                out.append(lp.gather(-1, gt[i:i + 1].expand(len(classes), -1).unsqueeze(-1)).squeeze(-1))
+                del logits, lp
+            return torch.stack(out)
+
+        def timed(fn, classes, stream):
+            with torch.cuda.stream(stream):
+                torch.cuda.synchronize()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                e0, e1 = ev(), ev()
+                e0.record()
+                r = fn(classes)
+                e1.record()
+                torch.cuda.synchronize()
+                return r, e0.elapsed_time(e1), torch.cuda.max_memory_allocated() - base
+
+        res = dict(images=N, cfg=a.cfg, dtype=a.dtype, max_rows=a.max_rows, encode_ms_per_image=sum(enc) / len(enc) / N)
+        for K in (10, a.k_large):
+            classes = [(c * 97) % 1000 for c in range(K)]
+            ms = {'new': [], 'old': []}
+            peak = {'new': 0, 'old': 0}
+            timed(new_route, classes, torch.cuda.current_stream()); timed(old_route, classes, side)      # warm-up: weights, workspaces
+            for it in range(a.iters):                                                                        # alternated
+                ln, tn, pn_ = timed(new_route, classes, torch.cuda.current_stream())
+                lo, to, po = timed(old_route, classes, side)
+                ms['new'].append(tn); ms['old'].append(to)
+                peak['new'] = max(peak['new'], pn_); peak['old'] = max(peak['old'], po)
+            best = {k: min(v) for k, v in ms.items()}
+            res[f'K{K}'] = dict(
+                new_ms_per_image=best['new'] / N, new_images_per_s=1e3 * N / best['new'],
+                old_ms_per_image=best['old'] / N, old_images_per_s=1e3 * N / best['old'], speedup=best['old'] / best['new'],
+                new_peak_alloc_mb=peak['new'] / 1e6, old_peak_alloc_mb=peak['old'] / 1e6,
+                max_abs_delta=float((ln - lo).abs().max()), agree_argmax=bool(torch.equal(ln.sum(-1).argmax(-1), lo.sum(-1).argmax(-1))))
+            # the scoring kernel alone, from the timing table (HIP events around each of its launches)
+            hip.timing_reset(); hip.timing_enable(True, ['sampler'])
+            new_route(classes)
+            torch.cuda.synchronize()
+            tt = hip.timing_read()['sampler']
+            hip.timing_enable(False)
+            res[f'K{K}'].update(kernel_ms_per_call=tt['ms'], kernel_launches=tt['launches'], kernel_bytes=tt['bytes'],
+                                kernel_TBps=tt['bytes'] / (tt['ms'] * 1e-3) / 1e12 if tt['ms'] > 0 else None,
+                                kernel_frac_of_hbm_peak=tt['bytes'] / (tt['ms'] * 1e-3) / HBM_PEAK if tt['ms'] > 0 else None,
+                                kernel_share_of_call=tt['ms'] / best['new'])
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()

@@ -1015,11 +1015,23 @@ class SamplingEngine:
         self.resolve_precision()
         self.refresh()
         self._wait_ready()
-        w = self.w
         R = int(label_B.numel())                               # rows: one per image, no CFG pair
         dev = var.pos_start.device
-        C, H, V, Cv, L = var.C, var.num_heads, var.V, var.Cvae, var.L
+        L, V = var.L, var.V
         self._check_labels(label_B)
+        ws = self._tf_workspace(R)
+        lab = label_B.to(dev).long().contiguous()
+        out = torch.empty(R, L, V, dtype=torch.float32, device=dev)
+        xin = None if x_BLCv_wo_first_l is None else x_BLCv_wo_first_l.to(dev, torch.float32).contiguous()
+        for si, cur, l in self._tf_scales(ws, lab, xin, R):
+            out[:, cur:cur + l] = ws['lg'][:R * l].view(R, l, V)
+        return out
+
+    def _tf_workspace(self, R: int) -> dict:
+        """buffers of a teacher-forced pass of up to R rows, cached per (rows, HIP stream, precision); a pass of fewer rows uses a prefix"""
+        var = self.var
+        dev = var.pos_start.device
+        C, H, V, L = var.C, var.num_heads, var.V, var.L
         lmax = max(p * p for p in var.patch_nums)
         hid = var.blocks[0].ffn.fc1.weight.shape[0]
         sid = int(torch.cuda.current_stream().cuda_stream)
@@ -1036,7 +1048,13 @@ class SamplingEngine:
                       vc=[torch.zeros(R, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)])
             self._ws_tf = self._evict(self._ws_tf, sid)
             self._ws_tf[(R, sid, self.precision)] = ws
-        lab = label_B.to(dev).long().contiguous()
+        return ws
+
+    def _tf_scales(self, ws: dict, lab: torch.Tensor, xin: Optional[torch.Tensor], R: int):
+        """the teacher-forced loop over R rows (labels `lab`, next-scale inputs `xin` (R, L - first_l, Cvae)): yields (si, cur, l) after the
+        head of each scale has left that scale's fp32 logits in ws['lg'][:R * l] (row r, token t at r * l + t)"""
+        var, w = self.var, self.w
+        C, Cv, L = var.C, var.Cvae, var.L
         hip.call('lvl_pos_f32', w['lvl_embed'], w['lvl_1L'], w['pos_1LC'], ws['lvl_pos'], L, C)
         hip.call('first_map_f32', w['class_emb'], lab, var.num_classes, w['pos_start'], ws['lvl_pos'], ws['cond'], ws['x'], R, C, var.first_l)
         hip.call('silu_f32', ws['cond'], ws['cond_silu'], R * C)
@@ -1055,10 +1073,8 @@ class SamplingEngine:
                 hip.call('gemm_nt_f32', ws['cond_silu'], C, blk['ada_w'], C, blk['ada_b'], ws['ada_view'][bi][0], var.depth * 6 * C, R, 6 * C, C, EPI_NONE,
                          None, 0, None, 0, 1, 0, 1, 0, 0, 0)
         self.gemm(ws['cond_silu'], w['hn_w'], w['hn_b'], ws['hn'], R)
-        out = torch.empty(R, L, V, dtype=torch.float32, device=dev)
         x, x2 = ws['x'], ws['x2']
         cur = 0
-        xin = None if x_BLCv_wo_first_l is None else x_BLCv_wo_first_l.to(dev, torch.float32).contiguous()
         for si, pn in enumerate(var.patch_nums):
             l = pn * pn
             M = R * l
@@ -1068,8 +1084,51 @@ class SamplingEngine:
             for bi, blk in enumerate(w['blocks']):
                 self.block(blk, ws, bi, x, x2, R, l, cur)
             self.head(x, ws['hn'], ws['xn'], ws['lg'], M, l)
-            out[:, cur:cur + l] = ws['lg'][:M].view(R, l, V)
+            yield si, cur, l
             cur += l
+
+    # -- teacher-forced class scoring (VAR.token_log_likelihood) --------------------------------------------------------------
+    @torch.no_grad()
+    def token_log_likelihood(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int) -> torch.Tensor:
+        """(N, K, L) fp32 log p(gt token) of every image under every candidate class (fork eval_prob.py:437-463; cfg > 0: the guided
+        likelihood of var_analysis.py:322-349).  gt_tokens (N, L) int64 and labels (N, K) int64 on the device, already validated by the caller.
+        The N x K rows are packed into passes of at most max_rows rows: images_in_pass x (classes_in_pass + [cfg > 0]), the unconditional
+        row of every image of a pass (label num_classes) after its class rows.  Each scale's logits are reduced to one value per row by
+        varhip_token_loglik_f32 right after the head: no (rows, L, V) tensor exists at any time."""
+        var = self.var
+        self.resolve_precision()
+        self.refresh()
+        self._wait_ready()
+        dev = var.pos_start.device
+        N, K = labels.shape
+        L, V, S = var.L, var.V, len(var.patch_nums)
+        u = 1 if cfg > 0 else 0
+        if K + u <= max_rows:
+            ipp, kpp = max(1, max_rows // (K + u)), K            # whole images per pass
+        else:
+            ipp, kpp = 1, max_rows - u                           # one image per pass, its classes in chunks (each pass with its own uncond row)
+        passes = [(i0, min(ipp, N - i0), k0, min(kpp, K - k0)) for i0 in range(0, N, ipp) for k0 in range(0, K, kpp)]
+        ws = self._tf_workspace(max(ni * (nk + u) for _, ni, _, nk in passes))   # sized once: a shorter pass uses a prefix
+        gt = gt_tokens.to(dev, torch.int64).contiguous()
+        lab_all = labels.to(dev, torch.int64).contiguous()
+        # teacher-forcing input of every image (eval_prob.py:437), one encode-side call for all of them
+        xin_img = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in var.begin_ends]).to(dev, torch.float32)
+        out = torch.empty(N, K, L, dtype=torch.float32, device=dev)
+        # guidance factors per scale, rounded where var_analysis.py:333-344 rounds them (a float32 ratio tensor times the Python cfg)
+        t32 = [np.float32(np.float32(cfg) * np.float32(si / (S - 1) if S > 1 else 0.0)) for si in range(S)]
+        for i0, ni, k0, nk in passes:
+            R = ni * (nk + u)
+            rows_img = torch.arange(i0, i0 + ni, device=dev)
+            lab = lab_all[i0:i0 + ni, k0:k0 + nk].reshape(-1)
+            src = rows_img.repeat_interleave(nk)
+            if u:
+                lab = torch.cat((lab, torch.full((ni,), var.num_classes, dtype=torch.int64, device=dev)))
+                src = torch.cat((src, rows_img))
+            xin = xin_img.index_select(0, src).contiguous()     # each image's input broadcast to its rows
+            for si, cur, l in self._tf_scales(ws, lab.contiguous(), xin, R):
+                t = t32[si]
+                hip.call('token_loglik_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
+                         out[i0:, k0:, cur:], K * L, L)
         return out
 
     # -- model arithmetic (for bench.py's roofline) -------------------------------------------------------------------

@@ -125,10 +125,16 @@ class VAR(nn.Module):
             # inference (no autograd): scale-by-scale over the KV cache on the HIP kernels, fp32, same label dropping as below
             label_B = torch.where(torch.rand(label_B.shape[0], device=label_B.device) < self.cond_drop_rate, self.num_classes, label_B)
             return self.engine().teacher_forced_logits(label_B, x_BLCv_wo_first_l)
-        bg, ed = self.begin_ends[self.prog_si] if self.prog_si >= 0 else (0, self.L)
         B = x_BLCv_wo_first_l.shape[0]
         with torch.autocast(device_type=x_BLCv_wo_first_l.device.type, enabled=False):
             label_B = torch.where(torch.rand(B, device=label_B.device) < self.cond_drop_rate, self.num_classes, label_B)
+        return self._forward_torch(label_B, x_BLCv_wo_first_l)
+
+    def _forward_torch(self, label_B: torch.LongTensor, x_BLCv_wo_first_l: torch.Tensor) -> torch.Tensor:
+        """the PyTorch teacher-forced pass of forward() on labels as given (no condition dropping)"""
+        bg, ed = self.begin_ends[self.prog_si] if self.prog_si >= 0 else (0, self.L)
+        B = x_BLCv_wo_first_l.shape[0]
+        with torch.autocast(device_type=x_BLCv_wo_first_l.device.type, enabled=False):
             cond_BD = self.class_emb(label_B)
             sos = cond_BD.unsqueeze(1).expand(B, self.first_l, -1) + self.pos_start.expand(B, self.first_l, -1)
             x = sos if self.prog_si == 0 else torch.cat((sos, self.word_embed(x_BLCv_wo_first_l.float())), dim=1)
@@ -143,6 +149,65 @@ class VAR(nn.Module):
         if self.prog_si == 0:      # keep word_embed in the graph for DDP
             x[0, 0, 0] += self.word_embed.weight[0, 0] * 0 + self.word_embed.bias[0] * 0
         return x
+
+    @torch.no_grad()
+    def token_log_likelihood(self, gt_tokens, label, cfg: float = 0.0, max_rows: int = 64) -> torch.Tensor:
+        """(N, K, L) fp32: log p(gt token) of every image under every candidate class, teacher-forced.
+
+        Fork API for VAR as a zero-shot classifier: one call replaces eval_prob.py:437-463 (bayesian mode: forward, log_softmax, gather, per
+        candidate class) and, with cfg > 0, var_analysis.py:322-349 (z = (1+t)*cond - t*uncond, t = cfg * si/(S-1) per scale, one
+        unconditional pass per image shared by all its classes).  gt_tokens: (N, L) int64, torch.cat(vae.img_to_idxBl(img), 1); label: (K,)
+        (the same candidates for every image) or (N, K), a tensor or a list; labels in [0, num_classes] are used as given (no condition
+        dropping, whatever cond_drop_rate is).  Classification: lp.sum(-1).argmax(-1); eval_prob --Clayer c: lp[..., cumsum[c]:].sum(-1).
+        max_rows bounds the transformer rows of one pass (images_in_pass x (classes_in_pass + [cfg > 0])).
+        On the HIP path (CUDA, eval mode, prog_si < 0, fp32 head, head_dim 64) the per-token values are reduced from each scale's logits by a
+        gfx950 kernel: no (rows, L, V) tensor is made, the precision follows set_hip_precision / torch.autocast as forward() does.  Elsewhere
+        the reference's formula runs in PyTorch."""
+        dev = self.lvl_1L.device
+        gt = torch.as_tensor(gt_tokens)
+        if gt.dim() != 2 or gt.shape[1] != self.L or gt.shape[0] < 1 or gt.dtype in (torch.bool,) or gt.is_floating_point() or gt.is_complex():
+            raise ValueError(f'gt_tokens must be an (N, {self.L}) integer tensor of token ids')
+        lab = torch.as_tensor(label)
+        if lab.dim() == 1:
+            lab = lab.unsqueeze(0).expand(gt.shape[0], -1)
+        if lab.dim() != 2 or lab.shape[0] != gt.shape[0] or lab.shape[1] < 1 or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
+            raise ValueError(f'label must be (K,) or (N, K) integer class ids with K >= 1, N = {gt.shape[0]}')
+        cfg = float(cfg)
+        if not math.isfinite(cfg) or cfg < 0:
+            raise ValueError('cfg must be finite and >= 0')
+        if int(max_rows) != max_rows or max_rows < 1 + (cfg > 0):
+            raise ValueError(f'max_rows must be an integer >= {1 + (cfg > 0)} (the class rows of a pass plus the unconditional row with cfg > 0)')
+        # explicit range checks (one host sync each): a bad token would index past a logits row, a bad label past class_emb
+        lo, hi = torch.stack(torch.aminmax(gt)).tolist()
+        if lo < 0 or hi >= self.V:
+            raise ValueError(f'gt_tokens must lie in [0, {self.V})')
+        lo, hi = torch.stack(torch.aminmax(lab)).tolist()
+        if lo < 0 or hi > self.num_classes:
+            raise ValueError(f'labels must lie in [0, {self.num_classes}]')
+        gt, lab = gt.to(dev, torch.int64), lab.to(dev, torch.int64)
+        if not self.training and self.prog_si < 0 and dev.type == 'cuda' and self.head.weight.dtype == torch.float32 and self.C == 64 * self.num_heads:
+            return self.engine().token_log_likelihood(gt, lab, cfg, int(max_rows))
+        # the reference's formula (eval_prob.py:441-463; var_analysis.py:322-344), one image at a time
+        N, K = lab.shape
+        ed = self.begin_ends[self.prog_si][1] if self.prog_si >= 0 else self.L
+        x_all = self.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in self.begin_ends])
+        ratio = torch.tensor([si / self.num_stages_minus_1 if self.num_stages_minus_1 > 0 else 0.0 for si, pn in enumerate(self.patch_nums) for _ in range(pn * pn)],
+                             device=dev)[:ed]
+        t = cfg * ratio.unsqueeze(0).unsqueeze(-1)
+        out = []
+        for i in range(N):
+            x_i = x_all[i:i + 1]
+            rows = []
+            for k0 in range(0, K, max_rows):
+                kk = lab[i, k0:k0 + max_rows]
+                rows.append(self._forward_torch(kk, x_i.expand(kk.shape[0], -1, -1)).float())
+            logits = torch.cat(rows, 0)
+            if cfg > 0:
+                uncond = self._forward_torch(torch.full((1,), self.num_classes, dtype=torch.int64, device=dev), x_i).float()
+                logits = (1 + t) * logits - t * uncond
+            lp = torch.nn.functional.log_softmax(logits, dim=-1)
+            out.append(lp.gather(dim=-1, index=gt[i:i + 1, :ed].expand(K, -1).unsqueeze(-1)).squeeze(-1))
+        return torch.stack(out, 0)
 
     @torch.no_grad()
     def inpainting(self, gt_tokens: torch.Tensor, mask: torch.Tensor, label: Optional[Union[int, torch.LongTensor]] = None,
