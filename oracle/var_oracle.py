@@ -167,6 +167,38 @@ class OracleVAR:
             return out
         return self.linear(cond_silu, f'blocks.{b}.ada_lin.1.weight', self.sd[f'blocks.{b}.ada_lin.1.bias'])
 
+    def block(self, b: int, x: np.ndarray, ada: np.ndarray, kc: np.ndarray, vc: np.ndarray, cur: int, l: int) -> np.ndarray:
+        """AdaLNSelfAttn.forward of block b (basic_var.py:152-159) on x [B2*l, C] with its ada rows [B2, 6C]: writes this scale's k / v rows
+        into kc / vc [B2, H, Lmax, 64] at positions [cur, cur + l) in place and returns the new x"""
+        Lf, sd, C, H = self.L_, self.sd, self.C, self.H
+        B2, Lmax = x.shape[0] // l, kc.shape[2]
+        g1, g2, s1, s2, h1, h2 = (ada[:, i * C:(i + 1) * C] for i in range(6))
+        h16 = self.f16
+        hN = self.ln_mod(x, s1, h1, l)
+        if h16: hN = r16(hN, self.kind16)
+        bias_qkv = np.concatenate([sd[f'blocks.{b}.attn.q_bias'], np.zeros(C, np.float32), sd[f'blocks.{b}.attn.v_bias']]).astype(np.float32)
+        qkv = self.linear(hN, f'blocks.{b}.attn.mat_qkv.weight', bias_qkv, w16=h16)          # basic_var.py:93
+        q = np.empty((B2 * l, C), np.float32)
+        sm = f32(sd[f'blocks.{b}.attn.scale_mul_1H11'].reshape(-1)) if self.l2 else None
+        _ck(Lf['qkv_prep_f32'](_p(qkv), _p(sm), 0.25 / 8.0, int(self.l2), _p(q), _p(kc), _p(vc), B2, l, H, cur, Lmax), 'qkv_prep')
+        att = np.empty((B2 * l, C), np.float32)
+        if h16:            # fp16 q and fp16 cache rows; p rounded to fp16 for p.v, fp16 output
+            k16 = self.kind16
+            q = r16(q, k16)
+            kc[:, :, cur:cur + l] = r16(kc[:, :, cur:cur + l], k16); vc[:, :, cur:cur + l] = r16(vc[:, :, cur:cur + l], k16)
+            _ck(Lf['attn_cached_pbf16_f32' if k16 == 'bf16' else 'attn_cached_p16_f32'](_p(q), _p(kc), _p(vc), _p(att), B2, l, H, cur + l, Lmax), 'attn p16')
+        else:
+            _ck(Lf['attn_cached_f32'](_p(q), _p(kc), _p(vc), _p(att), B2, l, H, cur + l, Lmax), 'attn')
+        x = self.linear(att, f'blocks.{b}.attn.proj.weight', sd[f'blocks.{b}.attn.proj.bias'], abi.EPI_RESID, resid=x,
+                        gamma=g1, ldg=ada.shape[1], rows_per_group=l, w16=h16)                 # basic_var.py:157
+        hN = self.ln_mod(x, s2, h2, l)
+        if h16: hN = r16(hN, self.kind16)
+        hid = self.linear(hN, f'blocks.{b}.ffn.fc1.weight', sd[f'blocks.{b}.ffn.fc1.bias'], abi.EPI_GELU, w16=h16)
+        if h16: hid = r16(hid, self.kind16)
+        x = self.linear(hid, f'blocks.{b}.ffn.fc2.weight', sd[f'blocks.{b}.ffn.fc2.bias'], abi.EPI_RESID, resid=x,
+                        gamma=g2, ldg=ada.shape[1], rows_per_group=l, w16=h16)                 # basic_var.py:158
+        return x
+
     def run(self, labels: Sequence[int], noises: List[np.ndarray], cfg: float, top_k: int, top_p: float,
             force_idx: Optional[np.ndarray] = None, decode: bool = True, keep_masked: bool = False,
             gt_tokens: Optional[np.ndarray] = None, keep_mask: Optional[np.ndarray] = None,
@@ -200,32 +232,7 @@ class OracleVAR:
             l = pn * pn
             shared = self.linear(cond_silu, 'shared_ada_lin.1.weight', sd['shared_ada_lin.1.bias']) if self.saln else None   # var.py:165
             for b in range(self.depth):                                    # var.py:168-169 -> AdaLNSelfAttn.forward basic_var.py:152-159
-                ada = self.ada(b, cond_silu, shared)
-                g1, g2, s1, s2, h1, h2 = (ada[:, i * C:(i + 1) * C] for i in range(6))
-                h16 = self.f16
-                hN = self.ln_mod(x, s1, h1, l)
-                if h16: hN = r16(hN, self.kind16)
-                bias_qkv = np.concatenate([sd[f'blocks.{b}.attn.q_bias'], np.zeros(C, np.float32), sd[f'blocks.{b}.attn.v_bias']]).astype(np.float32)
-                qkv = self.linear(hN, f'blocks.{b}.attn.mat_qkv.weight', bias_qkv, w16=h16)          # basic_var.py:93
-                q = np.empty((B2 * l, C), np.float32)
-                sm = f32(sd[f'blocks.{b}.attn.scale_mul_1H11'].reshape(-1)) if self.l2 else None
-                _ck(Lf['qkv_prep_f32'](_p(qkv), _p(sm), 0.25 / 8.0, int(self.l2), _p(q), _p(kc[b]), _p(vc[b]), B2, l, H, cur, self.L), 'qkv_prep')
-                att = np.empty((B2 * l, C), np.float32)
-                if h16:            # fp16 q and fp16 cache rows; p rounded to fp16 for p.v, fp16 output
-                    k16 = self.kind16
-                    q = r16(q, k16)
-                    kc[b][:, :, cur:cur + l] = r16(kc[b][:, :, cur:cur + l], k16); vc[b][:, :, cur:cur + l] = r16(vc[b][:, :, cur:cur + l], k16)
-                    _ck(Lf['attn_cached_pbf16_f32' if k16 == 'bf16' else 'attn_cached_p16_f32'](_p(q), _p(kc[b]), _p(vc[b]), _p(att), B2, l, H, cur + l, self.L), 'attn p16')
-                else:
-                    _ck(Lf['attn_cached_f32'](_p(q), _p(kc[b]), _p(vc[b]), _p(att), B2, l, H, cur + l, self.L), 'attn')
-                x = self.linear(att, f'blocks.{b}.attn.proj.weight', sd[f'blocks.{b}.attn.proj.bias'], abi.EPI_RESID, resid=x,
-                                gamma=g1, ldg=ada.shape[1], rows_per_group=l, w16=h16)                 # basic_var.py:157
-                hN = self.ln_mod(x, s2, h2, l)
-                if h16: hN = r16(hN, self.kind16)
-                hid = self.linear(hN, f'blocks.{b}.ffn.fc1.weight', sd[f'blocks.{b}.ffn.fc1.bias'], abi.EPI_GELU, w16=h16)
-                if h16: hid = r16(hid, self.kind16)
-                x = self.linear(hid, f'blocks.{b}.ffn.fc2.weight', sd[f'blocks.{b}.ffn.fc2.bias'], abi.EPI_RESID, resid=x,
-                                gamma=g2, ldg=ada.shape[1], rows_per_group=l, w16=h16)                 # basic_var.py:158
+                x = self.block(b, x, self.ada(b, cond_silu, shared), kc[b], vc[b], cur, l)
             cur += l
             if gt_tokens is not None and bool(np.all(keep_mask[:, cur - l:cur])):
                 # VAR.inpainting, whole scale kept (var.py:312-313): ground-truth tokens, no logits, no RNG draw

@@ -165,15 +165,32 @@ def test_gemm_rejects_bad_shapes():
     with pytest.raises(VarHipError):                                                      # A rows spanning 4 GiB
         hip.call('gemm_qkv_f32', a, 1 << 22, a, 64, q, 257, 64, 64, q, 1.0, 0, a, a, a, 257, 1, 1, 0, 1)
 
-@pytest.mark.parametrize('M,C,rpg', [(4, 128, 1), (37, 1024, 9), (512, 1024, 4), (10, 1920, 5), (6, 2304, 2)])
-def test_ln_modulate_exact(M, C, rpg):
+@pytest.mark.parametrize('M,C,rpg,ld', [(4, 128, 1, 6), (37, 1024, 9, 6), (512, 1024, 4, 6), (10, 1920, 5, 6), (6, 2304, 2, 6),
+                                        (5000, 1024, 256, 6), (4, 2560, 1, 2), (33, 132, 33, 2), (37, 1024, 9, 2), (6, 2304, 2, 2)])
+def test_ln_modulate_exact(M, C, rpg, ld):
+    """fp32 against the oracle bit for bit; the 16-bit outputs (ln_modulate_{f16,bf16}out: the same template, the same fp32 arithmetic) must be
+    torch's round-to-nearest-even cast of that fp32 result, bit for bit.  Both kernel variants (EARLY: M <= 4096 and C <= 1024; the late one
+    otherwise), scale / shift rows at the block's stride (ld = 6C: the ada rows) and the head's (2C), rows with a large mean, and a row group
+    whose scale pushes results beyond 65504 (fp16: +-inf, as the cast)"""
     rng = np.random.default_rng(M + C)
     G = (M + rpg - 1) // rpg
     x = rnd(rng, M, C, scale=2.0) + 0.3
-    ada = rnd(rng, G, 6 * C, scale=0.5)
+    x[1::3] += 1000.0
+    ada = rnd(rng, G, ld * C, scale=0.5)
+    so, ho = (2 * C, 4 * C) if ld == 6 else (0, C)
+    ada[G - 1, so:so + C // 2] = 6e4
     out = np.zeros_like(x)
-    (g,), (w,) = both('ln_modulate_f32', [x, (ada, 2 * C), 6 * C, (ada, 4 * C), 6 * C, out, M, C, rpg, 1e-6], [5])
+    (g,), (w,) = both('ln_modulate_f32', [x, (ada, so), ld * C, (ada, ho), ld * C, out, M, C, rpg, 1e-6], [5])
     check(f'ln_modulate {M}x{C}', g, w)
+    _, hip = _setup()
+    xd, ad = torch.from_numpy(x).cuda(), torch.from_numpy(ada).cuda()
+    for dt, fl in ((torch.float16, 'f16'), (torch.bfloat16, 'bf16')):
+        o16 = torch.empty(M, C, dtype=dt, device='cuda')
+        hip.call(f'ln_modulate_{fl}out', xd, ad[:, so:], ld * C, ad[:, ho:], ld * C, o16, M, C, rpg, 1e-6)
+        want = torch.from_numpy(g).to(dt)
+        got = o16.cpu()
+        assert torch.equal(got, want), f'ln_modulate_{fl}out {M}x{C}: {int((got != want).sum())} of {got.numel()} differ from the rounded fp32 result'
+    assert bool(torch.from_numpy(g).half().isinf().any()), 'no fp16 overflow exercised'
 
 
 @pytest.mark.parametrize('B2,l,H,pos0,Lmax,l2', [(4, 1, 2, 0, 14, 1), (4, 9, 2, 5, 14, 1), (2, 16, 16, 14, 55, 1), (4, 4, 2, 1, 14, 0)])
