@@ -271,6 +271,25 @@ int varhip_smooth_select_f32(const float* logits, const int64_t* gt, const int32
 int varhip_token_loglik_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V,
                             int with_uncond, float ca, float cb, float* out, int64_t ld_out_img, int64_t ld_out_cls, varhip_stream_t stream);
 
+/* ---- the fork's other class scores (eval_prob.py:37-92 + 518-553 smooth_bayesian, :389-393 + 559-577 fast_neighbor_bayesian,
+ * var_analysis.py:252-258 + 468-500 l2_dist) -------------------------------------------------------------------------------------------
+ * The codebook distance table: out[v * V + u] = sqrt(sum_c (cb[v][c] - cb[u][c])^2) with the arithmetic of varhip_neighbor_table_f32 (one fma
+ * chain over the channels in channel order, then sqrt): every entry equals that table's distance for the same pair bit for bit; the table is
+ * exactly symmetric with a zero diagonal.  codebook: [V][D], 1 <= V <= 65535; out: [V][V]. */
+int varhip_code_dist_f32(const float* codebook, int V, int D, float* out, varhip_stream_t stream);
+/* One scale of one pass of teacher-forced scoring: the pass layout, gt / out addressing and CFG combine of varhip_token_loglik_f32, and
+ * p = softmax(z) per row, codes ordered by z descending with ties by ascending code index:
+ *   mode 1 (group_smoothed, param = group G >= 1): r = rank of gt, lo = r - r % G, hi = min(lo + G, V):
+ *          out = log(sum_{rank in [lo, hi)} p / (hi - lo) + 1e-10)                                                  (eval_prob.py:37-92)
+ *   mode 2 (neighbor_max, thr finite >= 0):      out = max_{v : dist[gt][v] <= thr} log p_v                    (eval_prob.py:389-393, var.py:504-520)
+ *   mode 3 (expected_distance, param = top_k):   param == 0: out = -sum_v p_v dist[gt][v];  1 <= param <= V: the same over the top_k codes
+ *          with their p renormalised to sum to 1                                                                   (var_analysis.py:252-258)
+ * dist: [>= V rows][ld_dist] (modes 2 and 3; the table of varhip_code_dist_f32, ld_dist >= V), may be NULL in mode 1.  V <= 2^24.
+ * Bad sizes, an unknown mode or a parameter out of its range: VARHIP_EINVAL. */
+int varhip_token_score_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V,
+                           int with_uncond, float ca, float cb, int mode, int param, float thr, const float* dist, int64_t ld_dist,
+                           float* out, int64_t ld_out_img, int64_t ld_out_cls, varhip_stream_t stream);
+
 /* ---- nearest-codebook lookup (encode side; quant.py:150-157) --------------------------------------------
  * idx[n] = argmin_v ( |z_n|^2 + |e_v|^2 - 2 z_n.e_v ), first index on ties; z: [N][Cv], codebook: [V][Cv] */
 int varhip_nearest_code_f32(const float* z, const float* codebook, int64_t* idx_out, int N, int V, int Cv, varhip_stream_t stream);

@@ -2,13 +2,16 @@
 """Timing of VAR as a zero-shot classifier (fork eval_prob.py --mode bayesian, var_analysis.py --cfg) on one MI355X, random-init weights
 (detinit seed 0), N images of 256x256, d16:
 
-    new route  VAR.token_log_likelihood(gt_tokens, classes, cfg)                   (N x K rows packed into passes of <= --max-rows rows)
+    new route  VAR.token_scores(gt_tokens, classes, --score, cfg)                  (N x K rows packed into passes of <= --max-rows rows;
+               --score log_prob is VAR.token_log_likelihood)
     old route  per image: x = idxBl_to_var_input, VAR.forward(classes, x.expand(K, ...)) [+ one unconditional forward and the CFG combine],
-               log_softmax, gather                                                   (what a caller of this library writes today)
+               then the fork's formula on the (K, L, V) logits: log_softmax + gather (log_prob), or sort / softmax / gathers of the
+               distance table rows (token_score_torch: group_smoothed, neighbor_max, expected_distance)
 
 both in the same process, alternated, the old one on a stream of its own (each route keeps its own workspace).
 
     python tools/bench_classify.py [--images 16] [--k-large 100] [--cfg 0] [--dtype f32|f16|bf16] [--iters 3]
+                                   [--score log_prob|group_smoothed|neighbor_max|expected_distance] [--group 50] [--threshold T] [--top-k k]
 
 Prints one JSON object: encode ms per image; per K: ms per image and images per second of both routes, their peak allocation increase,
 max |delta| of the per-token values; the scoring kernel's time from the library's timing table (family 'sampler', which no other kernel of
@@ -25,6 +28,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from var_amd import detinit, hip      # noqa: E402
+from var_amd.models.var import token_score_torch      # noqa: E402
 
 HBM_PEAK = 8.0e12
 
@@ -37,6 +41,10 @@ def main():
     ap.add_argument('--max-rows', type=int, default=64)
     ap.add_argument('--iters', type=int, default=3)
     ap.add_argument('--dtype', default='f32', choices=['f32', 'f16', 'bf16'])
+    ap.add_argument('--score', default='log_prob', choices=['log_prob', 'group_smoothed', 'neighbor_max', 'expected_distance'])
+    ap.add_argument('--group', type=int, default=50)
+    ap.add_argument('--threshold', type=float, default=None, help='neighbor_max; default: the median code distance')
+    ap.add_argument('--top-k', type=int, default=None, help='expected_distance; default: all codes')
     a = ap.parse_args()
     torch.cuda.set_device(0)
     dev = torch.device('cuda', 0)
@@ -65,8 +73,18 @@ def main():
         ratio = torch.tensor([si / (S - 1) for si, pn in enumerate(pns) for _ in range(pn * pn)], device=dev)
         t = a.cfg * ratio.unsqueeze(0).unsqueeze(-1)
 
+        dist = var.engine().code_distance_table() if a.score in ('neighbor_max', 'expected_distance') else None     # built once, outside the timing
+        kw, desc = {}, None
+        if a.score == 'group_smoothed':
+            kw, desc = dict(group=a.group), ('group_smoothed', a.group)
+        elif a.score == 'neighbor_max':
+            thr = float(dist[:64].median()) if a.threshold is None else a.threshold
+            kw, desc = dict(threshold=thr), ('neighbor_max', thr)
+        elif a.score == 'expected_distance':
+            kw, desc = dict(top_k=a.top_k), ('expected_distance', a.top_k or 0)
+
         def new_route(classes):
-            return var.token_log_likelihood(gt, classes, cfg=a.cfg, max_rows=a.max_rows)
+            return var.token_scores(gt, classes, a.score, cfg=a.cfg, max_rows=a.max_rows, **kw)
 
         def old_route(classes):
             lab = torch.tensor(classes, device=dev)
@@ -76,9 +94,12 @@ def main():
                 logits = var(lab, x.expand(len(classes), -1, -1).contiguous())
                 if a.cfg > 0:
                     logits = (1 + t) * logits - t * var(torch.tensor([var.num_classes], device=dev), x)
-                lp = torch.nn.functional.log_softmax(logits, dim=-1)
-                out.append(lp.gather(-1, gt[i:i + 1].expand(len(classes), -1).unsqueeze(-1)).squeeze(-1))
-                del logits, lp
+                if desc is None:
+                    lp = torch.nn.functional.log_softmax(logits, dim=-1)
+                    out.append(lp.gather(-1, gt[i:i + 1].expand(len(classes), -1).unsqueeze(-1)).squeeze(-1))
+                else:
+                    out.append(token_score_torch(logits, gt[i], desc, None if dist is None else dist[gt[i]]))
+                del logits
             return torch.stack(out)
 
         def timed(fn, classes, stream):
@@ -93,7 +114,7 @@ def main():
                 torch.cuda.synchronize()
                 return r, e0.elapsed_time(e1), torch.cuda.max_memory_allocated() - base
 
-        res = dict(images=N, cfg=a.cfg, dtype=a.dtype, max_rows=a.max_rows, encode_ms_per_image=sum(enc) / len(enc) / N)
+        res = dict(images=N, cfg=a.cfg, dtype=a.dtype, max_rows=a.max_rows, score=a.score, score_args=kw, encode_ms_per_image=sum(enc) / len(enc) / N)
         for K in (10, a.k_large):
             classes = [(c * 97) % 1000 for c in range(K)]
             ms = {'new': [], 'old': []}

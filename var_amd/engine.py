@@ -612,6 +612,10 @@ class EncoderEngine(DecoderEngine):
 AUTOCAST_PRECISION = {torch.float16: 'f16', torch.bfloat16: 'bf16'}
 
 
+# score -> mode of varhip_token_score_f32 (0: varhip_token_loglik_f32)
+_SCORE_MODES = {'log_prob': 0, 'group_smoothed': 1, 'neighbor_max': 2, 'expected_distance': 3}
+
+
 class SamplingEngine:
     """The AR loop of VAR.autoregressive_infer_cfg on HIP kernels.  One engine per VAR module; calls on different HIP streams may be in flight
     together (per-stream workspaces), the host side is not thread-safe."""
@@ -1087,7 +1091,7 @@ class SamplingEngine:
             yield si, cur, l
             cur += l
 
-    # -- teacher-forced class scoring (VAR.token_log_likelihood) --------------------------------------------------------------
+    # -- teacher-forced class scoring (VAR.token_log_likelihood, VAR.token_scores) --------------------------------------------------
     @torch.no_grad()
     def token_log_likelihood(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int) -> torch.Tensor:
         """(N, K, L) fp32 log p(gt token) of every image under every candidate class (fork eval_prob.py:437-463; cfg > 0: the guided
@@ -1095,6 +1099,17 @@ class SamplingEngine:
         The N x K rows are packed into passes of at most max_rows rows: images_in_pass x (classes_in_pass + [cfg > 0]), the unconditional
         row of every image of a pass (label num_classes) after its class rows.  Each scale's logits are reduced to one value per row by
         varhip_token_loglik_f32 right after the head: no (rows, L, V) tensor exists at any time."""
+        return self._score_passes(gt_tokens, labels, cfg, max_rows, ('log_prob',))
+
+    @torch.no_grad()
+    def token_scores(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, score: tuple) -> torch.Tensor:
+        """(N, K, L) fp32 per-token scores of VAR.token_scores: as token_log_likelihood, with each scale's logits reduced by
+        varhip_token_score_f32.  score: ('group_smoothed', group) | ('neighbor_max', threshold) | ('expected_distance', top_k or 0),
+        already validated by the caller."""
+        return self._score_passes(gt_tokens, labels, cfg, max_rows, score)
+
+    def _score_passes(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, score: tuple) -> torch.Tensor:
+        """the pass loop of token_log_likelihood / token_scores; `score` picks the kernel that reduces each scale's logits"""
         var = self.var
         self.resolve_precision()
         self.refresh()
@@ -1102,6 +1117,17 @@ class SamplingEngine:
         dev = var.pos_start.device
         N, K = labels.shape
         L, V, S = var.L, var.V, len(var.patch_nums)
+        mode = _SCORE_MODES[score[0]]
+        param, thr, dist = 0, 0.0, None
+        if score[0] == 'group_smoothed':
+            param = int(score[1])
+        elif score[0] == 'neighbor_max':
+            thr = float(score[1])
+        elif score[0] == 'expected_distance':
+            param = int(score[1])
+        if score[0] in ('neighbor_max', 'expected_distance'):
+            dist = self.code_distance_table()
+            self._wait_ready()
         u = 1 if cfg > 0 else 0
         if K + u <= max_rows:
             ipp, kpp = max(1, max_rows // (K + u)), K            # whole images per pass
@@ -1127,9 +1153,28 @@ class SamplingEngine:
             xin = xin_img.index_select(0, src).contiguous()     # each image's input broadcast to its rows
             for si, cur, l in self._tf_scales(ws, lab.contiguous(), xin, R):
                 t = t32[si]
-                hip.call('token_loglik_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
-                         out[i0:, k0:, cur:], K * L, L)
+                if mode == 0:
+                    hip.call('token_loglik_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
+                             out[i0:, k0:, cur:], K * L, L)
+                else:
+                    hip.call('token_score_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
+                             mode, param, thr, dist, V, out[i0:, k0:, cur:], K * L, L)
         return out
+
+    def code_distance_table(self) -> torch.Tensor:
+        """(V, V) fp32 L2 distances between codebook vectors in the direct form of neighbor_table (one fma chain over the channels, then
+        sqrt; not cdist's |a|^2 + |b|^2 - 2ab): entry (v, u) equals neighbor_table's distance for the pair bit for bit.  64 MiB at V = 4096;
+        cached next to the neighbour tables until the codebook changes."""
+        self.refresh()
+        if 'code_dist' not in self.w:
+            cb = self.w['codebook']
+            V, D = cb.shape
+            dist = torch.empty(V, V, dtype=torch.float32, device=cb.device)
+            self._wait_ready()
+            hip.call('code_dist_f32', cb, V, D, dist)
+            self.w['code_dist'] = dist
+            self._built()
+        return self.w['code_dist']
 
     # -- model arithmetic (for bench.py's roofline) -------------------------------------------------------------------
     def flops_per_image(self) -> float:

@@ -17,6 +17,46 @@ from .helpers import gumbel_softmax_with_rng, sample_with_top_k_top_p_     # noq
 from .vqvae import VQVAE, VectorQuantizer2
 
 
+def code_distance_rows(codebook: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """(len(rows), V) fp32 direct-form L2 distances from the codes `rows` to every code: sqrt of one fma chain over the channels in channel
+    order, the arithmetic of varhip_code_dist_f32 / varhip_neighbor_table_f32.  Each fma is evaluated as the float64 sum of the exact square
+    and the fp32 accumulator, rounded once more to fp32 (equal to the fused result except in rare double-rounding cases)."""
+    cb = codebook.float()
+    a = cb[rows]
+    acc = torch.zeros(a.shape[0], cb.shape[0], dtype=torch.float32, device=cb.device)
+    for c in range(cb.shape[1]):
+        d = (a[:, c:c + 1] - cb[:, c].unsqueeze(0)).double()
+        acc = (acc.double() + d * d).float()
+    return acc.sqrt()
+
+
+def token_score_torch(z: torch.Tensor, gt: torch.Tensor, desc: tuple, d: Optional[torch.Tensor]) -> torch.Tensor:
+    """the per-token scores of VAR.token_scores in PyTorch.  z: (K, l, V) fp32 logits of one image's K class rows, gt: (l,) tokens,
+    desc: ('group_smoothed', G) | ('neighbor_max', threshold) | ('expected_distance', top_k or 0), d: (l, V) distance rows of the gt codes"""
+    K, l, V = z.shape
+    g = gt.view(1, l, 1).expand(K, l, 1)
+    mode, par = desc
+    if mode == 'neighbor_max':
+        lp = torch.log_softmax(z, dim=-1)
+        return lp.masked_fill(~(d <= par).unsqueeze(0), -math.inf).amax(-1)
+    p = torch.softmax(z, dim=-1)
+    if mode == 'expected_distance' and par == 0:
+        return -(p * d.unsqueeze(0)).sum(-1)
+    order = torch.sort(z, dim=-1, descending=True, stable=True).indices        # z descending, ties by ascending index
+    if mode == 'expected_distance':
+        top = order[..., :par]
+        pk = p.gather(-1, top)
+        return -(pk * d.unsqueeze(0).expand(K, l, V).gather(-1, top)).sum(-1) / pk.sum(-1)
+    G = par
+    ng = (V + G - 1) // G
+    ps = torch.nn.functional.pad(p.gather(-1, order), (0, ng * G - V))
+    sums = ps.view(K, l, ng, G).sum(-1)
+    size = (V - torch.arange(ng, device=z.device) * G).clamp(max=G).to(z.dtype)
+    rank = torch.empty_like(order).scatter_(-1, order, torch.arange(V, device=z.device).expand(K, l, V))
+    grp = rank.gather(-1, g) // G
+    return torch.log((sums / size).gather(-1, grp) + 1e-10).squeeze(-1)
+
+
 class SharedAdaLin(nn.Linear):
     def forward(self, cond_BD):
         return super().forward(cond_BD).view(-1, 1, 6, self.weight.shape[0] // 6)
@@ -163,6 +203,72 @@ class VAR(nn.Module):
         On the HIP path (CUDA, eval mode, prog_si < 0, fp32 head, head_dim 64) the per-token values are reduced from each scale's logits by a
         gfx950 kernel: no (rows, L, V) tensor is made, the precision follows set_hip_precision / torch.autocast as forward() does.  Elsewhere
         the reference's formula runs in PyTorch."""
+        gt, lab, cfg = self._scoring_args(gt_tokens, label, cfg, max_rows)
+        if self._scoring_on_hip(gt):
+            return self.engine().token_log_likelihood(gt, lab, cfg, int(max_rows))
+        # the reference's formula (eval_prob.py:441-463; var_analysis.py:322-344), one image at a time
+        out = []
+        for i, logits in self._teacher_forced_torch(gt, lab, cfg, max_rows):
+            lp = torch.nn.functional.log_softmax(logits, dim=-1)
+            out.append(lp.gather(dim=-1, index=gt[i:i + 1, :logits.shape[1]].expand(lab.shape[1], -1).unsqueeze(-1)).squeeze(-1))
+        return torch.stack(out, 0)
+
+    @torch.no_grad()
+    def token_scores(self, gt_tokens, label, score: str, cfg: float = 0.0, max_rows: int = 64, *, group: Optional[int] = None,
+                     threshold: Optional[float] = None, top_k: Optional[int] = None) -> torch.Tensor:
+        """(N, K, L) fp32 per-token class scores, teacher-forced: the fork's four scoring modes in one call each.
+
+        gt_tokens, label, cfg and max_rows mean exactly what they mean in token_log_likelihood (same validation, packing and guided z).  With
+        p = softmax(z) per token and the codes ordered by z descending, ties by ascending code index (a total order; torch.sort, which the
+        fork uses, leaves the order of ties unspecified):
+          'log_prob'           log p_gt: token_log_likelihood's values bit for bit (eval_prob.py bayesian).
+          'group_smoothed'     group G (None -> the fork's 50, G >= 1): r = rank of gt, [lo, hi) = [r - r % G, min(lo + G, V)):
+                               log(sum of p over the ranks [lo, hi) / (hi - lo) + 1e-10)   (eval_prob.py:37-92 smooth_bayesian).  Only which
+                               group gt falls into depends on the tie order, not the values of a group.
+          'neighbor_max'       threshold (finite, >= 0, required): max of log p_v over the codes v with d(gt, v) <= threshold; gt itself is
+                               always in (eval_prob.py:389-393 fast_neighbor_bayesian, the rule of smooth_sampling's threshold mode at its last scale).
+          'expected_distance'  -sum_v p_v d(gt, v); with top_k in [1, V] the sum runs over the top_k codes of the order above with their p
+                               renormalised to sum to 1 (var_analysis.py:252-258 l2_dist, negated: higher is better).
+        d is the direct-form L2 distance between codebook vectors, sqrt of one fma chain over the channels in channel order (the neighbour
+        table's arithmetic), not torch.cdist's |a|^2 + |b|^2 - 2ab form.  A parameter given to a mode that does not use it, an
+        unknown score or a parameter out of range raises ValueError.
+        On the HIP path (the conditions of token_log_likelihood) each scale's logits are reduced by varhip_token_score_f32; the distance modes
+        read the (V, V) table of SamplingEngine.code_distance_table (64 MiB at V = 4096, built once per codebook).  Elsewhere the same formulas
+        run in PyTorch on the per-image logits."""
+        if score not in ('log_prob', 'group_smoothed', 'neighbor_max', 'expected_distance'):
+            raise ValueError(f"score must be 'log_prob', 'group_smoothed', 'neighbor_max' or 'expected_distance', not {score!r}")
+        uses = {'log_prob': (), 'group_smoothed': ('group',), 'neighbor_max': ('threshold',), 'expected_distance': ('top_k',)}[score]
+        for name, val in (('group', group), ('threshold', threshold), ('top_k', top_k)):
+            if val is not None and name not in uses:
+                raise ValueError(f'{name} is not a parameter of score {score!r}')
+        if score == 'group_smoothed':
+            group = 50 if group is None else group
+            if isinstance(group, bool) or int(group) != group or group < 1:
+                raise ValueError('group must be an integer >= 1')
+            desc = (score, int(group))
+        elif score == 'neighbor_max':
+            if threshold is None or isinstance(threshold, bool) or not math.isfinite(float(threshold)) or float(threshold) < 0:
+                raise ValueError('neighbor_max needs a finite threshold >= 0')
+            desc = (score, float(threshold))
+        elif score == 'expected_distance':
+            if top_k is not None and (isinstance(top_k, bool) or int(top_k) != top_k or not 1 <= top_k <= self.V):
+                raise ValueError(f'top_k must be None or an integer in [1, {self.V}]')
+            desc = (score, 0 if top_k is None else int(top_k))
+        else:
+            return self.token_log_likelihood(gt_tokens, label, cfg, max_rows)
+        gt, lab, cfg = self._scoring_args(gt_tokens, label, cfg, max_rows)
+        if self._scoring_on_hip(gt):
+            return self.engine().token_scores(gt, lab, cfg, int(max_rows), desc)
+        cb = self.vae_proxy[0].quantize.embedding.weight.detach().float()
+        out = []
+        for i, z in self._teacher_forced_torch(gt, lab, cfg, max_rows):
+            g = gt[i, :z.shape[1]]
+            d = code_distance_rows(cb, g) if score != 'group_smoothed' else None
+            out.append(token_score_torch(z.float(), g, desc, d))
+        return torch.stack(out, 0)
+
+    def _scoring_args(self, gt_tokens, label, cfg, max_rows):
+        """validation of token_log_likelihood / token_scores: -> (gt (N, L) int64, labels (N, K) int64 on the model's device, cfg)"""
         dev = self.lvl_1L.device
         gt = torch.as_tensor(gt_tokens)
         if gt.dim() != 2 or gt.shape[1] != self.L or gt.shape[0] < 1 or gt.dtype in (torch.bool,) or gt.is_floating_point() or gt.is_complex():
@@ -184,17 +290,21 @@ class VAR(nn.Module):
         lo, hi = torch.stack(torch.aminmax(lab)).tolist()
         if lo < 0 or hi > self.num_classes:
             raise ValueError(f'labels must lie in [0, {self.num_classes}]')
-        gt, lab = gt.to(dev, torch.int64), lab.to(dev, torch.int64)
-        if not self.training and self.prog_si < 0 and dev.type == 'cuda' and self.head.weight.dtype == torch.float32 and self.C == 64 * self.num_heads:
-            return self.engine().token_log_likelihood(gt, lab, cfg, int(max_rows))
-        # the reference's formula (eval_prob.py:441-463; var_analysis.py:322-344), one image at a time
+        return gt.to(dev, torch.int64), lab.to(dev, torch.int64), cfg
+
+    def _scoring_on_hip(self, gt: torch.Tensor) -> bool:
+        return not self.training and self.prog_si < 0 and gt.device.type == 'cuda' and self.head.weight.dtype == torch.float32 and self.C == 64 * self.num_heads
+
+    def _teacher_forced_torch(self, gt, lab, cfg, max_rows):
+        """the reference's per-image teacher-forced logits (eval_prob.py:437-440; var_analysis.py:322-344 with cfg > 0): yields
+        (image, (K, ed, V) z), z the guided combination when cfg > 0"""
+        dev = gt.device
         N, K = lab.shape
         ed = self.begin_ends[self.prog_si][1] if self.prog_si >= 0 else self.L
         x_all = self.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in self.begin_ends])
         ratio = torch.tensor([si / self.num_stages_minus_1 if self.num_stages_minus_1 > 0 else 0.0 for si, pn in enumerate(self.patch_nums) for _ in range(pn * pn)],
                              device=dev)[:ed]
         t = cfg * ratio.unsqueeze(0).unsqueeze(-1)
-        out = []
         for i in range(N):
             x_i = x_all[i:i + 1]
             rows = []
@@ -205,9 +315,7 @@ class VAR(nn.Module):
             if cfg > 0:
                 uncond = self._forward_torch(torch.full((1,), self.num_classes, dtype=torch.int64, device=dev), x_i).float()
                 logits = (1 + t) * logits - t * uncond
-            lp = torch.nn.functional.log_softmax(logits, dim=-1)
-            out.append(lp.gather(dim=-1, index=gt[i:i + 1, :ed].expand(K, -1).unsqueeze(-1)).squeeze(-1))
-        return torch.stack(out, 0)
+            yield i, logits
 
     @torch.no_grad()
     def inpainting(self, gt_tokens: torch.Tensor, mask: torch.Tensor, label: Optional[Union[int, torch.LongTensor]] = None,
