@@ -229,6 +229,15 @@ int varhip_conv_gn_blocks(int H, int W, int Cout, int phase);
 int varhip_conv3x3_gn_nhwc_f32(const float* in, const float* w, const float* bias, const float* resid, float* out, double* gn_part,
                                int B, int H, int W, int Cin, int Cout, int up2, varhip_stream_t stream);
 int varhip_gn_stats_part_f32(const double* gn_part, float* stats, int B, int nblk, int HW, int C, int G, float eps, varhip_stream_t stream);
+/* The stride-1 3x3 convolution (padding 1, NHWC, out_mode 0) as fused Winograd F(2x2,3x3): in [B][H][W][Cin], u = G g G^T of the kernel
+ * [16][Cin/16][Cout][16] (xi = 4 i + j of the 4x4 transform, then input-channel tile, output channel, input channel in the tile; made once
+ * per weight, DecoderEngine.refresh), out [B][H][W][Cout] = conv + bias (+ resid).  Mathematically varhip_conv3x3_nhwc_f32 (up2 0); the
+ * rounding differs (measured 0.32-0.34x the direct kernel's max error against float64).  gn_part (may be NULL): as
+ * varhip_conv3x3_gn_nhwc_f32 with the same block count H*W/128, but block 2 t + h is the 8-row half h (0 upper, 1 lower) of the t-th
+ * 16 x 16 patch of the image in row-major patch order.  Needs H % 16 == 0, W % 16 == 0, Cin % 32 == 0, Cout % 32 == 0, 16-byte
+ * aligned pointers; else VARHIP_EINVAL.  Results do not depend on B or on the image's position in the batch. */
+int varhip_conv3x3_wino_nhwc_f32(const float* in, const float* u, const float* bias, const float* resid, float* out, double* gn_part,
+                                 int B, int H, int W, int Cin, int Cout, varhip_stream_t stream);
 int varhip_conv3x3_s2_nhwc_f32(const float* in, const float* w, const float* bias, float* out,
                                int B, int H, int W, int Cin, int Cout, varhip_stream_t stream);
 /* image [B][C][HW] -> [B][HW][Cpad] with zero channels C..Cpad-1 (conv kernels need Cin % 32 == 0; zero channels add exact zeros) */
@@ -418,9 +427,10 @@ int varhip_cast_bf16_to_f32(const void* in, float* out, int64_t n, varhip_stream
  * of the transformer GEMMs and the element-wise-load fallback), 9 conv_small (every other conv tile: nearest-2x gather, Cout not
  * a multiple of 160); the 16-bit mode's kernels in families of their own (one arithmetic type, hence one MFMA peak, per family):
  * 10 gemm16 (k_gemm16p, the persistent 256x256-tile kernel), 11 gemm16_small (every k_gemm16 tile), 12 conv16h (k_conv16h<5,32>),
- * 13 conv16_small (every other fp16 conv kernel), 14 attn16.  Families 0, 1, 10 and 12 each map to exactly one kernel symbol, so their
- * averages can be checked against a rocprofv3 kernel trace.  Returns the number of families. */
-#define VARHIP_NFAM 15
+ * 13 conv16_small (every other fp16 conv kernel), 14 attn16; 15 conv_wino (k_conv3x3_wino, the fused Winograd F(2x2,3x3) conv; its FLOPs
+ * are the executed multiplies, 16 per 2x2 tile, so it is not priced as a direct conv).  Families 0, 1, 10, 12 and 15 each map to exactly
+ * one kernel symbol, so their averages can be checked against a rocprofv3 kernel trace.  Returns the number of families. */
+#define VARHIP_NFAM 16
 int varhip_timing_enable(int on);
 /* restrict the timing to the families whose bit is set (default: all).  Every timed launch costs two event records on the stream —
  * about 2 % of a sampling call when all ~3000 launches are timed; bench.py times only what its roofline object reports. */

@@ -59,6 +59,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define VH_FAM_CONV16H 12
 #define VH_FAM_CONV16_SMALL 13
 #define VH_FAM_ATTN16 14
+// the fused Winograd F(2x2,3x3) convolution (winograd.hip): FLOPs counted as executed (16 multiplies per 2x2 tile), not as a direct conv
+#define VH_FAM_CONV_WINO 15
 
 // ---- timing table (timing.cpp) ------------------------------------------------------------------------------------
 int vh_timing_on(int fam);
@@ -70,6 +72,16 @@ struct VhScope {           // brackets one launch with events when timing is ena
     VhScope(int f, hipStream_t st, double flops, double bytes) : fam(f), s(st), on(vh_timing_on(f) != 0) { if (on) vh_timing_begin(fam, s, flops, bytes); }
     ~VhScope() { if (on) vh_timing_end(fam, s); }
 };
+
+// One LDS-DMA request through a buffer descriptor: 16 bytes per lane from rsrc.base + soff + voff to LDS address `lds` (+ 16 * lane).
+// A request whose voff lies at or beyond rsrc.num_records is out of range for the hardware bounds check and delivers zeros to its
+// LDS slot.  M0 (the LDS destination) is written inside the statement and named in the clobber list.  The waitcnt pass does not
+// see these requests: every barrier that publishes their data spells out its own s_waitcnt vmcnt.
+__device__ __forceinline__ void vh_dma16_buf(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, uint32_t lds) {
+    // (readfirstlane: a value the compiler computed on the vector ALU although it is wave-uniform must still reach an SGPR operand)
+    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
+                 : : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(soff)), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory", "m0");
+}
 
 static inline int vh_launch_status() {
     hipError_t e = hipGetLastError();

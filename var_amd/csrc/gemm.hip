@@ -88,14 +88,8 @@ __device__ __forceinline__ void vh_dma16(const void* base, uint32_t voff, uint32
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(base), "s"(lds) : "memory", "m0");
 }
 
-// The same through a buffer descriptor: 16 bytes per lane from rsrc.base + soff + voff.  A request whose voff lies at or beyond
-// rsrc.num_records is out of range for the hardware bounds check and delivers zeros to its LDS slot — the zero padding of the
-// convolution costs one OR into the offset instead of a 64-bit address select.
-__device__ __forceinline__ void vh_dma16_buf(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, uint32_t lds) {
-    // (readfirstlane: a value the compiler computed on the vector ALU although it is wave-uniform must still reach an SGPR operand)
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 : : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(soff)), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory", "m0");
-}
+// The same through a buffer descriptor: vh_dma16_buf (common.h; winograd.hip uses it too).  A request whose voff lies at or beyond
+// rsrc.num_records delivers zeros — the zero padding of the convolution costs one OR into the offset instead of a 64-bit address select.
 
 // The same with a full 64-bit per-lane source address (the nearest-2x GATHER mode, whose source is not "base + offset").  Every LDS-DMA
 // of this file is one of these three statements: each writes M0 itself and declares it clobbered, and the compiler's own

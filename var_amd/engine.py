@@ -144,6 +144,19 @@ class _VaeOps:
         return w
 
 
+# Winograd F(2x2,3x3) filter transform (Lavin & Gray 2016): U = G g G^T per (output, input) channel pair
+_WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+
+
+def wino_filter(w: torch.Tensor) -> torch.Tensor:
+    """[Cout][3][3][Cin] fp32 kernel -> U = G g G^T in float64, rounded once to fp32 and laid out [16][Cin/16][Cout][16] (xi = 4 i + j
+    of the 4x4 transform, input-channel tile, output channel, input channel in the tile) for varhip_conv3x3_wino_nhwc_f32"""
+    co, _, _, ci = w.shape
+    G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
+    u = torch.einsum('ik,jl,oklc->ijoc', G, G, w.double()).float()                      # [4][4][Cout][Cin]
+    return u.reshape(16, co, ci // 16, 16).permute(0, 2, 1, 3).contiguous()
+
+
 class DecoderEngine(_VaeOps):
     """VQVAE.fhat_to_img on HIP kernels (reference vqvae.py:62-63, basic_vae.py:163-226)."""
 
@@ -153,6 +166,13 @@ class DecoderEngine(_VaeOps):
     # sharing one VQVAE, or a VAR in the 16-bit mode next to direct VQVAE calls, never fight over a mode flag.
     precision = 'f32'
     unfused_tail = False         # tests: run norm_out / conv_out of the decoder as two launches
+    # The ResnetBlock convolutions (stride 1, 3x3) as fused Winograd F(2x2,3x3) (winograd.hip) where wino_ok() holds; False (tests, A/B runs):
+    # every conv on the direct implicit-GEMM kernel.  VARHIP_WINOGRAD=0 sets the default for a whole process.
+    winograd = os.environ.get('VARHIP_WINOGRAD', '1') != '0'
+    WINO_MIN_HW = 16 * 16        # smallest map that takes it (1.63-1.72x faster than the direct kernel at every decoder level)
+    # the precision flops_per_image_executed counts when not given one: that of the last decode_nhwc, or the one the owning SamplingEngine was
+    # last set to (SamplingEngine.set_precision), whichever came later; None: `precision`.  Only an f32 decode runs the Winograd kernel.
+    flops_precision = None
 
     def set_precision(self, precision: str):
         if precision not in PRECISIONS:
@@ -170,6 +190,8 @@ class DecoderEngine(_VaeOps):
             wp = torch.empty(4, cout, 2, 2, cin, dtype=torch.float32, device=w[k].device)
             hip.call('upconv_pack_f32', w[k], wp, cin, cout)
             w[k[:-len('weight')] + 'phase'] = wp
+        for k in [k for k in w if k.endswith(('.conv1.weight', '.conv2.weight'))]:   # ResnetBlock convs: Winograd filter transforms
+            w[k[:-len('weight')] + 'wino'] = wino_filter(w[k])
         self.w = w
         self.w16s = {}                       # {'f16' | 'bf16': 16-bit copies}: made by _ensure16() the first time such a decode runs on these weights
         self.nlev = 1 + max(int(k.split('.')[2]) for k in w if k.startswith('decoder.up.'))
@@ -198,13 +220,21 @@ class DecoderEngine(_VaeOps):
         Cout, Cin = wt.shape[0], wt.shape[3]
         out = torch.empty((B, Cout, Hh, Ww) if out_mode else (B, Hh, Ww, Cout), dtype=torch.float32, device=x.device)
         nblk = hip.conv_gn_blocks(Hh, Ww, Cout) if (stats and out_mode == 0) else 0
-        if nblk:
+        if up2 == 0 and out_mode == 0 and self.winograd and (key + '.wino') in self.w and self.wino_ok(Hh, Ww, Cin, Cout):
+            part = self._part_buffer(B, nblk, Cout, x.device) if nblk else None
+            hip.call('conv3x3_wino_nhwc_f32', x, self.w[key + '.wino'], self.w[key + '.bias'], resid, out, part, B, Hh, Ww, Cin, Cout)
+            if nblk: self._gn_part = (out, part, nblk)
+        elif nblk:
             part = self._part_buffer(B, nblk, Cout, x.device)
             hip.call('conv3x3_gn_nhwc_f32', x, wt, self.w[key + '.bias'], resid, out, part, B, Hh, Ww, Cin, Cout, up2)
             self._gn_part = (out, part, nblk)              # holds `out` so its address cannot be recycled before the next gn()
         else:
             hip.call('conv3x3_nhwc_f32', x, wt, self.w[key + '.bias'], resid, out, B, Hh, Ww, Cin, Cout, up2, out_mode)
         return out
+
+    def wino_ok(self, Hh, Ww, Cin, Cout):
+        """the shape rule of the Winograd path: maps of at least WINO_MIN_HW pixels in whole 16 x 16 patches, channels in multiples of 32"""
+        return Hh * Ww >= self.WINO_MIN_HW and Hh % 16 == 0 and Ww % 16 == 0 and Cin % 32 == 0 and Cout % 32 == 0
 
     def gn_stats(self, x, B, HW):
         return self._stats_from(x, B, HW, 'gn_stats_f32')
@@ -282,14 +312,25 @@ class DecoderEngine(_VaeOps):
                 hw *= 4; f += c3(f'decoder.up.{lev}.upsample.conv', hw)
         return f + c3('decoder.conv_out', hw)
 
-    def flops_per_image_executed(self, P: int) -> float:
-        """FLOPs the kernels execute for one decode: as flops_per_image_reference, with the Upsample2x convolutions in their folded
-        four-phase form (4 taps per output pixel instead of 9)"""
+    def flops_per_image_executed(self, P: int, precision: Optional[str] = None) -> float:
+        """FLOPs the kernels execute for one decode in `precision` (None: `flops_precision`): as flops_per_image_reference, with the Upsample2x
+        convolutions in their folded four-phase form (4 taps per output pixel instead of 9) and, in an f32 decode, the ResnetBlock convolutions
+        that take the Winograd path at 16 multiplies per 2x2 output tile (4 per output pixel instead of 9; the 16-bit decode has no such path)"""
+        prec = precision or self.flops_precision or self.precision
         f = self.flops_per_image_reference(P)
-        hw = P * P
+        hw, side = P * P, P
+        def wino(pre, hw, side):
+            d = 0.0
+            for c in ('.conv1', '.conv2'):
+                co, _, _, ci = self.w[pre + c + '.weight'].shape
+                if prec == 'f32' and self.winograd and self.wino_ok(side, side, ci, co): d += 2.0 * hw * co * 5 * ci
+            return d
+        f -= wino('decoder.mid.block_1', hw, side) + wino('decoder.mid.block_2', hw, side)
         for lev in reversed(range(self.nlev)):
+            for ib in range(3):
+                f -= wino(f'decoder.up.{lev}.block.{ib}', hw, side)
             if lev != 0:
-                hw *= 4
+                hw *= 4; side *= 2
                 co, _, _, ci = self.w[f'decoder.up.{lev}.upsample.conv.weight'].shape
                 f -= 2.0 * hw * co * 5 * ci
         return f
@@ -426,6 +467,7 @@ class DecoderEngine(_VaeOps):
         precision: 'f32' / 'f16' / 'bf16' for THIS call (None: the engine's default, `self.precision`)"""
         self.refresh()
         prec = precision or self.precision
+        self.flops_precision = prec
         if prec != 'f32':
             self._ensure16(prec)
             self._wait_ready()
@@ -733,6 +775,8 @@ class SamplingEngine:
         if precision not in PRECISIONS + ('auto',):
             raise ValueError(f"precision must be one of {PRECISIONS + ('auto',)}")
         self.policy = precision
+        if precision != 'auto':
+            self.dec.flops_precision = precision                    # what the decoder's FLOP count describes from now on (bench.py prices each mode)
         if precision != 'auto' and precision != self.precision:
             self.precision = precision
             self._ws = {k: v for k, v in self._ws.items() if k[2] == precision}          # an explicit switch releases the other modes' buffers (6-11 GB each at d16 / B=64)

@@ -81,7 +81,7 @@ def conv16_gn_fusable(B, H, W, Cin, Cout) -> bool:
 
 
 # ---- timing table --------------------------------------------------------------------------------------------------
-NFAM = 15            # VARHIP_NFAM of include/var_hip.h
+NFAM = 16            # VARHIP_NFAM of include/var_hip.h
 
 
 def timing_enable(on: bool, families=None):
