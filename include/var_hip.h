@@ -299,6 +299,16 @@ int varhip_token_score_f32(const float* logits, const int64_t* gt, int64_t ld_gt
                            int with_uncond, float ca, float cb, int mode, int param, float thr, const float* dist, int64_t ld_dist,
                            float* out, int64_t ld_out_img, int64_t ld_out_cls, varhip_stream_t stream);
 
+/* ---- the pruning step of zero-shot classification (VAR.classify) ---------------------------------------------------------------------
+ * One workgroup per image i.  Every candidate c < cand adds its stage's per-token scores to its float64 running total, one plain addition
+ * per token in ascending token order:  totals[i * cand + c] += (double)tokens[i * ld_img + c * ld_cls + t],  t = t0 .. t1-1  (t1 == t0: the
+ * totals are ranked as given and tokens may be NULL).  Then the candidates are ranked by the rule of VAR.classify: higher total first, NaN
+ * below everything (-inf included), equal totals (+0 / -0, NaN / NaN) by lower index; the min(keep, cand) best indices are written to
+ * kept[i * min(keep, cand) + j] in ascending index order.  keep = 1 gives the argmax of the rule.  cand <= 16384 (the totals are staged in
+ * LDS); a larger cand, keep < 1, t1 < t0 or ld_cls < t1 / ld_img < cand * ld_cls with t1 > t0: VARHIP_EINVAL. */
+int varhip_class_select_f32(const float* tokens, int64_t ld_img, int64_t ld_cls, int images, int cand, int t0, int t1, double* totals,
+                            int keep, int32_t* kept, varhip_stream_t stream);
+
 /* ---- nearest-codebook lookup (encode side; quant.py:150-157) --------------------------------------------
  * idx[n] = argmin_v ( |z_n|^2 + |e_v|^2 - 2 z_n.e_v ), first index on ties; z: [N][Cv], codebook: [V][Cv] */
 int varhip_nearest_code_f32(const float* z, const float* codebook, int64_t* idx_out, int N, int V, int Cv, varhip_stream_t stream);

@@ -8,9 +8,15 @@
                then the fork's formula on the (K, L, V) logits: log_softmax + gather (log_prob), or sort / softmax / gathers of the
                distance table rows (token_score_torch: group_smoothed, neighbor_max, expected_distance)
 
-both in the same process, alternated, the old one on a stream of its own (each route keeps its own workspace).
+both in the same process, alternated, the old one on a stream of its own (each route keeps its own workspace).  With --keep s:m,... the old
+route is replaced by
 
-    python tools/bench_classify.py [--images 16] [--k-large 100] [--cfg 0] [--dtype f32|f16|bf16] [--iters 3]
+    classify   VAR.classify(gt_tokens, classes, --score, cfg, keep={s: m, ...})   (per-scale pruning; the new route is its unpruned baseline)
+
+and each K reports both routes' ms per image and peak allocation, the class row-tokens the transformer ran (engine.classify_work) against the
+unpruned N x K x L, and how often classify's pred equals the unpruned rule argmax (informational: the weights are random).
+
+    python tools/bench_classify.py [--images 16] [--k-large 100] [--cfg 0] [--dtype f32|f16|bf16] [--iters 3] [--keep 4:50,7:10]
                                    [--score log_prob|group_smoothed|neighbor_max|expected_distance] [--group 50] [--threshold T] [--top-k k]
 
 Prints one JSON object: encode ms per image; per K: ms per image and images per second of both routes, their peak allocation increase,
@@ -28,7 +34,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from var_amd import detinit, hip      # noqa: E402
-from var_amd.models.var import token_score_torch      # noqa: E402
+from var_amd.models.var import classify_rule, token_score_torch      # noqa: E402
 
 HBM_PEAK = 8.0e12
 
@@ -45,7 +51,9 @@ def main():
     ap.add_argument('--group', type=int, default=50)
     ap.add_argument('--threshold', type=float, default=None, help='neighbor_max; default: the median code distance')
     ap.add_argument('--top-k', type=int, default=None, help='expected_distance; default: all codes')
+    ap.add_argument('--keep', default=None, help='s:m,s:m,...  time VAR.classify with this pruning schedule instead of the old route')
     a = ap.parse_args()
+    keep = None if a.keep is None else {int(k): int(m) for k, m in (item.split(':') for item in a.keep.split(','))}
     torch.cuda.set_device(0)
     dev = torch.device('cuda', 0)
     from models import build_vae_var
@@ -102,6 +110,12 @@ def main():
                 del logits
             return torch.stack(out)
 
+        def classify_route(classes):
+            return var.classify(gt, classes, a.score, cfg=a.cfg, max_rows=a.max_rows, keep=keep, **kw)
+
+        if keep is not None:
+            old_route = classify_route
+
         def timed(fn, classes, stream):
             with torch.cuda.stream(stream):
                 torch.cuda.synchronize()
@@ -114,7 +128,8 @@ def main():
                 torch.cuda.synchronize()
                 return r, e0.elapsed_time(e1), torch.cuda.max_memory_allocated() - base
 
-        res = dict(images=N, cfg=a.cfg, dtype=a.dtype, max_rows=a.max_rows, score=a.score, score_args=kw, encode_ms_per_image=sum(enc) / len(enc) / N)
+        res = dict(images=N, cfg=a.cfg, dtype=a.dtype, max_rows=a.max_rows, score=a.score, score_args=kw, keep=a.keep,
+                   encode_ms_per_image=sum(enc) / len(enc) / N)
         for K in (10, a.k_large):
             classes = [(c * 97) % 1000 for c in range(K)]
             ms = {'new': [], 'old': []}
@@ -129,8 +144,22 @@ def main():
             res[f'K{K}'] = dict(
                 new_ms_per_image=best['new'] / N, new_images_per_s=1e3 * N / best['new'],
                 old_ms_per_image=best['old'] / N, old_images_per_s=1e3 * N / best['old'], speedup=best['old'] / best['new'],
-                new_peak_alloc_mb=peak['new'] / 1e6, old_peak_alloc_mb=peak['old'] / 1e6,
-                max_abs_delta=float((ln - lo).abs().max()), agree_argmax=bool(torch.equal(ln.sum(-1).argmax(-1), lo.sum(-1).argmax(-1))))
+                new_peak_alloc_mb=peak['new'] / 1e6, old_peak_alloc_mb=peak['old'] / 1e6)
+            if keep is None:
+                res[f'K{K}'].update(max_abs_delta=float((ln - lo).abs().max()), agree_argmax=bool(torch.equal(ln.sum(-1).argmax(-1), lo.sum(-1).argmax(-1))))
+            else:                   # 'old' is classify: speedup = unpruned time / classify time
+                work = var.engine().classify_work
+                ref_pred = classify_rule(ln.cpu().numpy(), [e for _, e in var.begin_ends], [])[0]
+                res[f'K{K}'].update(classify_speedup=best['new'] / best['old'], classify_work=work, classify_row_tokens=sum(w for _, _, w in work), unpruned_row_tokens=N * K * var.L,
+                                    row_token_ratio=N * K * var.L / sum(w for _, _, w in work),
+                                    pred_agrees_with_unpruned=float((lo.pred.cpu().numpy() == ref_pred).mean()))
+                # where classify's time goes: every kernel family of one call, from the timing table (events around each launch)
+                hip.timing_reset(); hip.timing_enable(True)
+                classify_route(classes)
+                torch.cuda.synchronize()
+                fam = hip.timing_read()
+                hip.timing_enable(False)
+                res[f'K{K}']['classify_family_ms'] = {k: round(v['ms'], 3) for k, v in fam.items() if v['launches']}
             # the scoring kernel alone, from the timing table (HIP events around each of its launches)
             hip.timing_reset(); hip.timing_enable(True, ['sampler'])
             new_route(classes)

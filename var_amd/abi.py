@@ -77,6 +77,7 @@ SIGNATURES_HIP_ONLY = {
     'code_dist_f32':     [P, I, I, P],                                  # pinned against neighbor_table_f32 (tests/test_token_scores_gpu.py)
     'token_score_f32':   [P, P, L, I, I, I, I, I, F, F, I, I, F, P, L, P, L, L],   # pinned against float64 (tests/test_token_scores_gpu.py)
     'conv3x3_wino_nhwc_f32': [P, P, P, P, P, P, I, I, I, I, I],      # pinned against float64 and the direct conv (tests/test_winograd_gpu.py)
+    'class_select_f32':  [P, L, L, I, I, I, I, P, I, P],             # pinned against a numpy lexsort of the rule (tests/test_classify_gpu.py)
 }
 
 # ... and with bfloat16 storage: one entry point per _f16 entry point, same arguments (include/var_hip.h, "bf16")

@@ -814,10 +814,10 @@ class SamplingEngine:
         self._ws[(B, sid, self.precision)] = ws
         return ws
 
-    def _evict(self, cache: dict, sid: int) -> dict:
-        """make room for a new buffer set: one batch size resident at a time per (stream, precision), and a bounded number of sets (oldest first: a
-        d16 / B=64 set is 6-11 GB; its memory returns to the stream it was allocated on, so work still queued there is safe)"""
-        cache = {k: v for k, v in cache.items() if (k[1], k[2]) != (sid, self.precision)}
+    def _evict(self, cache: dict, sid: int, slot: tuple = ()) -> dict:
+        """make room for a new buffer set: one batch size resident at a time per (stream, precision[, slot]), and a bounded number of sets (oldest
+        first: a d16 / B=64 set is 6-11 GB; its memory returns to the stream it was allocated on, so work still queued there is safe)"""
+        cache = {k: v for k, v in cache.items() if k[1:] != (sid, self.precision) + slot}
         while len(cache) >= self.MAX_WORKSPACES:
             cache.pop(next(iter(cache)))
         return cache
@@ -855,21 +855,23 @@ class SamplingEngine:
             self._built()
         return tabs[n]
 
-    def block(self, blk, ws, bi, x, x2, rows, l, cur):
-        """one AdaLNSelfAttn block (basic_var.py:152-159): seven launches behind one library call; the result is left in x"""
+    def block(self, blk, ws, bi, x, x2, rows, l, cur, Lmax: Optional[int] = None):
+        """one AdaLNSelfAttn block (basic_var.py:152-159): seven launches behind one library call; the result is left in x.  Lmax: the token
+        length of the KV caches in ws (default var.L)"""
         var = self.var
         C = var.C
+        Lmax = var.L if Lmax is None else Lmax
         if self.precision != 'f32':
             b16 = self.w['b16'][self.precision][bi]
             hip.call('adaln_block_' + self.precision, x, x2, ws['xn'], ws['q'], ws['att'], ws['hid'], ws['ada_view'][bi][0], ws['ada_view'][bi][1],
                      b16['qkv_w16'], blk['qkv_b'], blk['smul'], blk['plain_scale'], int(blk['l2']), b16['proj_w16'], blk['proj_b'],
                      b16['fc1_w16'], blk['fc1_b'], b16['fc2_w16'], blk['fc2_b'], ws['kc'][bi], ws['vc'][bi],
-                     rows, l, C, var.num_heads, blk['fc1_w'].shape[0], cur, var.L, var.norm_eps)
+                     rows, l, C, var.num_heads, blk['fc1_w'].shape[0], cur, Lmax, var.norm_eps)
             return
         hip.call('adaln_block_f32', x, x2, ws['xn'], ws['q'], ws['att'], ws['hid'], ws['ada_view'][bi][0], ws['ada_view'][bi][1],
                  blk['qkv_w'], blk['qkv_b'], blk['smul'], blk['plain_scale'], int(blk['l2']), blk['proj_w'], blk['proj_b'],
                  blk['fc1_w'], blk['fc1_b'], blk['fc2_w'], blk['fc2_b'], ws['kc'][bi], ws['vc'][bi],
-                 rows, l, C, var.num_heads, blk['fc1_w'].shape[0], cur, var.L, var.norm_eps)
+                 rows, l, C, var.num_heads, blk['fc1_w'].shape[0], cur, Lmax, var.norm_eps)
 
     def head(self, x, hn, xn, logits, M, l):
         """get_logits (var.py:118-124): AdaLNBeforeHead (LayerNorm + scale/shift) then the vocabulary projection -> fp32 logits"""
@@ -1075,16 +1077,20 @@ class SamplingEngine:
             out[:, cur:cur + l] = ws['lg'][:R * l].view(R, l, V)
         return out
 
-    def _tf_workspace(self, R: int) -> dict:
-        """buffers of a teacher-forced pass of up to R rows, cached per (rows, HIP stream, precision); a pass of fewer rows uses a prefix"""
+    def _tf_workspace(self, R: int, last: Optional[int] = None) -> dict:
+        """buffers of a teacher-forced pass of up to R rows through scale `last` (default: the last scale): KV caches of L_e = end of that scale
+        tokens, activations of its l_e = pn^2 rows per row; cached per (rows, HIP stream, precision, L_e), one R resident per L_e; a pass of fewer
+        rows uses a prefix"""
         var = self.var
         dev = var.pos_start.device
         C, H, V, L = var.C, var.num_heads, var.V, var.L
-        lmax = max(p * p for p in var.patch_nums)
+        last = len(var.patch_nums) - 1 if last is None else last
+        Le, lmax = var.begin_ends[last][1], var.patch_nums[last] ** 2
         hid = var.blocks[0].ffn.fc1.weight.shape[0]
         sid = int(torch.cuda.current_stream().cuda_stream)
-        ws = self._ws_tf.get((R, sid, self.precision))
+        ws = self._ws_tf.get((R, sid, self.precision, Le))
         if ws is None or ws['dev'] != dev:
+            self._ws_tf = self._evict(self._ws_tf, sid, (Le,))          # (before allocating: the replaced set is freed first)
             e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
             act = DT16.get(self.precision, torch.float32)
             M = R * lmax
@@ -1092,15 +1098,15 @@ class SamplingEngine:
             ws = dict(dev=dev, x=e(2 * M, C), x2=e(M, C), xn=e(M, C, dt=act), q=e(M, C, dt=act), att=e(M, C, dt=act), hid=e(M, hid, dt=act), lg=e(R * lmax, V),
                       lvl_pos=e(L, C), cond=e(2 * R, C), cond_silu=e(2 * R, C), hn=e(R, 2 * C), ada=e(var.depth, R, 6 * C) if var.shared_aln else e(R, var.depth * 6 * C),
                       shared=e(R, 6 * C) if var.shared_aln else None,
-                      kc=[torch.zeros(R, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
-                      vc=[torch.zeros(R, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)])
-            self._ws_tf = self._evict(self._ws_tf, sid)
-            self._ws_tf[(R, sid, self.precision)] = ws
+                      kc=[torch.zeros(R, H, Le, 64, dtype=act, device=dev) for _ in range(var.depth)],
+                      vc=[torch.zeros(R, H, Le, 64, dtype=act, device=dev) for _ in range(var.depth)], Lmax=Le)
+            self._ws_tf[(R, sid, self.precision, Le)] = ws
         return ws
 
-    def _tf_scales(self, ws: dict, lab: torch.Tensor, xin: Optional[torch.Tensor], R: int):
-        """the teacher-forced loop over R rows (labels `lab`, next-scale inputs `xin` (R, L - first_l, Cvae)): yields (si, cur, l) after the
-        head of each scale has left that scale's fp32 logits in ws['lg'][:R * l] (row r, token t at r * l + t)"""
+    def _tf_scales(self, ws: dict, lab: torch.Tensor, xin: Optional[torch.Tensor], R: int, last: Optional[int] = None, head_from: int = 0):
+        """the teacher-forced loop over R rows (labels `lab`, next-scale inputs `xin` (R, >= L_e - first_l, Cvae)) through scale `last` (default:
+        the last; ws must reach it): yields (si, cur, l) after the head of each scale si >= head_from has left that scale's fp32 logits in
+        ws['lg'][:R * l] (row r, token t at r * l + t); scales below head_from only fill the KV caches"""
         var, w = self.var, self.w
         C, Cv, L = var.C, var.Cvae, var.L
         hip.call('lvl_pos_f32', w['lvl_embed'], w['lvl_1L'], w['pos_1LC'], ws['lvl_pos'], L, C)
@@ -1123,16 +1129,17 @@ class SamplingEngine:
         self.gemm(ws['cond_silu'], w['hn_w'], w['hn_b'], ws['hn'], R)
         x, x2 = ws['x'], ws['x2']
         cur = 0
-        for si, pn in enumerate(var.patch_nums):
+        for si, pn in enumerate(var.patch_nums[:(len(var.patch_nums) if last is None else last + 1)]):
             l = pn * pn
             M = R * l
             if si > 0:                                           # word_embed(teacher-forcing input) + lvl_pos  (var.py:206-207)
                 seg = xin[:, cur - var.first_l:cur - var.first_l + l].contiguous()
                 hip.call('word_embed_f32', seg, w['word_w'], w['word_b'], ws['lvl_pos'][cur:], x, R, l, C, Cv)
             for bi, blk in enumerate(w['blocks']):
-                self.block(blk, ws, bi, x, x2, R, l, cur)
-            self.head(x, ws['hn'], ws['xn'], ws['lg'], M, l)
-            yield si, cur, l
+                self.block(blk, ws, bi, x, x2, R, l, cur, ws['Lmax'])
+            if si >= head_from:
+                self.head(x, ws['hn'], ws['xn'], ws['lg'], M, l)
+                yield si, cur, l
             cur += l
 
     # -- teacher-forced class scoring (VAR.token_log_likelihood, VAR.token_scores) --------------------------------------------------
@@ -1153,39 +1160,56 @@ class SamplingEngine:
         return self._score_passes(gt_tokens, labels, cfg, max_rows, score)
 
     def _score_passes(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, score: tuple) -> torch.Tensor:
-        """the pass loop of token_log_likelihood / token_scores; `score` picks the kernel that reduces each scale's logits"""
+        """the pass loop of token_log_likelihood / token_scores: one stage through the last scale over every candidate"""
+        sc = self._score_setup(gt_tokens, labels, cfg, score)
+        N, K = labels.shape
+        out = torch.empty(N, K, self.var.L, dtype=torch.float32, device=sc['gt'].device)
+        self._score_stage(sc, sc['lab'], len(self.var.patch_nums) - 1, -1, max_rows, out)
+        return out
+
+    def _score_setup(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, score: tuple) -> dict:
+        """what every stage of a scoring call shares: tokens, labels, teacher-forcing inputs, guidance factors, the kernel's mode"""
         var = self.var
         self.resolve_precision()
         self.refresh()
         self._wait_ready()
         dev = var.pos_start.device
-        N, K = labels.shape
-        L, V, S = var.L, var.V, len(var.patch_nums)
-        mode = _SCORE_MODES[score[0]]
-        param, thr, dist = 0, 0.0, None
+        S = len(var.patch_nums)
+        sc = dict(mode=_SCORE_MODES[score[0]], param=0, thr=0.0, dist=None, u=1 if cfg > 0 else 0)
         if score[0] == 'group_smoothed':
-            param = int(score[1])
+            sc['param'] = int(score[1])
         elif score[0] == 'neighbor_max':
-            thr = float(score[1])
+            sc['thr'] = float(score[1])
         elif score[0] == 'expected_distance':
-            param = int(score[1])
+            sc['param'] = int(score[1])
         if score[0] in ('neighbor_max', 'expected_distance'):
-            dist = self.code_distance_table()
+            sc['dist'] = self.code_distance_table()
             self._wait_ready()
-        u = 1 if cfg > 0 else 0
+        sc['gt'] = gt = gt_tokens.to(dev, torch.int64).contiguous()
+        sc['lab'] = labels.to(dev, torch.int64).contiguous()
+        # teacher-forcing input of every image (eval_prob.py:437), one encode-side call for all of them
+        sc['xin'] = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in var.begin_ends]).to(dev, torch.float32)
+        # guidance factors per scale, rounded where var_analysis.py:333-344 rounds them (a float32 ratio tensor times the Python cfg)
+        sc['t32'] = [np.float32(np.float32(cfg) * np.float32(si / (S - 1) if S > 1 else 0.0)) for si in range(S)]
+        return sc
+
+    def _score_stage(self, sc: dict, lab_all: torch.Tensor, last: int, done: int, max_rows: int, out: torch.Tensor):
+        """one stage: the rows of labels lab_all (N, K) through scale `last`, packed into passes of at most max_rows rows:
+        images_in_pass x (classes_in_pass + [cfg > 0]), the unconditional row of every image of a pass (label num_classes) after its class rows.
+        Scales <= `done` only rebuild the KV caches; each later scale's logits are reduced by the scoring kernel into out (N, K, >= L_e)."""
+        var = self.var
+        dev = lab_all.device
+        N, K = lab_all.shape
+        L, V = var.L, var.V
+        Lo = out.shape[2]
+        u, mode, t32, gt = sc['u'], sc['mode'], sc['t32'], sc['gt']
         if K + u <= max_rows:
             ipp, kpp = max(1, max_rows // (K + u)), K            # whole images per pass
         else:
             ipp, kpp = 1, max_rows - u                           # one image per pass, its classes in chunks (each pass with its own uncond row)
         passes = [(i0, min(ipp, N - i0), k0, min(kpp, K - k0)) for i0 in range(0, N, ipp) for k0 in range(0, K, kpp)]
-        ws = self._tf_workspace(max(ni * (nk + u) for _, ni, _, nk in passes))   # sized once: a shorter pass uses a prefix
-        gt = gt_tokens.to(dev, torch.int64).contiguous()
-        lab_all = labels.to(dev, torch.int64).contiguous()
-        # teacher-forcing input of every image (eval_prob.py:437), one encode-side call for all of them
-        xin_img = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in var.begin_ends]).to(dev, torch.float32)
-        out = torch.empty(N, K, L, dtype=torch.float32, device=dev)
-        # guidance factors per scale, rounded where var_analysis.py:333-344 rounds them (a float32 ratio tensor times the Python cfg)
-        t32 = [np.float32(np.float32(cfg) * np.float32(si / (S - 1) if S > 1 else 0.0)) for si in range(S)]
+        ws = self._tf_workspace(max(ni * (nk + u) for _, ni, _, nk in passes), last)   # sized once: a shorter pass uses a prefix
+        xin_img = sc['xin'][:, :var.begin_ends[last][1] - var.first_l]
         for i0, ni, k0, nk in passes:
             R = ni * (nk + u)
             rows_img = torch.arange(i0, i0 + ni, device=dev)
@@ -1195,15 +1219,60 @@ class SamplingEngine:
                 lab = torch.cat((lab, torch.full((ni,), var.num_classes, dtype=torch.int64, device=dev)))
                 src = torch.cat((src, rows_img))
             xin = xin_img.index_select(0, src).contiguous()     # each image's input broadcast to its rows
-            for si, cur, l in self._tf_scales(ws, lab.contiguous(), xin, R):
+            for si, cur, l in self._tf_scales(ws, lab.contiguous(), xin, R, last, done + 1):
                 t = t32[si]
                 if mode == 0:
                     hip.call('token_loglik_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
-                             out[i0:, k0:, cur:], K * L, L)
+                             out[i0:, k0:, cur:], K * Lo, Lo)
                 else:
                     hip.call('token_score_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
-                             mode, param, thr, dist, V, out[i0:, k0:, cur:], K * L, L)
-        return out
+                             mode, sc['param'], sc['thr'], sc['dist'], V, out[i0:, k0:, cur:], K * Lo, Lo)
+
+    # -- zero-shot classification with per-scale pruning (VAR.classify) -------------------------------------------------------------
+    CLASSIFY_MAX_CAND = 16384          # varhip_class_select_f32 stages a stage's totals in LDS
+
+    @torch.no_grad()
+    def classify(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, score: tuple, schedule: list):
+        """VAR.classify on the HIP path -> (pred (N,) int64, total (N, K) float64, depth (N, K) int64, tokens (N, K, L) fp32).
+        schedule: [(scale, m), ...] ascending, each m below the survivor count before it (validated by the caller).  One stage per boundary and a
+        final stage through the last scale.  A stage rebuilds its rows' KV caches from scale 0 (the caches of the previous stage are not kept
+        or compacted), scores only the scales no earlier stage scored into a compact (N, m_j, L_e) buffer, which is scattered into `tokens`;
+        varhip_class_select_f32 then adds those tokens to the survivors' float64 totals and keeps each image's best m (keep 1 after the final
+        stage: pred).  Survivor positions stay on the device: the pass counts follow from the schedule alone, nothing waits for the host.
+        A stage ending at scale e packs max_rows * min(L // L_e, l_max // l_e) rows per pass, so no buffer outgrows a full pass's.
+        self.classify_work: [(e_j, m_j, N * m_j * L_e_j), ...] the class row-tokens the transformer ran per stage (unconditional rows excluded)."""
+        var = self.var
+        N, K = labels.shape
+        if K > self.CLASSIFY_MAX_CAND:
+            raise ValueError(f'classify takes at most {self.CLASSIFY_MAX_CAND} candidates per image on the HIP path, got {K}')
+        sc = self._score_setup(gt_tokens, labels, cfg, score)
+        dev = sc['gt'].device
+        L, S = var.L, len(var.patch_nums)
+        lmax = max(p * p for p in var.patch_nums)
+        ends = [e for _, e in var.begin_ends]
+        img = torch.arange(N, device=dev).view(N, 1)
+        tokens = torch.full((N, K, L), float('nan'), dtype=torch.float32, device=dev)
+        total = torch.empty(N, K, dtype=torch.float64, device=dev)
+        depth = torch.empty(N, K, dtype=torch.int64, device=dev)
+        pos = torch.arange(K, device=dev).expand(N, K).contiguous()         # the stage's candidates, ascending positions per image
+        tot = torch.full((N, K), -0.0, dtype=torch.float64, device=dev)      # their running totals (-0.0 + x == x for every x)
+        work, done, m = [], -1, K
+        for last, keep in list(schedule) + [(S - 1, 1)]:
+            Le, t0 = ends[last], ends[done] if done >= 0 else 0
+            rows = max_rows * min(L // Le, lmax // var.patch_nums[last] ** 2)
+            buf = torch.empty(N, m, Le, dtype=torch.float32, device=dev)
+            self._score_stage(sc, sc['lab'].gather(1, pos), last, done, rows, buf)
+            tokens[img, pos, t0:Le] = buf[:, :, t0:]
+            nk = min(keep, m)
+            kept = torch.empty(N, nk, dtype=torch.int32, device=dev)
+            hip.call('class_select_f32', buf, m * Le, Le, N, m, t0, Le, tot, keep, kept)
+            total[img, pos] = tot
+            depth[img, pos] = last
+            work.append((last, m, N * m * Le))
+            kept = kept.long()
+            pos, tot, done, m = pos.gather(1, kept), tot.gather(1, kept), last, nk
+        self.classify_work = work
+        return pos[:, 0], total, depth, tokens
 
     def code_distance_table(self) -> torch.Tensor:
         """(V, V) fp32 L2 distances between codebook vectors in the direct form of neighbor_table (one fma chain over the channels, then

@@ -6,8 +6,9 @@ implementation of that loop in this file: on a machine without the HIP library o
 `forward` (teacher forcing, autograd) is plain PyTorch for trainer.py / likelihood scripts."""
 import math
 from functools import partial
-from typing import Optional, Tuple, Union
+from typing import NamedTuple, Optional, Tuple, Union
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -55,6 +56,41 @@ def token_score_torch(z: torch.Tensor, gt: torch.Tensor, desc: tuple, d: Optiona
     rank = torch.empty_like(order).scatter_(-1, order, torch.arange(V, device=z.device).expand(K, l, V))
     grp = rank.gather(-1, g) // G
     return torch.log((sums / size).gather(-1, grp) + 1e-10).squeeze(-1)
+
+
+class ClassifyResult(NamedTuple):
+    """VAR.classify's result: pred (N,) int64 positions into the label row, total (N, K) float64, depth (N, K) int64, tokens (N, K, L) fp32"""
+    pred: torch.Tensor
+    total: torch.Tensor
+    depth: torch.Tensor
+    tokens: torch.Tensor
+
+
+def rule_order(totals: np.ndarray) -> np.ndarray:
+    """indices of a 1-D float64 array in VAR.classify's order: higher total first, NaN below everything, equal totals by lower index"""
+    nan = np.isnan(totals)
+    return np.lexsort((np.arange(totals.shape[0]), np.where(nan, 0.0, -totals), nan))
+
+
+def classify_rule(tokens: np.ndarray, ends, schedule) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """VAR.classify applied to full per-token scores (N, K, L) fp32: ends[s] the token end of scale s, schedule [(s, m), ...] ascending.
+    -> (pred, total, depth, tokens with the entries past each candidate's depth set to NaN)"""
+    N, K, L = tokens.shape
+    S = len(ends)
+    cum = np.add.accumulate(tokens.astype(np.float64), axis=-1)          # sequential, in token order
+    depth = np.full((N, K), S - 1, dtype=np.int64)
+    pred = np.empty(N, dtype=np.int64)
+    for n in range(N):
+        alive = np.arange(K)
+        for s, m in schedule:
+            order = rule_order(cum[n, alive, ends[s] - 1])
+            depth[n, alive[order[m:]]] = s
+            alive = np.sort(alive[order[:m]])
+        pred[n] = alive[rule_order(cum[n, alive, L - 1])[0]]
+    end = np.asarray(ends)[depth]
+    total = np.take_along_axis(cum, (end - 1)[..., None], -1)[..., 0]
+    out = np.where(np.arange(L) < end[..., None], tokens, np.float32(np.nan)).astype(np.float32)
+    return pred, total, depth, out
 
 
 class SharedAdaLin(nn.Linear):
@@ -235,6 +271,22 @@ class VAR(nn.Module):
         On the HIP path (the conditions of token_log_likelihood) each scale's logits are reduced by varhip_token_score_f32; the distance modes
         read the (V, V) table of SamplingEngine.code_distance_table (64 MiB at V = 4096, built once per codebook).  Elsewhere the same formulas
         run in PyTorch on the per-image logits."""
+        desc = self._score_desc(score, group, threshold, top_k)
+        if score == 'log_prob':
+            return self.token_log_likelihood(gt_tokens, label, cfg, max_rows)
+        gt, lab, cfg = self._scoring_args(gt_tokens, label, cfg, max_rows)
+        if self._scoring_on_hip(gt):
+            return self.engine().token_scores(gt, lab, cfg, int(max_rows), desc)
+        cb = self.vae_proxy[0].quantize.embedding.weight.detach().float()
+        out = []
+        for i, z in self._teacher_forced_torch(gt, lab, cfg, max_rows):
+            g = gt[i, :z.shape[1]]
+            d = code_distance_rows(cb, g) if score != 'group_smoothed' else None
+            out.append(token_score_torch(z.float(), g, desc, d))
+        return torch.stack(out, 0)
+
+    def _score_desc(self, score, group, threshold, top_k) -> tuple:
+        """validation of token_scores' score and its parameter -> the engine's score descriptor (mode, parameter)"""
         if score not in ('log_prob', 'group_smoothed', 'neighbor_max', 'expected_distance'):
             raise ValueError(f"score must be 'log_prob', 'group_smoothed', 'neighbor_max' or 'expected_distance', not {score!r}")
         uses = {'log_prob': (), 'group_smoothed': ('group',), 'neighbor_max': ('threshold',), 'expected_distance': ('top_k',)}[score]
@@ -255,17 +307,54 @@ class VAR(nn.Module):
                 raise ValueError(f'top_k must be None or an integer in [1, {self.V}]')
             desc = (score, 0 if top_k is None else int(top_k))
         else:
-            return self.token_log_likelihood(gt_tokens, label, cfg, max_rows)
+            desc = (score,)
+        return desc
+
+    @torch.no_grad()
+    def classify(self, gt_tokens, label, score: str = 'log_prob', cfg: float = 0.0, max_rows: int = 64, *, keep=None,
+                 group: Optional[int] = None, threshold: Optional[float] = None, top_k: Optional[int] = None) -> ClassifyResult:
+        """Zero-shot classification with per-scale class pruning -> ClassifyResult(pred, total, depth, tokens).
+
+        gt_tokens, label, score, cfg, max_rows, group, threshold and top_k mean exactly what they mean in token_scores.  keep: None / {} (no
+        pruning) or {scale: m}, 0 <= scale < S-1, integer m >= 1: after that scale each image keeps its m best surviving candidates (an m at or
+        above the survivor count drops nothing).  The block-causal mask makes a candidate's scores through scale s final once computed, so
+        pruned candidates are simply not scored further.
+        Rule (a total order, used at every boundary and for pred): the float64 running total, highest first; NaN below everything (-inf
+        included); ties by lower position in the image's label row (duplicate labels are distinct candidates).  The running total of a candidate
+        scored through scale e is the float64 sum of its fp32 token scores 0 .. end(e)-1, added one by one in ascending token order
+        (np.add.accumulate reproduces it bit for bit).
+          tokens (N, K, L) fp32: the scored entries equal token_scores(...) bit for bit, in the same precision; every other entry is NaN
+          depth  (N, K) int64: the last scale each candidate was scored through;  total (N, K) float64: its running total there
+          pred   (N,) int64: the position of the best full-depth candidate under the rule (the class is label[n, pred[n]]); with keep=None the
+                 rule's argmax of the full totals, lp.sum(-1).argmax(-1) with the ties and NaNs settled
+        On the HIP path (the conditions of token_log_likelihood) the pruned candidates' later scales are never run: SamplingEngine.classify,
+        at most 16384 candidates per image (more raise ValueError).  Elsewhere token_scores runs in full and the same rule is applied to its
+        result: identical semantics, without the saving."""
+        desc = self._score_desc(score, group, threshold, top_k)
         gt, lab, cfg = self._scoring_args(gt_tokens, label, cfg, max_rows)
+        S = len(self.patch_nums)
+        if keep is None:
+            keep = {}
+        if not isinstance(keep, dict):
+            raise ValueError('keep must be None or a dict {scale_index: m}')
+        sched = []
+        for si, m in keep.items():
+            if isinstance(si, bool) or not isinstance(si, (int, np.integer)) or not 0 <= si < S - 1:
+                raise ValueError(f'keep: a boundary must be an integer scale index in [0, {S - 2}], got {si!r}')
+            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 1:
+                raise ValueError(f'keep: the number of candidates kept must be an integer >= 1, got {m!r}')
+            sched.append((int(si), int(m)))
+        schedule, alive = [], lab.shape[1]
+        for si, m in sorted(sched):
+            if m < alive:                        # a boundary that drops nothing is no boundary
+                schedule.append((si, m))
+                alive = m
         if self._scoring_on_hip(gt):
-            return self.engine().token_scores(gt, lab, cfg, int(max_rows), desc)
-        cb = self.vae_proxy[0].quantize.embedding.weight.detach().float()
-        out = []
-        for i, z in self._teacher_forced_torch(gt, lab, cfg, max_rows):
-            g = gt[i, :z.shape[1]]
-            d = code_distance_rows(cb, g) if score != 'group_smoothed' else None
-            out.append(token_score_torch(z.float(), g, desc, d))
-        return torch.stack(out, 0)
+            return ClassifyResult(*self.engine().classify(gt, lab, cfg, int(max_rows), desc, schedule))
+        kw = {k: v for k, v in (('group', group), ('threshold', threshold), ('top_k', top_k)) if v is not None}
+        full = self.token_scores(gt, lab, score, cfg, max_rows, **kw)
+        res = classify_rule(full.cpu().numpy(), [e for _, e in self.begin_ends], schedule)
+        return ClassifyResult(*(torch.from_numpy(r).to(full.device) for r in res))
 
     def _scoring_args(self, gt_tokens, label, cfg, max_rows):
         """validation of token_log_likelihood / token_scores: -> (gt (N, L) int64, labels (N, K) int64 on the model's device, cfg)"""
