@@ -240,6 +240,14 @@ int varhip_conv3x3_wino_nhwc_f32(const float* in, const float* u, const float* b
                                  int B, int H, int W, int Cin, int Cout, varhip_stream_t stream);
 int varhip_conv3x3_s2_nhwc_f32(const float* in, const float* w, const float* bias, float* out,
                                int B, int H, int W, int Cin, int Cout, varhip_stream_t stream);
+/* The 16-bit Downsample2x of the encoder (basic_vae.py:31-37: F.pad(0, 1, 0, 1) + 3x3 conv of stride 2): the index rule of
+ * varhip_conv3x3_s2_nhwc_f32 on 16-bit operands (in [B][2H][2W][Cin], w [Cout][3][3][Cin]), fp32 accumulation on the 16-bit MFMA, + bias
+ * (fp32), rounded once to the storage type: out [B][H][W][Cout].  Needs Cin % 32 == 0, Cout % 16 == 0, 16-byte aligned in / w, 8-byte
+ * aligned out; else VARHIP_EINVAL.  "f16" / "bf16": the two storage types (elem16.h). */
+int varhip_conv3x3_s2_nhwc_f16(const void* in, const void* w, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
+                               varhip_stream_t stream);
+int varhip_conv3x3_s2_nhwc_bf16(const void* in, const void* w, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
+                                varhip_stream_t stream);
 /* image [B][C][HW] -> [B][HW][Cpad] with zero channels C..Cpad-1 (conv kernels need Cin % 32 == 0; zero channels add exact zeros) */
 int varhip_nchw_to_nhwc_pad_f32(const float* in, float* out, int B, int C, int HW, int Cpad, varhip_stream_t stream);
 /* pooled[b][t][:] = mean of f[b] over the adaptive window of output cell t   (F.interpolate(mode='area'), quant.py:150,183) */
@@ -308,6 +316,23 @@ int varhip_token_score_f32(const float* logits, const int64_t* gt, int64_t ld_gt
  * LDS); a larger cand, keep < 1, t1 < t0 or ld_cls < t1 / ld_img < cand * ld_cls with t1 > t0: VARHIP_EINVAL. */
 int varhip_class_select_f32(const float* tokens, int64_t ld_img, int64_t ld_cls, int images, int cand, int t0, int t1, double* totals,
                             int keep, int32_t* kept, varhip_stream_t stream);
+
+/* ---- generative zero-shot classification (VAR.classify_generative; reference eval_prob.py:466-516) ------------------------------------------
+ * Greedy CFG token selection: what var.py:172-175 + helpers.py:6-19 (fork's `gen` mode calls var.inpainting(top_k=1, top_p=0), var.py:236-364)
+ * reduce to without the Exp(1) draw.  Row r = b * l + j of B * l: z = (1+t)*cond - t*uncond, rounded as cfg_sample_f32 rounds it (cond =
+ * logits row r, uncond = row B*l + r), idx_out[r] = the lowest index of max(z) (+0 == -0); a row holding a NaN selects its lowest NaN index
+ * (torch.argmax).  keep != NULL fuses torch.where(mask, gt_tokens, sampled) (var.py:326-328, fork): keep[b * ld_keep + j] != 0 writes
+ * gt[b * ld_keep + j] and reads no logits.  Equal to cfg_sample_f32(top_k=1, top_p=0) (+ token_select_i64) on every row without an exact tie
+ * at its maximum.  Bad sizes, keep without gt or ld_keep < l: VARHIP_EINVAL. */
+int varhip_cfg_argmax_f32(const float* logits, const uint8_t* keep, const int64_t* gt, int64_t ld_keep, int64_t* idx_out,
+                          int B, int l, int V, double t_cfg, varhip_stream_t stream);
+
+/* Feature distance of the `gen` mode (eval_prob.py:509-513, `-torch.abs(feat_input - feat_inpaint).mean(dim=-1)`): for each row r < rows,
+ * score[r] = -(float)(sum_d |f_in[img[r] * D + d] - f_rec[r * D + d]| / D), the |.| in fp32 and the sum in float64 in one fixed order (thread t
+ * of 256 adds d = t, t+256, ... ascending; the 256 partials by a pairwise tree), so a row's score does not depend on the rows beside it.
+ * D < 1 or rows < 0: VARHIP_EINVAL. */
+int varhip_feature_l1_f32(const float* f_in, const float* f_rec, const int64_t* img, int64_t rows, int64_t D, float* score,
+                          varhip_stream_t stream);
 
 /* ---- nearest-codebook lookup (encode side; quant.py:150-157) --------------------------------------------
  * idx[n] = argmin_v ( |z_n|^2 + |e_v|^2 - 2 z_n.e_v ), first index on ties; z: [N][Cv], codebook: [V][Cv] */

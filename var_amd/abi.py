@@ -78,6 +78,10 @@ SIGNATURES_HIP_ONLY = {
     'token_score_f32':   [P, P, L, I, I, I, I, I, F, F, I, I, F, P, L, P, L, L],   # pinned against float64 (tests/test_token_scores_gpu.py)
     'conv3x3_wino_nhwc_f32': [P, P, P, P, P, P, I, I, I, I, I],      # pinned against float64 and the direct conv (tests/test_winograd_gpu.py)
     'class_select_f32':  [P, L, L, I, I, I, I, P, I, P],             # pinned against a numpy lexsort of the rule (tests/test_classify_gpu.py)
+    'cfg_argmax_f32':    [P, P, P, L, P, I, I, I, D],                # pinned against cfg_sample_f32(top_k=1) (tests/test_generative_gpu.py)
+    'conv3x3_s2_nhwc_f16': [P, P, P, P, I, I, I, I, I],            # pinned against a CPU twin (tests/test_generative_gpu.py)
+    'conv3x3_s2_nhwc_bf16': [P, P, P, P, I, I, I, I, I],
+    'feature_l1_f32':    [P, P, P, L, L, P],                         # pinned against the torch L1 (tests/test_generative_gpu.py)
 }
 
 # ... and with bfloat16 storage: one entry point per _f16 entry point, same arguments (include/var_hip.h, "bf16")

@@ -391,7 +391,14 @@ class DecoderEngine(_VaeOps):
         HW = Hh * Ww
         h = self.gnconv3_16(x, pre + '.norm1', pre + '.conv1', B, Hh, Ww)
         sc = x
-        if (pre + '.nin_shortcut.weight') in self.w16:              # 1x1 conv == fp16 GEMM over the pixels
+        if (pre + '.nin_shortcut.weight') in self.w16 and self.w16[pre + '.nin_shortcut.weight'].shape[1] % 64:
+            # (the encoder's 160 -> 320 shortcut: the 16-bit GEMM contracts 64 at a time) the fp32 GEMM between two casts
+            x32 = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            hip.call(f'cast_{self.sfx}_to_f32', x, x32, x.numel())
+            sc32 = self.lin(x32.view(B * HW, -1), pre + '.nin_shortcut')
+            sc = torch.empty((B, Hh, Ww, sc32.shape[1]), dtype=self.dt16, device=x.device)
+            hip.call('cast_f32_to_' + self.sfx, sc32, sc, sc.numel())
+        elif (pre + '.nin_shortcut.weight') in self.w16:              # 1x1 conv == fp16 GEMM over the pixels
             wt = self.w16[pre + '.nin_shortcut.weight']
             N, K = wt.shape
             sc = torch.empty((B, Hh, Ww, N), dtype=self.dt16, device=x.device)
@@ -529,8 +536,9 @@ class QuantizerEngine:
         return self._taps[(pn, P)]
 
     @torch.no_grad()
-    def quantize(self, f_nhwc: torch.Tensor, to_fhat: bool, patch_nums):
-        """residual quantisation scale by scale (quant.py:147-164): idx lists (B, pn^2) int64, or the cumulative f_hat's (NCHW)"""
+    def quantize(self, f_nhwc: torch.Tensor, to_fhat: bool, patch_nums, last_fhat: bool = False):
+        """residual quantisation scale by scale (quant.py:147-164): idx lists (B, pn^2) int64, or the cumulative f_hat's (NCHW).
+        last_fhat=True (with to_fhat False): (idx lists, the last f_hat (B, Cvae, P, P)) from the one pass"""
         self.refresh()
         B, P, _, Cv = f_nhwc.shape
         dev = f_nhwc.device
@@ -551,6 +559,8 @@ class QuantizerEngine:
             pw, pb, ratio = self.phi[phi_index(si, S, len(self.phi))]
             hip.call('quant_residual_f32', idx, self.codebook, ti, tw, pw, pb, ratio, up, f_hat, f_rest, B, pn, P, Cv)
             out.append(f_hat.permute(0, 3, 1, 2).contiguous() if to_fhat else idx.view(B, pn * pn))
+        if last_fhat and not to_fhat:
+            return out, f_hat.permute(0, 3, 1, 2).contiguous()
         return out
 
     @torch.no_grad()
@@ -614,6 +624,7 @@ class EncoderEngine(DecoderEngine):
             return
         self._retire()
         self.w = self._pack()
+        self.w16s = {}                       # 16-bit copies per flavour, made by _ensure16() when an encode(precision='f16' | 'bf16') first runs
         self.nlev = 1 + max(int(k.split('.')[2]) for k in self.w if k.startswith('encoder.down.'))
         self._sig = sig
         self._built()
@@ -625,10 +636,21 @@ class EncoderEngine(DecoderEngine):
         hip.call('conv3x3_s2_nhwc_f32', x, wt, self.w[key + '.bias'], out, B, Hh, Ww, Cin, Cout)
         return out
 
+    last_precision = None        # the precision the last encode() ran in ('f32' | 'f16' | 'bf16')
+    conv_in16 = True             # the 16-bit encoder's conv_in on the 16-bit conv (padded image rounded to 16 bits); False (A/B runs): fp32 conv + cast
+
     @torch.no_grad()
-    def encode(self, img: torch.Tensor) -> torch.Tensor:
-        """img (B,3,H,W) fp32 in [-1,1] -> f (B, H/16, W/16, Cvae) channels-last == quant_conv(encoder(img))"""
+    def encode(self, img: torch.Tensor, precision: Optional[str] = None) -> torch.Tensor:
+        """img (B,3,H,W) fp32 in [-1,1] -> f (B, H/16, W/16, Cvae) fp32 channels-last == quant_conv(encoder(img)).
+        precision: None or 'f32' — the fp32 encoder; 'f16' / 'bf16' — the 16-bit encoder (_encode16) for THIS call"""
+        if precision not in (None,) + PRECISIONS:
+            raise ValueError(f"precision must be None or one of {PRECISIONS}")
         self.refresh()
+        self.last_precision = precision or 'f32'
+        if precision in DT16:
+            self._ensure16(precision)
+            self._wait_ready()
+            return self._encode16(img)
         self._wait_ready()
         B, Ci, Hh, Ww = img.shape
         cin_pad = self.w['encoder.conv_in.weight'].shape[3]
@@ -648,6 +670,50 @@ class EncoderEngine(DecoderEngine):
         h = self.resblock(h, 'encoder.mid.block_2', B, Hh, Ww)
         h = self.conv3(self.gn(h, 'encoder.norm_out', B, Hh * Ww, True), 'encoder.conv_out', B, Hh, Ww)
         return self.conv3(h, 'quant_conv', B, Hh, Ww)
+
+    def _to16(self, x32):
+        y = torch.empty(x32.shape, dtype=self.dt16, device=x32.device)
+        hip.call('cast_f32_to_' + self.sfx, x32, y, y.numel())
+        return y
+
+    def _to32(self, x16):
+        y = torch.empty(x16.shape, dtype=torch.float32, device=x16.device)
+        hip.call(f'cast_{self.sfx}_to_f32', x16, y, y.numel())
+        return y
+
+    def _encode16(self, img: torch.Tensor) -> torch.Tensor:
+        """the encoder on 16-bit activations and conv weights with fp32 accumulation (conv16.hip, rowops16.hip, the 16-bit AttnBlock of the
+        decoder, conv16s2.hip for Downsample2x): the image is rounded to 16 bits once, after its channels are zero-padded to conv_in's 32
+        (conv_in16 False: conv_in in fp32, its output cast).  quant_conv runs in fp32 on the cast conv_out map, so f (what the quantizer and
+        the feature distance read) is fp32 as in the fp32 encoder."""
+        B, Ci, Hh, Ww = img.shape
+        cin_pad = self.w['encoder.conv_in.weight'].shape[3]
+        x = torch.empty((B, Hh, Ww, cin_pad), dtype=torch.float32, device=img.device)
+        hip.call('nchw_to_nhwc_pad_f32', img.contiguous(), x, B, Ci, Hh * Ww, cin_pad)
+        self._gn_part = None
+        if self.conv_in16:
+            h = self.conv3_16(self._to16(x), 'encoder.conv_in', B, Hh, Ww, stats=True)
+        else:
+            h = self._to16(self.conv3(x, 'encoder.conv_in', B, Hh, Ww))
+        for lev in range(self.nlev):
+            for ib in range(2):
+                h = self.resblock16(h, f'encoder.down.{lev}.block.{ib}', B, Hh, Ww)
+                if f'encoder.down.{lev}.attn.{ib}.norm.weight' in self.w:
+                    h = self.attnblock16(h, f'encoder.down.{lev}.attn.{ib}', B, Hh, Ww)
+            if lev != self.nlev - 1:
+                Hh, Ww = Hh // 2, Ww // 2
+                key = f'encoder.down.{lev}.downsample.conv'
+                wt = self.w16[key + '.weight']
+                out = torch.empty((B, Hh, Ww, wt.shape[0]), dtype=self.dt16, device=h.device)
+                self._gn_part = None
+                hip.call('conv3x3_s2_nhwc_' + self.sfx, h, wt, self.w[key + '.bias'], out, B, Hh, Ww, wt.shape[3], wt.shape[0])
+                h = out
+        h = self.resblock16(h, 'encoder.mid.block_1', B, Hh, Ww)
+        h = self.attnblock16(h, 'encoder.mid.attn_1', B, Hh, Ww)
+        h = self.resblock16(h, 'encoder.mid.block_2', B, Hh, Ww)
+        h = self.gnconv3_16(h, 'encoder.norm_out', 'encoder.conv_out', B, Hh, Ww)
+        self._gn_part = None
+        return self.conv3(self._to32(h), 'quant_conv', B, Hh, Ww)
 
 
 
@@ -895,7 +961,8 @@ class SamplingEngine:
     def sample(self, B: int, label_B: torch.Tensor, rng: Optional[torch.Generator], cfg: float, top_k: int, top_p: float,
                noises=None, force_idx: Optional[torch.Tensor] = None, trace: bool = False,
                decode: bool = True, gt_tokens: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
-               more_smooth: bool = False, gumbel_noises=None, smooth: Optional[dict] = None) -> torch.Tensor:
+               more_smooth: bool = False, gumbel_noises=None, smooth: Optional[dict] = None, greedy: bool = False,
+               tokens_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """label_B: int64 [B] on the device.  noises: optional per-scale Exp(1) tensors [B*l, V] — a list, or a callable
         (si, l) -> tensor (tests inject the CPU generator's stream; var_amd.multi hands each rank its rows); by default they
         are drawn with `exponential_(generator=rng)` exactly as torch.multinomial (helpers.py:19) would.
@@ -904,6 +971,9 @@ class SamplingEngine:
         smooth = dict(gt=[B, L] tokens, n=int, thr=float|None): VAR.smooth_sampling (var.py:367-572, fork) — no sampler, no Exp(1)
         draw: every position takes the most likely of the nearest codebook neighbours of its ground-truth token; the two
         accumulated log-likelihoods are left in self.last_smooth.
+        greedy=True: no sampler and no Exp(1) draw (rng, noises, top_k and top_p are not read): every sampled position takes the lowest index
+        of the CFG logits' maximum (varhip_cfg_argmax_f32, the keep mask fused in) — cfg_sample_f32 with top_k=1 on every row without an
+        exact tie at its maximum.  tokens_out: optional int64 [B, L] on the device, receives every scale's tokens (kept and chosen).
         force_idx/trace are test hooks (teacher forcing; keep per-scale logits/tokens/f_hat)."""
         var = self.var
         self.resolve_precision()
@@ -917,6 +987,10 @@ class SamplingEngine:
             raise ValueError('label_B must be an int64 tensor of B labels')
         self._check_labels(label_B)
         label_B = label_B.to(dev).contiguous()
+        if greedy and (more_smooth or smooth is not None):
+            raise ValueError('greedy selection replaces the sampler: it does not combine with more_smooth or smooth sampling')
+        if tokens_out is not None and (tokens_out.dtype != torch.int64 or tuple(tokens_out.shape) != (B, var.L) or not tokens_out.is_contiguous()):
+            raise ValueError(f'tokens_out must be a contiguous int64 ({B}, {var.L}) tensor')
         tr = dict(logits=[], idx=[], f_hat=[], pooled=[]) if trace else None
         gt = keep_u8 = skip = masked = None
         draws = 0
@@ -1009,6 +1083,12 @@ class SamplingEngine:
                     # var.py:537: new_tensor(max_vals) has the tokens' dtype, so every value is truncated to an integer before the sum
                     sm_ll = sm_ll + sm_val[:B * l].to(torch.int64).sum()
                     sm_dl = sm_dl + sm_dlp[:B * l].sum()
+                elif greedy:
+                    # CFG + argmax, the keep mask fused in (what top_k=1 + multinomial select on rows without a tie)
+                    if gt is not None:
+                        hip.call('cfg_argmax_f32', ws['logits'], keep_u8[:, cur - l:], gt[:, cur - l:], var.L, idx, B, l, V, float(t))
+                    else:
+                        hip.call('cfg_argmax_f32', ws['logits'], None, None, 0, idx, B, l, V, float(t))
                 else:
                     # CFG + top-k/top-p + multinomial (var.py:172-175)
                     if noises is not None:        # a list is indexed by draw count: skipped (fully kept) scales draw nothing
@@ -1017,11 +1097,13 @@ class SamplingEngine:
                     else:
                         noise = torch.empty(B * l, V, dtype=torch.float32, device=dev).exponential_(1, generator=rng)
                     hip.call('cfg_sample_f32', ws['logits'], noise, idx, masked, B, l, V, float(t), int(top_k), float(top_p))
-                if gt is not None:                                        # torch.where(mask, gt_tokens, sampled) (var.py:326-328)
+                if gt is not None and not greedy:                         # torch.where(mask, gt_tokens, sampled) (var.py:326-328)
                     hip.call('token_select_i64', keep_u8[:, cur - l:cur].contiguous(), gt[:, cur - l:cur].contiguous(), idx, idx, B * l)
                 if trace: tr['idx'].append(idx.view(B, l).clone())
             if force_idx is not None:
                 idx = force_idx[:, cur - l:cur].to(dev, torch.int64).contiguous().view(-1)
+            if tokens_out is not None:
+                tokens_out[:, cur - l:cur].copy_(idx.view(B, l))
             # quantizer step (var.py:177-183)
             ti, tw = w['taps'].get(pn, (None, None))
             pw, pb, ratio = w['phi'][phi_index(si, S, len(w['phi']))]
@@ -1273,6 +1355,89 @@ class SamplingEngine:
             pos, tot, done, m = pos.gather(1, kept), tot.gather(1, kept), last, nk
         self.classify_work = work
         return pos[:, 0], total, depth, tokens
+
+    @torch.no_grad()
+    def classify_generative(self, img: torch.Tensor, labels: torch.Tensor, last_kept: int, feature, cfg: float, max_rows: int,
+                            match_input_range: bool):
+        """VAR.classify_generative on the HIP path (eval_prob.py:466-516, `--mode gen`): -> (score (N, K) fp32, tokens (N, K, L) int64).
+        The image side runs once per image: encode -> quantize -> tokens, and the image's feature.  The N * K (image, class) rows then run in
+        passes of at most max_rows rows, packed across images in row-major (image, position) order; per pass:
+          sample(greedy=True, the image's tokens kept through scale last_kept, decode=False) -> decode_nhwc -> the feature -> feature_l1_f32.
+        Every stage is row-independent, so the results do not depend on the packing.  self.generative_ms: per-stage milliseconds of the last
+        call when self.profile_generative is set (a synchronising event pair around each stage)."""
+        var = self.var
+        vae = var.vae_proxy[0]
+        prec = self.resolve_precision()
+        enc, qe = vae._encoder_engine(), var.vae_quant_proxy[0].hip_engine()
+        eprec = prec if prec != 'f32' else None
+        pns = tuple(var.patch_nums)
+        N, K = labels.shape
+        dev = var.lvl_1L.device
+        prof = getattr(self, 'profile_generative', False)
+        ms = dict(image=0.0, ar=0.0, decode=0.0, encode=0.0, quantize=0.0, distance=0.0)
+
+        def stage(name, fn):
+            if not prof:
+                return fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); out = fn(); e1.record(); e1.synchronize()
+            ms[name] += e0.elapsed_time(e1)
+            return out
+
+        def feat_of(x):                            # (rows, D) fp32 view of the feature of images x, and its token ids when wanted
+            if callable(feature):
+                f = feature(x)
+                return f.reshape(f.shape[0], -1).float().contiguous(), None
+            f = stage('encode', lambda: enc.encode(x, precision=eprec))
+            if feature == 'vae_fhat':
+                f = stage('quantize', lambda: qe.quantize(f, True, pns)[-1])
+            return f.reshape(f.shape[0], -1), f
+
+        def image_side(i0, i1):
+            img_d = img[i0:i1].to(dev, torch.float32).contiguous()
+            f_img = enc.encode(img_d, precision=eprec)
+            idx, fh = qe.quantize(f_img, False, pns, last_fhat=True)              # tokens (vae.img_to_idxBl) and img_to_fhat(...)[-1]
+            if callable(feature):
+                fin = feature(img_d)
+                fin = fin.reshape(i1 - i0, -1).float().contiguous()
+            elif feature == 'vae_fhat':
+                fin = fh.reshape(i1 - i0, -1)
+            else:
+                fin = f_img.reshape(i1 - i0, -1)
+            return torch.cat(idx, dim=1), fin
+
+        # the image side in chunks of at most max_rows images: its activations are bounded like a pass's
+        parts = [stage('image', lambda i0=i0: image_side(i0, min(i0 + max_rows, N))) for i0 in range(0, N, max_rows)]
+        gt = torch.cat([p[0] for p in parts]) if len(parts) > 1 else parts[0][0]
+        fin = torch.cat([p[1] for p in parts]) if len(parts) > 1 else parts[0][1]
+        del parts
+        lab = labels.to(dev, torch.int64).reshape(-1)
+        keep_n = var.begin_ends[last_kept][1]                                     # cumsum(pn^2)[c]: the kept prefix
+        score = torch.empty(N * K, dtype=torch.float32, device=dev)
+        tokens = torch.empty(N * K, var.L, dtype=torch.int64, device=dev)
+        row_img = torch.arange(N, device=dev).repeat_interleave(K)
+        # every pass runs the AR loop on RP rows, so all passes share one workspace; a shorter last pass is padded with copies of its last row
+        # (rows are independent: the copies change nothing and are dropped)
+        RP = min(max_rows, N * K)
+        keep = torch.zeros(RP, var.L, dtype=torch.bool, device=dev)
+        keep[:, :keep_n] = True
+        tok_pass = torch.empty(RP, var.L, dtype=torch.int64, device=dev)
+        for q0 in range(0, N * K, max_rows):
+            q1 = min(q0 + max_rows, N * K)
+            R = q1 - q0
+            ri = row_img[q0:q1]
+            rows = torch.arange(q0, q0 + RP, device=dev).clamp_(max=q1 - 1)
+            stage('ar', lambda: self.sample(RP, lab[rows], None, cfg, 1, 0.0, decode=False, gt_tokens=gt[row_img[rows]], keep_mask=keep,
+                                            greedy=True, tokens_out=tok_pass))
+            tokens[q0:q1] = tok_pass[:R]
+            f_hat = self.workspace(RP)['f_hat'][:R]
+            rec = stage('decode', lambda: self.dec.decode_nhwc(f_hat, denorm=not match_input_range, precision=prec))
+            frec, _ = feat_of(rec)
+            if frec.shape[1] != fin.shape[1]:
+                raise ValueError(f'the feature of the reconstructions has {frec.shape[1]} elements per image, that of the input {fin.shape[1]}')
+            stage('distance', lambda: hip.call('feature_l1_f32', fin, frec, ri.contiguous(), R, fin.shape[1], score[q0:q1]))
+        self.generative_ms = ms if prof else None
+        return score.view(N, K), tokens.view(N, K, var.L)
 
     def code_distance_table(self) -> torch.Tensor:
         """(V, V) fp32 L2 distances between codebook vectors in the direct form of neighbor_table (one fma chain over the channels, then

@@ -66,6 +66,17 @@ class ClassifyResult(NamedTuple):
     tokens: torch.Tensor
 
 
+class GenerativeResult(NamedTuple):
+    """VAR.classify_generative's result: pred (N,) int64 positions into the label row, score (N, K) fp32 -mean|f_in - f_rec|, tokens (N, K, L)
+    int64 the reconstructions' tokens (kept prefix + greedy tokens)"""
+    pred: torch.Tensor
+    score: torch.Tensor
+    tokens: torch.Tensor
+
+
+GENERATIVE_FEATURES = ('vae_post', 'vae_fhat')
+
+
 def rule_order(totals: np.ndarray) -> np.ndarray:
     """indices of a 1-D float64 array in VAR.classify's order: higher total first, NaN below everything, equal totals by lower index"""
     nan = np.isnan(totals)
@@ -355,6 +366,65 @@ class VAR(nn.Module):
         full = self.token_scores(gt, lab, score, cfg, max_rows, **kw)
         res = classify_rule(full.cpu().numpy(), [e for _, e in self.begin_ends], schedule)
         return ClassifyResult(*(torch.from_numpy(r).to(full.device) for r in res))
+
+    def classify_generative(self, img, label, last_kept_scale: int, feature='vae_post', cfg: float = 0.0, max_rows: int = 64, *,
+                            match_input_range: bool = False) -> GenerativeResult:
+        """Generative zero-shot classification, the fork's `eval_prob.py --mode gen` (reference eval_prob.py:466-516), as one batched call
+        -> GenerativeResult(pred, score, tokens).
+
+        For each image and each candidate class: keep the image's tokens of scales 0 .. last_kept_scale, regenerate the later scales greedily
+        under the class (var.inpainting(top_k=1, top_p=0, cfg=cfg)), decode, and score -mean|f_in - f_rec| between the features of the input
+        image and of the reconstruction.  pred is the highest score; NaN ranks below everything, equal scores go to the lower position.
+          img     (N, 3, 16P, 16P) fp32 in [-1, 1] (the fork's dataloader range); its tokens and feature are computed inside the call
+          label   (K,) or (N, K) class ids in [0, num_classes] (num_classes: the unconditional class); duplicates are distinct candidates
+          last_kept_scale  c, 0 <= c <= S-2: equals the fork's --Clayer c for c >= 1.  Divergence: the fork generates nothing for --Clayer 0
+                  (Python falsiness; every class then ties), here c = 0 keeps scale 0 only
+          feature 'vae_post' (quant_conv(encoder(x)), vae.img_to_post), 'vae_fhat' (vae.img_to_fhat(x)[-1]), or a callable f(images) -> (R, ...)
+                  applied to the input images and to the reconstructions (the hook for dinov2 / CLIP / ResNet features users bring)
+          cfg     the inpainting CFG schedule t = cfg * si / (S-1) (the fork's default is 4)
+          max_rows  (image, class) rows per pass, packed across images; results are bitwise invariant to it
+          match_input_range  False (default) reproduces the fork: the reconstruction handed to the feature is inpainting's output in [0, 1]
+                  while the input image is in [-1, 1]; True hands it over in [-1, 1] (fhat_to_img's contract)
+        Greedy rule: the lowest index among tied maxima of the CFG logits, no noise drawn (the fork's top_k=1 + torch.multinomial breaks exact
+        fp32 ties with its Exp(1) draw), so the tokens equal var.inpainting(..., top_k=1, top_p=0) on every row without an exact tie; there
+        is no g_seed.  Precision follows set_hip_precision as classify does ('auto': the caller's autocast); the transformer, decoder and
+        encoder then run in it, and the scores are computed in fp32.  Scores are computed by varhip_feature_l1_f32 in a fixed order.
+        Off the HIP path (a CPU model, training mode) RuntimeError, after the arguments are validated (ValueError)."""
+        S = len(self.patch_nums)
+        P = self.patch_nums[-1]
+        x = img
+        if (not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype != torch.float32 or x.shape[0] < 1 or x.shape[1] != 3
+                or x.shape[2] != 16 * P or x.shape[3] != 16 * P):
+            raise ValueError(f'img must be an (N, 3, {16 * P}, {16 * P}) float32 tensor with N >= 1')
+        N = x.shape[0]
+        lab = torch.as_tensor(label)
+        if lab.dim() == 1:
+            lab = lab.unsqueeze(0).expand(N, -1)
+        if lab.dim() != 2 or lab.shape[0] != N or lab.shape[1] < 1 or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
+            raise ValueError(f'label must be (K,) or (N, K) integer class ids with K >= 1, N = {N}')
+        lo, hi = torch.stack(torch.aminmax(lab)).tolist()
+        if lo < 0 or hi > self.num_classes:
+            raise ValueError(f'labels must lie in [0, {self.num_classes}]')
+        c = last_kept_scale
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c <= S - 2:
+            raise ValueError(f'last_kept_scale must be an integer scale index in [0, {S - 2}], got {c!r}')
+        if not callable(feature) and feature not in GENERATIVE_FEATURES:
+            raise ValueError(f'feature must be one of {GENERATIVE_FEATURES} or a callable, got {feature!r}')
+        cfg = float(cfg)
+        if not math.isfinite(cfg) or cfg < 0:
+            raise ValueError('cfg must be finite and >= 0')
+        if isinstance(max_rows, bool) or int(max_rows) != max_rows or max_rows < 1 + (cfg > 0):
+            raise ValueError(f'max_rows must be an integer >= {1 + (cfg > 0)}')
+        if not isinstance(match_input_range, bool):
+            raise ValueError('match_input_range must be a bool')
+        vae = self.vae_proxy[0]
+        if not (self._scoring_on_hip(self.lvl_1L) and vae.quant_conv.kernel_size == (3, 3)):
+            raise RuntimeError('VAR.classify_generative: this build runs the generative classifier on MI355X HIP kernels only (an eval-mode fp32 '
+                               'model on a CUDA/ROCm device; no CPU fallback by design)')
+        score, tokens = self.engine().classify_generative(x, lab.contiguous(), int(c), feature, cfg, int(max_rows), match_input_range)
+        sc = score.cpu().numpy().astype(np.float64)
+        pred = torch.tensor([int(rule_order(sc[n])[0]) for n in range(N)], dtype=torch.int64, device=score.device)
+        return GenerativeResult(pred, score, tokens)
 
     def _scoring_args(self, gt_tokens, label, cfg, max_rows):
         """validation of token_log_likelihood / token_scores: -> (gt (N, L) int64, labels (N, K) int64 on the model's device, cfg)"""
