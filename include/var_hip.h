@@ -334,6 +334,27 @@ int varhip_cfg_argmax_f32(const float* logits, const uint8_t* keep, const int64_
 int varhip_feature_l1_f32(const float* f_in, const float* f_rec, const int64_t* img, int64_t rows, int64_t D, float* score,
                           varhip_stream_t stream);
 
+/* ---- zero-shot editing (VAR.autoregressive_infer_cfg_with_mask; demo_zero_shot_edit.ipynb cell 2: replace_embedding, the h_BChw replacement) ----
+ * Keep map of every scale in one launch: keep_out[b * L + begin_s + y * pn + x] = F.interpolate(mask[b or 0][None, None], (pn, pn), 'bilinear',
+ * align_corners=False)[y][x] > 0.5, and 1 on every scale with pn * pn <= 3.  mask: [Bm][h][w] fp32 (Bm == 1: one map for every row, else Bm == B),
+ * patch_nums: a HOST array of S int32 (1 <= S <= 32), L = sum pn^2, keep_out: [B][L] uint8.  upsample_bilinear2d's fp32 arithmetic: scale = (float)h / pn,
+ * src = max(fma(scale, d + 0.5f, -0.5f), 0), i0 = (int)src, i1 = i0 + (i0 < h - 1), l1 = src - i0, l0 = 1 - l1, then
+ * v = l0h * (l0w * x00 + l1w * x01) + l1h * (l0w * x10 + l1w * x11), each operation rounded.  Bad sizes: VARHIP_EINVAL. */
+int varhip_edit_keep_u8(const float* mask, int Bm, int h, int w, const int32_t* patch_nums, int S, int B, uint8_t* keep_out, varhip_stream_t stream);
+
+/* varhip_quant_accum_f32 with replace_embedding fused in: position j of row b takes codebook[gt[b * ld_gt + j]] where keep[b * ld_gt + j] != 0,
+ * else codebook[idx[b * pn * pn + j]].  keep / gt point at the scale's first token of a [B][ld_gt] map, ld_gt >= pn * pn.  Bitwise equal to
+ * varhip_token_select_i64 into idx followed by varhip_quant_accum_f32.  Bad sizes, NULL keep or gt: VARHIP_EINVAL. */
+int varhip_quant_accum_edit_f32(const int64_t* idx, const uint8_t* keep, const int64_t* gt, int64_t ld_gt, const float* codebook,
+                                const int32_t* tap_idx, const float* tap_w, const float* phi_w, const float* phi_b, float ratio,
+                                float* up, float* f_hat, int B, int pn, int P, int Cv, varhip_stream_t stream);
+
+/* the more_smooth flavour: kept positions read codebook[gt[b * ld_gt + j]], the others h[b * pn * pn + j] ([B][pn*pn][Cv], the gumbel-softmax
+ * embedding); bitwise equal to overwriting the kept rows of h and calling varhip_quant_accum_h_f32. */
+int varhip_quant_accum_h_edit_f32(const float* h, const uint8_t* keep, const int64_t* gt, int64_t ld_gt, const float* codebook,
+                                  const int32_t* tap_idx, const float* tap_w, const float* phi_w, const float* phi_b, float ratio,
+                                  float* up, float* f_hat, int B, int pn, int P, int Cv, varhip_stream_t stream);
+
 /* ---- nearest-codebook lookup (encode side; quant.py:150-157) --------------------------------------------
  * idx[n] = argmin_v ( |z_n|^2 + |e_v|^2 - 2 z_n.e_v ), first index on ties; z: [N][Cv], codebook: [V][Cv] */
 int varhip_nearest_code_f32(const float* z, const float* codebook, int64_t* idx_out, int N, int V, int Cv, varhip_stream_t stream);

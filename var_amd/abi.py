@@ -82,6 +82,9 @@ SIGNATURES_HIP_ONLY = {
     'conv3x3_s2_nhwc_f16': [P, P, P, P, I, I, I, I, I],            # pinned against a CPU twin (tests/test_generative_gpu.py)
     'conv3x3_s2_nhwc_bf16': [P, P, P, P, I, I, I, I, I],
     'feature_l1_f32':    [P, P, P, L, L, P],                         # pinned against the torch L1 (tests/test_generative_gpu.py)
+    'edit_keep_u8':      [P, I, I, I, P, I, I, P],                   # pinned against F.interpolate > 0.5 and the reference's maps (tests/test_edit_gpu.py)
+    'quant_accum_edit_f32': [P, P, P, L, P, P, P, P, P, F, P, P, I, I, I, I],     # pinned against token_select_i64 + quant_accum_f32 (tests/test_edit_gpu.py)
+    'quant_accum_h_edit_f32': [P, P, P, L, P, P, P, P, P, F, P, P, I, I, I, I],   # pinned against an overwrite of h + quant_accum_h_f32
 }
 
 # ... and with bfloat16 storage: one entry point per _f16 entry point, same arguments (include/var_hip.h, "bf16")

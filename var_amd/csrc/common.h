@@ -83,6 +83,9 @@ __device__ __forceinline__ void vh_dma16_buf(__amdgpu_buffer_rsrc_t rsrc, uint32
                  : : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(soff)), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory", "m0");
 }
 
+// quant.hip: Phi (3x3 residual mix) + f_hat accumulation of one quantizer step on a gathered `up` map (also behind edit.hip's fused steps)
+void vh_quant_phi_accum(const float* up, const float* phi_w, const float* phi_b, float ratio, float* f_hat, int B, int P, int Cv, hipStream_t s);
+
 static inline int vh_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(1000 + (int)e);

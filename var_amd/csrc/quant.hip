@@ -95,6 +95,14 @@ static bool launch_phi_accum(const float* up, const float* phi_w, const float* p
     return true;
 }
 
+// the Phi + f_hat step behind a gather into `up` (edit.hip's fused quantizer steps share it with the entry points below)
+void vh_quant_phi_accum(const float* up, const float* phi_w, const float* phi_b, float ratio, float* f_hat, int B, int P, int Cv, hipStream_t s) {
+    if (!launch_phi_accum(up, phi_w, phi_b, ratio, f_hat, nullptr, B, P, Cv, s)) {
+        const unsigned blocks = (unsigned)(((int64_t)B * P * P * Cv + 255) / 256);
+        hipLaunchKernelGGL(k_phi_accum, dim3(blocks), dim3(256), 0, s, up, phi_w, phi_b, ratio, 1.0f - ratio, f_hat, B, P, Cv);
+    }
+}
+
 extern "C" int varhip_quant_accum_f32(const int64_t* idx, const float* codebook, const int32_t* tap_idx, const float* tap_w,
                                       const float* phi_w, const float* phi_b, float ratio, float* up, float* f_hat,
                                       int B, int pn, int P, int Cv, varhip_stream_t stream) {

@@ -962,7 +962,7 @@ class SamplingEngine:
                noises=None, force_idx: Optional[torch.Tensor] = None, trace: bool = False,
                decode: bool = True, gt_tokens: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
                more_smooth: bool = False, gumbel_noises=None, smooth: Optional[dict] = None, greedy: bool = False,
-               tokens_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               tokens_out: Optional[torch.Tensor] = None, edit: Optional[dict] = None) -> torch.Tensor:
         """label_B: int64 [B] on the device.  noises: optional per-scale Exp(1) tensors [B*l, V] — a list, or a callable
         (si, l) -> tensor (tests inject the CPU generator's stream; var_amd.multi hands each rank its rows); by default they
         are drawn with `exponential_(generator=rng)` exactly as torch.multinomial (helpers.py:19) would.
@@ -974,6 +974,11 @@ class SamplingEngine:
         greedy=True: no sampler and no Exp(1) draw (rng, noises, top_k and top_p are not read): every sampled position takes the lowest index
         of the CFG logits' maximum (varhip_cfg_argmax_f32, the keep mask fused in) — cfg_sample_f32 with top_k=1 on every row without an
         exact tie at its maximum.  tokens_out: optional int64 [B, L] on the device, receives every scale's tokens (kept and chosen).
+        edit = dict(tokens=[B, L] int64, mask=[Bm, h, w] fp32, Bm in {1, B}): VAR.autoregressive_infer_cfg_with_mask (demo_zero_shot_edit.ipynb
+        cell 2) — the mask is resized to every scale on the device (varhip_edit_keep_u8), kept positions take codebook[token] in the quantizer
+        step (varhip_quant_accum[_h]_edit_f32).  Unlike inpainting every scale draws its Exp(1) fill (and with more_smooth its gumbel fill), so
+        the RNG stream is that of a plain call; a fully kept scale draws them and skips the head, the sampler and the gumbel softmax.  The
+        trace's 'idx' holds the final tokens, its 'sampled' the sampler's (None on fully kept scales).
         force_idx/trace are test hooks (teacher forcing; keep per-scale logits/tokens/f_hat)."""
         var = self.var
         self.resolve_precision()
@@ -989,6 +994,8 @@ class SamplingEngine:
         label_B = label_B.to(dev).contiguous()
         if greedy and (more_smooth or smooth is not None):
             raise ValueError('greedy selection replaces the sampler: it does not combine with more_smooth or smooth sampling')
+        if edit is not None and (gt_tokens is not None or keep_mask is not None or smooth is not None or greedy):
+            raise ValueError('edit does not combine with gt_tokens / keep_mask, smooth sampling or greedy selection')
         if tokens_out is not None and (tokens_out.dtype != torch.int64 or tuple(tokens_out.shape) != (B, var.L) or not tokens_out.is_contiguous()):
             raise ValueError(f'tokens_out must be a contiguous int64 ({B}, {var.L}) tensor')
         tr = dict(logits=[], idx=[], f_hat=[], pooled=[]) if trace else None
@@ -1014,6 +1021,23 @@ class SamplingEngine:
                 # var.py:312-341 (fork): on a fully kept scale the reference feeds the gumbel softmax the PREVIOUS scale's logits
                 # (a NameError on the first scale, a shape error afterwards) — there is no behaviour to reproduce
                 raise NotImplementedError('inpainting(more_smooth=True) with a fully kept scale: undefined in the reference (it reads logits it did not compute)')
+
+        ed_gt = ed_keep = None
+        if edit is not None:
+            ed_gt, ed_mask = edit['tokens'], edit['mask']
+            if ed_gt.dtype != torch.int64 or tuple(ed_gt.shape) != (B, var.L):
+                raise ValueError(f'edit tokens must be an int64 ({B}, {var.L}) tensor')
+            if ed_mask.dtype != torch.float32 or ed_mask.dim() != 3 or ed_mask.shape[0] not in (1, B) or min(ed_mask.shape[1:]) < 1:
+                raise ValueError(f'edit mask must be a float32 (1 or {B}, h, w) tensor')
+            ed_gt = ed_gt.to(dev).contiguous()
+            if int(ed_gt.min()) < 0 or int(ed_gt.max()) >= V:
+                raise ValueError(f'edit tokens must lie in [0, {V})')
+            ed_mask = ed_mask.to(dev).contiguous()
+            ed_keep = torch.empty(B, var.L, dtype=torch.uint8, device=dev)
+            pns = torch.tensor(var.patch_nums, dtype=torch.int32)               # a host array: the launcher copies it into the kernel's arguments
+            hip.call('edit_keep_u8', ed_mask, ed_mask.shape[0], ed_mask.shape[1], ed_mask.shape[2], pns, S, B, ed_keep)
+            skip = torch.stack([ed_keep[:, b0:e0].all() for b0, e0 in var.begin_ends]).tolist()      # one host sync for all scales
+            if trace: tr['sampled'] = []
 
         sm_gt = sm_ll = sm_dl = None
         if smooth is not None:
@@ -1064,7 +1088,18 @@ class SamplingEngine:
             for bi, blk in enumerate(w['blocks']):                        # AdaLNSelfAttn.forward, basic_var.py:152-159
                 self.block(blk, ws, bi, x, x2, B2, l, cur)
             cur += l
-            if skip is not None and skip[si]:
+            if skip is not None and skip[si] and ed_gt is not None:
+                # edit, every token of this scale is kept: no head, no sampler, no gumbel softmax, but the scale's fills are drawn as the
+                # notebook's loop draws them (it samples, then replaces), and its tokens go to the plain quantizer step below
+                if noises is not None:
+                    draws += 1
+                else:
+                    torch.empty(B * l, V, dtype=torch.float32, device=dev).exponential_(1, generator=rng)
+                if more_smooth and gumbel_noises is None:
+                    torch.empty(B * l, V, dtype=torch.float32, device=dev).exponential_(generator=rng)
+                idx = ed_gt[:, cur - l:cur].contiguous().view(-1)
+                if trace: tr['logits'].append(None); tr['sampled'].append(None); tr['idx'].append(idx.view(B, l).clone())
+            elif skip is not None and skip[si]:
                 # inpainting, every token of this scale is kept: no head, no sampling, no RNG draw (var.py:312-313, fork)
                 idx = gt[:, cur - l:cur].contiguous().view(-1)
                 if trace: tr['logits'].append(None); tr['idx'].append(idx.view(B, l).clone())
@@ -1099,15 +1134,24 @@ class SamplingEngine:
                     hip.call('cfg_sample_f32', ws['logits'], noise, idx, masked, B, l, V, float(t), int(top_k), float(top_p))
                 if gt is not None and not greedy:                         # torch.where(mask, gt_tokens, sampled) (var.py:326-328)
                     hip.call('token_select_i64', keep_u8[:, cur - l:cur].contiguous(), gt[:, cur - l:cur].contiguous(), idx, idx, B * l)
-                if trace: tr['idx'].append(idx.view(B, l).clone())
+                if trace and ed_gt is not None: tr['sampled'].append(idx.view(B, l).clone())
+                if trace and ed_gt is None: tr['idx'].append(idx.view(B, l).clone())
             if force_idx is not None:
                 idx = force_idx[:, cur - l:cur].to(dev, torch.int64).contiguous().view(-1)
-            if tokens_out is not None:
+            # edit on a scale that is not fully kept: the replacement happens inside the quantizer step; the final tokens are only
+            # materialised for the caller (tokens_out, trace)
+            ed_step = ed_gt is not None and not skip[si]
+            if ed_step and (tokens_out is not None or trace):
+                fin = torch.empty(B, l, dtype=torch.int64, device=dev)
+                hip.call('token_select_i64', ed_keep[:, cur - l:cur].contiguous(), ed_gt[:, cur - l:cur].contiguous(), idx, fin, B * l)
+                if trace: tr['idx'].append(fin.clone())
+                if tokens_out is not None: tokens_out[:, cur - l:cur].copy_(fin)
+            elif tokens_out is not None:
                 tokens_out[:, cur - l:cur].copy_(idx.view(B, l))
             # quantizer step (var.py:177-183)
             ti, tw = w['taps'].get(pn, (None, None))
             pw, pb, ratio = w['phi'][phi_index(si, S, len(w['phi']))]
-            if more_smooth:
+            if more_smooth and not (ed_gt is not None and skip[si]):
                 # h = gumbel_softmax(filtered logits * (1+ratio), tau) @ codebook, a second Exp(1) fill per scale (var.py:178-180)
                 r_ = si / var.num_stages_minus_1 if var.num_stages_minus_1 > 0 else 0.0
                 gum_t = max(0.27 * (1 - r_ * 0.95), 0.005)
@@ -1117,7 +1161,14 @@ class SamplingEngine:
                     gn = torch.empty(B * l, V, dtype=torch.float32, device=dev).exponential_(generator=rng)
                 hip.call('gumbel_softmax_f32', masked, gn, ws['probs'], B * l, V, float(1 + r_), float(gum_t))
                 self.gemm(ws['probs'], w['codebook_T'], None, ws['h'], B * l)
-                hip.call('quant_accum_h_f32', ws['h'], ti, tw, pw, pb, ratio, ws['up'], ws['f_hat'], B, pn, P, Cv)
+                if ed_step:               # h_BChw = codebook[gt] where kept, else the gumbel-softmax embedding (replace_embedding)
+                    hip.call('quant_accum_h_edit_f32', ws['h'], ed_keep[:, cur - l:], ed_gt[:, cur - l:], var.L, w['codebook'], ti, tw, pw, pb, ratio,
+                             ws['up'], ws['f_hat'], B, pn, P, Cv)
+                else:
+                    hip.call('quant_accum_h_f32', ws['h'], ti, tw, pw, pb, ratio, ws['up'], ws['f_hat'], B, pn, P, Cv)
+            elif ed_step:                 # codebook[keep ? gt : sampled]
+                hip.call('quant_accum_edit_f32', idx, ed_keep[:, cur - l:], ed_gt[:, cur - l:], var.L, w['codebook'], ti, tw, pw, pb, ratio,
+                         ws['up'], ws['f_hat'], B, pn, P, Cv)
             else:
                 hip.call('quant_accum_f32', idx, w['codebook'], ti, tw, pw, pb, ratio, ws['up'], ws['f_hat'], B, pn, P, Cv)
             if trace: tr['f_hat'].append(ws['f_hat'].permute(0, 3, 1, 2).clone())

@@ -104,6 +104,16 @@ def classify_rule(tokens: np.ndarray, ends, schedule) -> Tuple[np.ndarray, np.nd
     return pred, total, depth, out
 
 
+def get_edit_mask(patch_nums, y0: float, x0: float, y1: float, x1: float, device, inpainting: bool = True) -> torch.Tensor:
+    """(P, P) fp32 box mask of the editing notebook (demo_zero_shot_edit.ipynb cell 2), P = patch_nums[-1]: rows round(y0*P):round(y1*P) and
+    columns round(x0*P):round(x1*P) (Python round) are 1, the rest 0 — out-painting keeps the box; inpainting=True returns 1 - that (the box
+    is generated, the rest kept).  1 keeps the input token, 0 generates a new one (VAR.autoregressive_infer_cfg_with_mask)."""
+    P = patch_nums[-1]
+    m = torch.zeros(P, P, device=device)
+    m[round(y0 * P):round(y1 * P), round(x0 * P):round(x1 * P)] = 1
+    return 1 - m if inpainting else m
+
+
 class SharedAdaLin(nn.Linear):
     def forward(self, cond_BD):
         return super().forward(cond_BD).view(-1, 1, 6, self.weight.shape[0] // 6)
@@ -196,6 +206,75 @@ class VAR(nn.Module):
         elif isinstance(label_B, int):
             label_B = torch.full((B,), fill_value=self.num_classes if label_B < 0 else label_B, device=dev)
         return self.engine().sample(B, label_B.to(dev).long(), rng, cfg, top_k, top_p, more_smooth=bool(more_smooth))
+
+    @torch.no_grad()
+    def autoregressive_infer_cfg_with_mask(self, B: int, label_B: Optional[Union[int, torch.LongTensor]], g_seed: Optional[int] = None, cfg=1.5,
+                                           top_k=0, top_p=0.0, more_smooth=False, input_img_tokens=None, edit_mask=None) -> torch.Tensor:
+        """Zero-shot editing (in-painting, out-painting, class-conditional editing): the loop of demo_zero_shot_edit.ipynb (cell 2) as a
+        method, on the HIP engine.  Returns (B, 3, H, W) in [0, 1].  Labels, g_seed and RNG consumption are those of autoregressive_infer_cfg:
+        every scale draws its (B*l, V) Exp(1) fill (and with more_smooth its gumbel fill) whatever the mask keeps.
+          input_img_tokens  the S per-scale (B, pn^2) token tensors of vae.img_to_idxBl, or their (B, L) concatenation.  A single row is
+                            used for all B rows (an extension: the notebook's loop needs B rows; one image with B edits is the usual case)
+          edit_mask         (h, w) or (B, h, w) (a leading 1 broadcasts), any real or bool dtype, h, w >= 1: 1 keeps the input token, 0
+                            generates a new one.  Per scale keep = F.interpolate(mask, (pn, pn), 'bilinear', align_corners=False) > 0.5, and
+                            scales with pn * pn <= 3 are kept whole; kept positions take codebook[input token] (with more_smooth too).
+        Both None: exactly autoregressive_infer_cfg.  Only one of them, or a malformed one: ValueError (checked before the device).  A model
+        off the GPU: RuntimeError (no CPU fallback)."""
+        if (input_img_tokens is None) != (edit_mask is None):
+            raise ValueError('input_img_tokens and edit_mask go together: give both (editing) or neither (plain sampling)')
+        if edit_mask is None:
+            return self.autoregressive_infer_cfg(B, label_B, g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p, more_smooth=more_smooth)
+        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+            raise ValueError('B must be an integer >= 1')
+        tokens = self._edit_tokens(input_img_tokens, B)
+        mask = self._edit_mask(edit_mask, B)
+        if isinstance(label_B, torch.Tensor) and (label_B.dtype.is_floating_point or label_B.dtype == torch.bool or label_B.numel() != B):
+            raise ValueError(f'label_B must be None, an int or {B} integer class ids')
+        dev = self.lvl_1L.device
+        if dev.type != 'cuda':
+            raise RuntimeError('VAR.autoregressive_infer_cfg_with_mask: this build runs the editing loop on MI355X HIP kernels only; move the model '
+                               'to a CUDA/ROCm device (there is no CPU fallback by design)')
+        if g_seed is None: rng = None
+        else: self.rng.manual_seed(g_seed); rng = self.rng
+        if label_B is None:
+            label_B = torch.multinomial(self.uniform_prob, num_samples=B, replacement=True, generator=rng).reshape(B)
+        elif isinstance(label_B, int):
+            label_B = torch.full((B,), fill_value=self.num_classes if label_B < 0 else label_B, device=dev)
+        tokens = tokens.to(dev).expand(B, -1).contiguous()
+        return self.engine().sample(B, label_B.to(dev).long().reshape(B), rng, cfg, top_k, top_p, more_smooth=bool(more_smooth),
+                                    edit=dict(tokens=tokens, mask=mask.to(dev)))
+
+    def _edit_tokens(self, toks, B: int) -> torch.Tensor:
+        """input_img_tokens -> (1 or B, L) int64 (still on the caller's device), shape, dtype and range checked"""
+        if isinstance(toks, (list, tuple)):
+            if len(toks) != len(self.patch_nums) or not all(isinstance(t, torch.Tensor) for t in toks):
+                raise ValueError(f'input_img_tokens must be a list of {len(self.patch_nums)} per-scale token tensors (vae.img_to_idxBl)')
+            rows = toks[0].shape[0] if toks[0].dim() == 2 else -1
+            for t, pn in zip(toks, self.patch_nums):
+                if t.dim() != 2 or t.shape[0] != rows or t.shape[1] != pn * pn:
+                    raise ValueError(f'input_img_tokens: scale tensors must be (1 or B, pn^2) with pn in {self.patch_nums}, got {tuple(t.shape)}')
+            if len({t.device for t in toks}) != 1:
+                raise ValueError('input_img_tokens: every scale must be on one device')
+            toks = torch.cat(toks, dim=1)
+        elif not isinstance(toks, torch.Tensor) or toks.dim() != 2 or toks.shape[1] != self.L:
+            raise ValueError(f'input_img_tokens must be the per-scale list of vae.img_to_idxBl or a (1 or B, {self.L}) tensor')
+        if toks.shape[0] not in (1, B):
+            raise ValueError(f'input_img_tokens must have 1 or B = {B} rows, got {toks.shape[0]}')
+        if toks.dtype.is_floating_point or toks.dtype.is_complex or toks.dtype == torch.bool:
+            raise ValueError('input_img_tokens must hold integer token ids')
+        if toks.numel() and (int(toks.min()) < 0 or int(toks.max()) >= self.V):
+            raise ValueError(f'input_img_tokens must lie in [0, {self.V})')
+        return toks.long()
+
+    def _edit_mask(self, mask, B: int) -> torch.Tensor:
+        """edit_mask -> (1 or B, h, w) float32, as replace_embedding's .to(torch.float) converts it"""
+        if not isinstance(mask, torch.Tensor) or mask.dtype.is_complex or mask.dim() not in (2, 3):
+            raise ValueError('edit_mask must be a real or bool (h, w) or (B, h, w) tensor')
+        if mask.dim() == 2:
+            mask = mask.unsqueeze(0)
+        if mask.shape[0] not in (1, B) or mask.shape[1] < 1 or mask.shape[2] < 1:
+            raise ValueError(f'edit_mask must be (h, w) or (B = {B}, h, w) with h, w >= 1, got {tuple(mask.shape)}')
+        return mask.to(torch.float32).contiguous()
 
     # ---- teacher-forced forward (PyTorch; reference var.py:118-124,192-234) ---------------------------------------------
     def get_logits(self, h_or_h_and_residual, cond_BD: Optional[torch.Tensor]):
