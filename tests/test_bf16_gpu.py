@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests import util
-from tests.test_f16_gpu import _models
+from tests.test_f16_gpu import QKV_ONE_ROW, _models, qkv16_one_row_every_tile
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
@@ -25,7 +25,8 @@ def _hip():
 
 @pytest.mark.parametrize('tile', [0, 1, 2, 3])
 @pytest.mark.parametrize('M,N,K,mode', [(128, 1024, 1024, 'none16'), (1152, 4096, 1024, 'gelu16'), (200, 1024, 4096, 'resid32'), (513, 520, 128, 'resid16in'),
-                                        (1000, 3072, 192, 'none32'), (300, 2304, 9216, 'resid32'), (300, 5760, 1920, 'none16'), (4352, 4096, 128, 'gelu16')])
+                                        (1000, 3072, 192, 'none32'), (300, 2304, 9216, 'resid32'), (300, 5760, 1920, 'none16'), (4352, 4096, 128, 'gelu16'),
+                                        (1, 68, 64, 'none16'), (1, 132, 128, 'resid32'), (1, 260, 64, 'gelu16')])      # one row, N the first legal width past a tile
 def test_gemm_bf16_every_tile_against_float64(tile, M, N, K, mode):
     """varhip_gemm_nt_bf16: every epilogue, every tile instantiation forced (256x256 whole tiles on the persistent kernel), ragged M and N,
     the d30 / d36 widths; all tiles identical bit for bit and right against float64 on the same bf16 operands"""
@@ -43,7 +44,7 @@ def test_gemm_bf16_every_tile_against_float64(tile, M, N, K, mode):
     def run(t):
         out = torch.empty(M, N, dtype=BF if out16 else torch.float32, device='cuda')
         hip.lib().so.varhip_gemm16_force_tile(t)
-        try: hip.call('gemm_nt_bf16', A, K, W, K, bias, out, N, int(out16), M, N, K, epi, resid, N, int(mode == 'resid16in'), gm, N, rpg, 1, 0, 0, 0)
+        try: util.guarded_call('gemm_nt_bf16', A, K, W, K, bias, out, N, int(out16), M, N, K, epi, resid, N, int(mode == 'resid16in'), gm, N, rpg, 1, 0, 0, 0)
         finally: hip.lib().so.varhip_gemm16_force_tile(-1)
         return out
     got = run(tile)
@@ -62,7 +63,7 @@ def test_gemm_bf16_every_tile_against_float64(tile, M, N, K, mode):
     assert bool((err <= tol).all()), f'{mode} {M}x{N}x{K} tile {tile}: {int((err > tol).sum())} outside tolerance, max err {float(err.max()):.3e}'
 
 
-@pytest.mark.parametrize('B2,l,H,pos0,l2', [(4, 9, 2, 5, 1), (2, 64, 4, 91, 1), (3, 25, 16, 0, 0), (4, 100, 4, 10, 1), (2, 169, 36, 55, 1)])
+@pytest.mark.parametrize('B2,l,H,pos0,l2', [(4, 9, 2, 5, 1), (2, 64, 4, 91, 1), (3, 25, 16, 0, 0), (4, 100, 4, 10, 1), (2, 169, 36, 55, 1), (1, 1, 1, 0, 1)])
 def test_gemm_qkv_bf16_against_float64(B2, l, H, pos0, l2):
     hip = _hip()
     C, K, Lmax = H * 64, H * 64, max(160, pos0 + l + 8)
@@ -75,7 +76,7 @@ def test_gemm_qkv_bf16_against_float64(B2, l, H, pos0, l2):
     for tile in (-1, 2):
         q = torch.empty(M, C, dtype=BF, device='cuda'); kc = torch.zeros(B2, H, Lmax, 64, dtype=BF, device='cuda'); vc = torch.zeros_like(kc)
         hip.lib().so.varhip_gemm16_force_tile(tile)
-        try: hip.call('gemm_qkv_bf16', A.cuda(), K, W.cuda(), K, bias.cuda(), M, C, K, smul.cuda(), 0.125, l2, q, kc, vc, B2, l, H, pos0, Lmax)
+        try: util.guarded_call('gemm_qkv_bf16', A.cuda(), K, W.cuda(), K, bias.cuda(), M, C, K, smul.cuda(), 0.125, l2, q, kc, vc, B2, l, H, pos0, Lmax)
         finally: hip.lib().so.varhip_gemm16_force_tile(-1)
         res.append((q, kc, vc))
     for a, b in zip(*res): assert torch.equal(a, b)              # one summation order of the head's squares on every tile
@@ -96,23 +97,38 @@ def test_gemm_qkv_bf16_against_float64(B2, l, H, pos0, l2):
     assert float(kc[:, :, :pos0].abs().max() if pos0 else 0) == 0 and float(kc[:, :, pos0 + l:].abs().max()) == 0
 
 
+@pytest.mark.parametrize('B2,l,H,pos0,l2,Lmax', QKV_ONE_ROW)
+def test_gemm_qkv_bf16_one_row_on_every_tile(B2, l, H, pos0, l2, Lmax):
+    """tests/test_f16_gpu.py::qkv16_one_row_every_tile in the bf16 flavour: forced tiles 0 to 3 and the automatic choice, one row"""
+    qkv16_one_row_every_tile('bf16', BF, ULP, B2, l, H, pos0, l2, Lmax)
+
+
 @pytest.mark.parametrize('B2,l,H,curL', [(2, 1, 2, 1), (3, 9, 2, 14), (2, 36, 3, 91), (2, 169, 2, 424), (1, 256, 2, 680), (2, 40, 1, 33),
                                          (2, 1024, 1, 2240), (1, 576, 36, 1112)])
 def test_attn_bf16_against_twin(B2, l, H, curL):
     """bf16 attention vs its CPU twin (fp32 chains, p rounded to bf16 for p.v, bf16 output) on the same bf16 q / K / V; up to config #5's lengths"""
+    _attn_bf16_case(B2, l, H, curL, curL + 7)
+
+
+@pytest.mark.parametrize('B2,l,H,curL', [(1, 1, 1, 33), (3, 2, 2, 65), (2, 5, 3, 129), (2, 40, 2, 257)])
+def test_attn_bf16_cache_ends_with_the_last_key(B2, l, H, curL):
+    """Lmax == curL, one key past a key tile: the last (b, h) slice's last key is the last element of the cache allocation"""
+    _attn_bf16_case(B2, l, H, curL, curL)
+
+
+def _attn_bf16_case(B2, l, H, curL, Lmax):
     hip = _hip()
     util.ensure_oracle_built()
     from oracle.var_oracle import lib, _p
-    Lmax = curL + 7
     g = torch.Generator().manual_seed(l * 1000 + curL)
     q = torch.randn(B2 * l, H * 64, generator=g)
     q = (q.view(B2 * l, H, 64) / q.view(B2 * l, H, 64).norm(dim=-1, keepdim=True) * 6.0).view(B2 * l, H * 64).to(BF)
     k = torch.randn(B2, H, Lmax, 64, generator=g); k = (k / k.norm(dim=-1, keepdim=True)).to(BF)
     v = torch.randn(B2, H, Lmax, 64, generator=g).to(BF)
     out = torch.empty(B2 * l, H * 64, dtype=BF, device='cuda')
-    hip.call('attn_cached_bf16', q.cuda(), k.cuda(), v.cuda(), out, B2, l, H, curL, Lmax)
+    util.guarded_call('attn_cached_bf16', q.cuda(), k.cuda(), v.cuda(), out, B2, l, H, curL, Lmax)
     out2 = torch.empty_like(out)
-    hip.call('attn_cached_bf16', q.cuda(), k.cuda(), v.cuda(), out2, B2, l, H, curL, Lmax)
+    util.guarded_call('attn_cached_bf16', q.cuda(), k.cuda(), v.cuda(), out2, B2, l, H, curL, Lmax)
     assert torch.equal(out, out2)
     want = np.empty((B2 * l, H * 64), np.float32)
     assert lib()['attn_cached_pbf16_f32'](_p(q.float().numpy()), _p(k.float().numpy()), _p(v.float().numpy()), _p(want), B2, l, H, curL, Lmax) == 0
@@ -129,7 +145,8 @@ def test_attn_bf16_against_twin(B2, l, H, curL):
 
 
 @pytest.mark.parametrize('B,H,W,Cin,Cout,res,omode', [(2, 16, 16, 32, 32, 0, 0), (2, 16, 16, 640, 640, 1, 0), (1, 32, 32, 320, 160, 0, 0),
-                                                      (2, 32, 32, 160, 3, 0, 1), (1, 24, 40, 96, 64, 1, 0), (2, 8, 64, 32, 128, 1, 0), (2, 16, 32, 160, 320, 1, 0)])
+                                                      (2, 32, 32, 160, 3, 0, 1), (1, 24, 40, 96, 64, 1, 0), (2, 8, 64, 32, 128, 1, 0), (2, 16, 32, 160, 320, 1, 0),
+                                                      (1, 5, 7, 64, 128, 1, 0)])                                  # one image, pixel count off every tile
 @pytest.mark.parametrize('wm', [2, 4, 8])
 def test_conv_bf16_against_float64(B, H, W, Cin, Cout, res, omode, wm):
     """varhip_conv3x3_nhwc_bf16 on its three kernels (forced) against float64 on the same bf16 data; GroupNorm partials = sums of the rounded outputs"""
@@ -149,7 +166,7 @@ def test_conv_bf16_against_float64(B, H, W, Cin, Cout, res, omode, wm):
     else:
         out = torch.empty(B, H, W, Cout, dtype=BF, device='cuda')
     hip.lib().so.varhip_conv16_force_tile(wm)
-    try: hip.call('conv3x3_nhwc_bf16', x.cuda(), w.cuda(), bias.cuda(), None if resid is None else resid.cuda(), out, part, B, H, W, Cin, Cout, omode)
+    try: util.guarded_call('conv3x3_nhwc_bf16', x.cuda(), w.cuda(), bias.cuda(), None if resid is None else resid.cuda(), out, part, B, H, W, Cin, Cout, omode)
     finally: hip.lib().so.varhip_conv16_force_tile(0)
     got = out.double().cpu() if omode else out.double().cpu().permute(0, 3, 1, 2)
     tol = 1e-5 + (0 if omode else ref.abs() * ULP) + 2e-6 * (9 * Cin) ** 0.5
@@ -160,7 +177,7 @@ def test_conv_bf16_against_float64(B, H, W, Cin, Cout, res, omode, wm):
         assert torch.allclose(part[..., 0].sum(1).cpu(), o.sum(1), rtol=1e-5, atol=1e-3) and torch.allclose(part[..., 1].sum(1).cpu(), (o * o).sum(1), rtol=1e-5, atol=1e-3)
 
 
-@pytest.mark.parametrize('B,H,W,Cin,Cout', [(2, 16, 16, 64, 32), (1, 32, 32, 320, 320), (2, 64, 32, 160, 160)])
+@pytest.mark.parametrize('B,H,W,Cin,Cout', [(2, 16, 16, 64, 32), (1, 32, 32, 320, 320), (2, 64, 32, 160, 160), (1, 6, 10, 32, 32)])
 @pytest.mark.parametrize('wm', [2, 4])
 def test_upconv_phase_bf16_against_float64(B, H, W, Cin, Cout, wm):
     """Upsample2x (basic_vae.py:22-28) in its folded four-phase form on bf16 data against the phase form in float64 with the bf16-rounded phase weights"""
@@ -171,11 +188,11 @@ def test_upconv_phase_bf16_against_float64(B, H, W, Cin, Cout, wm):
     w = torch.randn(Cout, 3, 3, Cin, generator=g) * (1.0 / (9 * Cin) ** 0.5)
     bias = torch.randn(Cout, generator=g) * 0.1
     wp = torch.empty(4, Cout, 2, 2, Cin, dtype=torch.float32, device='cuda')
-    hip.call('upconv_pack_f32', w.cuda(), wp, Cin, Cout)
+    util.guarded_call('upconv_pack_f32', w.cuda(), wp, Cin, Cout)
     wp16 = wp.to(BF)
     out = torch.empty(B, H, W, Cout, dtype=BF, device='cuda')
     hip.lib().so.varhip_conv16_force_tile(wm)
-    try: hip.call('upconv_phase_bf16', x.cuda(), wp16, bias.cuda(), out, None, B, H, W, Cin, Cout)
+    try: util.guarded_call('upconv_phase_bf16', x.cuda(), wp16, bias.cuda(), out, None, B, H, W, Cin, Cout)
     finally: hip.lib().so.varhip_conv16_force_tile(0)
     xd = x.double().permute(0, 3, 1, 2)
     ref = torch.empty(B, Cout, H, W, dtype=torch.float64)
@@ -196,27 +213,27 @@ def test_groupnorm_bf16_against_float64(B, HW, C, silu):
     gamma, beta = torch.randn(C, generator=g) * 0.2 + 1.0, torch.randn(C, generator=g) * 0.2
     stats = torch.empty(B, 32, 2, dtype=torch.float32, device='cuda')
     scratch = torch.empty(hip.gn_scratch_elems(B, HW, C, 32), dtype=torch.float64, device='cuda')
-    hip.call('gn_stats_bf16', x.cuda(), stats, scratch, B, HW, C, 32, 1e-6)
+    util.guarded_call('gn_stats_bf16', x.cuda(), stats, scratch, B, HW, C, 32, 1e-6)
     xd = x.double().view(B, HW, 32, C // 32)
     mean = xd.mean(dim=(1, 3)); var = xd.var(dim=(1, 3), unbiased=False)
     assert torch.allclose(stats[..., 0].double().cpu(), mean, atol=1e-6) and torch.allclose(stats[..., 1].double().cpu(), (var + 1e-6).rsqrt(), rtol=1e-6)
     out = torch.empty(B, HW, C, dtype=BF, device='cuda')
-    hip.call('gn_apply_bf16', x.cuda(), stats, gamma.cuda(), beta.cuda(), out, B, HW, C, 32, silu)
+    util.guarded_call('gn_apply_bf16', x.cuda(), stats, gamma.cuda(), beta.cuda(), out, B, HW, C, 32, silu)
     ref = torch.nn.functional.group_norm(x.double().permute(0, 2, 1), 32, gamma.double(), beta.double(), eps=1e-6).permute(0, 2, 1)
     if silu: ref = torch.nn.functional.silu(ref)
     err = (out.double().cpu() - ref).abs()
     assert bool((err <= ref.abs() * ULP + 1e-3).all()), f'max err {float(err.max()):.3e}'
     y32 = torch.empty(B, HW, C, dtype=torch.float32, device='cuda')
-    hip.call('cast_bf16_to_f32', out, y32, out.numel())
+    util.guarded_call('cast_bf16_to_f32', out, y32, out.numel())
     back = torch.empty_like(out)
-    hip.call('cast_f32_to_bf16', y32, back, out.numel())
+    util.guarded_call('cast_f32_to_bf16', y32, back, out.numel())
     assert torch.equal(y32, out.float()) and torch.equal(back, out)
     z = torch.randn(1000, generator=g).cuda(); z16 = torch.empty(1000, dtype=BF, device='cuda')       # round-to-nearest-even like torch's
-    hip.call('cast_f32_to_bf16', z, z16, 1000)
+    util.guarded_call('cast_f32_to_bf16', z, z16, 1000)
     assert torch.equal(z16, z.to(BF))
     xn = torch.randn(60, 256, generator=g).cuda(); sc = torch.randn(2, 256, generator=g).cuda(); sh = torch.randn(2, 256, generator=g).cuda()
     o = torch.empty(60, 256, dtype=BF, device='cuda')
-    hip.call('ln_modulate_bf16out', xn, sc, 256, sh, 256, o, 60, 256, 30, 1e-6)
+    util.guarded_call('ln_modulate_bf16out', xn, sc, 256, sh, 256, o, 60, 256, 30, 1e-6)
     want = torch.nn.functional.layer_norm(xn.double(), (256,), eps=1e-6) * (sc.double().repeat_interleave(30, 0) + 1) + sh.double().repeat_interleave(30, 0)
     assert bool(((o.double() - want).abs() <= want.abs() * ULP + 1e-5).all())
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import util
 from tests.test_classify_cpu import expect, same
 from tests.test_token_scores_gpu import d16, tokens
 from var_amd import abi, hip
@@ -140,7 +141,7 @@ def test_select_kernel_vs_lexsort(cand):
                 want = want + toks[:, :, t].astype(np.float64)
             dev_tot = torch.from_numpy(tot).cuda()
             kept = torch.full((images, min(keep, cand)), -7, dtype=torch.int32, device='cuda')
-            hip.call('class_select_f32', torch.from_numpy(toks).cuda(), cand * T, T, images, cand, t0, t1, dev_tot, keep, kept)
+            util.guarded_call('class_select_f32', torch.from_numpy(toks).cuda(), cand * T, T, images, cand, t0, t1, dev_tot, keep, kept)
             torch.cuda.synchronize()
             assert same(dev_tot.cpu().numpy(), want), (cand, keep, with_tokens)
             for n in range(images):

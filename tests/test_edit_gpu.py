@@ -27,7 +27,7 @@ def keep_kernel(mask, pns, B):
     from var_amd import hip
     L = sum(p * p for p in pns)
     out = torch.full((B, L), 7, dtype=torch.uint8, device='cuda')
-    hip.call('edit_keep_u8', mask, mask.shape[0], mask.shape[1], mask.shape[2], torch.tensor(pns, dtype=torch.int32), len(pns), B, out)
+    util.guarded_call('edit_keep_u8', mask, mask.shape[0], mask.shape[1], mask.shape[2], torch.tensor(pns, dtype=torch.int32), len(pns), B, out)
     return out
 
 
@@ -129,6 +129,17 @@ def test_keep_kernel_rejects_bad_sizes():
 @pytest.mark.parametrize('pn', [1, 3, 4, 5])
 @pytest.mark.parametrize('smooth', [False, True])
 def test_fused_quantizer_step_equals_select_then_step(pn, smooth):
+    _fused_step_case(pn, smooth, at_end=False)
+
+
+@pytest.mark.parametrize('pn', [1, 3, 4, 5])
+@pytest.mark.parametrize('smooth', [False, True])
+def test_fused_quantizer_step_with_keep_and_gt_ending_their_rows(pn, smooth):
+    """the scale's l tokens are the LAST l columns of the (B, ld) keep / gt rows: the last row's last element ends both allocations"""
+    _fused_step_case(pn, smooth, at_end=True)
+
+
+def _fused_step_case(pn, smooth, at_end):
     from var_amd import hip
     from var_amd.engine import phi_index
     meta = dict(depth=2, ch=32, patch_nums=(1, 2, 3, 4, 5), attn_l2_norm=True, shared_aln=False)
@@ -136,7 +147,8 @@ def test_fused_quantizer_step_equals_select_then_step(pn, smooth):
     eng = var.engine(); eng.refresh(); eng._wait_ready()
     w = eng.w
     B, P, Cv, V, S = 3, 5, var.Cvae, var.V, 5
-    l, ld, off = pn * pn, var.L + 7, 11
+    l, ld = pn * pn, var.L + 7
+    off = ld - l if at_end else 11
     g = torch.Generator(device='cuda').manual_seed(pn)
     idx = torch.randint(0, V, (B * l,), device='cuda', generator=g)
     gt = torch.randint(0, V, (B, ld), device='cuda', generator=g)
@@ -149,15 +161,15 @@ def test_fused_quantizer_step_equals_select_then_step(pn, smooth):
     ks, gs = keep[:, off:off + l].contiguous(), gt[:, off:off + l].contiguous()
     if not smooth:
         sel = torch.empty_like(idx)
-        hip.call('token_select_i64', ks, gs, idx, sel, B * l)
-        hip.call('quant_accum_f32', sel, w['codebook'], ti, tw, pw, pb, ratio, up_a, fa, B, pn, P, Cv)
-        hip.call('quant_accum_edit_f32', idx, keep[:, off:], gt[:, off:], ld, w['codebook'], ti, tw, pw, pb, ratio, up_b, fb, B, pn, P, Cv)
+        util.guarded_call('token_select_i64', ks, gs, idx, sel, B * l)
+        util.guarded_call('quant_accum_f32', sel, w['codebook'], ti, tw, pw, pb, ratio, up_a, fa, B, pn, P, Cv)
+        util.guarded_call('quant_accum_edit_f32', idx, keep[:, off:], gt[:, off:], ld, w['codebook'], ti, tw, pw, pb, ratio, up_b, fb, B, pn, P, Cv)
     else:
         h = torch.randn(B * l, Cv, device='cuda', generator=g)
         h2 = h.clone().view(B, l, Cv)
         h2[ks.bool()] = w['codebook'][gs[ks.bool()]]
-        hip.call('quant_accum_h_f32', h2, ti, tw, pw, pb, ratio, up_a, fa, B, pn, P, Cv)
-        hip.call('quant_accum_h_edit_f32', h, keep[:, off:], gt[:, off:], ld, w['codebook'], ti, tw, pw, pb, ratio, up_b, fb, B, pn, P, Cv)
+        util.guarded_call('quant_accum_h_f32', h2, ti, tw, pw, pb, ratio, up_a, fa, B, pn, P, Cv)
+        util.guarded_call('quant_accum_h_edit_f32', h, keep[:, off:], gt[:, off:], ld, w['codebook'], ti, tw, pw, pb, ratio, up_b, fb, B, pn, P, Cv)
     torch.cuda.synchronize()
     assert torch.equal(up_a, up_b) and torch.equal(fa, fb)
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import util
 from var_amd import hip
 
 pytestmark = pytest.mark.gpu
@@ -128,7 +129,7 @@ def test_against_hand_built_route_d16(feat):
             # callable give the same score bits
             s_k = torch.empty(K, device='cuda')
             lay = (lambda f: f.permute(0, 2, 3, 1)) if feat == 'vae_post' else (lambda f: f)      # the layout the call keeps each feature in
-            hip.call('feature_l1_f32', lay(f_in).contiguous().view(N, -1), lay(f_rec).contiguous().view(K, -1),
+            util.guarded_call('feature_l1_f32', lay(f_in).contiguous().view(N, -1), lay(f_rec).contiguous().view(K, -1),
                      torch.full((K,), n, dtype=torch.int64, device='cuda'), K, f_rec[0].numel(), s_k)
             assert torch.equal(r.score[n], s_k)
             x_ref = -(img[n].reshape(1, -1) - rec_all[n * K:(n + 1) * K].reshape(K, -1)).abs().mean(-1)
@@ -187,7 +188,7 @@ def test_packing_and_order_invariance(golden_dir, feat):
 # ---- 4. varhip_cfg_argmax_f32 ----------------------------------------------------------------------------------------------------------
 def _argmax(logits, B, l, V, t, keep=None, gt=None, ld=0):
     idx = torch.empty(B * l, dtype=torch.int64, device='cuda')
-    hip.call('cfg_argmax_f32', logits, keep, gt, ld, idx, B, l, V, float(t))
+    util.guarded_call('cfg_argmax_f32', logits, keep, gt, ld, idx, B, l, V, float(t))
     return idx
 
 
@@ -201,7 +202,7 @@ def test_cfg_argmax_equals_top1_sampler(t, V):
     assert bool(((z == z.amax(-1, keepdim=True)).sum(-1) == 1).all()), 'test data has a tie'
     noise = torch.empty(B * l, V, device='cuda').exponential_(1, generator=g)
     ref = torch.empty(B * l, dtype=torch.int64, device='cuda')
-    hip.call('cfg_sample_f32', logits, noise, ref, None, B, l, V, float(t), 1, 0.0)
+    util.guarded_call('cfg_sample_f32', logits, noise, ref, None, B, l, V, float(t), 1, 0.0)
     got = _argmax(logits, B, l, V, t)
     assert torch.equal(got, ref)
     assert torch.equal(got, z.argmax(-1))
@@ -229,8 +230,26 @@ def test_cfg_argmax_ties_nan_and_keep_mask():
     fused = _argmax(logits, B, l, V, 0.5, keep_full[:, off:], gt_full[:, off:], L)
     plain = _argmax(logits, B, l, V, 0.5)
     sel = torch.empty_like(plain)
-    hip.call('token_select_i64', keep_full[:, off:off + l].contiguous(), gt_full[:, off:off + l].contiguous(), plain, sel, B * l)
+    util.guarded_call('token_select_i64', keep_full[:, off:off + l].contiguous(), gt_full[:, off:off + l].contiguous(), plain, sel, B * l)
     assert torch.equal(fused, sel)
+
+
+def test_cfg_argmax_keep_mask_at_the_end_of_its_rows():
+    """the keep mask and the tokens read from the LAST l columns of (B, L) rows: the last row's last element ends both allocations;
+    B * l = 21 rows, a vocabulary off every power of two; == argmax + token_select_i64"""
+    B, l, V, L = 3, 7, 1000, 19
+    g = torch.Generator(device='cuda').manual_seed(5)
+    logits = torch.randn(2 * B * l, V, device='cuda', generator=g)
+    keep_full = (torch.rand(B, L, device='cuda', generator=g) < 0.5).to(torch.uint8)
+    gt_full = torch.randint(0, V, (B, L), device='cuda', generator=g)
+    off = L - l
+    fused = _argmax(logits, B, l, V, 0.5, keep_full[:, off:], gt_full[:, off:], L)
+    plain = _argmax(logits, B, l, V, 0.5)
+    z = 1.5 * logits[:B * l] - 0.5 * logits[B * l:]
+    assert torch.equal(plain, z.argmax(-1))
+    sel = torch.empty_like(plain)
+    util.guarded_call('token_select_i64', keep_full[:, off:].contiguous(), gt_full[:, off:].contiguous(), plain, sel, B * l)
+    assert torch.equal(fused, sel) and torch.equal(sel, torch.where(keep_full[:, off:].reshape(-1).bool(), gt_full[:, off:].reshape(-1), plain))
 
 
 def test_feature_l1_kernel():
@@ -240,13 +259,20 @@ def test_feature_l1_kernel():
     fr = torch.randn(R, D, device='cuda', generator=g)
     img = torch.randint(0, N, (R,), device='cuda', generator=g)
     s = torch.empty(R, device='cuda')
-    hip.call('feature_l1_f32', fi, fr, img, R, D, s)
+    util.guarded_call('feature_l1_f32', fi, fr, img, R, D, s)
     ref = -(fi.double()[img] - fr.double()).abs().mean(-1)
     assert torch.allclose(s.double(), ref, rtol=1e-6, atol=0)
     # a row's score does not depend on its neighbours
     s1 = torch.empty(1, device='cuda')
-    hip.call('feature_l1_f32', fi, fr[4:5].contiguous(), img[4:5].contiguous(), 1, D, s1)
+    util.guarded_call('feature_l1_f32', fi, fr[4:5].contiguous(), img[4:5].contiguous(), 1, D, s1)
     assert s1.item() == s[4].item()
+    # 7 rows of an odd length: rows, features and image indices all end their allocations off any block or vector width
+    R2, D2 = 7, 4099
+    fi2 = torch.randn(N, D2, device='cuda', generator=g); fr2 = torch.randn(R2, D2, device='cuda', generator=g)
+    img2 = torch.tensor([2, 0, 1, 2, 2, 0, 2], device='cuda')
+    s2 = torch.empty(R2, device='cuda')
+    util.guarded_call('feature_l1_f32', fi2, fr2, img2, R2, D2, s2)
+    assert torch.allclose(s2.double(), -(fi2.double()[img2] - fr2.double()).abs().mean(-1), rtol=1e-6, atol=0)
 
 
 # ---- 5. / 6. the 16-bit encoder and 16-bit classification ----------------------------------------------------------------------------
@@ -255,7 +281,7 @@ U16 = {'f16': 2.0 ** -11, 'bf16': 2.0 ** -8}
 
 
 @pytest.mark.parametrize('prec', ['f16', 'bf16'])
-@pytest.mark.parametrize('shape', [(2, 16, 16, 160, 160), (3, 5, 7, 64, 48), (1, 8, 8, 32, 16)])
+@pytest.mark.parametrize('shape', [(2, 16, 16, 160, 160), (3, 5, 7, 64, 48), (1, 8, 8, 32, 16), (1, 5, 7, 32, 64)])
 def test_conv3x3_s2_16bit_vs_cpu_twin(prec, shape):
     """varhip_conv3x3_s2_nhwc_{f16,bf16} against its CPU twin: the same 16-bit operands, F.pad(0, 1, 0, 1) + stride-2 conv in float64, + bias.
     Tolerance: fp32 accumulation of K = 9 Cin products, at most K * 2^-24 * sum |a w| (the products are exact in fp32), plus the one rounding
@@ -267,7 +293,7 @@ def test_conv3x3_s2_16bit_vs_cpu_twin(prec, shape):
     w = (torch.randn(Cout, 3, 3, Cin, device='cuda', generator=g) * 0.05).to(dt)
     bias = torch.randn(Cout, device='cuda', generator=g) * 0.1
     out = torch.empty(B, H, W, Cout, dtype=dt, device='cuda')
-    hip.call('conv3x3_s2_nhwc_' + prec, x, w, bias, out, B, H, W, Cin, Cout)
+    util.guarded_call('conv3x3_s2_nhwc_' + prec, x, w, bias, out, B, H, W, Cin, Cout)
     xd = torch.nn.functional.pad(x.double().permute(0, 3, 1, 2).cpu(), (0, 1, 0, 1))
     wd = w.double().permute(0, 3, 1, 2).cpu()
     ref = torch.nn.functional.conv2d(xd, wd, bias.double().cpu(), stride=2).permute(0, 2, 3, 1)

@@ -25,27 +25,29 @@ def _setup():
 
 
 def both(name, args, outs):
-    """Call varref_<name> on numpy copies and varhip_<name> on device copies of `args`.
-    An arg may be (array, element_offset) to pass an interior pointer.  Returns ([hip outs], [ref outs])."""
+    """Call varref_<name> on numpy copies and varhip_<name> on device copies of `args`, every array inside a guard arena on both sides
+    (tests/util.py: band | operand | band; a band that changed fails the call).  An arg may be (array, element_offset) to pass an interior
+    pointer: the operand is then the array from that element on; an array passed more than once is one copy (and one arena) per side.
+    Returns ([hip outs], [ref outs])."""
     L, hip = _setup()
+    copies = {}
     ref_arrays, dev_arrays, ref_args, dev_args = [], [], [], []
     for a in args:
         off = 0
         if isinstance(a, tuple):
             a, off = a
         if isinstance(a, np.ndarray):
-            ra = np.ascontiguousarray(a).copy()
-            da = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+            if id(a) not in copies:
+                copies[id(a)] = (np.ascontiguousarray(a).copy(), torch.from_numpy(np.ascontiguousarray(a)).cuda())
+            ra, da = copies[id(a)]
             ref_arrays.append(ra); dev_arrays.append(da)
-            ref_args.append(ctypes.c_void_p(ra.ctypes.data + off * ra.itemsize))
-            dev_args.append(ctypes.c_void_p(da.data_ptr() + off * da.element_size()))
+            ref_args.append(ra.reshape(-1)[off:]); dev_args.append(da.view(-1)[off:])
         else:
             ref_arrays.append(None); dev_arrays.append(None)
             ref_args.append(a); dev_args.append(a)
-    rc = L[name](*ref_args)
+    rc = util.guarded_invoke(f'varref_{name}', ref_args, L[name])
     assert rc == 0, f'oracle {name} rc={rc}'
-    hip.call(name, *dev_args)
-    torch.cuda.synchronize()
+    util.guarded_call(name, *dev_args)
     return [dev_arrays[i].cpu().numpy() for i in outs], [ref_arrays[i] for i in outs]
 
 
@@ -64,6 +66,26 @@ def test_library_loads_and_reports_version():
     _, hip = _setup()
     assert 'gfx950' in hip.lib().version()
     assert torch.cuda.is_available()
+
+
+def test_guard_bands_see_a_device_store_next_to_the_operand():
+    """the harness on the device (tests/test_guard_cpu.py plants its overruns on the host): silu_f32 called with its output pointer moved
+    four elements forward / back inside y's arena is a legal call on memory the test owns, and writes four elements into the band behind /
+    in front of the operand: reported there; the plain call passes and returns the kernel's result through the copy-back"""
+    _, hip = _setup()
+    n = 1000
+    x = torch.randn(n, device='cuda', generator=torch.Generator(device='cuda').manual_seed(0)); y = torch.zeros(n, device='cuda')
+    for shift, band, lo, hi in ((16, 'back', 4 * n, 4 * n + 15), (-16, 'front', -16, -1)):
+        with pytest.raises(util.GuardError) as e:
+            util.guarded_invoke('varhip_silu_f32 (shifted output)', [x, y, n],
+                                lambda xp, yp, n_: hip.call('silu_f32', xp, ctypes.c_void_p(yp.value + shift), n_), torch.cuda.synchronize)
+        (f,) = e.value.findings
+        assert f['args'] == [1] and f['band'] == band and lo <= f['first'] <= f['last'] <= hi, f
+        assert 'argument 1' in str(e.value) and 'varhip_silu_f32' in str(e.value)
+    util.guarded_call('silu_f32', x, y, n)
+    direct = torch.zeros(n, device='cuda')
+    hip.call('silu_f32', x, direct, n); torch.cuda.synchronize()
+    assert torch.equal(y, direct) and float(y.abs().max()) > 0
 
 
 def test_timing_table_counts_only_the_selected_families():
@@ -108,7 +130,7 @@ def test_timing_table_counts_only_the_selected_families():
     assert t['gemm16_small']['launches'] == 1 and t['gemm16']['launches'] == 1 and t['gemm']['launches'] == 0 and t['gemm_small']['launches'] == 0      # (forced 256x256 on whole tiles: the persistent kernel)
 
 
-@pytest.mark.parametrize('M,N,K', [(128, 128, 128), (4, 384, 128), (36, 512, 128), (300, 320, 640), (1152, 1024, 1024), (2048, 3072, 1024), (64, 4096, 256), (1, 128, 32), (130, 40, 8), (9, 128, 9), (25, 33, 25), (70, 70, 13), (70, 50, 64), (3, 52, 96), (200, 17, 32)])
+@pytest.mark.parametrize('M,N,K', [(128, 128, 128), (4, 384, 128), (36, 512, 128), (300, 320, 640), (1152, 1024, 1024), (2048, 3072, 1024), (64, 4096, 256), (1, 128, 32), (130, 40, 8), (9, 128, 9), (25, 33, 25), (70, 70, 13), (70, 50, 64), (3, 52, 96), (200, 17, 32), (1, 129, 64), (1, 65, 33)])
 @pytest.mark.parametrize('epi', [0, 1, 2])
 def test_gemm_exact(M, N, K, epi):
     rng = np.random.default_rng(M * 7 + N * 3 + K + epi)
@@ -186,7 +208,7 @@ def test_ln_modulate_exact(M, C, rpg, ld):
     xd, ad = torch.from_numpy(x).cuda(), torch.from_numpy(ada).cuda()
     for dt, fl in ((torch.float16, 'f16'), (torch.bfloat16, 'bf16')):
         o16 = torch.empty(M, C, dtype=dt, device='cuda')
-        hip.call(f'ln_modulate_{fl}out', xd, ad[:, so:], ld * C, ad[:, ho:], ld * C, o16, M, C, rpg, 1e-6)
+        util.guarded_call(f'ln_modulate_{fl}out', xd, ad[:, so:], ld * C, ad[:, ho:], ld * C, o16, M, C, rpg, 1e-6)
         want = torch.from_numpy(g).to(dt)
         got = o16.cpu()
         assert torch.equal(got, want), f'ln_modulate_{fl}out {M}x{C}: {int((got != want).sum())} of {got.numel()} differ from the rounded fp32 result'
@@ -207,7 +229,8 @@ def test_qkv_prep_exact(B2, l, H, pos0, Lmax, l2):
 
 
 @pytest.mark.parametrize('B2,l,H,K,pos0,Lmax,l2', [(4, 1, 2, 128, 0, 14, 1), (4, 9, 2, 128, 5, 14, 1), (2, 16, 16, 1024, 14, 55, 1), (4, 4, 3, 192, 1, 14, 0),
-                                                   (6, 100, 5, 320, 30, 130, 1), (128, 4, 16, 1024, 1, 5, 1), (3, 169, 1, 64, 0, 169, 1)])
+                                                   (6, 100, 5, 320, 30, 130, 1), (128, 4, 16, 1024, 1, 5, 1), (3, 169, 1, 64, 0, 169, 1),
+                                                   (1, 1, 3, 192, 4, 5, 1), (2, 1, 1, 64, 0, 1, 0)])       # M = 1 / 2; the new cache row is the cache's last
 def test_gemm_qkv_fused_epilogue_exact(B2, l, H, K, pos0, Lmax, l2):
     """The fused entry point is DEFINED as gemm_nt followed by qkv_prep: same bits, both tile shapes, ragged M, odd H (3C % 128 != 0)."""
     rng = np.random.default_rng(B2 * l + H + K)
@@ -272,7 +295,9 @@ def test_smooth_select_exact(B, l, V, n, cc, thr):
         check(f'smooth_select {nm}', g, w)
 
 
-@pytest.mark.parametrize('B2,l,H,curL,Lmax', [(4, 1, 2, 1, 14), (4, 4, 2, 5, 14), (4, 9, 2, 14, 14), (2, 25, 2, 55, 55), (2, 100, 3, 255, 300), (2, 256, 2, 680, 680), (1, 169, 1, 424, 680)])
+@pytest.mark.parametrize('B2,l,H,curL,Lmax', [(4, 1, 2, 1, 14), (4, 4, 2, 5, 14), (4, 9, 2, 14, 14), (2, 25, 2, 55, 55), (2, 100, 3, 255, 300), (2, 256, 2, 680, 680), (1, 169, 1, 424, 680),
+                                              # Lmax == curL one past a key tile (32 / 128 keys): the last (b, h) slice's last key ends the cache
+                                              (1, 1, 1, 33, 33), (3, 2, 2, 65, 65), (2, 5, 3, 129, 129)])
 def test_attn_cached_exact(B2, l, H, curL, Lmax):
     rng = np.random.default_rng(l * 3 + curL)
     C = 64 * H
@@ -470,7 +495,7 @@ def test_encode_side_kernels_exact():
     """stride-2 conv (Downsample2x), padded NCHW->NHWC, area pool, word embed, residual quantiser step vs their CPU twins"""
     from oracle.var_oracle import bicubic_taps
     rng = np.random.default_rng(123)
-    for (B, H, W, Cin, Cout) in [(2, 8, 8, 32, 64), (1, 40, 24, 160, 160), (2, 5, 5, 64, 32)]:
+    for (B, H, W, Cin, Cout) in [(2, 8, 8, 32, 64), (1, 40, 24, 160, 160), (2, 5, 5, 64, 32), (1, 5, 7, 32, 64)]:
         x = rnd(rng, B, 2 * H, 2 * W, Cin); w = rnd(rng, Cout, 3, 3, Cin, scale=(1.0 / (9 * Cin)) ** 0.5); bias = rnd(rng, Cout, scale=0.1)
         out = np.zeros((B, H, W, Cout), np.float32)
         (g,), (r,) = both('conv3x3_s2_nhwc_f32', [x, w, bias, out, B, H, W, Cin, Cout], [3]); check(f'conv s2 {Cin}->{Cout} {H}x{W}', g, r)
@@ -518,7 +543,10 @@ def test_prologue_and_small_ops_exact():
 
 @pytest.mark.parametrize('B,H,W,Cin,Cout,up2,resid,mode', [(2, 3, 3, 32, 32, 0, 0, 0), (2, 16, 16, 32, 640, 0, 0, 0), (1, 16, 16, 640, 640, 0, 1, 0),
                                                           (2, 32, 32, 128, 64, 1, 0, 0), (1, 64, 64, 320, 320, 1, 0, 0), (2, 24, 24, 160, 160, 0, 1, 0),
-                                                          (2, 48, 48, 32, 3, 0, 0, 1), (1, 40, 40, 160, 3, 0, 0, 1), (3, 5, 7, 64, 128, 0, 1, 0)])
+                                                          (2, 48, 48, 32, 3, 0, 0, 1), (1, 40, 40, 160, 3, 0, 0, 1), (3, 5, 7, 64, 128, 0, 1, 0),
+                                                          # one image whose pixel count is off the 128-row tile: the first tile's window starts in the band in front of x,
+                                                          # the last tile's clamped rows end at the band behind it
+                                                          (1, 5, 7, 64, 128, 0, 1, 0), (1, 10, 14, 32, 32, 1, 0, 0), (1, 9, 15, 32, 3, 0, 0, 1)])
 def test_conv3x3_exact(B, H, W, Cin, Cout, up2, resid, mode):
     rng = np.random.default_rng(H * W + Cin + Cout)
     Hi, Wi = (H // 2, W // 2) if up2 else (H, W)
@@ -552,7 +580,7 @@ def test_conv3x3_random_shapes_exact():
         check(f'conv random #{case} kind{kind} {Cin}->{Cout} {H}x{W} B{B}', g, wv)
 
 
-@pytest.mark.parametrize('B,H,W,Cin,Cout', [(2, 6, 6, 32, 32), (1, 32, 32, 640, 640), (2, 64, 48, 160, 160), (1, 16, 16, 64, 128)])
+@pytest.mark.parametrize('B,H,W,Cin,Cout', [(2, 6, 6, 32, 32), (1, 32, 32, 640, 640), (2, 64, 48, 160, 160), (1, 16, 16, 64, 128), (1, 6, 10, 32, 32)])
 def test_upconv_phase(B, H, W, Cin, Cout):
     """Upsample2x as four 2x2 phase convs: bit-exact vs its CPU twin, and equal to the plain nearest-2x + 3x3 conv up to the
     rounding of the pre-summed weights (tolerance; the decoder is off the token path)"""
@@ -686,13 +714,13 @@ def test_gn_silu_conv_out_f32_fused_equals_two_launches(B, H, W, Cin, Cout, omod
     gamma, beta = (torch.randn(Cin, generator=g) * 0.2 + 1.0).cuda(), (torch.randn(Cin, generator=g) * 0.2).cuda()
     stats = torch.empty(B, 32, 2, dtype=torch.float32, device='cuda')
     scratch = torch.empty(hip.gn_scratch_elems(B, H * W, Cin, 32), dtype=torch.float64, device='cuda')
-    hip.call('gn_stats_f32', x, stats, scratch, B, H * W, Cin, 32, 1e-6)
+    util.guarded_call('gn_stats_f32', x, stats, scratch, B, H * W, Cin, 32, 1e-6)
     fused = torch.full((B, Cout, H, W), float('nan'), dtype=torch.float32, device='cuda')
-    hip.call('gn_silu_conv_out_f32', x, stats, gamma, beta, w, bias, fused, B, H, W, Cin, Cout, 32, omode)
+    util.guarded_call('gn_silu_conv_out_f32', x, stats, gamma, beta, w, bias, fused, B, H, W, Cin, Cout, 32, omode)
     xn = torch.empty_like(x)
-    hip.call('gn_apply_f32', x, stats, gamma, beta, xn, B, H * W, Cin, 32, 1)
+    util.guarded_call('gn_apply_f32', x, stats, gamma, beta, xn, B, H * W, Cin, 32, 1)
     two = torch.empty_like(fused)
-    hip.call('conv3x3_nhwc_f32', xn, w, bias, None, two, B, H, W, Cin, Cout, 0, omode)
+    util.guarded_call('conv3x3_nhwc_f32', xn, w, bias, None, two, B, H, W, Cin, Cout, 0, omode)
     assert torch.equal(fused, two), f'fused tail differs from the two launches in {int((fused != two).sum())} elements, max {float((fused - two).abs().max()):.3e}'
     if B * H * W <= 70000:
         ref = torch.nn.functional.conv2d(xn.double().cpu().permute(0, 3, 1, 2), w.double().cpu().permute(0, 3, 1, 2), bias.double().cpu(), padding=1).clamp(-1, 1)

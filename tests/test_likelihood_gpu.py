@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import util
 from var_amd import abi, hip
 
 pytestmark = pytest.mark.gpu
@@ -62,7 +63,18 @@ def ref_rows(var, vae, gt, classes, cfg):
 @pytest.mark.parametrize('cfg', [0.0, 1.5])
 def test_kernel_vs_float64(V, cfg):
     """random rows (the pass layout of SamplingEngine.token_log_likelihood) written into a slice of a larger (N, K, L) output"""
-    images, classes, l, K, L, k0, tok0 = 3, 4, 7, 6, 20, 1, 9
+    _kernel_vs_float64(V, cfg, (3, 4, 7, 6, 20, 1, 9))
+
+
+@pytest.mark.parametrize('V', [4096, 4099])
+@pytest.mark.parametrize('cfg', [0.0, 1.5])
+def test_kernel_vs_float64_slices_end_their_allocations(V, cfg):
+    """the same with tok0 + l == L and k0 + classes == K: the last image's tokens are the last elements of gt, its last class row ends the output"""
+    _kernel_vs_float64(V, cfg, (3, 4, 7, 6, 16, 2, 9))
+
+
+def _kernel_vs_float64(V, cfg, layout):
+    images, classes, l, K, L, k0, tok0 = layout
     u = 1 if cfg > 0 else 0
     g = torch.Generator(device='cuda').manual_seed(V)
     rows = images * (classes + u) * l
@@ -72,7 +84,7 @@ def test_kernel_vs_float64(V, cfg):
     out = torch.full((images, K, L), 12345.0, device='cuda')
     t = np.float32(np.float32(cfg) * np.float32(0.5))
     ca, cb = np.float32(1) + t, t
-    hip.call('token_loglik_f32', logits, gt[:, tok0:], L, images, classes, l, V, u, float(ca), float(cb), out[:, k0:, tok0:], K * L, L)
+    util.guarded_call('token_loglik_f32', logits, gt[:, tok0:], L, images, classes, l, V, u, float(ca), float(cb), out[:, k0:, tok0:], K * L, L)
     torch.cuda.synchronize()
     cond = logits[:images * classes * l].view(images, classes, l, V)
     if u:

@@ -100,20 +100,20 @@ def test_adaln_block16(fl, B2, l, H, hidden, pos0, Lmax, l2):
                     hid=torch.zeros(M, hidden, dtype=dt, device='cuda'), kc=kc.cuda(), vc=vc.cuda())
     smp = d['sm'] if l2 else None
     A = fresh()
-    hip.call('adaln_block_' + fl, A['x'], A['x2'], A['xn'], A['q'], A['att'], A['hid'], d['ada'], 6 * C, d['wq'], d['bq'], smp, 0.03125, l2,
+    util.guarded_call('adaln_block_' + fl, A['x'], A['x2'], A['xn'], A['q'], A['att'], A['hid'], d['ada'], 6 * C, d['wq'], d['bq'], smp, 0.03125, l2,
              d['wp'], d['bp'], d['w1'], d['b1'], d['w2'], d['b2'], A['kc'], A['vc'], B2, l, C, H, hidden, pos0, Lmax, 1e-6)
     S = fresh()
     g1, g2, s1, s2, h1, h2 = (d['ada'][:, i * C:] for i in range(6))
     ln, gemm = f'ln_modulate_{fl}out', 'gemm_nt_' + fl
-    hip.call(ln, S['x'], s1, 6 * C, h1, 6 * C, S['xn'], M, C, l, 1e-6)
-    hip.call('gemm_qkv_' + fl, S['xn'], C, d['wq'], C, d['bq'], M, C, C, smp, 0.03125, l2, S['q'], S['kc'], S['vc'], B2, l, H, pos0, Lmax)
-    hip.call('attn_cached_' + fl, S['q'], S['kc'], S['vc'], S['att'], B2, l, H, pos0 + l, Lmax)
-    hip.call(gemm, S['att'], C, d['wp'], C, d['bp'], S['x2'], C, 0, M, C, C, EPI_RESID, S['x'], C, 0, g1, 6 * C, l, 1, 0, 0, 0)
-    hip.call(ln, S['x2'], s2, 6 * C, h2, 6 * C, S['xn'], M, C, l, 1e-6)
-    hip.call(gemm, S['xn'], C, d['w1'], C, d['b1'], S['hid'], hidden, 1, M, hidden, C, EPI_GELU, None, 0, 0, None, 0, 1, 1, 0, 0, 0)
-    hip.call(gemm, S['hid'], hidden, d['w2'], hidden, d['b2'], S['x'], C, 0, M, C, hidden, EPI_RESID, S['x2'], C, 0, g2, 6 * C, l, 1, 0, 0, 0)
+    util.guarded_call(ln, S['x'], s1, 6 * C, h1, 6 * C, S['xn'], M, C, l, 1e-6)
+    util.guarded_call('gemm_qkv_' + fl, S['xn'], C, d['wq'], C, d['bq'], M, C, C, smp, 0.03125, l2, S['q'], S['kc'], S['vc'], B2, l, H, pos0, Lmax)
+    util.guarded_call('attn_cached_' + fl, S['q'], S['kc'], S['vc'], S['att'], B2, l, H, pos0 + l, Lmax)
+    util.guarded_call(gemm, S['att'], C, d['wp'], C, d['bp'], S['x2'], C, 0, M, C, C, EPI_RESID, S['x'], C, 0, g1, 6 * C, l, 1, 0, 0, 0)
+    util.guarded_call(ln, S['x2'], s2, 6 * C, h2, 6 * C, S['xn'], M, C, l, 1e-6)
+    util.guarded_call(gemm, S['xn'], C, d['w1'], C, d['b1'], S['hid'], hidden, 1, M, hidden, C, EPI_GELU, None, 0, 0, None, 0, 1, 1, 0, 0, 0)
+    util.guarded_call(gemm, S['hid'], hidden, d['w2'], hidden, d['b2'], S['x'], C, 0, M, C, hidden, EPI_RESID, S['x2'], C, 0, g2, 6 * C, l, 1, 0, 0, 0)
     xn1 = torch.empty(M, C, dtype=dt, device='cuda')
-    hip.call(ln, x.cuda(), s1, 6 * C, h1, 6 * C, xn1, M, C, l, 1e-6)
+    util.guarded_call(ln, x.cuda(), s1, 6 * C, h1, 6 * C, xn1, M, C, l, 1e-6)
     torch.cuda.synchronize()
     for k in A:                                                                       # (a)
         assert torch.equal(A[k], S[k]), f'(a) {k}: composite and its seven steps differ in {int((A[k] != S[k]).sum())} elements'
@@ -206,12 +206,18 @@ def _batched_operands(case, B, dt, g):
         A = torch.full((B * sA,), 8.0, dtype=dt, device='cuda')                    # the gaps hold 8.0: reading them shows in the sums
         A.as_strided((B, M, K), (sA, lda, 1)).copy_(r16(B, M, K))
         return A, lda, r16(B * sW), K, (torch.randn(N, generator=g) * 0.2).cuda(), 1, M, N, K, B, sA, sW, sO, ldo
+    if case == 'ragged_tight':        # the same partial tiles with nothing behind the last slice: A, W and the output end with their last batch's last element
+        M, N, K, lda, ldo = 200, 132, 128, 136, 140
+        sA, sW, sO = M * lda + 8, N * K + 8, M * ldo + 20
+        A = torch.full(((B - 1) * sA + (M - 1) * lda + K,), 8.0, dtype=dt, device='cuda')
+        A.as_strided((B, M, K), (sA, lda, 1)).copy_(r16(B, M, K))
+        return A, lda, r16((B - 1) * sW + N * K), K, (torch.randn(N, generator=g) * 0.2).cuda(), 1, M, N, K, B, sA, sW, sO, ldo
     assert case == 'whole256'         # whole 256x256 tiles: forced tile 2 runs the persistent kernel with blockIdx.z > 0
     return r16(B * 512 * 128), 128, r16(B * 512 * 128, sc=0.1), 128, None, 0, 512, 512, 128, B, 512 * 128, 512 * 128, 512 * 512, 512
 
 
 @pytest.mark.parametrize('fl', ['f16', 'bf16'])
-@pytest.mark.parametrize('case,B', [('scores', 2), ('vt', 2), ('pv', 2), ('scores', 64), ('vt', 64), ('pv', 64), ('ragged', 3), ('whole256', 4)])
+@pytest.mark.parametrize('case,B', [('scores', 2), ('vt', 2), ('pv', 2), ('scores', 64), ('vt', 64), ('pv', 64), ('ragged', 3), ('whole256', 4), ('ragged_tight', 3)])
 def test_gemm16_batched(fl, case, B):
     """varhip_gemm_nt_{f16,bf16} with batch > 1 on every tile (forced 0-3, automatic, 256x256 with and without the persistent kernel):
     all runs the same bits, every slice against float64 within test_gemm16_against_float64's bar (ACC * sum |a||w| + 1e-6, + U |ref| for a
@@ -225,11 +231,11 @@ def test_gemm16_batched(fl, case, B):
     sentinel = -7.0
     first = None
     for tile, persist in RUNS:
-        out = torch.full((batch * sO,), sentinel, dtype=dt if o16 else torch.float32, device='cuda')
+        out = torch.full(((batch - 1) * sO + (M - 1) * ldo + N if case == 'ragged_tight' else batch * sO,), sentinel, dtype=dt if o16 else torch.float32, device='cuda')
         so.varhip_gemm16_force_tile(tile); so.varhip_gemm16_persistent(persist)
         hip.timing_reset(); hip.timing_enable(True)
         try:
-            hip.call('gemm_nt_' + fl, A, lda, W, ldw, bias, out, ldo, o16, M, N, K, 0, None, 0, 0, None, 0, 1, batch, sA, sW, sO)
+            util.guarded_call('gemm_nt_' + fl, A, lda, W, ldw, bias, out, ldo, o16, M, N, K, 0, None, 0, 0, None, 0, 1, batch, sA, sW, sO)
         finally:
             hip.timing_enable(False); so.varhip_gemm16_force_tile(-1); so.varhip_gemm16_persistent(1)
         t = hip.timing_read()
@@ -247,7 +253,7 @@ def test_gemm16_batched(fl, case, B):
     bar = ACC * (As.abs() @ Ws.abs().transpose(1, 2)) + 1e-6 + (U * ref.abs() if o16 else 0.0)
     got = first.as_strided((batch, M, N), (sO, ldo, 1)).double()
     _ratio(f'{fl} {case} B={B}', (got - ref).abs(), bar)
-    written = torch.zeros(batch * sO, dtype=torch.bool, device='cuda')
+    written = torch.zeros(first.numel(), dtype=torch.bool, device='cuda')
     written.as_strided((batch, M, N), (sO, ldo, 1)).fill_(True)
     assert bool((first[~written] == sentinel).all()), 'an element outside the output slices was written'
 

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import util
 from var_amd import abi, hip
 
 pytestmark = pytest.mark.gpu
@@ -82,7 +83,7 @@ def table(V, D=8, seed=0):
     g = torch.Generator(device='cuda').manual_seed(seed)
     cb = torch.randn(V, D, device='cuda', generator=g)
     dist = torch.empty(V, V, device='cuda')
-    hip.call('code_dist_f32', cb, V, D, dist)
+    util.guarded_call('code_dist_f32', cb, V, D, dist)
     return dist
 
 
@@ -113,7 +114,18 @@ def make_rows(rows, V, g):
 @pytest.mark.parametrize('cfg', [0.0, 1.5])
 def test_kernel_vs_float64(V, cfg):
     """the pass layout of test_likelihood_gpu.py::test_kernel_vs_float64, every mode, written into a slice of a larger output"""
-    images, classes, l, K, L, k0, tok0 = 3, 4, 7, 6, 20, 1, 9
+    _kernel_vs_float64(V, cfg, (3, 4, 7, 6, 20, 1, 9))
+
+
+@pytest.mark.parametrize('V', [4096, 4099])
+@pytest.mark.parametrize('cfg', [0.0, 1.5])
+def test_kernel_vs_float64_slices_end_their_allocations(V, cfg):
+    """the same with tok0 + l == L and k0 + classes == K: the last image's tokens are the last elements of gt, its last class row ends the output"""
+    _kernel_vs_float64(V, cfg, (3, 4, 7, 6, 16, 2, 9))
+
+
+def _kernel_vs_float64(V, cfg, layout):
+    images, classes, l, K, L, k0, tok0 = layout
     u = 1 if cfg > 0 else 0
     g = torch.Generator(device='cuda').manual_seed(V + 7)
     rows = images * (classes + u) * l
@@ -141,7 +153,7 @@ def test_kernel_vs_float64(V, cfg):
     for score, par in cases:
         out = torch.full((images, K, L), 12345.0, device='cuda')
         ip = 0 if score == 'neighbor_max' else par
-        hip.call('token_score_f32', logits, gt[:, tok0:], L, images, classes, l, V, u, float(ca), float(cb), MODES[score], ip,
+        util.guarded_call('token_score_f32', logits, gt[:, tok0:], L, images, classes, l, V, u, float(ca), float(cb), MODES[score], ip,
                  float(par) if score == 'neighbor_max' else 0.0, dist, V, out[:, k0:, tok0:], K * L, L)
         torch.cuda.synchronize()
         got = out[:, k0:k0 + classes, tok0:tok0 + l].reshape(-1)

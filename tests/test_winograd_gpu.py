@@ -12,6 +12,8 @@ import pytest
 torch = pytest.importorskip('torch')
 import torch.nn.functional as F
 
+from tests import util
+
 pytestmark = pytest.mark.gpu
 
 # (H = W, Cin, Cout) of every decoder level at ch=160 (ch_mult 1, 1, 2, 2, 4): 256^2 / 128^2 at 160, 64^2 160 -> 320 and 320, 32^2, 16^2
@@ -23,24 +25,25 @@ def _hip():
     return hip
 
 
-def _data(B, H, Cin, Cout, seed=0):
+def _data(B, H, Cin, Cout, seed=0, W=None):
+    W = H if W is None else W
     g = torch.Generator(device='cuda').manual_seed(seed)
-    x = F.silu(torch.randn(B, H, H, Cin, device='cuda', generator=g))
+    x = F.silu(torch.randn(B, H, W, Cin, device='cuda', generator=g))
     wt = (torch.rand(Cout, 3, 3, Cin, device='cuda', generator=g) * 2 - 1) / (9 * Cin) ** 0.5
     bias = torch.rand(Cout, device='cuda', generator=g) * 0.2 - 0.1
-    resid = torch.randn(B, H, H, Cout, device='cuda', generator=g)
+    resid = torch.randn(B, H, W, Cout, device='cuda', generator=g)
     return x, wt, bias, resid
 
 
 def _wino(x, u, bias, resid, B, H, W, Cin, Cout, part=None):
     out = torch.empty(B, H, W, Cout, device='cuda')
-    _hip().call('conv3x3_wino_nhwc_f32', x, u, bias, resid, out, part, B, H, W, Cin, Cout)
+    util.guarded_call('conv3x3_wino_nhwc_f32', x, u, bias, resid, out, part, B, H, W, Cin, Cout)
     return out
 
 
 def _direct(x, wt, bias, resid, B, H, W, Cin, Cout):
     out = torch.empty(B, H, W, Cout, device='cuda')
-    _hip().call('conv3x3_nhwc_f32', x, wt, bias, resid, out, B, H, W, Cin, Cout, 0, 0)
+    util.guarded_call('conv3x3_nhwc_f32', x, wt, bias, resid, out, B, H, W, Cin, Cout, 0, 0)
     return out
 
 
@@ -70,15 +73,49 @@ def test_wino_vs_float64_direct_and_gn_partials(H, Cin, Cout, with_resid):
     # the partials cover every (block, channel) and give the statistics of a full pass over the output (fp64 block order: ~1e-16 relative)
     assert not torch.isnan(part).any()
     st_part = torch.empty(B, 32, 2, device='cuda'); st_full = torch.empty(B, 32, 2, device='cuda')
-    hip.call('gn_stats_part_f32', part, st_part, B, nblk, H * H, Cout, 32, 1e-6)
+    util.guarded_call('gn_stats_part_f32', part, st_part, B, nblk, H * H, Cout, 32, 1e-6)
     scratch = torch.empty(hip.gn_scratch_elems(B, H * H, Cout, 32), dtype=torch.float64, device='cuda')
-    hip.call('gn_stats_f32', yw, st_full, scratch, B, H * H, Cout, 32, 1e-6)
+    util.guarded_call('gn_stats_f32', yw, st_full, scratch, B, H * H, Cout, 32, 1e-6)
     torch.testing.assert_close(st_part, st_full, rtol=1e-6, atol=1e-7)
     # block 2 t + h = half h of 16 x 16 patch t (row-major patches): check one block's channel sums directly
     t, h, pw = (H // 16) * (H // 16) - 1, 1, H // 16
     py, px = divmod(t, pw)
     blk = yw[1, py * 16 + 8 * h: py * 16 + 8 * h + 8, px * 16: px * 16 + 16, :].double()
     torch.testing.assert_close(part[1, 2 * t + h, :, 0], blk.sum((0, 1)), rtol=1e-12, atol=1e-9)
+
+
+@pytest.mark.parametrize('B,H,W,Cin,Cout', [(1, 16, 48, 64, 64), (1, 48, 16, 64, 64), (1, 16, 48, 160, 160), (2, 48, 16, 160, 160), (1, 32, 32, 64, 64), (1, 16, 16, 160, 160)])
+@pytest.mark.parametrize('with_resid', [False, True])
+def test_wino_single_image_and_non_square(B, H, W, Cin, Cout, with_resid):
+    """B = 1 and H != W (a swap of H and W in the patch indexing is invisible on square images): against float64 and the direct kernel with this
+    file's bar.  The kernel's descriptor window is exactly one image (halo pixels outside it carry offset 0x80000000), so with one image the
+    window is the whole allocation and a request that strays past either end of the image lands in a band instead of a neighbouring image;
+    the GroupNorm partials, allocated at exactly conv_gn_blocks' answer, give the statistics of a full pass over the output"""
+    from var_amd.engine import wino_filter
+    hip = _hip()
+    x, wt, bias, resid = _data(B, H, Cin, Cout, seed=H + W, W=W)
+    rs = resid if with_resid else None
+    nblk = hip.conv_gn_blocks(H, W, Cout)
+    assert nblk == H * W // 128
+    part = torch.full((B, nblk, Cout, 2), float('nan'), dtype=torch.float64, device='cuda')
+    yw = _wino(x, wino_filter(wt), bias, rs, B, H, W, Cin, Cout, part)
+    yd = _direct(x, wt, bias, rs, B, H, W, Cin, Cout)
+    r = _ref64(x, wt, bias, rs)
+    ew, ed = (yw.double() - r).abs().max().item(), (yd.double() - r).abs().max().item()
+    print(f'B={B} {H}x{W} {Cin}->{Cout} resid={with_resid}: |wino - f64| {ew:.3g}, |direct - f64| {ed:.3g}')
+    assert ed > 0 and ew <= 2 * ed
+    assert (yw - yd).abs().max().item() <= 3 * ed
+    assert not torch.isnan(part).any()
+    st_part = torch.empty(B, 32, 2, device='cuda'); st_full = torch.empty(B, 32, 2, device='cuda')
+    util.guarded_call('gn_stats_part_f32', part, st_part, B, nblk, H * W, Cout, 32, 1e-6)
+    scratch = torch.empty(hip.gn_scratch_elems(B, H * W, Cout, 32), dtype=torch.float64, device='cuda')
+    util.guarded_call('gn_stats_f32', yw, st_full, scratch, B, H * W, Cout, 32, 1e-6)
+    torch.testing.assert_close(st_part, st_full, rtol=1e-6, atol=1e-7)
+    # block 2 t + h = half h of 16 x 16 patch t, patches row-major over (H / 16, W / 16): the last block's channel sums directly
+    t, h, pw = (H // 16) * (W // 16) - 1, 1, W // 16
+    py, px = divmod(t, pw)
+    blk = yw[B - 1, py * 16 + 8 * h: py * 16 + 8 * h + 8, px * 16: px * 16 + 16, :].double()
+    torch.testing.assert_close(part[B - 1, 2 * t + h, :, 0], blk.sum((0, 1)), rtol=1e-12, atol=1e-9)
 
 
 @pytest.mark.parametrize('H,Cin,Cout', [(32, 320, 320), (16, 640, 640), (64, 160, 320)])
