@@ -484,8 +484,9 @@ int varhip_cast_bf16_to_f32(const void* in, float* out, int64_t n, varhip_stream
  * a multiple of 160); the 16-bit mode's kernels in families of their own (one arithmetic type, hence one MFMA peak, per family):
  * 10 gemm16 (k_gemm16p, the persistent 256x256-tile kernel), 11 gemm16_small (every k_gemm16 tile), 12 conv16h (k_conv16h<5,32>),
  * 13 conv16_small (every other fp16 conv kernel), 14 attn16; 15 conv_wino (k_conv3x3_wino, the fused Winograd F(2x2,3x3) conv; its FLOPs
- * are the executed multiplies, 16 per 2x2 tile, so it is not priced as a direct conv).  Families 0, 1, 10, 12 and 15 each map to exactly
- * one kernel symbol, so their averages can be checked against a rocprofv3 kernel trace.  Returns the number of families. */
+ * are the executed multiplies, 16 per 2x2 tile, so it is not priced as a direct conv).  Families 0, 1, 10 and 12 each map to exactly
+ * one kernel symbol and 15 to the instantiations of one template (k_conv3x3_wino<residual, partials, 0>), so their averages can be checked
+ * against a rocprofv3 kernel trace.  Returns the number of families. */
 #define VARHIP_NFAM 16
 int varhip_timing_enable(int on);
 /* restrict the timing to the families whose bit is set (default: all).  Every timed launch costs two event records on the stream —

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the hot kernels at the shapes the d16 / B=64 sampling call launches (run on the GPU box).
 
-  python tools/bench_kernels.py gemm|qkv|conv|attn|all [--iters N]
+  python tools/bench_kernels.py gemm|qkv|conv|attn|wino|all [--iters N]
 Times each shape with torch CUDA events on the launch stream, interleaving shapes over rounds (cdna guide rule 24), and
 prints TFLOP/s against the fp32 MFMA peak.  Used to A/B kernel variants; numbers quoted in DESIGN.md come from bench.py."""
 import argparse
@@ -91,6 +91,37 @@ def run_conv(iters):
         ms = timeit(fn, max(iters // 4, 2)); tf = 2.0 * B * H * W * Cout * 9 * Cin / ms / 1e9
         print(f'conv {Cin:3d}->{Cout:3d} {H:3d}x{W:3d} up{up2} res{res}: {ms:8.3f} ms  {tf:7.1f} TF  {tf/PEAK*100:5.1f}%', flush=True)
         del x, w, out, r
+
+
+def run_wino(iters, rounds=3):
+    """the fp32 decoder's ResnetBlock convs at B = 64 (the six shapes of tests/test_winograd_gpu.py::SHAPES): the direct kernel against the
+    fused Winograd kernel, residual and GroupNorm partials on as in conv2 of a block; executed TF = 16 multiplies per 2x2 tile and (ci, co).
+    A/B of two builds: run once per library (VARHIP_LIB=...).  VARHIP_WINO_DBG=<bits> times the kernel's knock-outs (1 no epilogue,
+    2 no GroupNorm partials, 4 no residual, 8 no B^T d B; results are wrong, only the time means anything); WINO_SHAPES=0,5 picks shapes."""
+    from var_amd.engine import wino_filter
+    dev, B = 'cuda', 64
+    shapes = [(256, 160, 160), (128, 160, 160), (64, 160, 320), (64, 320, 320), (32, 320, 320), (16, 640, 640)]
+    pick = os.environ.get('WINO_SHAPES')
+    if pick: shapes = [shapes[int(i)] for i in pick.split(',')]
+    dbg = int(os.environ.get('VARHIP_WINO_DBG', '0'))
+    res = {}
+    for r in range(rounds):
+        for (H, Cin, Cout) in shapes:
+            x = torch.nn.functional.silu(torch.randn(B, H, H, Cin, device=dev)); w = (torch.rand(Cout, 3, 3, Cin, device=dev) * 2 - 1) / (9 * Cin) ** 0.5
+            b = torch.randn(Cout, device=dev) * 0.1; rs = torch.randn(B, H, H, Cout, device=dev); out = torch.empty(B, H, H, Cout, device=dev)
+            part = torch.zeros(B, hip.conv_gn_blocks(H, H, Cout), Cout, 2, dtype=torch.float64, device=dev)
+            u = wino_filter(w)
+            n = max(iters // 2, 2) if H >= 128 else iters * 2
+            if not dbg: res.setdefault((H, Cin, Cout, 'd'), []).append(timeit(lambda: hip.call('conv3x3_nhwc_f32', x, w, b, rs, out, B, H, H, Cin, Cout, 0, 0), n))
+            res.setdefault((H, Cin, Cout, 'w'), []).append(timeit(lambda: hip.call('conv3x3_wino_nhwc_f32', x, u, b, rs, out, part, B, H, H, Cin, Cout), n))
+            del x, w, rs, out, part, u
+    for (H, Cin, Cout) in shapes:
+        mw = min(res[(H, Cin, Cout, 'w')]); tf = 2.0 * B * H * H / 4 * 16 * Cin * Cout / mw / 1e9
+        line = f'wino dbg={dbg} {H:3d}^2 {Cin:3d}->{Cout:3d}: Winograd {mw:7.3f} ms  {tf:6.1f} TF executed ({tf / PEAK * 100:4.1f}%)'
+        if not dbg:
+            md = min(res[(H, Cin, Cout, 'd')])
+            line += f'   direct {md:7.3f} ms  {2.0 * B * H * H * 9 * Cin * Cout / md / 1e9:6.1f} TF   speed-up {md / mw:4.2f}x'
+        print(line, flush=True)
 
 
 def run_attn(iters):
@@ -234,6 +265,7 @@ if __name__ == '__main__':
     if a.what in ('qkv', 'all'): run_qkv(a.iters)
     if a.what in ('conv', 'all'): run_conv(a.iters)
     if a.what in ('attn', 'all'): run_attn(a.iters)
+    if a.what == 'wino': run_wino(a.iters)
     if a.what == 'conv16': run_conv16(a.iters)
     if a.what in ('gemm16', 'all16'): run_gemm16(a.iters)
     if a.what in ('attn16', 'all16'): run_attn16(a.iters)
