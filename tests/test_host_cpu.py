@@ -387,3 +387,66 @@ def test_device_side_detinit_matches_numpy():
     for x, y in ((m1, m2), (v1, v2)):
         for (k, p), q in zip(x.state_dict().items(), y.state_dict().values()):
             assert torch.equal(p, q), k
+
+
+# ---- engine state that outlives a call -----------------------------------------------------------------------
+def test_label_check_cache_is_hit_only_by_the_tensor_that_was_checked(monkeypatch):
+    """SamplingEngine._check_labels skips the range check for the tensor OBJECT it checked last while that tensor's version counter stands,
+    and for nothing else.  One numpy buffer wrapped twice by torch.from_numpy gives two tensors of one address, one length and version 0, which
+    is what the allocator makes of `del a; b = torch.tensor(...)`: the second, with a label out of range, must be refused."""
+    vae, var = _quiet_build(depth=2, ch=32, patch_nums=(1, 2, 3))
+    eng = var.engine()
+    assert var.num_classes == 1000
+    buf = np.array([1, 2, 3, 4])
+    a = torch.from_numpy(buf)
+    eng._check_labels(a)
+    ident = (a.data_ptr(), a._version, a.numel(), a.device)
+    del a
+    buf[0] = 5000
+    b = torch.from_numpy(buf)
+    assert (b.data_ptr(), b._version, b.numel(), b.device) == ident         # everything an address-based key can see is equal
+    with pytest.raises(ValueError, match='labels must lie in'):
+        eng._check_labels(b)
+    buf[0] = 1
+    eng._check_labels(b)                                                     # a refused tensor was not remembered as checked
+
+    calls = []
+    real = torch.aminmax
+    monkeypatch.setattr(torch, 'aminmax', lambda *a_, **k: calls.append(1) or real(*a_, **k))
+    c = torch.tensor([0, 7, 1000])
+    eng._check_labels(c); eng._check_labels(c); eng._check_labels(c)
+    assert len(calls) == 1, 'the same tensor object, unwritten, is checked once (no host sync per repeated call)'
+    d = c.clone()                                                            # equal values, another object: checked
+    eng._check_labels(d)
+    assert len(calls) == 2
+    eng._check_labels(c)                                                     # only the LAST checked tensor is remembered
+    assert len(calls) == 3
+    c.add_(0)                                                                # a write the counter sees: checked again
+    eng._check_labels(c)
+    assert len(calls) == 4
+    c[0] = 1001
+    with pytest.raises(ValueError):
+        eng._check_labels(c)
+    with torch.inference_mode():
+        e = torch.tensor([1, 2])                                             # no version counter: checked every time
+    eng._check_labels(e); eng._check_labels(e)
+    assert len(calls) == 7
+
+
+def test_weight_signature_is_not_fooled_by_a_recycled_address():
+    """the engines' key on their packed weight copies: a new parameter with the address and the version counter of a dropped one is another
+    parameter (two wraps of one numpy buffer stand for the allocator handing a freed block back)"""
+    from var_amd.engine import _signature
+    buf = np.zeros(8, np.float32)
+    p = torch.nn.Parameter(torch.from_numpy(buf), requires_grad=False)
+    sig = _signature([p], (3,))
+    assert sig == _signature([p], (3,)) and not (sig != _signature([p], (3,)))
+    assert sig != _signature([p], (4,)) and sig != _signature([p, p], (3,)) and sig != None   # noqa: E711
+    q = torch.nn.Parameter(torch.from_numpy(buf), requires_grad=False)
+    assert (q.data_ptr(), q._version) == (p.data_ptr(), p._version)
+    assert sig != _signature([q], (3,)), 'same address, same version counter, another parameter object'
+    del p
+    assert sig != _signature([q], (3,)) and sig != sig, 'a signature whose parameter is gone equals nothing'
+    with torch.no_grad():
+        q.add_(1)
+    assert _signature([q]) != sig

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import math
 import os
+import weakref
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -62,11 +63,30 @@ def _ver(p: torch.Tensor) -> int:
         return -1
 
 
-def _signature(params) -> tuple:
-    """what the engines key their re-laid weight copies on: storage address + version counter of every parameter.  In-place writes
-    through `.data` (p.data.mul_(), p.data.copy_()) bump no counter: after such surgery call `engine.invalidate()` (VAR / VQVAE
-    do it from load_state_dict and init_weights)."""
-    return tuple((p.data_ptr(), _ver(p)) for p in params)
+class _Signature:
+    """what the engines key their re-laid weight copies on: the parameter OBJECTS (by weak reference), with the storage address and version
+    counter of each.  Address and counter alone prove nothing: where an engine keeps only a packed copy of a parameter (ada_w_all, qkv_b,
+    the Phi and decoder kernels) nothing holds the parameter's storage, and a replacement parameter comes out of the freed block with the
+    old address and, filled the same way, the old version counter.  The weak reference to a parameter that was dropped is dead and equals
+    nothing, and a parameter that is still alive somewhere keeps its address to itself.
+    In-place writes through `.data` (p.data.mul_(), p.data.copy_()) bump no counter: after such surgery call `engine.invalidate()` (VAR /
+    VQVAE do it from load_state_dict and init_weights)."""
+
+    def __init__(self, params, extra: tuple = ()):
+        params = list(params)
+        self.refs = [weakref.ref(p) for p in params]
+        self.key = tuple((p.data_ptr(), _ver(p)) for p in params) + tuple(extra)
+
+    def __eq__(self, other):
+        if not isinstance(other, _Signature) or self.key != other.key or len(self.refs) != len(other.refs):
+            return False
+        return all(a() is not None and a() is b() for a, b in zip(self.refs, other.refs))
+
+    __hash__ = None
+
+
+def _signature(params, extra: tuple = ()) -> _Signature:
+    return _Signature(params, extra)
 
 
 def _chk(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -737,7 +757,7 @@ class SamplingEngine:
         self._ws: Dict[tuple, dict] = {}            # (batch size, HIP stream, precision) -> buffers of a call
         self._ws_tf: Dict[tuple, dict] = {}         # the same for teacher_forced_logits
         self._ready = None                          # event behind the kernels that built the derived weight copies (see _VaeOps._built)
-        self._labels_ok = None                      # identity of the last label tensor whose range was checked (one host sync saved per repeated call)
+        self._labels_ok = None                      # (the last label tensor whose range was checked, its version counter, address, length): one host sync saved per repeated call
 
         self.policy = 'auto' if os.environ.get('VARHIP_FOLLOW_AUTOCAST', '0') not in ('', '0') else 'f32'      # what set_precision() was given: 'f32' | 'f16' | 'bf16' | 'auto' (follow the caller's torch.autocast)
         self.precision = 'f32'              # the arithmetic of the call in progress (the policy, resolved): 'f16' / 'bf16' = the 16-bit throughput mode (include/var_hip.h)
@@ -748,7 +768,7 @@ class SamplingEngine:
     def refresh(self):
         var = self.var
         quant = var.vae_quant_proxy[0]
-        sig = _signature(list(var.parameters()) + list(quant.parameters())) + (getattr(var.vae_proxy[0], '_hip_generation', 0),)
+        sig = _signature(list(var.parameters()) + list(quant.parameters()), (getattr(var.vae_proxy[0], '_hip_generation', 0),))
         if sig == self._sig:
             self._ensure16()
             return
@@ -890,16 +910,22 @@ class SamplingEngine:
 
     def _check_labels(self, label_B: torch.Tensor):
         """labels index class_emb: out-of-range ones must not reach the kernel.  One device-side reduction and ONE host sync (a sync drains the
-        stream, so back-to-back calls would otherwise never overlap their host side with the previous call's kernels); a tensor that was checked
-        before and has not been written since (same storage, same version counter) is not checked again."""
-        ident = (label_B.data_ptr(), _ver(label_B), label_B.numel(), label_B.device)
-        if ident == self._labels_ok and ident[1] >= 0:
+        stream, so back-to-back calls would otherwise never overlap their host side with the previous call's kernels); the tensor OBJECT that was
+        checked last is not checked again while its version counter stands.  The engine keeps a reference to that object, so its storage cannot
+        go back to the allocator and come out again under another tensor: an address alone proves nothing (a fresh tensor in a recycled block
+        has the same address, the same length and version 0).  Tensors made under torch.inference_mode() have no counter and are checked every
+        time.  What stays the caller's business: writes to that same object that bump no counter — through `.data`, or through memory the tensor
+        only wraps (a numpy array under torch.from_numpy, DLPack, another view of its storage made with `.data`)."""
+        ver = _ver(label_B)
+        ok = self._labels_ok
+        if ok is not None and ok[0] is label_B and ver >= 0 and ok[1:] == (ver, label_B.data_ptr(), label_B.numel()):
             return
+        self._labels_ok = None
         lo, hi = torch.aminmax(label_B)
         lo, hi = torch.stack((lo, hi)).tolist()
         if lo < 0 or hi > self.var.num_classes:
             raise ValueError(f'labels must lie in [0, {self.var.num_classes}]')
-        self._labels_ok = ident
+        self._labels_ok = (label_B, ver, label_B.data_ptr(), label_B.numel())
 
     def gemm(self, A, W, bias, out, M, epi=EPI_NONE, resid=None, gamma=None, ldg=0, rpg=1):
         N, K = W.shape
