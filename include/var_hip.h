@@ -130,6 +130,35 @@ int varhip_cfg_sample_f32(const float* logits, const float* noise, int64_t* idx_
  * that provably gives the same cut, by the walk otherwise.  Same results either way. */
 int varhip_sampler_force_walk(int on);
 
+/* The same sampler with one parameter set per image (VAR.autoregressive_infer_cfg_per_image): t_cfg [B] double, top_k [B] int32 and
+ * top_p [B] double are DEVICE arrays; the workgroup of row r reads entry r / l and rounds it as varhip_cfg_sample_f32 rounds its scalars:
+ * ca = (float)(1.0 + t), cb = (float)t, thr = (float)(1.0 - top_p), top-p active where top_p > 0.  Contract: for every image b, idx_out and
+ * masked_out of its l rows are bit-identical to varhip_cfg_sample_f32 called on those rows alone (B = 1) with the scalars
+ * (t_cfg[b], top_k[b], top_p[b]), under both settings of varhip_sampler_force_walk.  top_k_cap sizes the launch's sort buffer (the kernel's
+ * results do not depend on it: ties with the k-th value beyond the buffer are handled unsorted): the largest top_k[b], or V if any
+ * top_k[b] == 0; the host holds the table it uploads, so it passes the number.  An image whose top_k is outside [0, V] or needs more than
+ * top_k_cap gets idx_out = -1 on its rows and leaves masked_out alone (no LDS is touched).  Constraints as varhip_cfg_sample_f32, and
+ * 1 <= top_k_cap <= V: VARHIP_EINVAL otherwise. */
+int varhip_cfg_sample_rows_f32(const float* logits, const float* noise, int64_t* idx_out, float* masked_out, int B, int l, int V,
+                               const double* t_cfg, const int32_t* top_k, const double* top_p, int top_k_cap, varhip_stream_t stream);
+
+/* ---- counter-based Exp(1) fill (per-image sampling) ----------------------------------------------------------------------------------------
+ * out[(b*l + t)*V + v] = -vm_log(u),  u = (2n + 1) * 2^-24,  n = x >> 9,  x = word v % 4 of Philox4x32-10(counter, key) with
+ *   key = (low 32 bits of seeds[b], high 32 bits of seeds[b]),  counter = (v / 4, t, scale, draw)
+ * (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85: Random123's philox4x32_10).  The value is a function of
+ * (seed, scale, t, v, draw) alone: not of B, of the image's position in the batch, or of what was drawn before.  draw: 0 = the multinomial
+ * fill (the noise of varhip_cfg_sample*_f32), 1 = the gumbel fill of more_smooth (the noise of varhip_gumbel_softmax_f32).  u is exact in
+ * fp32 and lies in [2^-24, 1 - 2^-24]; vm_log (include/var_math.h) consists of correctly rounded operations only, so the kernel and the
+ * host twin give the same bits.  This is the project's own stream, not torch's.  seeds: DEVICE int64 [B] (the host twin: host pointers);
+ * out 16-byte aligned (the kernel stores 16 bytes per lane).  V % 4 != 0, B or l < 1, scale or draw < 0, a misaligned out: VARHIP_EINVAL. */
+int varhip_exp1_philox_f32(const int64_t* seeds, int B, int l, int V, int scale, int draw, float* out, varhip_stream_t stream);
+/* the host twin: plain host code (usable without a GPU), same arguments with host pointers, no alignment constraint */
+int varhip_exp1_philox_host_f32(const int64_t* seeds, int B, int l, int V, int scale, int draw, float* out);
+/* one Philox4x32-10 block on the host (known-answer tests of the integer stage against the published vectors) */
+int varhip_philox4x32_host(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* the fill's transform alone on the host: out[i] = -vm_log((2 (bits[i] >> 9) + 1) * 2^-24)  (exhaustive tests over the 2^23 values of n) */
+int varhip_exp1_from_bits_host_f32(const uint32_t* bits, int64_t n, float* out);
+
 /* ---- multi-scale quantizer step ---------------------------------------------------------------------------
  * Feature maps are kept channels-last: f_hat[B][P][P][Cv].
  * (1) h = codebook[idx] as [B][pn][pn][Cv]                                          (var.py:177,182; quant.py:39)

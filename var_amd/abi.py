@@ -85,6 +85,15 @@ SIGNATURES_HIP_ONLY = {
     'edit_keep_u8':      [P, I, I, I, P, I, I, P],                   # pinned against F.interpolate > 0.5 and the reference's maps (tests/test_edit_gpu.py)
     'quant_accum_edit_f32': [P, P, P, L, P, P, P, P, P, F, P, P, I, I, I, I],     # pinned against token_select_i64 + quant_accum_f32 (tests/test_edit_gpu.py)
     'quant_accum_h_edit_f32': [P, P, P, L, P, P, P, P, P, F, P, P, I, I, I, I],   # pinned against an overwrite of h + quant_accum_h_f32
+    'cfg_sample_rows_f32': [P, P, P, P, I, I, I, P, P, P, I],         # pinned against cfg_sample_f32 per image (tests/test_per_image_gpu.py)
+    'exp1_philox_f32':   [P, I, I, I, I, I, P],                      # pinned against its host twin below (tests/test_per_image_gpu.py)
+}
+
+# plain host functions of the HIP library (no stream argument, no device pointer, no GPU needed); bound by var_amd/hip.py
+SIGNATURES_HOST = {
+    'exp1_philox_host_f32': [P, I, I, I, I, I, P],                   # pinned against a numpy Philox4x32-10 (tests/test_per_image_cpu.py)
+    'philox4x32_host':   [P, P, P],                                  # pinned against the Random123 known answers
+    'exp1_from_bits_host_f32': [P, L, P],
 }
 
 # ... and with bfloat16 storage: one entry point per _f16 entry point, same arguments (include/var_hip.h, "bf16")

@@ -50,10 +50,12 @@ __device__ __forceinline__ unsigned long long vs_scan256_u64(unsigned long long 
 
 // NV = V / 256 when the caller's V is the common 4096 (the exponentials of a thread's NV elements then stay in registers between the
 // phases: one evaluation instead of three), 0 = any V (evaluated where needed)
+// The body is shared by the two kernels below (forced inline into each): k_cfg_sample hands it the batch's scalars, k_cfg_sample_rows the
+// ones of the row's image.
 template <int NV>
-__global__ void __launch_bounds__(256) k_cfg_sample(const float* __restrict__ logits, const float* __restrict__ noise, int64_t* __restrict__ idx_out,
-                                                    float* __restrict__ masked_out, int64_t rows, int V, float ca, float cb,
-                                                    int top_k, int use_top_p, float thr, int cap, int force_walk) {
+__device__ __forceinline__ void vs_cfg_sample_row(const float* __restrict__ logits, const float* __restrict__ noise, int64_t* __restrict__ idx_out,
+                                                  float* __restrict__ masked_out, int64_t rows, int V, float ca, float cb,
+                                                  int top_k, int use_top_p, float thr, int cap, int force_walk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm_raw[];
     float* xs = reinterpret_cast<float*>(sm_raw);                                   // [V] working logits
     unsigned long long* srt = reinterpret_cast<unsigned long long*>(sm_raw + sizeof(float) * V);   // [cap] (key<<32 | idx), cap = pow2 >= top_k (or V)
@@ -385,6 +387,30 @@ __global__ void __launch_bounds__(256) k_cfg_sample(const float* __restrict__ lo
     if (masked_out) for (int i = tid; i < V; i += 256) masked_out[row * V + i] = xs[i];
 }
 
+template <int NV>
+__global__ void __launch_bounds__(256) k_cfg_sample(const float* __restrict__ logits, const float* __restrict__ noise, int64_t* __restrict__ idx_out,
+                                                    float* __restrict__ masked_out, int64_t rows, int V, float ca, float cb,
+                                                    int top_k, int use_top_p, float thr, int cap, int force_walk) {
+    vs_cfg_sample_row<NV>(logits, noise, idx_out, masked_out, rows, V, ca, cb, top_k, use_top_p, thr, cap, force_walk);
+}
+
+// per-image parameters: the workgroup of row r reads those of image r / l and rounds them as varhip_cfg_sample_f32 rounds its scalars on the
+// host (fp64 add / subtract, one conversion to fp32: the same IEEE operations).  Everything that follows is workgroup-uniform.  An image
+// whose top_k does not fit the sort buffer the launch was sized for (the host checks the table it uploads; this guards the LDS) gets -1.
+template <int NV>
+__global__ void __launch_bounds__(256) k_cfg_sample_rows(const float* __restrict__ logits, const float* __restrict__ noise, int64_t* __restrict__ idx_out,
+                                                         float* __restrict__ masked_out, int64_t rows, int l, int V, const double* __restrict__ t_cfg,
+                                                         const int* __restrict__ top_k, const double* __restrict__ top_p, int cap, int force_walk) {
+    const int64_t b = (int64_t)blockIdx.x / l;
+    const double t = t_cfg[b], p = top_p[b];
+    const int k = top_k[b];
+    if (k < 0 || k > V || (k > 0 ? k : V) > cap) {
+        if (threadIdx.x == 0) idx_out[blockIdx.x] = -1;
+        return;
+    }
+    vs_cfg_sample_row<NV>(logits, noise, idx_out, masked_out, rows, V, (float)(1.0 + t), (float)t, k, p > 0.0 ? 1 : 0, (float)(1.0 - p), cap, force_walk);
+}
+
 static int g_sampler_force_walk = 0;
 // testing: 1 = decide every top-p cut by the sequential walk (the definition), 0 = by the parallel prefix sum wherever that is provably the same
 extern "C" int varhip_sampler_force_walk(int on) { g_sampler_force_walk = on ? 1 : 0; return 0; }
@@ -406,6 +432,26 @@ extern "C" int varhip_cfg_sample_f32(const float* logits, const float* noise, in
     else
         hipLaunchKernelGGL(k_cfg_sample<0>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, logits, noise, idx_out, masked_out, rows, V,
                            (float)(1.0 + t_cfg), (float)t_cfg, top_k, top_p > 0.0 ? 1 : 0, (float)(1.0 - top_p), cap, g_sampler_force_walk);
+    return vh_launch_status();
+}
+
+extern "C" int varhip_cfg_sample_rows_f32(const float* logits, const float* noise, int64_t* idx_out, float* masked_out, int B, int l, int V,
+                                          const double* t_cfg, const int32_t* top_k, const double* top_p, int top_k_cap, varhip_stream_t stream) {
+    if (B <= 0 || l <= 0 || V <= 0 || (V & 255) || V > 8192 || top_k_cap < 1 || top_k_cap > V || !t_cfg || !top_k || !top_p) return VARHIP_EINVAL;
+    if ((uintptr_t)logits & 15) return VARHIP_EINVAL;
+    const int64_t rows = (int64_t)B * l;
+    int cap = 2; while (cap < top_k_cap) cap <<= 1;                     // one sort buffer size for the launch: the largest any image needs
+    const size_t lds = sizeof(float) * (size_t)V + sizeof(unsigned long long) * (size_t)cap;
+    static bool attr_done = false;
+    if (!attr_done) { (void)hipFuncSetAttribute((const void*)k_cfg_sample_rows<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 12 * 8192);
+                      (void)hipFuncSetAttribute((const void*)k_cfg_sample_rows<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 12 * 8192); attr_done = true; }
+    VhScope sc(VH_FAM_SAMPLER, (hipStream_t)stream, 0, 4.0 * rows * V * 3.0);
+    if (V == 4096)
+        hipLaunchKernelGGL(k_cfg_sample_rows<16>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, logits, noise, idx_out, masked_out, rows, l, V,
+                           t_cfg, top_k, top_p, cap, g_sampler_force_walk);
+    else
+        hipLaunchKernelGGL(k_cfg_sample_rows<0>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, logits, noise, idx_out, masked_out, rows, l, V,
+                           t_cfg, top_k, top_p, cap, g_sampler_force_walk);
     return vh_launch_status();
 }
 

@@ -45,6 +45,16 @@ def bicubic_taps(pn: int, P: int):
     return idx, w
 
 
+def per_image_tables(cfg, top_k, top_p, S: int, V: int) -> dict:
+    """the host tables of a per-image call: t [S, B] float64 with t[si][b] = cfg[b] * (si / (S - 1)) formed as the plain call forms its scalar (one
+    fp64 division, one fp64 multiplication), top_k [B] int32, top_p [B] float64, and cap = the largest top_k (V if any image has none)"""
+    B = len(cfg)
+    c = np.asarray([float(x) for x in cfg], dtype=np.float64)
+    t = np.stack([c * (si / (S - 1)) if S > 1 else np.zeros(B) for si in range(S)])
+    k = np.asarray([int(x) for x in top_k], dtype=np.int32)
+    return dict(t=t, top_k=k, top_p=np.asarray([float(x) for x in top_p], dtype=np.float64), cap=int(V if (k == 0).any() else k.max()))
+
+
 def phi_index(si: int, S: int, K: int) -> int:
     """which shared Phi conv serves scale si (reference quant.py:218-226)"""
     ticks = np.linspace(1 / 3 / K, 1 - 1 / 3 / K, K) if K == 4 else np.linspace(1 / 2 / K, 1 - 1 / 2 / K, K)
@@ -988,7 +998,7 @@ class SamplingEngine:
                noises=None, force_idx: Optional[torch.Tensor] = None, trace: bool = False,
                decode: bool = True, gt_tokens: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
                more_smooth: bool = False, gumbel_noises=None, smooth: Optional[dict] = None, greedy: bool = False,
-               tokens_out: Optional[torch.Tensor] = None, edit: Optional[dict] = None) -> torch.Tensor:
+               tokens_out: Optional[torch.Tensor] = None, edit: Optional[dict] = None, per_image: Optional[dict] = None) -> torch.Tensor:
         """label_B: int64 [B] on the device.  noises: optional per-scale Exp(1) tensors [B*l, V] — a list, or a callable
         (si, l) -> tensor (tests inject the CPU generator's stream; var_amd.multi hands each rank its rows); by default they
         are drawn with `exponential_(generator=rng)` exactly as torch.multinomial (helpers.py:19) would.
@@ -1005,6 +1015,9 @@ class SamplingEngine:
         step (varhip_quant_accum[_h]_edit_f32).  Unlike inpainting every scale draws its Exp(1) fill (and with more_smooth its gumbel fill), so
         the RNG stream is that of a plain call; a fully kept scale draws them and skips the head, the sampler and the gumbel softmax.  The
         trace's 'idx' holds the final tokens, its 'sampled' the sampler's (None on fully kept scales).
+        per_image = dict(t=[S, B] float64, top_k=[B] int32, top_p=[B] float64 on the device, cap=int): every image samples with its own
+        parameters (varhip_cfg_sample_rows_f32; sample_per_image builds the tables); cfg, top_k and top_p are not read.  gumbel_noises may be
+        a callable (si, l) -> tensor like noises.
         force_idx/trace are test hooks (teacher forcing; keep per-scale logits/tokens/f_hat)."""
         var = self.var
         self.resolve_precision()
@@ -1022,6 +1035,8 @@ class SamplingEngine:
             raise ValueError('greedy selection replaces the sampler: it does not combine with more_smooth or smooth sampling')
         if edit is not None and (gt_tokens is not None or keep_mask is not None or smooth is not None or greedy):
             raise ValueError('edit does not combine with gt_tokens / keep_mask, smooth sampling or greedy selection')
+        if per_image is not None and (greedy or smooth is not None):
+            raise ValueError('per-image parameters belong to the sampler: they do not combine with greedy selection or smooth sampling')
         if tokens_out is not None and (tokens_out.dtype != torch.int64 or tuple(tokens_out.shape) != (B, var.L) or not tokens_out.is_contiguous()):
             raise ValueError(f'tokens_out must be a contiguous int64 ({B}, {var.L}) tensor')
         tr = dict(logits=[], idx=[], f_hat=[], pooled=[]) if trace else None
@@ -1157,7 +1172,11 @@ class SamplingEngine:
                         draws += 1
                     else:
                         noise = torch.empty(B * l, V, dtype=torch.float32, device=dev).exponential_(1, generator=rng)
-                    hip.call('cfg_sample_f32', ws['logits'], noise, idx, masked, B, l, V, float(t), int(top_k), float(top_p))
+                    if per_image is not None:
+                        hip.call('cfg_sample_rows_f32', ws['logits'], noise, idx, masked, B, l, V, per_image['t'][si], per_image['top_k'],
+                                 per_image['top_p'], int(per_image['cap']))
+                    else:
+                        hip.call('cfg_sample_f32', ws['logits'], noise, idx, masked, B, l, V, float(t), int(top_k), float(top_p))
                 if gt is not None and not greedy:                         # torch.where(mask, gt_tokens, sampled) (var.py:326-328)
                     hip.call('token_select_i64', keep_u8[:, cur - l:cur].contiguous(), gt[:, cur - l:cur].contiguous(), idx, idx, B * l)
                 if trace and ed_gt is not None: tr['sampled'].append(idx.view(B, l).clone())
@@ -1182,7 +1201,7 @@ class SamplingEngine:
                 r_ = si / var.num_stages_minus_1 if var.num_stages_minus_1 > 0 else 0.0
                 gum_t = max(0.27 * (1 - r_ * 0.95), 0.005)
                 if gumbel_noises is not None:
-                    gn = gumbel_noises[si].to(dev, torch.float32).contiguous()
+                    gn = (gumbel_noises(si, l) if callable(gumbel_noises) else gumbel_noises[si]).to(dev, torch.float32).contiguous()
                 else:
                     gn = torch.empty(B * l, V, dtype=torch.float32, device=dev).exponential_(generator=rng)
                 hip.call('gumbel_softmax_f32', masked, gn, ws['probs'], B * l, V, float(1 + r_), float(gum_t))
@@ -1212,6 +1231,33 @@ class SamplingEngine:
             ev[S + 1].record(); torch.cuda.synchronize()
             self.last_scale_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(S + 1)]
         return img
+
+    # -- per-image parameters and seeds (VAR.autoregressive_infer_cfg_per_image) --------------------------------------------
+    @torch.no_grad()
+    def sample_per_image(self, label_B: torch.Tensor, seeds, cfg, top_k, top_p, more_smooth: bool = False,
+                         tokens_out: Optional[torch.Tensor] = None, trace: bool = False) -> torch.Tensor:
+        """sample() on a batch of unrelated requests: image b uses seeds[b], cfg[b], top_k[b], top_p[b] (host sequences of length B, already
+        validated: VAR.autoregressive_infer_cfg_per_image).  The noise is the project's counter-based stream (varhip_exp1_philox_f32): image
+        b's rows depend on (seeds[b], scale, row, column, draw) only, the sampler reads image b's parameters from device tables
+        (varhip_cfg_sample_rows_f32) — so a request's tokens do not depend on what it is batched with.  The tables are built and uploaded once,
+        outside the scale loop; per scale: one fill launch, one sampler launch (and the draw-1 fill under more_smooth)."""
+        var = self.var
+        B, S, V = len(seeds), len(var.patch_nums), var.V
+        dev = var.pos_start.device
+        tab = per_image_tables(cfg, top_k, top_p, S, V)
+        # one upload: [S*B t | B top_p] float64, then the two integer tables
+        f64 = torch.from_numpy(np.concatenate((tab['t'].reshape(-1), tab['top_p']))).to(dev, non_blocking=False)
+        per = dict(t=f64[:S * B].view(S, B), top_p=f64[S * B:], top_k=torch.from_numpy(tab['top_k']).to(dev), cap=tab['cap'])
+        seeds_d = torch.from_numpy(np.asarray(seeds, dtype=np.int64)).to(dev)
+
+        def fill(draw):
+            def fn(si, l):
+                out = torch.empty(B * l, V, dtype=torch.float32, device=dev)
+                hip.call('exp1_philox_f32', seeds_d, B, l, V, si, draw, out)
+                return out
+            return fn
+        return self.sample(B, label_B, None, 0.0, 0, 0.0, noises=fill(0), gumbel_noises=fill(1) if more_smooth else None,
+                           more_smooth=more_smooth, tokens_out=tokens_out, trace=trace, per_image=per)
 
     # -- teacher-forced logits (VAR.forward without autograd) ------------------------------------------------------------
     @torch.no_grad()

@@ -29,6 +29,11 @@ class _Lib:
         so.varhip_conv16_force_tile.argtypes = [ctypes.c_int]; so.varhip_conv16_force_tile.restype = ctypes.c_int
         so.varhip_gemm16_persistent.argtypes = [ctypes.c_int]; so.varhip_gemm16_persistent.restype = ctypes.c_int
         so.varhip_sampler_force_walk.argtypes = [ctypes.c_int]; so.varhip_sampler_force_walk.restype = ctypes.c_int
+        self.host = {}
+        for name, args in abi.SIGNATURES_HOST.items():
+            fn = getattr(so, 'varhip_' + name)
+            fn.argtypes = list(args); fn.restype = ctypes.c_int
+            self.host[name] = fn
 
     def version(self) -> str:
         return self.fn['version']().decode()
@@ -64,6 +69,20 @@ def call(name: str, *args, stream=None):
     rc = L.fn[name](*[_arg(a) for a in args], st)
     if rc != 0:
         raise VarHipError(f'varhip_{name} returned {rc}' + (' (VARHIP_EINVAL: unsupported shape/argument)' if rc == abi.EINVAL else ' (HIP launch error %d)' % (-rc - 1000)))
+
+
+def call_host(name: str, *args):
+    """Run the plain host function `varhip_<name>` (abi.SIGNATURES_HOST: no stream, no GPU; CPU tensors and numpy arrays are passed by
+    address); raises on a non-zero code."""
+    def arg(a):
+        if hasattr(a, 'ctypes'):
+            return ctypes.c_void_p(a.ctypes.data)
+        return _arg(a)
+    if name not in abi.SIGNATURES_HOST:
+        raise VarHipError(f'varhip_{name} is not a host function')
+    rc = lib().host[name](*[arg(a) for a in args])
+    if rc != 0:
+        raise VarHipError(f'varhip_{name} returned {rc}' + (' (VARHIP_EINVAL: unsupported shape/argument)' if rc == abi.EINVAL else ''))
 
 
 def gn_scratch_elems(B, HW, C, G) -> int:

@@ -208,6 +208,125 @@ class VAR(nn.Module):
         return self.engine().sample(B, label_B.to(dev).long(), rng, cfg, top_k, top_p, more_smooth=bool(more_smooth))
 
     @torch.no_grad()
+    def autoregressive_infer_cfg_per_image(self, label_B, g_seeds, cfg=1.5, top_k=0, top_p=0.0, more_smooth=False, return_tokens=False):
+        """Sample a batch of unrelated requests: image b is drawn with its own seed g_seeds[b] and its own cfg / top_k / top_p (each a scalar
+        for all, or B values).  Returns (B, 3, H, W) fp32 in [0, 1]; with return_tokens=True also the (B, L) int64 tokens.
+        Guarantee: the tokens of a request depend on (label, seed, cfg, top_k, top_p, more_smooth) and the weights only — not on the batch
+        size, the request's position in the batch or its neighbours.  The noise is the project's own counter-based stream (Philox4x32-10
+        keyed by the seed, counter (column / 4, row, scale, draw): include/var_hip.h, varhip_exp1_philox_f32), NOT torch's: the images
+        differ from autoregressive_infer_cfg(g_seed=...) with the same numbers, and self.rng is neither read nor advanced.
+          label_B   (B,) integer tensor or list, labels in [0, num_classes] (num_classes = unconditional)
+          g_seeds   (B,) integers in [0, 2^63)
+        more_smooth is one bool for the batch.  Precision follows set_hip_precision / 'auto' as the plain call does.  On the HIP path (a CUDA /
+        ROCm model in eval mode, prog_si < 0) the loop is SamplingEngine.sample_per_image; elsewhere (a CPU model, train mode, prog_si >= 0)
+        the same stream comes from the library's host twin and the loop runs in PyTorch, image by image."""
+        lab = torch.as_tensor(label_B)
+        if lab.dim() != 1 or lab.numel() < 1 or lab.dtype.is_floating_point or lab.dtype.is_complex or lab.dtype == torch.bool:
+            raise ValueError('label_B must hold B >= 1 integer class ids')
+        B = lab.numel()
+
+        def per(x, name, conv):
+            if isinstance(x, torch.Tensor):
+                x = x.detach().cpu().tolist()
+            elif isinstance(x, np.ndarray):
+                x = x.tolist()
+            if isinstance(x, (list, tuple)):
+                if len(x) != B:
+                    raise ValueError(f'{name} must be a scalar or {B} values, got {len(x)}')
+                vals = list(x)
+            else:
+                vals = [x] * B
+            try:
+                return [conv(v) for v in vals]
+            except (TypeError, OverflowError) as e:
+                raise ValueError(f'{name}: {e}') from None
+
+        def as_int(v):
+            if isinstance(v, bool) or (isinstance(v, float) and v != int(v)) or not isinstance(v, (int, float, np.integer)):
+                raise ValueError(f'expected an integer, got {v!r}')
+            return int(v)
+        if isinstance(g_seeds, (int, np.integer)) or (isinstance(g_seeds, torch.Tensor) and g_seeds.dim() == 0):
+            raise ValueError(f'g_seeds must hold one seed per image ({B} values)')
+        seeds = per(g_seeds, 'g_seeds', as_int)
+        cfgs, ks, ps = per(cfg, 'cfg', float), per(top_k, 'top_k', as_int), per(top_p, 'top_p', float)
+        if any(sd < 0 or sd >= 1 << 63 for sd in seeds):
+            raise ValueError('g_seeds must lie in [0, 2^63)')
+        if not all(math.isfinite(c) for c in cfgs):
+            raise ValueError('cfg must be finite')
+        if any(k < 0 or k > self.V for k in ks):
+            raise ValueError(f'top_k must lie in [0, {self.V}]')
+        if not all(0.0 <= p <= 1.0 for p in ps):                 # (NaN fails the comparison)
+            raise ValueError('top_p must lie in [0, 1]')
+        dev = self.lvl_1L.device
+        lab = lab.to(dev).long()
+        if dev.type == 'cuda' and not self.training and self.prog_si < 0:
+            tok = torch.empty(B, self.L, dtype=torch.int64, device=dev) if return_tokens else None
+            img = self.engine().sample_per_image(lab, seeds, cfgs, ks, ps, more_smooth=bool(more_smooth), tokens_out=tok)
+            return (img, tok) if return_tokens else img
+        self.engine()._check_labels(lab)
+        img, tok = self._per_image_torch(lab, seeds, cfgs, ks, ps, bool(more_smooth))
+        return (img, tok) if return_tokens else img
+
+    def _per_image_torch(self, lab, seeds, cfgs, ks, ps, more_smooth: bool):
+        """the PyTorch side of autoregressive_infer_cfg_per_image (reference var.py:126-190, one request at a time): the Exp(1) fills are
+        the host twin's (varhip_exp1_philox_host_f32), the sampler is helpers.py:6-19 with the multinomial written as argmax(p / noise)"""
+        from .. import hip
+        vae, quant = self.vae_proxy[0], self.vae_quant_proxy[0]
+        dev, S, V = lab.device, len(self.patch_nums), self.V
+        imgs, toks = [], []
+
+        def fill(seed, l, si, draw):
+            out = np.empty((l, V), np.float32)
+            hip.call_host('exp1_philox_host_f32', np.asarray([seed], np.int64), 1, l, V, si, draw, out)
+            return torch.from_numpy(out).to(dev)
+        for b in range(lab.numel()):
+            cond_BD = self.class_emb(torch.stack((lab[b], torch.full_like(lab[b], self.num_classes))))
+            sos = cond_BD
+            lvl_pos = self.lvl_embed(self.lvl_1L) + self.pos_1LC
+            x = sos.unsqueeze(1).expand(2, self.first_l, -1) + self.pos_start.expand(2, self.first_l, -1) + lvl_pos[:, :self.first_l]
+            f_hat = sos.new_zeros(1, self.Cvae, self.patch_nums[-1], self.patch_nums[-1])
+            cond_or_gss = self.shared_ada_lin(cond_BD)
+            for blk in self.blocks: blk.attn.kv_caching(True)
+            cur, tok = 0, []
+            try:
+                for si, pn in enumerate(self.patch_nums):
+                    l = pn * pn
+                    ratio = si / self.num_stages_minus_1 if self.num_stages_minus_1 > 0 else 0.0
+                    cur += l
+                    for blk in self.blocks:
+                        x = blk(x=x, cond_BD=cond_or_gss, attn_bias=None)
+                    z = self.get_logits(x, cond_BD)
+                    t = cfgs[b] * ratio
+                    z = (1 + t) * z[:1] - t * z[1:]
+                    if ks[b] > 0:
+                        z = z.masked_fill(z < z.topk(ks[b], largest=True, sorted=False, dim=-1)[0].amin(dim=-1, keepdim=True), -torch.inf)
+                    if ps[b] > 0:
+                        srt, order = z.sort(dim=-1, descending=False)
+                        drop = srt.softmax(dim=-1).cumsum_(dim=-1) <= (1 - ps[b])
+                        drop[..., -1:] = False
+                        z = z.masked_fill(drop.scatter(order.ndim - 1, order, drop), -torch.inf)
+                    idx = (z.softmax(dim=-1)[0] / fill(seeds[b], l, si, 0)).argmax(dim=-1).view(1, l)
+                    tok.append(idx)
+                    if more_smooth:
+                        gum_t = max(0.27 * (1 - ratio * 0.95), 0.005)
+                        g = -fill(seeds[b], l, si, 1).log()
+                        h = ((z[0] * (1 + ratio) + g) / gum_t).softmax(dim=-1) @ quant.embedding.weight
+                        h = h.view(1, l, self.Cvae)
+                    else:
+                        h = quant.embedding(idx)
+                    h = h.transpose(1, 2).reshape(1, self.Cvae, pn, pn)
+                    f_hat, nxt = quant.get_next_autoregressive_input(si, S, f_hat, h)
+                    if si != S - 1:
+                        nxt = nxt.view(1, self.Cvae, -1).transpose(1, 2)
+                        nl = self.patch_nums[si + 1] ** 2
+                        x = (self.word_embed(nxt) + lvl_pos[:, cur:cur + nl]).repeat(2, 1, 1)
+            finally:
+                for blk in self.blocks: blk.attn.kv_caching(False)
+            imgs.append(vae.fhat_to_img(f_hat).add_(1).mul_(0.5))
+            toks.append(torch.cat(tok, dim=1))
+        return torch.cat(imgs), torch.cat(toks)
+
+    @torch.no_grad()
     def autoregressive_infer_cfg_with_mask(self, B: int, label_B: Optional[Union[int, torch.LongTensor]], g_seed: Optional[int] = None, cfg=1.5,
                                            top_k=0, top_p=0.0, more_smooth=False, input_img_tokens=None, edit_mask=None) -> torch.Tensor:
         """Zero-shot editing (in-painting, out-painting, class-conditional editing): the loop of demo_zero_shot_edit.ipynb (cell 2) as a

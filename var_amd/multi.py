@@ -24,8 +24,14 @@ def shard_range(B_total: int, rank: int, world: int):
 
 def sample_sharded(var, B_total: int, label_B: torch.Tensor, g_seed: Optional[int], cfg: float = 1.5, top_k: int = 0, top_p: float = 0.0,
                    rng_mode: str = 'exact', gather: bool = True, sample_fn: Optional[Callable] = None,
-                   rank: Optional[int] = None, world: Optional[int] = None, gather_events: Optional[list] = None) -> torch.Tensor:
+                   rank: Optional[int] = None, world: Optional[int] = None, gather_events: Optional[list] = None,
+                   g_seeds=None, more_smooth: bool = False, return_tokens: bool = False) -> torch.Tensor:
     """Sample `B_total` images split evenly over the ranks; returns all images on every rank (gather=True) or the local shard.
+
+    g_seeds (B_total seeds, the same on every rank): the batch goes through VAR.autoregressive_infer_cfg_per_image — cfg, top_k and top_p may
+    then be B_total values each; every rank passes its slice of the seeds and parameters, draws the rows of its own images only, and the
+    gathered result is the one-GPU per-image call's by construction (a request's result does not depend on its batch).  g_seed, rng_mode and
+    sample_fn are not used; return_tokens=True returns (images, (B, L) tokens).
 
     `label_B`: the GLOBAL int64 label vector (same on every rank).  `sample_fn(B_local, labels_local, noise_fn)` defaults to the
     HIP engine; the CPU tests of the sharding logic substitute a stand-in.  `gather_events`: a list that receives one (start, end) pair of
@@ -34,6 +40,22 @@ def sample_sharded(var, B_total: int, label_B: torch.Tensor, g_seed: Optional[in
     world = dist.get_world_size() if world is None else world
     lo, hi = shard_range(B_total, rank, world)
     B_local = hi - lo
+    if g_seeds is not None:
+        def cut(x, name):
+            if isinstance(x, (list, tuple, torch.Tensor)) and not (isinstance(x, torch.Tensor) and x.dim() == 0):
+                if len(x) != B_total:
+                    raise ValueError(f'{name} must be a scalar or {B_total} values, got {len(x)}')
+                return x[lo:hi]
+            return x
+        if not isinstance(g_seeds, (list, tuple, torch.Tensor)) or len(g_seeds) != B_total or len(label_B) != B_total:
+            raise ValueError(f'g_seeds and label_B must hold {B_total} values')
+        img, tok = var.autoregressive_infer_cfg_per_image(label_B[lo:hi], g_seeds[lo:hi], cfg=cut(cfg, 'cfg'), top_k=cut(top_k, 'top_k'),
+                                                          top_p=cut(top_p, 'top_p'), more_smooth=more_smooth, return_tokens=True)
+        if gather and world > 1:
+            img, tok = dist.allgather(img, cat=True), dist.allgather(tok, cat=True)
+        return (img, tok) if return_tokens else img
+    if return_tokens or more_smooth:
+        raise ValueError('return_tokens and more_smooth belong to the per-image path: pass g_seeds')
     dev = var.lvl_1L.device
     V = var.V
     rng = var.rng
