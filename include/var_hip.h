@@ -201,6 +201,7 @@ int varhip_first_map_f32(const float* class_emb, const int64_t* labels, int num_
  *   out_mode 0: out is [B][H][W][Cout];  out_mode 1: out is [B][Cout][H][W] and holds (clamp(v,-1,1)+1)*0.5
  *             (vqvae.py:63 clamp_ and var.py:190 add_(1).mul_(0.5) fused into the last conv);
  *   out_mode 2: [B][Cout][H][W] holding clamp(v,-1,1) only (VQVAE.fhat_to_img's own contract)
+ *   out_mode 3: [B][Cout][H][W] holding v itself (VQVAE.forward, vqvae.py:59: the decoder's output without a clamp)
  * replaces every Conv2d(k=3) of basic_vae.py (ResnetBlock :48,:51; conv_in :180; conv_out :208; Upsample2x :25)
  * and vqvae.py:49 post_quant_conv.   Constraints: Cin % 32 == 0 (a K tile of the implicit GEMM lies inside one tap); the input
  * samples one 128-pixel tile can touch (one sample when H*W >= 128) plus one row must span < 2 GiB and the packed weights < 4 GiB
@@ -233,6 +234,7 @@ int varhip_gn_apply_f32(const float* x, const float* stats, const float* gamma, 
 
 /* the decoder's tail in one pass (basic_vae.py:224-226 norm_out -> swish -> conv_out, the callers' clamp vqvae.py:63 and (x + 1) / 2 var.py:190):
  * out = clamp(conv3x3(SiLU(GroupNorm(x))) + bias, -1, 1) as fp32 NCHW (out_mode 2) or de-normalised to [0, 1] (out_mode 1); stats [B][G][2] = (mean, rstd).
+ * out_mode 3: no clamp (vqvae.py:59, VQVAE.forward): the value modes 1 and 2 clamp, stored as it is.
  * Bit-identical to varhip_gn_apply_f32 (silu = 1) followed by varhip_conv3x3_nhwc_f32 (same out_mode): same operations per element, same
  * chunk / tap / channel summation order.  Shapes it does not take (H % 8, W % 32, Cin % 32, Cout > 4): VARHIP_EINVAL. */
 int varhip_gn_silu_conv_out_f32(const float* x, const float* stats, const float* gamma, const float* beta, const float* w, const float* bias,
@@ -391,6 +393,31 @@ int varhip_nearest_code_f32(const float* z, const float* codebook, int64_t* idx_
 /* the same lookup for VectorQuantizer2(using_znorm=True) (quant.py:151-153): idx[n] = argmax_v (z_n / max(|z_n|,1e-12)) . (e_v / max(|e_v|,1e-12)),
  * first index on ties; every element is divided by its vector's norm before the (c-ascending fma) dot product, as F.normalize does */
 int varhip_nearest_code_cos_f32(const float* z, const float* codebook, int64_t* idx_out, int N, int V, int Cv, varhip_stream_t stream);
+
+/* ---- VectorQuantizer2.forward: the tokenizer's own pass (quant.py:52-104, vqvae.py:56-59) ------------------------------------------------
+ * One scale's statistics, launched behind varhip_quant_residual_f32 of that scale (replaces quant.py:77 `idx_N.bincount(minlength=V)` and
+ * quant.py:95 `F.mse_loss(f_hat, f)`).  f_hat, f: n fp32 elements each (any layout, the same for both); idx: n_idx token ids.
+ *   hits[v] += |{i : idx[i] == v}| for v in [0, V) (int64, the caller zeroes the row): integer atomics only, first in LDS per workgroup
+ *            (V <= 8192), then one global integer add per non-zero bin: exact and independent of the order of execution;
+ *   an index outside [0, V) is neither dereferenced nor counted: *bad (int32, the caller zeroes it) += the number of such indices.  The launch
+ *            is asynchronous, so the return code cannot carry it: the caller that does not trust its indices reads *bad after the stream;
+ *   sum = sum_i ((double)f_hat[i] - (double)f[i])^2 in float64 in one fixed order that depends on n alone (vqstats.hip: per-thread strided
+ *            partials, xor butterfly per wave, four waves in order, G = varhip_vq_stats_blocks(n) workgroup partials in scratch, added the same
+ *            way by a second one-workgroup launch): no floating-point atomics, the same bits on every run;
+ *   *mse_out = (float)(sum / n);  *sum_out = sum when sum_out is not NULL.
+ * scratch: >= VARHIP_VQ_STATS_MAX_BLOCKS doubles.  n < 1, V < 1, n_idx < 0 or > 2^26, a NULL operand: VARHIP_EINVAL. */
+#define VARHIP_VQ_STATS_MAX_BLOCKS 1024
+int varhip_vq_stats_blocks(int64_t n);
+int varhip_vq_scale_stats_f32(const float* f_hat, const float* f, int64_t n, const int64_t* idx, int64_t n_idx, int V, int64_t* hits,
+                              double* scratch, double* sum_out, float* mse_out, int32_t* bad, varhip_stream_t stream);
+/* quant.py:95,97: acc = 0; per scale in order acc = acc + (mse_S[si] * beta + mse_S[si]); *out = acc * (float)(1.0 / S).  fp32, every
+ * operation rounded on its own (no contraction), beta as the fp32 value of the module's float. */
+int varhip_vq_loss_combine_f32(const float* mse_S, int S, float beta, float* out, varhip_stream_t stream);
+/* quant.py:98 `(f_hat.data - f_no_grad).add_(f_BChw)`: v = (f_hat - f) + f per element in fp32, two roundings (not bit-equal to f_hat).
+ * f_hat, f: [B][HW][C] channels-last; out_nhwc (nullable) the same layout, out_nchw (nullable) [B][C][HW], both written in the one pass;
+ * at least one of them.  Bad sizes: VARHIP_EINVAL. */
+int varhip_vq_straight_through_f32(const float* f_hat, const float* f, float* out_nhwc, float* out_nchw, int B, int HW, int C,
+                                   varhip_stream_t stream);
 
 /* ==== 16-bit-input throughput mode ("f16") ===================================================================
  * The reference's harness runs the path under torch.autocast('cuda', dtype=torch.float16) (demo_sample.py:66-68): every F.linear of

@@ -87,6 +87,9 @@ SIGNATURES_HIP_ONLY = {
     'quant_accum_h_edit_f32': [P, P, P, L, P, P, P, P, P, F, P, P, I, I, I, I],   # pinned against an overwrite of h + quant_accum_h_f32
     'cfg_sample_rows_f32': [P, P, P, P, I, I, I, P, P, P, I],         # pinned against cfg_sample_f32 per image (tests/test_per_image_gpu.py)
     'exp1_philox_f32':   [P, I, I, I, I, I, P],                      # pinned against its host twin below (tests/test_per_image_gpu.py)
+    'vq_scale_stats_f32': [P, P, L, P, L, I, P, P, P, P, P],          # pinned against torch.bincount and a numpy float64 sum (tests/test_vae_forward_gpu.py)
+    'vq_loss_combine_f32': [P, I, F, P],                             # pinned against the fp32 sequence in torch
+    'vq_straight_through_f32': [P, P, P, P, I, I, I],                # pinned against (f_hat - f) + f in torch, bit for bit
 }
 
 # plain host functions of the HIP library (no stream argument, no device pointer, no GPU needed); bound by var_amd/hip.py

@@ -492,11 +492,12 @@ __global__ void __launch_bounds__(256) k_dma_gemm(GemmP p) {
             int64_t mo = m;                                                 // output row; phase mode scatters to the 2x grid
             if (CONV) {
                 const int hw = p.H * p.Wd, b = m / hw, rem2 = m - b * hw;
-                if (p.out_mode != 0) {                                      // last conv: NCHW store of <= 3 channels, clamp (+ de-normalise)
+                if (p.out_mode != 0) {                                      // last conv: NCHW store of <= 3 channels, clamp (+ de-normalise); 3: as it is
                     for (int e = 0; e < 4; ++e) {
                         if (n + e >= p.N) break;
-                        const float x = vm_min(vm_max(v[e] + b4[e], -1.0f), 1.0f);
-                        Ob[((int64_t)b * p.N + n + e) * hw + rem2] = p.out_mode == 1 ? (x + 1.0f) * 0.5f : x;
+                        const float r = v[e] + b4[e];
+                        const float x = vm_min(vm_max(r, -1.0f), 1.0f);
+                        Ob[((int64_t)b * p.N + n + e) * hw + rem2] = p.out_mode == 3 ? r : (p.out_mode == 1 ? (x + 1.0f) * 0.5f : x);
                     }
                     continue;
                 }
@@ -694,7 +695,7 @@ static int conv3x3_impl(const float* in, const float* w, const float* bias, cons
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 31) || !bias) return VARHIP_EINVAL;
     if (gn_part && (out_mode != 0 || !varhip_conv_gn_blocks(H, W, Cout, 0))) return VARHIP_EINVAL;
     if (up2 && ((H & 1) || (W & 1))) return VARHIP_EINVAL;
-    if (out_mode < 0 || out_mode > 2 || (out_mode != 0 && resid)) return VARHIP_EINVAL;
+    if (out_mode < 0 || out_mode > 3 || (out_mode != 0 && resid)) return VARHIP_EINVAL;
     if ((int64_t)B * H * W >= (1ll << 31)) return VARHIP_EINVAL;
     GemmP p{};
     p.A = in; p.W = w; p.bias = bias; p.out = out; p.resid = resid; p.gamma = nullptr;

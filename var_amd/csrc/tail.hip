@@ -105,8 +105,9 @@ __global__ void __launch_bounds__(256) k_gnconv32o(TailP p) {
     const int y = ty0 + ty, x = tx0 + tx;
 #pragma unroll
     for (int n = 0; n < NOUT; ++n) {
-        const float v = vm_min(vm_max(acc[n] + p.bias[n], -1.0f), 1.0f);
-        p.out[((int64_t)b * NOUT + n) * hw + y * p.Wd + x] = p.out_mode == 1 ? (v + 1.0f) * 0.5f : v;
+        const float r = acc[n] + p.bias[n];
+        const float v = vm_min(vm_max(r, -1.0f), 1.0f);
+        p.out[((int64_t)b * NOUT + n) * hw + y * p.Wd + x] = p.out_mode == 3 ? r : (p.out_mode == 1 ? (v + 1.0f) * 0.5f : v);
     }
 }
 
@@ -117,14 +118,14 @@ template <int NOUT> static int launch_tail(const TailP& p, int B, size_t lds, hi
     return vh_launch_status();
 }
 
-// out = clamp(conv3x3(SiLU(GroupNorm(x))) + bias, -1, 1) as fp32 NCHW (out_mode 2), de-normalised to [0, 1] (out_mode 1): x [B][H][W][Cin]
+// out = clamp(conv3x3(SiLU(GroupNorm(x))) + bias, -1, 1) as fp32 NCHW (out_mode 2), de-normalised to [0, 1] (out_mode 1), unclamped (out_mode 3): x [B][H][W][Cin]
 // channels-last, stats [B][G][2] = (mean, rstd) as varhip_gn_stats_f32 / varhip_gn_stats_part_f32 leave them, w [Cout][3][3][Cin].
 // Takes maps that tile into 8 x 32 patches with Cin % 32 == 0 and Cout <= 4; anything else: VARHIP_EINVAL (the caller then runs
 // varhip_gn_apply_f32 + varhip_conv3x3_nhwc_f32, which this call equals bit for bit).
 extern "C" int varhip_gn_silu_conv_out_f32(const float* x, const float* stats, const float* gamma, const float* beta, const float* w, const float* bias,
                                            float* out, int B, int H, int W, int Cin, int Cout, int G, int out_mode, varhip_stream_t stream) {
     if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || G <= 0 || !x || !stats || !gamma || !beta || !w || !bias || !out) return VARHIP_EINVAL;
-    if ((H % 8) || (W % 32) || (Cin % 32) || (Cin % G) || Cout > 4 || (out_mode != 1 && out_mode != 2)) return VARHIP_EINVAL;
+    if ((H % 8) || (W % 32) || (Cin % 32) || (Cin % G) || Cout > 4 || (out_mode < 1 || out_mode > 3)) return VARHIP_EINVAL;
     if ((((uintptr_t)x) & 15) || (int64_t)H * W * Cin >= (1ll << 31) || (int64_t)B * (H / 8) * (W / 32) >= (1ll << 31)) return VARHIP_EINVAL;
     const size_t lds = ((size_t)10 * 34 * 36 + (size_t)4 * Cin) * sizeof(float);
     if (lds > 64 * 1024) return VARHIP_EINVAL;

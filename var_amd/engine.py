@@ -275,19 +275,21 @@ class DecoderEngine(_VaeOps):
         hip.call('gn_apply_f32', x, stats, self.w[key + '.weight'], self.w[key + '.bias'], out, B, HW, x.shape[-1], 32, int(silu))
         return out
 
-    def tail(self, h, B, Hh, Ww, denorm):
+    def tail(self, h, B, Hh, Ww, denorm, clamp=True):
         """norm_out -> swish -> conv_out -> clamp (-> (x + 1) / 2) (basic_vae.py:224-226, vqvae.py:63, var.py:190): one pass over the map
-        (varhip_gn_silu_conv_out_f32) where it tiles into 8 x 32 patches, else GroupNorm apply + conv — the same bits either way"""
+        (varhip_gn_silu_conv_out_f32) where it tiles into 8 x 32 patches, else GroupNorm apply + conv — the same bits either way.
+        clamp=False: conv_out's value as it is (out_mode 3; vqvae.py:59, VQVAE.forward)"""
         wt = self.w['decoder.conv_out.weight']
         Cout, Cin = wt.shape[0], wt.shape[3]
+        mode = 3 if not clamp else (1 if denorm else 2)
         if Hh % 8 == 0 and Ww % 32 == 0 and Cin % 32 == 0 and Cout <= 4 and (10 * 34 * 36 + 4 * Cin) * 4 <= 64 * 1024 and not self.unfused_tail:
             stats = self.gn_stats(h, B, Hh * Ww)
             out = torch.empty((B, Cout, Hh, Ww), dtype=torch.float32, device=h.device)
             hip.call('gn_silu_conv_out_f32', h, stats, self.w['decoder.norm_out.weight'], self.w['decoder.norm_out.bias'], wt,
-                     self.w['decoder.conv_out.bias'], out, B, Hh, Ww, Cin, Cout, 32, 1 if denorm else 2)
+                     self.w['decoder.conv_out.bias'], out, B, Hh, Ww, Cin, Cout, 32, mode)
             return out
         h = self.gn(h, 'decoder.norm_out', B, Hh * Ww, True)
-        return self.conv3(h, 'decoder.conv_out', B, Hh, Ww, out_mode=1 if denorm else 2)
+        return self.conv3(h, 'decoder.conv_out', B, Hh, Ww, out_mode=mode)
 
     def lin(self, x2d, key, resid=None):
         wt = self.w[key + '.weight']
@@ -498,12 +500,15 @@ class DecoderEngine(_VaeOps):
                 h = up
         return self.tail16(h, B, Hh, Ww, denorm)
 
-    def decode_nhwc(self, f_hat: torch.Tensor, denorm: bool = True, precision: Optional[str] = None) -> torch.Tensor:
+    def decode_nhwc(self, f_hat: torch.Tensor, denorm: bool = True, precision: Optional[str] = None, clamp: bool = True) -> torch.Tensor:
         """[B,P,P,Cvae] channels-last -> [B,3,16P,16P]; denorm=True: in [0,1] (clamp and (x+1)/2 fused into the last conv, what
-        autoregressive_infer_cfg returns); denorm=False: clamped to [-1,1] (VQVAE.fhat_to_img's contract).
+        autoregressive_infer_cfg returns); denorm=False: clamped to [-1,1] (VQVAE.fhat_to_img's contract); clamp=False: the decoder's
+        output as it is (VQVAE.forward, vqvae.py:59; fp32 only, denorm is ignored).
         precision: 'f32' / 'f16' / 'bf16' for THIS call (None: the engine's default, `self.precision`)"""
         self.refresh()
         prec = precision or self.precision
+        if not clamp and prec != 'f32':
+            raise hip.VarHipError('decode_nhwc(clamp=False) is the fp32 decoder only')
         self.flops_precision = prec
         if prec != 'f32':
             self._ensure16(prec)
@@ -535,7 +540,7 @@ class DecoderEngine(_VaeOps):
                 else:
                     hip.call('upconv_phase_f32', h, wp, self.w[key + '.bias'], up, B, Hh, Ww, wp.shape[4], wp.shape[1])
                 h = up
-        return self.tail(h, B, Hh, Ww, denorm)
+        return self.tail(h, B, Hh, Ww, denorm, clamp)
 
 
 class QuantizerEngine:
@@ -566,9 +571,11 @@ class QuantizerEngine:
         return self._taps[(pn, P)]
 
     @torch.no_grad()
-    def quantize(self, f_nhwc: torch.Tensor, to_fhat: bool, patch_nums, last_fhat: bool = False):
+    def quantize(self, f_nhwc: torch.Tensor, to_fhat: bool, patch_nums, last_fhat: bool = False, stats: Optional[dict] = None):
         """residual quantisation scale by scale (quant.py:147-164): idx lists (B, pn^2) int64, or the cumulative f_hat's (NCHW).
-        last_fhat=True (with to_fhat False): (idx lists, the last f_hat (B, Cvae, P, P)) from the one pass"""
+        last_fhat=True (with to_fhat False): (idx lists, the last f_hat (B, Cvae, P, P)) from the one pass.
+        stats (a dict, with to_fhat False): one varhip_vq_scale_stats_f32 launch behind every scale fills it with hits_SV (S, V) int64,
+        mse_S (S,) fp32, sum_S (S,) fp64, bad (1,) int32 and f_hat_nhwc, the final channels-last f_hat (quant.py:77,95)"""
         self.refresh()
         B, P, _, Cv = f_nhwc.shape
         dev = f_nhwc.device
@@ -576,6 +583,11 @@ class QuantizerEngine:
         f_hat = torch.zeros_like(f_rest)
         up = torch.empty_like(f_rest)
         S, out = len(patch_nums), []
+        if stats is not None:
+            V = self.codebook.shape[0]
+            stats.update(hits_SV=torch.zeros((S, V), dtype=torch.int64, device=dev), mse_S=torch.empty(S, dtype=torch.float32, device=dev),
+                         sum_S=torch.empty(S, dtype=torch.float64, device=dev), bad=torch.zeros(1, dtype=torch.int32, device=dev), f_hat_nhwc=f_hat)
+            scratch = torch.empty(hip.VQ_STATS_MAX_BLOCKS, dtype=torch.float64, device=dev)
         for si, pn in enumerate(patch_nums):
             if si != S - 1:
                 z = torch.empty((B, pn * pn, Cv), dtype=torch.float32, device=dev)
@@ -588,10 +600,31 @@ class QuantizerEngine:
             ti, tw = self.taps(pn, P, dev) if pn != P else (None, None)
             pw, pb, ratio = self.phi[phi_index(si, S, len(self.phi))]
             hip.call('quant_residual_f32', idx, self.codebook, ti, tw, pw, pb, ratio, up, f_hat, f_rest, B, pn, P, Cv)
+            if stats is not None:
+                hip.call('vq_scale_stats_f32', f_hat, f_nhwc, f_hat.numel(), idx, B * pn * pn, V, stats['hits_SV'][si], scratch,
+                         stats['sum_S'][si:], stats['mse_S'][si:], stats['bad'])
             out.append(f_hat.permute(0, 3, 1, 2).contiguous() if to_fhat else idx.view(B, pn * pn))
         if last_fhat and not to_fhat:
             return out, f_hat.permute(0, 3, 1, 2).contiguous()
         return out
+
+    @torch.no_grad()
+    def quantize_stats(self, f_nhwc: torch.Tensor, patch_nums, beta: float, nchw: bool = True) -> dict:
+        """VectorQuantizer2.forward on HIP (quant.py:52-104): quantize() with its per-scale statistics, the loss combine (quant.py:95,97) and the
+        straight-through value (quant.py:98).  -> dict(idx_Bl, hits_SV, mse_S, sum_S, bad, vq_loss (0-dim fp32), f_hat_raw (B, P, P, Cvae) the
+        accumulated f_hat, f_hat_st_nhwc (f_hat - f) + f channels-last for the decoder, f_hat_st (B, Cvae, P, P) when nchw).  No host sync."""
+        f_nhwc = f_nhwc.contiguous()
+        st = {}
+        st['idx_Bl'] = self.quantize(f_nhwc, False, patch_nums, stats=st)
+        B, P, _, Cv = f_nhwc.shape
+        loss = torch.empty(1, dtype=torch.float32, device=f_nhwc.device)
+        hip.call('vq_loss_combine_f32', st['mse_S'], len(patch_nums), float(beta), loss)
+        st['vq_loss'] = loss[0]
+        st['f_hat_raw'] = st.pop('f_hat_nhwc')
+        st['f_hat_st_nhwc'] = torch.empty_like(f_nhwc)
+        st['f_hat_st'] = torch.empty((B, Cv, P, P), dtype=torch.float32, device=f_nhwc.device) if nchw else None
+        hip.call('vq_straight_through_f32', st['f_hat_raw'], f_nhwc, st['f_hat_st_nhwc'], st['f_hat_st'], B, P * P, Cv)
+        return st
 
     @torch.no_grad()
     def fhat_from_scales(self, items, patch_nums, from_tokens: bool, last_one: bool):

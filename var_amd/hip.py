@@ -29,6 +29,7 @@ class _Lib:
         so.varhip_conv16_force_tile.argtypes = [ctypes.c_int]; so.varhip_conv16_force_tile.restype = ctypes.c_int
         so.varhip_gemm16_persistent.argtypes = [ctypes.c_int]; so.varhip_gemm16_persistent.restype = ctypes.c_int
         so.varhip_sampler_force_walk.argtypes = [ctypes.c_int]; so.varhip_sampler_force_walk.restype = ctypes.c_int
+        so.varhip_vq_stats_blocks.argtypes = [ctypes.c_int64]; so.varhip_vq_stats_blocks.restype = ctypes.c_int
         self.host = {}
         for name, args in abi.SIGNATURES_HOST.items():
             fn = getattr(so, 'varhip_' + name)
@@ -97,6 +98,14 @@ def conv_gn_blocks(H, W, Cout, phase=False) -> int:
 def conv16_gn_fusable(B, H, W, Cin, Cout) -> bool:
     """can the 16-bit conv apply the GroupNorm + SiLU in front of it to its own input patch (varhip_gnconv3x3_nhwc_*)?"""
     return bool(lib().fn['conv16_gn_fusable'](B, H, W, Cin, Cout))
+
+
+VQ_STATS_MAX_BLOCKS = 1024      # VARHIP_VQ_STATS_MAX_BLOCKS of include/var_hip.h: doubles of scratch varhip_vq_scale_stats_f32 takes
+
+
+def vq_stats_blocks(n: int) -> int:
+    """workgroup partials of varhip_vq_scale_stats_f32's float64 sum over n elements (its summation order depends on n through this alone)"""
+    return int(lib().so.varhip_vq_stats_blocks(n))
 
 
 # ---- timing table --------------------------------------------------------------------------------------------------

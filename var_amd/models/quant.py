@@ -3,14 +3,25 @@
 The GPU sampling loop does NOT go through these methods: var_amd.engine runs the fused HIP quantizer step
 (varhip_quant_accum_f32 / varhip_next_map_f32) on `embedding` and the Phi convolutions held here.  The PyTorch methods
 below keep the encode / teacher-forcing API (trainer.py:105-111, fork scripts) available on any device."""
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
-from torch import nn
+from torch import distributed as tdist, nn
 from torch.nn import functional as F
 
-__all__ = ['VectorQuantizer2']
+from .. import dist
+
+__all__ = ['VectorQuantizer2', 'VQStats']
+
+
+class VQStats(NamedTuple):
+    """what VectorQuantizer2.forward_stats returns"""
+    f_hat: torch.Tensor                 # (B, Cvae, H, W) the straight-through value (f_hat - f) + f
+    idx_Bl: List[torch.Tensor]          # per scale (B, pn^2) int64 token ids
+    hits_SV: torch.Tensor               # (S, V) int64: this batch's (this rank's) code histogram per scale
+    mse_S: torch.Tensor                 # (S,) fp32: mse(f_hat after scale si, f)
+    vq_loss: torch.Tensor               # 0-dim fp32: sum_si (mse * beta + mse) * (1 / S)
 
 
 class Phi(nn.Conv2d):
@@ -93,7 +104,74 @@ class VectorQuantizer2(nn.Module):
         return f'{self.v_patch_nums}, znorm={self.using_znorm}, beta={self.beta}  |  S={len(self.v_patch_nums)}, quant_resi={self.quant_resi_ratio}'
 
     def forward(self, f_BChw, ret_usages=False):
-        raise NotImplementedError('VectorQuantizer2.forward is VAE *training* (reference quant.py:52-104): out of scope of the sampling-path build')
+        """the tokenizer's own pass (reference quant.py:52-104) -> (f_hat, usages, mean_vq_loss): forward_stats minus fields plus `usages`, which
+        are read from the buffer ema_vocab_hit_SV (quant.py:100-103).  One deviation: the reference calls torch.distributed.get_world_size()
+        unconditionally and raises without a process group; here the world size is 1 then."""
+        st = self.forward_stats(f_BChw)
+        return st.f_hat, (self._usages(f_BChw) if ret_usages else None), st.vq_loss
+
+    def _usages(self, f_BChw) -> List[float]:
+        world = tdist.get_world_size() if (tdist.is_available() and tdist.is_initialized()) else 1
+        margin = world * (f_BChw.numel() / f_BChw.shape[1]) / self.vocab_size * 0.08
+        return [(self.ema_vocab_hit_SV[si] >= margin).float().mean().item() * 100 for si in range(len(self.v_patch_nums))]
+
+    def _forward_on_hip(self, f: torch.Tensor) -> bool:
+        """the HIP route of forward / forward_stats: fp32 CUDA map, autograd off, square, and no EMA update to make"""
+        return (f.dim() == 4 and f.dtype == torch.float32 and f.shape[-1] == f.shape[-2] and self._hip_eligible(f)
+                and self.v_patch_nums[-1] == f.shape[-1] and not (self.training and dist.initialized()))
+
+    def forward_stats(self, f_BChw: torch.Tensor) -> VQStats:
+        """forward's pass with everything it computes on the way: tokens, per-scale histogram and mse, loss, straight-through f_hat"""
+        if self._forward_on_hip(f_BChw):
+            from .. import hip
+            B, C, H, W = f_BChw.shape
+            nhwc = torch.empty(B, H, W, C, dtype=torch.float32, device=f_BChw.device)
+            hip.call('nchw_to_nhwc_f32', f_BChw.contiguous(), nhwc, B, C, H * W)
+            return self._stats_hip(nhwc, nchw=True)[0]
+        return self._stats_torch(f_BChw)
+
+    def _stats_hip(self, f_nhwc: torch.Tensor, nchw: bool):
+        """-> (VQStats, the straight-through f_hat channels-last for the decoder); VQStats.f_hat is None unless nchw"""
+        st = self.hip_engine().quantize_stats(f_nhwc, tuple(self.v_patch_nums), float(self.beta), nchw=nchw)
+        return VQStats(st['f_hat_st'], st['idx_Bl'], st['hits_SV'], st['mse_S'], st['vq_loss']), st['f_hat_st_nhwc']
+
+    def _stats_torch(self, f_BChw: torch.Tensor) -> VQStats:
+        """reference quant.py:52-98 in PyTorch, any device, with autograd: the commitment term mse(f_hat.data, f) reaches f only, the
+        codebook term mse(f_hat, f.detach()) the codebook and Phi only, and f_hat's gradient passes straight through to f"""
+        if f_BChw.dtype != torch.float32: f_BChw = f_BChw.float()
+        B, C, H, W = f_BChw.shape
+        f_no_grad = f_BChw.detach()
+        f_rest = f_no_grad.clone()
+        f_hat = torch.zeros_like(f_rest)
+        SN = len(self.v_patch_nums)
+        ema = self.training and dist.initialized()
+        idx_Bl, hits, mses = [], [], []
+        with torch.autocast(device_type=f_BChw.device.type, enabled=False):
+            loss = 0.0
+            for si, pn in enumerate(self.v_patch_nums):
+                z = F.interpolate(f_rest, size=(pn, pn), mode='area') if si != SN - 1 else f_rest
+                idx_N = self._nearest(z.permute(0, 2, 3, 1).reshape(-1, C))
+                hit_i = idx_N.bincount(minlength=self.vocab_size)
+                hits.append(hit_i)
+                if ema:
+                    hit_V = hit_i.float()
+                    handler = tdist.all_reduce(hit_V, async_op=True)
+                h = self._lift(self.embedding(idx_N.view(B, pn, pn)).permute(0, 3, 1, 2), si, SN, (H, W))
+                f_hat = f_hat + h
+                f_rest.sub_(h.detach())
+                if ema:
+                    handler.wait()
+                    if self.record_hit == 0: self.ema_vocab_hit_SV[si].copy_(hit_V)
+                    elif self.record_hit < 100: self.ema_vocab_hit_SV[si].mul_(0.9).add_(hit_V.mul(0.1))
+                    else: self.ema_vocab_hit_SV[si].mul_(0.99).add_(hit_V.mul(0.01))
+                    self.record_hit += 1
+                m = F.mse_loss(f_hat, f_no_grad)
+                loss = loss + (F.mse_loss(f_hat.detach(), f_BChw).mul_(self.beta) + m)
+                mses.append(m.detach())
+                idx_Bl.append(idx_N.view(B, pn * pn))
+            loss = loss * (1. / SN)
+            f_hat = (f_hat.detach() - f_no_grad).add_(f_BChw)
+        return VQStats(f_hat, idx_Bl, torch.stack(hits), torch.stack(mses), loss)
 
     # ---- helpers shared by the methods below ---------------------------------------------------------------------
     def _nearest(self, z_NC: torch.Tensor) -> torch.Tensor:

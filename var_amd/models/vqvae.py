@@ -3,13 +3,24 @@
 `fhat_to_img` — the decode half of the sampling path — runs the HIP decoder (var_amd.engine.DecoderEngine) whenever it is
 handed an fp32 CUDA tensor outside autograd; anything else (CPU tensors, autograd, half precision) takes the PyTorch
 modules, which exist for the encode side and for API users, not for the measured path."""
-from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
 
+from .. import dist
 from .basic_vae import Decoder, Encoder
 from .quant import VectorQuantizer2
+
+
+class VAEStats(NamedTuple):
+    """what VQVAE.forward_stats returns: VQStats (models/quant.py) plus the reconstruction"""
+    f_hat: torch.Tensor
+    idx_Bl: List[torch.Tensor]
+    hits_SV: torch.Tensor
+    mse_S: torch.Tensor
+    vq_loss: torch.Tensor
+    rec: torch.Tensor                   # (B, 3, H, W) decoder(post_quant_conv(f_hat)), NOT clamped
 
 
 class VQVAE(nn.Module):
@@ -55,7 +66,32 @@ class VQVAE(nn.Module):
 
     # ---- encode side / utilities: PyTorch, API kept (reference vqvae.py:56-98) ---------------------------------------
     def forward(self, inp, ret_usages=False):
-        raise NotImplementedError('VQVAE.forward is VAE training (reference vqvae.py:56-59): out of scope of the sampling-path build')
+        """encode, quantise with the VQ loss, decode WITHOUT clamp (reference vqvae.py:56-59) -> (rec, usages, vq_loss)"""
+        st, f = self._forward_impl(inp, want_fhat=False)
+        return st.rec, (self.quantize._usages(f) if ret_usages else None), st.vq_loss
+
+    def forward_stats(self, inp) -> VAEStats:
+        """forward's pass with everything it computes on the way"""
+        return self._forward_impl(inp, want_fhat=True)[0]
+
+    def _forward_on_hip(self, x: torch.Tensor) -> bool:
+        """fp32 CUDA image outside autograd whose map is square and matches the quantizer's last scale, and the quantizer's own HIP conditions"""
+        q = self.quantize
+        return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.shape[-1] == x.shape[-2]
+                and x.shape[-1] % 16 == 0 and self.quant_conv.kernel_size == (3, 3) and self.post_quant_conv.kernel_size == (3, 3)
+                and q._hip_eligible(x) and q.v_patch_nums[-1] == x.shape[-1] // 16 and not (q.training and dist.initialized()))
+
+    def _forward_impl(self, inp, want_fhat: bool):
+        """-> (VAEStats, a tensor with f's shape for the usages margin).  HIP: encoder, quantizer with its statistics and decoder stay
+        channels-last (f_hat is transposed to NCHW only when the caller wants it); anything else: the PyTorch modules, with autograd."""
+        if self._forward_on_hip(inp):
+            f = self._encoder_engine().encode(inp)
+            st, st_nhwc = self.quantize._stats_hip(f, nchw=want_fhat)
+            rec = self._decoder_engine().decode_nhwc(st_nhwc, precision='f32', clamp=False)
+            return VAEStats(*st, rec), f.permute(0, 3, 1, 2)
+        f = self.quant_conv(self.encoder(inp))
+        st = self.quantize.forward_stats(f)
+        return VAEStats(*st, self.decoder(self.post_quant_conv(st.f_hat))), f
 
     def _encoder_engine(self):
         if self._hip_encoder is None:
