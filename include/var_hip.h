@@ -419,6 +419,35 @@ int varhip_vq_loss_combine_f32(const float* mse_S, int S, float beta, float* out
 int varhip_vq_straight_through_f32(const float* f_hat, const float* f, float* out_nhwc, float* out_nchw, int B, int HW, int C,
                                    varhip_stream_t stream);
 
+/* ---- validation metrics (VAR.evaluate; reference trainer.py:54-84 eval_ep, :126-156 the L_* / acc_* / z_voc_usage logging block) -------------
+ * One scale of one pass, launched behind the head of that scale; replaces trainer.py:72-75 (F.cross_entropy and argmax over the (B, L, V)
+ * logits tensor) and :140,151-153 without that tensor.  logits: the head's fp32 output, R rows of l tokens, row r * l + t; gt[r * ld_gt + t]
+ * the ground-truth token; the four outputs share one addressing, out[r * ld_out + t].  With z the row:
+ *   nll    = -((z_gt - max z) - log(sum exp(z - max z))): the negated value of varhip_token_loglik_f32 for the same row, bit for bit (one piece
+ *            of device code, rowlse.h);
+ *   pred   = the lowest index of max z (+0 == -0); a row holding a NaN gives its lowest NaN index (torch.argmax; varhip_cfg_argmax_f32's rule);
+ *   rank   = |{v : z_v > z_gt or (z_v == z_gt and v < gt)}| (varhip_token_score_f32's total order; a NaN compares false);
+ *   smooth = (float)((double)z_gt - sum / V), sum = sum_v (double)z_v in float64 in one order that depends on V alone (lane i of 64 adds the
+ *            elements j * 256 + 4 * i + c in ascending (j, c) order, the lanes by the xor butterfly 32 .. 1);
+ *            nn.CrossEntropyLoss(label_smoothing=e) of the row is nll + e * smooth.
+ * A token outside [0, V) is never dereferenced: nll = smooth = NaN, rank = -1 (pred is still the row's argmax).  V < 2^24.
+ * On a row holding a NaN, nll is what varhip_token_loglik_f32 gives there (NaN when z_gt is the NaN; otherwise its register path drops the NaN
+ * element from the exponential sum and its scalar path propagates it) and smooth is NaN.
+ * Bad sizes (R, l, V < 1, ld_gt < l, ld_out < l) or a NULL operand: VARHIP_EINVAL. */
+int varhip_token_eval_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int R, int l, int V, float* nll, float* smooth,
+                          int64_t* pred, int32_t* rank, int64_t ld_out, varhip_stream_t stream);
+/* Once per call, over the [N][ld] per-token arrays varhip_token_eval_f32 filled; begin_S1: a HOST array of S + 1 int32 token offsets, begin[0] = 0,
+ * strictly ascending, begin[S] = L <= ld, 1 <= S <= 32.  Per scale s (replaces the per-scale loop of trainer.py:149-155 and the sums of :72-75):
+ *   nll_S[s], smooth_S[s] = the float64 sums over the N * l_s tokens of the scale, every addition in float64 in one fixed order that depends on
+ *            (N, l_s) alone: element i = image * l_s + token, thread t of 256 adds i = t, t + 256, ... ascending, a wave its lanes by the xor
+ *            butterfly, the workgroup its four waves in order (the scheme of varhip_vq_scale_stats_f32); no floating-point atomics;
+ *   correct_S[s] = |{tokens with rank == 0}| (int64; an out-of-range gt has rank -1 and never counts).
+ * pred_hist_V[v] += |{tokens with pred == v}| (int64, the caller zeroes it; replaces trainer.py:140 bincount): integer atomics only, in LDS
+ * first for V <= 8192; a pred outside [0, V) is not counted.  N * L <= 2^26.  Bad sizes or a NULL operand: VARHIP_EINVAL. */
+int varhip_eval_reduce_f32(const float* nll, const float* smooth, const int64_t* pred, const int32_t* rank, int64_t ld, int N,
+                           const int32_t* begin_S1, int S, int V, double* nll_S, double* smooth_S, int64_t* correct_S,
+                           int64_t* pred_hist_V, varhip_stream_t stream);
+
 /* ==== 16-bit-input throughput mode ("f16") ===================================================================
  * The reference's harness runs the path under torch.autocast('cuda', dtype=torch.float16) (demo_sample.py:66-68): every F.linear of
  * basic_var.py then computes in fp16 and attention takes the flash path with fp16 q/k/v (basic_var.py:97,113).  These entry points are

@@ -90,6 +90,8 @@ SIGNATURES_HIP_ONLY = {
     'vq_scale_stats_f32': [P, P, L, P, L, I, P, P, P, P, P],          # pinned against torch.bincount and a numpy float64 sum (tests/test_vae_forward_gpu.py)
     'vq_loss_combine_f32': [P, I, F, P],                             # pinned against the fp32 sequence in torch
     'vq_straight_through_f32': [P, P, P, P, I, I, I],                # pinned against (f_hat - f) + f in torch, bit for bit
+    'token_eval_f32':    [P, P, L, I, I, I, P, P, P, P, L],             # pinned against float64, torch.argmax and the rank's definition (tests/test_evaluate_gpu.py)
+    'eval_reduce_f32':   [P, P, P, P, L, I, P, I, I, P, P, P, P],       # pinned against numpy float64 sums and torch.bincount; begin_S1 is a host array
 }
 
 # plain host functions of the HIP library (no stream argument, no device pointer, no GPU needed); bound by var_amd/hip.py

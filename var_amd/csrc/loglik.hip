@@ -7,14 +7,7 @@
 // Where the row fits (V <= 256 * NV, V % 4 == 0, 16-byte aligned rows) it is read once with dwordx4 loads into registers and both passes
 // (max, then the exponential sum) run there; anything else re-reads the row from the caches for the second pass.
 #include "common.h"
-
-template <bool CFG>
-__device__ __forceinline__ float ll_z(const float* lc, const float* lu, int64_t v, float ca, float cb) {
-    if (!CFG) return lc[v];
-    const float a = ca * lc[v];
-    const float b = cb * lu[v];
-    return a - b;
-}
+#include "rowlse.h"            // the row pass itself, shared with k_token_eval (evalstats.hip)
 
 // NV > 0: the row in NV float4 registers per lane (element j * 256 + 4 * lane + c); NV == 0: any V, scalar loads, two passes over memory
 template <int NV, bool CFG>
@@ -31,39 +24,19 @@ __global__ void __launch_bounds__(256) k_token_loglik(const float* __restrict__ 
     const int k = (int)(w - img * per_img - (int64_t)t * classes);
     const float* lc = logits + (((int64_t)img * classes + k) * l + t) * V;
     const float* lu = logits + (((int64_t)images * classes + img) * l + t) * V;      // unconditional rows follow the class rows
-    float m = -INFINITY, s = 0.f;
+    float m, s;
     if constexpr (NV > 0) {
         f32x4 z[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int e = j * 256 + 4 * lane;
-            if (e < V) {
-                const f32x4 c = *(const f32x4*)(lc + e);
-                if constexpr (CFG) { const f32x4 u = *(const f32x4*)(lu + e); const f32x4 a = ca * c; const f32x4 b = cb * u; z[j] = a - b; }
-                else z[j] = c;
-            } else {
-                z[j] = (f32x4)(-INFINITY);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NV; ++j) m = fmaxf(m, fmaxf(fmaxf(z[j][0], z[j][1]), fmaxf(z[j][2], z[j][3])));
-        m = vh_wave_max(m);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const f32x2 e0 = vh_exp_pair(f32x2{z[j][0] - m, z[j][1] - m});
-            const f32x2 e1 = vh_exp_pair(f32x2{z[j][2] - m, z[j][3] - m});
-            s = ((s + e0[0]) + e0[1]) + (e1[0] + e1[1]);
-        }
+        vh_row_load<NV, CFG>(z, lc, lu, ca, cb, V, lane);
+        vh_row_max_expsum<NV>(z, m, s);
     } else {
-        for (int v = lane; v < V; v += 64) m = fmaxf(m, ll_z<CFG>(lc, lu, v, ca, cb));
-        m = vh_wave_max(m);
-        for (int v = lane; v < V; v += 64) s = s + vm_exp(ll_z<CFG>(lc, lu, v, ca, cb) - m);
+        vh_row_max_expsum_mem<CFG>(lc, lu, ca, cb, V, lane, m, s);
     }
     s = vh_wave_sum(s);
     if (lane == 0) {
         const int64_t g = gt[(int64_t)img * ld_gt + t];
         // a token outside [0, V) is never read: it scores NaN (the host API rejects such tokens before any launch)
-        const float lp = (g >= 0 && g < V) ? (ll_z<CFG>(lc, lu, g, ca, cb) - m) - vm_log(s) : NAN;
+        const float lp = (g >= 0 && g < V) ? vh_row_logp(vh_row_z<CFG>(lc, lu, g, ca, cb), m, s) : NAN;
         out[(int64_t)img * ld_oi + (int64_t)k * ld_oc + t] = lp;
     }
 }

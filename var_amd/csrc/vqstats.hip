@@ -11,21 +11,7 @@
 //   a second one-workgroup launch adds the G partials the same way (thread t: partials t, t + 256, ... ascending; butterfly; four waves).
 #include "common.h"
 
-#define VQ_LDS_BINS 8192          // codebooks up to this size are counted in LDS first (32 KB of uint32); larger ones straight in global memory
-
-__device__ __forceinline__ double vq_wave_sum(double p) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p = p + __shfl_xor(p, off, 64);
-    return p;
-}
-// 256 threads; every thread returns the same value.  red: 4 doubles of LDS.
-__device__ __forceinline__ double vq_block_sum256(double p, double* red) {
-    p = vq_wave_sum(p);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = p;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
+#include "detstats.h"         // the float64 butterfly / four-wave sum and the LDS-first integer histogram, shared with evalstats.hip
 
 extern "C" int varhip_vq_stats_blocks(int64_t n) {
     if (n <= 0) return 0;
@@ -38,28 +24,12 @@ __global__ __launch_bounds__(256) void k_vq_scale_stats(const float* __restrict_
                                                         const int64_t* __restrict__ idx, int64_t n_idx, int V, unsigned long long* __restrict__ hits,
                                                         double* __restrict__ part, int* __restrict__ bad) {
     __shared__ double red[4];
-    __shared__ unsigned int bins[VQ_LDS_BINS];
+    __shared__ unsigned int bins[VH_HIST_LDS_BINS];
     const int tid = threadIdx.x;
     const int64_t i0 = (int64_t)blockIdx.x * 1024;
     if (i0 < n_idx) {
-        const bool lds = V <= VQ_LDS_BINS;
-        if (lds) {
-            for (int v = tid; v < V; v += 256) bins[v] = 0u;
-            __syncthreads();
-        }
-        int nbad = 0;
-        for (int k = 0; k < 4; ++k) {
-            const int64_t i = i0 + k * 256 + tid;
-            if (i >= n_idx) break;
-            const int64_t v = idx[i];
-            if (v < 0 || v >= (int64_t)V) { ++nbad; continue; }                 // never dereferenced, never counted
-            if (lds) atomicAdd(&bins[v], 1u); else atomicAdd(&hits[v], 1ull);
-        }
+        const int nbad = vh_hist_block1024([&](int64_t i) { return idx[i]; }, i0, n_idx, V, hits, bins);
         if (nbad) atomicAdd(bad, nbad);
-        if (lds) {
-            __syncthreads();
-            for (int v = tid; v < V; v += 256) { const unsigned int c = bins[v]; if (c) atomicAdd(&hits[v], (unsigned long long)c); }
-        }
     }
     if ((int)blockIdx.x < G) {                                                   // (uniform per block: the barriers inside are safe)
         const int64_t T = (int64_t)G * 256;
@@ -68,7 +38,7 @@ __global__ __launch_bounds__(256) void k_vq_scale_stats(const float* __restrict_
             const double d = (double)f_hat[i] - (double)f[i];
             s = s + d * d;
         }
-        s = vq_block_sum256(s, red);
+        s = vh_block_sum256_f64(s, red);
         if (tid == 0) part[blockIdx.x] = s;
     }
 }
@@ -77,7 +47,7 @@ __global__ __launch_bounds__(256) void k_vq_stats_final(const double* __restrict
     __shared__ double red[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < G; i += 256) s = s + part[i];
-    s = vq_block_sum256(s, red);
+    s = vh_block_sum256_f64(s, red);
     if (threadIdx.x == 0) {
         if (sum_out) *sum_out = s;
         *mse_out = (float)(s / (double)n);

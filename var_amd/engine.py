@@ -1466,6 +1466,40 @@ class SamplingEngine:
                     hip.call('token_score_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
                              mode, sc['param'], sc['thr'], sc['dist'], V, out[i0:, k0:, cur:], K * Lo, Lo)
 
+    # -- validation metrics (VAR.evaluate) -------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def evaluate(self, gt_tokens: torch.Tensor, label_B: torch.Tensor, max_rows: int) -> dict:
+        """the trainer's validation pass (reference trainer.py:54-84, :126-156) -> dict(nll_BL, smooth_BL (N, L) fp32, pred_BL int64, rank_BL
+        int32, nll_S, smooth_S (S,) float64, correct_S (S,) int64, pred_hist_V (V,) int64).  gt_tokens (N, L) int64 and label_B (N,) int64,
+        already validated by the caller; the labels are used as given.  The images are packed into passes of at most max_rows rows, one row per
+        image; varhip_token_eval_f32 reduces each scale's logits right behind the head, varhip_eval_reduce_f32 the per-token arrays at the
+        end: no (rows, L, V) tensor exists at any time."""
+        var = self.var
+        self.resolve_precision()
+        self.refresh()
+        self._wait_ready()
+        dev = var.pos_start.device
+        L, V, S = var.L, var.V, len(var.patch_nums)
+        gt = gt_tokens.to(dev, torch.int64).contiguous()
+        lab = label_B.to(dev, torch.int64).contiguous()
+        N = gt.shape[0]
+        xin = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in var.begin_ends]).to(dev, torch.float32)
+        out = dict(nll_BL=torch.empty(N, L, dtype=torch.float32, device=dev), smooth_BL=torch.empty(N, L, dtype=torch.float32, device=dev),
+                   pred_BL=torch.empty(N, L, dtype=torch.int64, device=dev), rank_BL=torch.empty(N, L, dtype=torch.int32, device=dev),
+                   nll_S=torch.empty(S, dtype=torch.float64, device=dev), smooth_S=torch.empty(S, dtype=torch.float64, device=dev),
+                   correct_S=torch.empty(S, dtype=torch.int64, device=dev), pred_hist_V=torch.zeros(V, dtype=torch.int64, device=dev))
+        rpp = min(int(max_rows), N)
+        ws = self._tf_workspace(rpp)                                  # sized once: a shorter last pass uses a prefix
+        for i0 in range(0, N, rpp):
+            R = min(rpp, N - i0)
+            for si, cur, l in self._tf_scales(ws, lab[i0:i0 + R].contiguous(), xin[i0:i0 + R].contiguous(), R):
+                hip.call('token_eval_f32', ws['lg'], gt[i0:, cur:], L, R, l, V, out['nll_BL'][i0:, cur:], out['smooth_BL'][i0:, cur:],
+                         out['pred_BL'][i0:, cur:], out['rank_BL'][i0:, cur:], L)
+        begins = torch.tensor([0] + [e for _, e in var.begin_ends], dtype=torch.int32)      # a host array: the launcher copies it into the kernel's arguments
+        hip.call('eval_reduce_f32', out['nll_BL'], out['smooth_BL'], out['pred_BL'], out['rank_BL'], L, N, begins, S, V,
+                 out['nll_S'], out['smooth_S'], out['correct_S'], out['pred_hist_V'])
+        return out
+
     # -- zero-shot classification with per-scale pruning (VAR.classify) -------------------------------------------------------------
     CLASSIFY_MAX_CAND = 16384          # varhip_class_select_f32 stages a stage's totals in LDS
 

@@ -74,6 +74,118 @@ class GenerativeResult(NamedTuple):
     tokens: torch.Tensor
 
 
+class EvalResult:
+    """VAR.evaluate's result: the validation metrics of the trainer (reference trainer.py:54-84 eval_ep, :126-156 the logging block) as SUMS on
+    the model's device, so that batches and ranks can be added (`a + b`, or an all-reduce of the stacked sums) before anything is divided.
+      images       int: N
+      nll_S        (S,) float64: per scale the sum over images and tokens of -log p(gt)
+      smooth_S     (S,) float64: per scale the sum of z_gt - mean_v z_v; CrossEntropyLoss(label_smoothing=e) of a token is nll + e * (z_gt - mean_v z_v)
+      correct_S    (S,) int64: per scale the count of pred == gt;   tokens_S (S,) int64: N * pn^2
+      pred_hist_V  (V,) int64: the histogram of pred over all tokens
+      nll_BL, pred_BL, rank_BL  (N, L) fp32 / int64 / int32: the per-token values; rank = the number of codes ahead of gt in the order z
+                   descending, ties by ascending index (rank < k: gt is in the top k)
+      label_smooth float, as passed;  patch_nums: the scales the result covers (resos: the trainer's names of them, 16 * pn)
+    The derived values are plain Python floats computed in float64 from one device-to-host transfer of the sums."""
+    __slots__ = ('images', 'nll_S', 'smooth_S', 'correct_S', 'tokens_S', 'pred_hist_V', 'nll_BL', 'pred_BL', 'rank_BL', 'label_smooth', 'patch_nums', '_h')
+
+    def __init__(self, images, nll_S, smooth_S, correct_S, tokens_S, pred_hist_V, nll_BL, pred_BL, rank_BL, label_smooth, patch_nums):
+        self.images, self.nll_S, self.smooth_S, self.correct_S, self.tokens_S = int(images), nll_S, smooth_S, correct_S, tokens_S
+        self.pred_hist_V, self.nll_BL, self.pred_BL, self.rank_BL = pred_hist_V, nll_BL, pred_BL, rank_BL
+        self.label_smooth, self.patch_nums = float(label_smooth), tuple(patch_nums)
+        self._h = None
+
+    @property
+    def resos(self) -> tuple:
+        return tuple(16 * pn for pn in self.patch_nums)
+
+    def _host(self):
+        """(nll_S, smooth_S, correct_S, tokens_S, pred_hist_V) as float64 numpy arrays (counts below 2^53 are exact), one transfer"""
+        if self._h is None:
+            S = self.nll_S.shape[0]
+            flat = torch.cat((self.nll_S, self.smooth_S, self.correct_S.double(), self.tokens_S.double(), self.pred_hist_V.double())).cpu().numpy()
+            self._h = (flat[:S], flat[S:2 * S], flat[2 * S:3 * S], flat[3 * S:4 * S], flat[4 * S:])
+        return self._h
+
+    @property
+    def L_mean(self) -> float:
+        """trainer.py:72: the mean cross entropy over every token"""
+        nll, _, _, tok, _ = self._host()
+        return float(nll.sum() / tok.sum())
+
+    @property
+    def L_tail(self) -> float:
+        """trainer.py:73: the mean cross entropy over the last scale"""
+        nll, _, _, tok, _ = self._host()
+        return float(nll[-1] / tok[-1])
+
+    @property
+    def acc_mean(self) -> float:
+        """trainer.py:74: percent of tokens with argmax == gt"""
+        _, _, cor, tok, _ = self._host()
+        return float(100.0 * cor.sum() / tok.sum())
+
+    @property
+    def acc_tail(self) -> float:
+        """trainer.py:75: the same over the last scale"""
+        _, _, cor, tok, _ = self._host()
+        return float(100.0 * cor[-1] / tok[-1])
+
+    @property
+    def loss(self) -> float:
+        """trainer.py:112-120 without progressive training: CrossEntropyLoss(label_smoothing) per token, weighted 1 / L, summed per image,
+        averaged over the images = the mean over every token of nll + label_smooth * (z_gt - mean_v z_v)"""
+        nll, smo, _, tok, _ = self._host()
+        return float((nll.sum() + self.label_smooth * smo.sum()) / tok.sum())
+
+    def per_scale(self) -> dict:
+        """trainer.py:149-155: {'acc_<reso>': percent, 'L_<reso>': mean cross entropy} per scale"""
+        nll, _, cor, tok, _ = self._host()
+        kw = {}
+        for si, reso in enumerate(self.resos):
+            kw[f'acc_{reso}'] = float(100.0 * cor[si] / tok[si])
+            kw[f'L_{reso}'] = float(nll[si] / tok[si])
+        return kw
+
+    @property
+    def z_voc_usage(self) -> float:
+        """trainer.py:140-143: percent of the codes predicted more often than 0.001 / V of the time"""
+        hist = self._host()[4]
+        return float(((hist / hist.sum()) > 0.001 / hist.shape[0]).mean() * 100.0)
+
+    def topk_correct_S(self, k: int) -> torch.Tensor:
+        """(S,) int64: per scale the number of tokens whose gt is among the k best codes (rank < k; k = 1: correct_S on NaN-free rows)"""
+        if isinstance(k, bool) or int(k) != k or k < 1:
+            raise ValueError('k must be an integer >= 1')
+        hit = (self.rank_BL >= 0) & (self.rank_BL < int(k))
+        ends = np.cumsum([pn * pn for pn in self.patch_nums]).tolist()
+        return torch.stack([hit[:, e - pn * pn:e].sum() for e, pn in zip(ends, self.patch_nums)]).to(torch.int64)
+
+    def __add__(self, other):
+        if not isinstance(other, EvalResult):
+            return NotImplemented
+        if (self.nll_S.shape != other.nll_S.shape or self.pred_hist_V.shape != other.pred_hist_V.shape or self.label_smooth != other.label_smooth
+                or self.patch_nums != other.patch_nums or self.nll_S.device != other.nll_S.device):
+            raise ValueError('EvalResult +: the two results differ in their scales, vocabulary, label_smooth or device')
+        return EvalResult(self.images + other.images, self.nll_S + other.nll_S, self.smooth_S + other.smooth_S, self.correct_S + other.correct_S,
+                          self.tokens_S + other.tokens_S, self.pred_hist_V + other.pred_hist_V, torch.cat((self.nll_BL, other.nll_BL)),
+                          torch.cat((self.pred_BL, other.pred_BL)), torch.cat((self.rank_BL, other.rank_BL)), self.label_smooth, self.patch_nums)
+
+    def __repr__(self):
+        return (f'EvalResult(images={self.images}, L_mean={self.L_mean:.4f}, L_tail={self.L_tail:.4f}, acc_mean={self.acc_mean:.2f}, '
+                f'acc_tail={self.acc_tail:.2f}, label_smooth={self.label_smooth})')
+
+
+def token_eval_torch(z: torch.Tensor, gt: torch.Tensor):
+    """VAR.evaluate's per-token definitions in PyTorch.  z: (n, l, V) fp32 logits, gt: (n, l) tokens -> (nll fp32, smooth fp32, pred int64, rank int32)"""
+    V = z.shape[-1]
+    g = gt.unsqueeze(-1)
+    nll = -torch.log_softmax(z, dim=-1).gather(-1, g).squeeze(-1)
+    zg = z.gather(-1, g)
+    ahead = (z > zg) | ((z == zg) & (torch.arange(V, device=z.device) < g))
+    smooth = (zg.squeeze(-1).double() - z.double().sum(-1) / V).float()
+    return nll, smooth, z.argmax(-1), ahead.sum(-1).to(torch.int32)
+
+
 GENERATIVE_FEATURES = ('vae_post', 'vae_fhat')
 
 
@@ -624,12 +736,74 @@ class VAR(nn.Module):
         pred = torch.tensor([int(rule_order(sc[n])[0]) for n in range(N)], dtype=torch.int64, device=score.device)
         return GenerativeResult(pred, score, tokens)
 
+    @torch.no_grad()
+    def evaluate(self, gt_tokens, label_B, *, label_smooth: float = 0.0, max_rows: int = 64) -> EvalResult:
+        """The trainer's validation pass and logging metrics in one call -> EvalResult (sums; see there).
+
+        Replaces reference trainer.py:54-84 (eval_ep: forward, cross entropy on all tokens and on the last scale, the two argmax accuracies)
+        and :126-156 (the per-scale L_* / acc_* and z_voc_usage), and adds the rank of the ground-truth token (top-k accuracy for any k) and
+        the label-smoothed objective.  gt_tokens: (N, L) integer tokens or the per-scale list of vae.img_to_idxBl(img); label_B: (N,) class
+        ids in [0, num_classes], a tensor or a list.  max_rows bounds the images of one transformer pass; the per-token values and the integer
+        sums do not depend on it.
+        Deviation from the reference: its forward() drops labels at random with cond_drop_rate even in eval mode (var.py:199), so the numbers
+        eval_ep prints are noisy; here the labels are used as given, as in token_log_likelihood.  A caller who wants the reference's numbers
+        passes labels that are already dropped (num_classes).
+        Per token, with z the fp32 logits row: nll = -log_softmax(z)[gt] (on the HIP path token_log_likelihood's value bit for bit, negated);
+        pred = torch.argmax(z); rank = |{v : z_v > z_gt or (z_v == z_gt and v < gt)}|; the smoothing term z_gt - mean_v z_v with the mean
+        taken in float64.
+        On the HIP path (the conditions of token_log_likelihood) each scale's logits are reduced behind the head by varhip_token_eval_f32 and
+        the sums by varhip_eval_reduce_f32 in a fixed order: no (N, L, V) logits tensor is made; the precision follows set_hip_precision /
+        torch.autocast.  Elsewhere (CPU, train mode, prog_si >= 0) the same definitions run in PyTorch on _forward_torch's logits, at most
+        max_rows images at a time; with prog_si >= 0 the result covers the scales 0 .. prog_si only."""
+        gt, lab, label_smooth = self._eval_args(gt_tokens, label_B, label_smooth, max_rows)
+        N, S = gt.shape[0], len(self.patch_nums)
+        dev = gt.device
+        if self._scoring_on_hip(gt):
+            r = self.engine().evaluate(gt, lab, int(max_rows))
+            tokens_S = torch.tensor([N * pn * pn for pn in self.patch_nums], dtype=torch.int64, device=dev)
+            return EvalResult(N, r['nll_S'], r['smooth_S'], r['correct_S'], tokens_S, r['pred_hist_V'], r['nll_BL'], r['pred_BL'], r['rank_BL'],
+                              label_smooth, self.patch_nums)
+        nsc = self.prog_si + 1 if self.prog_si >= 0 else S
+        ed = self.begin_ends[nsc - 1][1]
+        x_all = self.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in self.begin_ends])[:, :ed - self.first_l]
+        parts = []
+        for i0 in range(0, N, int(max_rows)):
+            z = self._forward_torch(lab[i0:i0 + max_rows], x_all[i0:i0 + max_rows]).float()
+            parts.append(token_eval_torch(z, gt[i0:i0 + max_rows, :ed]))
+        nll, smooth, pred, rank = (torch.cat(p) for p in zip(*parts))
+        be = self.begin_ends[:nsc]
+        return EvalResult(N, torch.stack([nll[:, b:e].double().sum() for b, e in be]), torch.stack([smooth[:, b:e].double().sum() for b, e in be]),
+                          torch.stack([(rank[:, b:e] == 0).sum() for b, e in be]).to(torch.int64),
+                          torch.tensor([N * (e - b) for b, e in be], dtype=torch.int64, device=dev),
+                          torch.bincount(pred.reshape(-1), minlength=self.V), nll, pred, rank, label_smooth, self.patch_nums[:nsc])
+
+    def _eval_args(self, gt_tokens, label_B, label_smooth, max_rows):
+        """validation of evaluate -> (gt (N, L) int64, labels (N,) int64 on the model's device, label_smooth)"""
+        dev = self.lvl_1L.device
+        toks = gt_tokens
+        if isinstance(toks, (list, tuple)) and len(toks) and all(isinstance(t, torch.Tensor) for t in toks):
+            if len(toks) != len(self.patch_nums) or any(t.dim() != 2 or t.shape[0] != toks[0].shape[0] or t.shape[1] != pn * pn
+                                                        for t, pn in zip(toks, self.patch_nums)):
+                raise ValueError(f'gt_tokens: the per-scale list must hold {len(self.patch_nums)} tensors (N, pn^2) with pn in {self.patch_nums}')
+            if len({t.device for t in toks}) != 1:
+                raise ValueError('gt_tokens: every scale must be on one device')
+            toks = torch.cat(list(toks), dim=1)
+        gt = self._token_shape(toks)
+        lab = torch.as_tensor(label_B)
+        if lab.dim() != 1 or lab.shape[0] != gt.shape[0] or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
+            raise ValueError(f'label_B must be (N,) integer class ids, N = {gt.shape[0]}')
+        if isinstance(label_smooth, bool) or not isinstance(label_smooth, (int, float, np.integer, np.floating)) or not math.isfinite(float(label_smooth)) \
+                or not 0.0 <= float(label_smooth) < 1.0:
+            raise ValueError('label_smooth must be a finite number in [0, 1)')
+        if isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 1:
+            raise ValueError('max_rows must be an integer >= 1')
+        self._token_label_range(gt, lab)
+        return gt.to(dev, torch.int64), lab.to(dev, torch.int64), float(label_smooth)
+
     def _scoring_args(self, gt_tokens, label, cfg, max_rows):
         """validation of token_log_likelihood / token_scores: -> (gt (N, L) int64, labels (N, K) int64 on the model's device, cfg)"""
         dev = self.lvl_1L.device
-        gt = torch.as_tensor(gt_tokens)
-        if gt.dim() != 2 or gt.shape[1] != self.L or gt.shape[0] < 1 or gt.dtype in (torch.bool,) or gt.is_floating_point() or gt.is_complex():
-            raise ValueError(f'gt_tokens must be an (N, {self.L}) integer tensor of token ids')
+        gt = self._token_shape(gt_tokens)
         lab = torch.as_tensor(label)
         if lab.dim() == 1:
             lab = lab.unsqueeze(0).expand(gt.shape[0], -1)
@@ -640,14 +814,24 @@ class VAR(nn.Module):
             raise ValueError('cfg must be finite and >= 0')
         if int(max_rows) != max_rows or max_rows < 1 + (cfg > 0):
             raise ValueError(f'max_rows must be an integer >= {1 + (cfg > 0)} (the class rows of a pass plus the unconditional row with cfg > 0)')
-        # explicit range checks (one host sync each): a bad token would index past a logits row, a bad label past class_emb
+        self._token_label_range(gt, lab)
+        return gt.to(dev, torch.int64), lab.to(dev, torch.int64), cfg
+
+    def _token_shape(self, gt_tokens) -> torch.Tensor:
+        """the token argument of the scoring calls and of evaluate -> an (N, L) integer tensor, shape and dtype checked"""
+        gt = torch.as_tensor(gt_tokens)
+        if gt.dim() != 2 or gt.shape[1] != self.L or gt.shape[0] < 1 or gt.dtype in (torch.bool,) or gt.is_floating_point() or gt.is_complex():
+            raise ValueError(f'gt_tokens must be an (N, {self.L}) integer tensor of token ids')
+        return gt
+
+    def _token_label_range(self, gt: torch.Tensor, lab: torch.Tensor):
+        """explicit range checks (one host sync each): a bad token would index past a logits row, a bad label past class_emb"""
         lo, hi = torch.stack(torch.aminmax(gt)).tolist()
         if lo < 0 or hi >= self.V:
             raise ValueError(f'gt_tokens must lie in [0, {self.V})')
         lo, hi = torch.stack(torch.aminmax(lab)).tolist()
         if lo < 0 or hi > self.num_classes:
             raise ValueError(f'labels must lie in [0, {self.num_classes}]')
-        return gt.to(dev, torch.int64), lab.to(dev, torch.int64), cfg
 
     def _scoring_on_hip(self, gt: torch.Tensor) -> bool:
         return not self.training and self.prog_si < 0 and gt.device.type == 'cuda' and self.head.weight.dtype == torch.float32 and self.C == 64 * self.num_heads
