@@ -51,6 +51,19 @@ int varhip_gemm_nt_f32(const float* A, int64_t lda, const float* W, int64_t ldw,
                        float* out, int64_t ldo, int M, int N, int K, int epi,
                        const float* resid, int64_t ldr, const float* gamma, int64_t ldg, int rows_per_group,
                        int bias_per_row, int batch, int64_t sA, int64_t sW, int64_t sO, varhip_stream_t stream);
+/* testing / experiments (host globals, no launch): force the tile of the following varhip_gemm_nt_f32 calls (0: 128x128, 1: 128x64, 2: 64x64,
+ * 3: 32x32 with the 8-stage pipeline; -1: automatic choice; starts from the environment variable VARHIP_GEMM_TILE).  Applies only where the
+ * fast path's conditions hold: a call that needs the element-wise-load variant still takes it.  Every tile computes the same bits. */
+int varhip_gemm_force_tile(int tile);
+/* the same for varhip_gemm_qkv_f32 below (0: 128-row tile, 1: 64-row tile; -1: automatic; starts from VARHIP_QKV_TILE) */
+int varhip_gemm_qkv_force_tile(int tile);
+/* the path the latest varhip_gemm_nt_f32 (0..2: the tiles above, 4: the 32x32 tile, 3: the element-wise-load variant) or varhip_gemm_qkv_f32
+ * (0 / 1) call dispatched to; -1 before any call and unchanged by a call that returned VARHIP_EINVAL or had M == 0 */
+int varhip_gemm_last_pick(void);
+/* whether the latest varhip_gemm_nt_f32 call on one of the four tiles could use 16-byte accesses in its epilogue: 1, or 0 where N % 4, ldo % 4,
+ * sO % 4, ldr % 4 (with resid), ldg % 4 (with gamma) or a misaligned out, column bias, resid or gamma forbids them (the results are the same
+ * bits either way, so only this reports the choice); -1 before any call, after the element-wise-load variant and after varhip_gemm_qkv_f32 */
+int varhip_gemm_last_evec(void);
 
 /* y[i] = x[i] * sigmoid(x[i])   — the SiLU in front of every ada_lin (basic_var.py:147,170; var.py:80) */
 int varhip_silu_f32(const float* x, float* y, int64_t n, varhip_stream_t stream);

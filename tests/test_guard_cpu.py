@@ -293,6 +293,8 @@ NO_DEVICE_POINTER = {                                        # everything else v
     'timing_name': 'timing table family name',
     'gemm16_force_tile': 'test hook: tile choice', 'conv16_force_tile': 'test hook: tile choice', 'gemm16_persistent': 'test hook: kernel choice',
     'sampler_force_walk': 'test hook: top-p walk',
+    'gemm_force_tile': 'test hook: tile choice', 'gemm_qkv_force_tile': 'test hook: tile choice', 'gemm_last_pick': 'test hook: reports the path of the latest dispatch',
+    'gemm_last_evec': 'test hook: reports the epilogue switch of the latest dispatch',
 }
 FLAVOURS = ('f16', 'bf16')
 

@@ -581,6 +581,17 @@ static int launch_dma(GemmP& p, int batch, hipStream_t stream) {
     return vh_launch_status();
 }
 
+// Test hooks (include/var_hip.h): host globals, no kernel.  The forced tiles start from the environment variables of the experiments
+// (tools/bench_kernels.py gemm with VARHIP_GEMM_TILE / VARHIP_QKV_TILE); vh_g_gemm_last_pick is the path of the latest dispatch and
+// vh_g_gemm_last_evec its p.evec (-1 where the path has no such switch: k_gemm_any, the q/k/v epilogue).
+static int vh_g_gemm_force_tile = [] { const char* e = getenv("VARHIP_GEMM_TILE"); const int t = e ? atoi(e) : -1; return (t >= 0 && t <= 3) ? t : -1; }();
+static int vh_g_qkv_force_tile = [] { const char* e = getenv("VARHIP_QKV_TILE"); const int t = e ? atoi(e) : -1; return t < 0 ? -1 : (t == 0 ? 0 : 1); }();
+static int vh_g_gemm_last_pick = -1, vh_g_gemm_last_evec = -1;
+extern "C" int varhip_gemm_force_tile(int tile) { vh_g_gemm_force_tile = (tile >= 0 && tile <= 3) ? tile : -1; return 0; }
+extern "C" int varhip_gemm_qkv_force_tile(int tile) { vh_g_qkv_force_tile = (tile == 0 || tile == 1) ? tile : -1; return 0; }
+extern "C" int varhip_gemm_last_pick(void) { return vh_g_gemm_last_pick; }
+extern "C" int varhip_gemm_last_evec(void) { return vh_g_gemm_last_evec; }
+
 static int launch_any(GemmP& p, int batch, hipStream_t stream) {
     p.tilesM = (p.M + 63) / 64; p.tilesN = (p.N + 63) / 64;
     hipLaunchKernelGGL(k_gemm_any, dim3(p.tilesM * p.tilesN, 1, batch), dim3(256), 0, stream, p);
@@ -620,12 +631,13 @@ extern "C" int varhip_gemm_nt_f32(const float* A, int64_t lda, const float* W, i
     const double e128 = (epi != VARHIP_EPI_NONE && K <= 2048) ? 0.95 : 1.0;
     const double c128 = cost(128, 128, 2, e128), c12864 = cost(128, 64, 3, 1.0), c64 = cost(64, 64, 4, 0.985);
     int pick = !vec ? 3 : (c128 <= c12864 && c128 <= c64) ? 0 : (c12864 <= c64 ? 1 : 2);
-    static const int forced = [] { const char* e = getenv("VARHIP_GEMM_TILE"); return e ? atoi(e) : -1; }();   // experiments only
+    const int forced = vh_g_gemm_force_tile;                     // tests and experiments only (varhip_gemm_force_tile)
     // fewer 64x64 tiles than half the CUs (the l = 1 and l = 4 scales): the lone workgroup of a CU is bound by one LDS round trip
     // per k-step and one memory latency per K tile, so 32x32 tiles (4x the workgroups) with 7 tiles of DMA in flight win
     if (pick == 2 && (int64_t)((M + 63) / 64) * ((N + 63) / 64) * batch <= 128) pick = 4;
     if (vec && forced >= 0 && forced <= 2) pick = forced;
     if (vec && forced == 3) pick = 4;
+    vh_g_gemm_last_pick = pick; vh_g_gemm_last_evec = pick == 3 ? -1 : p.evec;
     VhScope scope(pick == 0 ? VH_FAM_GEMM : VH_FAM_GEMM_SMALL, (hipStream_t)stream, 2.0 * M * N * (double)K * batch,
                   4.0 * batch * ((double)M * K + (double)N * K + (double)M * N));
     switch (pick) {
@@ -676,8 +688,9 @@ extern "C" int varhip_gemm_qkv_f32(const float* A, int64_t lda, const float* W, 
         const int64_t nb = (int64_t)((M + bm - 1) / bm) * ((3 * C + 127) / 128);
         return (double)((nb + 255) / 256) * bm / eff;
     };
-    static const int forced = [] { const char* e = getenv("VARHIP_QKV_TILE"); return e ? atoi(e) : -1; }();   // experiments only: 0 = 128 rows, 1 = 64
+    const int forced = vh_g_qkv_force_tile;                      // tests and experiments only (varhip_gemm_qkv_force_tile): 0 = 128 rows, 1 = 64
     const bool big = forced >= 0 ? forced == 0 : cost(128, 0.97) <= cost(64, 1.0);      // measured with the fused epilogue: the 64-row tile (3 workgroups per CU) is level or ahead at every d16 scale
+    vh_g_gemm_last_pick = big ? 0 : 1; vh_g_gemm_last_evec = -1;
     VhScope scope(big ? VH_FAM_GEMM : VH_FAM_GEMM_SMALL, (hipStream_t)stream, 2.0 * M * 3.0 * C * (double)K,
                   4.0 * ((double)M * K + 3.0 * C * K + 3.0 * M * C));
     return big ? launch_dma<4, 4>(p, 1, (hipStream_t)stream) : launch_dma<2, 4>(p, 1, (hipStream_t)stream);

@@ -29,6 +29,10 @@ class _Lib:
         so.varhip_conv16_force_tile.argtypes = [ctypes.c_int]; so.varhip_conv16_force_tile.restype = ctypes.c_int
         so.varhip_gemm16_persistent.argtypes = [ctypes.c_int]; so.varhip_gemm16_persistent.restype = ctypes.c_int
         so.varhip_sampler_force_walk.argtypes = [ctypes.c_int]; so.varhip_sampler_force_walk.restype = ctypes.c_int
+        so.varhip_gemm_force_tile.argtypes = [ctypes.c_int]; so.varhip_gemm_force_tile.restype = ctypes.c_int
+        so.varhip_gemm_qkv_force_tile.argtypes = [ctypes.c_int]; so.varhip_gemm_qkv_force_tile.restype = ctypes.c_int
+        so.varhip_gemm_last_pick.argtypes = []; so.varhip_gemm_last_pick.restype = ctypes.c_int
+        so.varhip_gemm_last_evec.argtypes = []; so.varhip_gemm_last_evec.restype = ctypes.c_int
         so.varhip_vq_stats_blocks.argtypes = [ctypes.c_int64]; so.varhip_vq_stats_blocks.restype = ctypes.c_int
         self.host = {}
         for name, args in abi.SIGNATURES_HOST.items():
