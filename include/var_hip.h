@@ -521,6 +521,15 @@ int varhip_gn_scale_shift_f32(const float* stats, const float* gamma, const floa
 /* testing / experiments: force the pixel tile of the following f16 convolutions (2: 128 pixels, 4 waves, two workgroups per CU;
  * 4: 256 pixels, 8 waves, two workgroups per CU; 8: the halo-patch kernel where the shape allows it; anything else: by size) */
 int varhip_conv16_force_tile(int wm);
+/* testing: the kernel instantiation that the latest varhip_conv3x3_nhwc_*, varhip_gnconv3x3_nhwc_* or varhip_upconv_phase_* call of either flavour
+ * launched (forcing is a request, this is what ran), as the decimal number  nz * 1000 + GN * 100 + TNW * 10 + kernel:
+ *   kernel  0 = k_conv16 on 128-pixel tiles, 3 = k_conv16 on 256-pixel tiles, 1 / 2 = k_conv16h on 8 x 32 / 16 x 16 halo patches
+ *   TNW     channels per tile / 32: 5, 4 (either kernel), 2, 1 (128-pixel tiles only: a forced 4 on them reports kernel 0)
+ *   GN      1 = the GroupNorm-fused form of k_conv16h (varhip_gnconv3x3_nhwc_*)
+ *   nz      1 = a 3x3 convolution, 4 = the four phases of varhip_upconv_phase_*
+ * e.g. 1051 = k_conv16h<5, 32, false>, 1142 = k_conv16h<4, 16, true>, 4043 = k_conv16<4, 3, 4, 2> in the phase form, 1010 = k_conv16<1, 4, 2>.
+ * -1 before the first launch; a refused call (VARHIP_EINVAL) leaves it unchanged.  Host only: it launches nothing and reads no device memory. */
+int varhip_conv16_last_pick(void);
 /* GroupNorm on fp16 [B][HW][C] (basic_vae.py:18-19): statistics in fp64, affine + optional SiLU in fp32, fp16 result */
 int varhip_gn_stats_f16(const void* x, float* stats, double* scratch, int B, int HW, int C, int G, float eps, varhip_stream_t stream);
 int varhip_gn_apply_f16(const void* x, const float* stats, const float* gamma, const float* beta, void* out,

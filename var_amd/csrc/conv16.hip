@@ -564,6 +564,7 @@ static int launch_conv16h(Conv16P& p, hipStream_t s) {
     auto kfn = k_conv16h<TNW, PW, GN>;
     static bool attr_done = false;
     if (!attr_done) { (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr_done = true; }
+    vh_g_conv16_last_pick = 1000 + (GN ? 100 : 0) + TNW * 10 + (PW == 32 ? 1 : 2);      // varhip_conv16_last_pick: nz, GN, TNW, kernel (include/var_hip.h)
     hipLaunchKernelGGL(kfn, dim3(p.tilesM * p.tilesN), dim3(512), lds, s, p);
     return vh_launch_status();
 }
@@ -577,6 +578,7 @@ static int launch_conv16(Conv16P& p, int nz, hipStream_t s) {
     auto kfn = k_conv16<TNW, NST, WM, OCC>;
     static bool attr_done = false;
     if (!attr_done) { if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
+    vh_g_conv16_last_pick = nz * 1000 + TNW * 10 + (WM == 4 ? 3 : 0);                     // varhip_conv16_last_pick: the instantiation that runs, not the picker's wish
     hipLaunchKernelGGL(kfn, dim3(p.tilesM * p.tilesN, 1, nz), dim3(WM * 128), lds, s, p);
     return vh_launch_status();
 }

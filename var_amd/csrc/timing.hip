@@ -50,6 +50,7 @@ int vh_g_force_tile16 = -1;
 int vh_g_gemm16_persist = [] { const char* e = getenv("VARHIP_GEMM16_PERSIST"); return e ? (atoi(e) != 0) : 1; }();
 int vh_g_gemm16_deep = [] { const char* e = getenv("VARHIP_GEMM16_DEEP"); return e ? (atoi(e) != 0) : 1; }();       // 0: the 2-stage 64-row tiles only
 int vh_g_conv16_force_wm = 0;
+int vh_g_conv16_last_pick = -1;      // the instantiation of the latest dispatch_conv16 of either flavour (varhip_conv16_last_pick)
 
 extern "C" {
 
@@ -59,6 +60,8 @@ int varhip_gemm16_force_tile(int tile) { vh_g_force_tile16 = (tile >= 0 && tile 
 int varhip_gemm16_persistent(int on) { vh_g_gemm16_persist = on ? 1 : 0; return 0; }
 // 0: by size; 2 / 4 / 8: force the 128-pixel / 256-pixel / halo-patch conv kernel (tests, tools/bench_kernels.py)
 int varhip_conv16_force_tile(int wm) { vh_g_conv16_force_wm = (wm == 2 || wm == 4 || wm == 8) ? wm : 0; return 0; }
+// tests: the kernel instantiation the latest 16-bit convolution of either flavour was dispatched to (include/var_hip.h has the packing); -1 before the first
+int varhip_conv16_last_pick(void) { return vh_g_conv16_last_pick; }
 
 const char* varhip_version(void) { return "var_hip 0.1.0 gfx950"; }
 
