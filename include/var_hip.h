@@ -481,6 +481,16 @@ int varhip_gemm16_force_tile(int tile);
 /* experiments / tests: 1 (default) = whole 256x256 tiles run on the persistent kernel k_gemm16p (one workgroup per CU walking a tile list),
  * 0 = on k_gemm16<8,4,2,4> (one workgroup per tile).  Identical results. */
 int varhip_gemm16_persistent(int on);
+/* tests: 1 (default, or what VARHIP_GEMM16_DEEP seeded at load) = the 64-row kernels with three / four LDS stages, 0 = k_gemm16<2,2> (gemm_nt) and
+ * k_gemm16<2,4> (gemm_qkv) with two.  Identical results. */
+int varhip_gemm16_deep(int on);
+/* testing: the kernel that launch i (0 or 1: a GEMM may go out as two launches over row ranges) of the latest varhip_gemm_nt_* / varhip_gemm_qkv_*
+ * call of either flavour ran, written by the launcher from its own template arguments just before the launch (forcing a tile is a request, this is
+ * what ran), as the decimal number  TMW * 1000 + TNW * 100 + WN * 10 + NST  of k_gemm16<TMW, TNW, 2, WN, NST>:
+ *   4422 128x128; 1124 32x32, four stages; 2224 64x64, four stages; 2222 64x64, two stages; 6442 192x256; 8442 256x256;
+ *   1423 / 2423 / 2422 the q/k/v kernels of 32 / 64 / 64 rows x 128 columns with three / three / two stages; 8440 = k_gemm16p, the persistent 256x256 kernel.
+ * 0: the call made no such launch (and before the first call); a refused call (VARHIP_EINVAL) leaves both unchanged.  Host only. */
+int varhip_gemm16_last_pick(int i);
 /* mat_qkv + q/k L2-norm + scale + KV-cache append (basic_var.py:93-109): fp16 x fp16 -> fp32 -> fp16 q [M][C] and fp16 caches [B2][H][Lmax][64] */
 int varhip_gemm_qkv_f16(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, int M, int C, int K,
                         const float* scale_mul, float plain_scale, int l2norm,
@@ -553,6 +563,8 @@ int varhip_gemm_nt_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, 
                        int batch, int64_t sA, int64_t sW, int64_t sO, varhip_stream_t stream);
 int varhip_gemm16_force_tile(int tile);
 int varhip_gemm16_persistent(int on);
+int varhip_gemm16_deep(int on);
+int varhip_gemm16_last_pick(int i);
 int varhip_gemm_qkv_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, int M, int C, int K,
                         const float* scale_mul, float plain_scale, int l2norm,
                         void* q_out, void* kcache, void* vcache, int B2, int l, int H, int pos0, int Lmax, varhip_stream_t stream);

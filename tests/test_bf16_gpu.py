@@ -48,7 +48,7 @@ def test_gemm_bf16_every_tile_against_float64(tile, M, N, K, mode):
         finally: hip.lib().so.varhip_gemm16_force_tile(-1)
         return out
     got = run(tile)
-    assert torch.equal(got, run(1)), f'tile {tile} differs from the 64x64 tile'
+    assert torch.equal(got, run(1)), f'tile {tile} differs from tile 1 (k_gemm16<2,2,2,2,4>, or <1,1,2,2,4> below 256 tiles of 64x64)'
     Ad, Wd = A.double().cpu(), W.double().cpu()
     ref = Ad @ Wd.T + bias.double().cpu()
     tol = 2e-6 * (Ad.abs() @ Wd.abs().T) + 1e-6

@@ -60,7 +60,8 @@ def test_gemm16_against_float64(M, N, K, mode):
                                         # one row, N the first legal width (N % 4 == 0) past a 64 / 128 / 256 wide tile
                                         (1, 68, 64, 'none16'), (1, 132, 128, 'resid32'), (1, 260, 64, 'gelu16'), (1, 260, 192, 'none32')])
 def test_gemm16_every_tile_on_ragged_shapes(tile, M, N, K, mode):
-    """the three tile instantiations (128x128, 64x64, 256x256 with 8 waves) forced onto shapes with partial tiles in both dimensions:
+    """the forced tiles (0: 128x128, 1: 64x64 — the 32x32 kernel k_gemm16<1,1,2,2,4> where the shape has fewer than 256 tiles of 64x64,
+    which is all of these but 1000 x 3072 —, 2: 256x256 with 8 waves, 3: 192x256; tests/test_gemm16_dispatch_gpu.py asserts which kernel runs) on shapes with partial tiles in both dimensions:
     identical results (same MFMA instruction, same k order), and right against float64"""
     hip = _hip()
     g = torch.Generator().manual_seed(M + N)
@@ -76,7 +77,7 @@ def test_gemm16_every_tile_on_ragged_shapes(tile, M, N, K, mode):
             hip.lib().so.varhip_gemm16_force_tile(-1)
         return out
     got, base = run(tile), run(1)
-    assert torch.equal(got, base), f'tile {tile} differs from the 64x64 tile in {int((got != base).sum())} elements'
+    assert torch.equal(got, base), f'tile {tile} differs from tile 1 (k_gemm16<2,2,2,2,4>, or <1,1,2,2,4> below 256 tiles of 64x64) in {int((got != base).sum())} elements'
     ref = A.double() @ W.double().T + bias.double()
     if epi == 1: ref = torch.nn.functional.gelu(ref, approximate='tanh')
     if epi == 2: ref = resid.double() + ref
@@ -108,7 +109,7 @@ def test_gemm16_at_d30_d36_widths_every_tile(tile, N, K, mode):
     got = run(tile)
     if tile != 1:
         base = run(1)
-        assert torch.equal(got, base), f'tile {tile} differs from the 64x64 tile in {int((got != base).sum())} elements'
+        assert torch.equal(got, base), f'tile {tile} differs from tile 1 (k_gemm16<2,2,2,2,4>, or <1,1,2,2,4> below 256 tiles of 64x64) in {int((got != base).sum())} elements'
     Ad, Wd = A.double().cpu(), W.double().cpu()
     ref = Ad @ Wd.T + bias.double().cpu()
     mag = Ad.abs() @ Wd.abs().T
@@ -141,7 +142,7 @@ def test_gemm16_persistent_kernel_equals_one_tile_kernel(M, N, K, mode):
         return out
     a, b, c = run(1, 2), run(0, 2), run(1, 1)
     assert torch.equal(a, b), f'persistent vs one-tile kernel: {int((a != b).sum())} elements differ'
-    assert torch.equal(a, c), f'persistent 256x256 vs 64x64 tiles: {int((a != c).sum())} elements differ'
+    assert torch.equal(a, c), f'persistent 256x256 vs tile 1 (64x64, or 32x32 below 256 tiles of 64x64): {int((a != c).sum())} elements differ'
     assert torch.equal(run(1, 2), a)                                      # run to run
     rows = torch.randperm(M, generator=g)[:64]
     ref = A[rows].double().cpu() @ W.double().cpu().T + bias.double().cpu()

@@ -27,7 +27,7 @@ def hooks_reset():
     yield
     _, hip = _setup()
     so = hip.lib().so
-    so.varhip_gemm_force_tile(-1); so.varhip_gemm_qkv_force_tile(-1); so.varhip_gemm16_force_tile(-1)
+    so.varhip_gemm_force_tile(-1); so.varhip_gemm_qkv_force_tile(-1); so.varhip_gemm16_force_tile(-1); so.varhip_gemm16_deep(1)
 
 
 def gpu_call(c, name, args, outs):

@@ -296,6 +296,7 @@ NO_DEVICE_POINTER = {                                        # everything else v
     'gemm_force_tile': 'test hook: tile choice', 'gemm_qkv_force_tile': 'test hook: tile choice', 'gemm_last_pick': 'test hook: reports the path of the latest dispatch',
     'gemm_last_evec': 'test hook: reports the epilogue switch of the latest dispatch',
     'conv16_last_pick': 'test hook: reports the kernel instantiation of the latest 16-bit convolution',
+    'gemm16_deep': 'test hook: kernel choice', 'gemm16_last_pick': 'test hook: reports the kernel instantiations of the latest 16-bit GEMM',
 }
 FLAVOURS = ('f16', 'bf16')
 

@@ -30,4 +30,4 @@ typedef _Float16 vh_e16;
 // a whole tap (19 MFMAs) later, an in-place accumulate, which the hardware interlocks anyway.
 #define VH16_MFMA_16x16x32_INPLACE(a, b, c) asm(VH16_MFMA_16x16x32_ASM " %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b))
 // test / experiment switches shared by both flavours (defined in timing.hip)
-extern int vh_g_force_tile16, vh_g_gemm16_persist, vh_g_gemm16_deep, vh_g_conv16_force_wm, vh_g_conv16_last_pick;
+extern int vh_g_force_tile16, vh_g_gemm16_persist, vh_g_gemm16_deep, vh_g_conv16_force_wm, vh_g_conv16_last_pick, vh_g_gemm16_last_pick[2], vh_g_gemm16_nlaunch;

@@ -608,6 +608,7 @@ static int launch16p(Gemm16P& p, int batch, hipStream_t stream) {
     int per_xcd = ncu / 8 / batch; if (per_xcd < 1) per_xcd = 1;     // workgroups per XCD (batched launches share the CUs over blockIdx.z)
     const int need = (T + 7) / 8;                                      // the largest XCD share
     if (per_xcd > need) per_xcd = need;
+    vh_g_gemm16_last_pick[vh_g_gemm16_nlaunch++ & 1] = 8440;          // varhip_gemm16_last_pick: NST digit 0 = the persistent kernel
     hipLaunchKernelGGL(k_gemm16p, dim3(per_xcd * 8, 1, batch), dim3(512), lds, stream, p);
     return vh_launch_status();
 }
@@ -621,6 +622,7 @@ static int launch16(Gemm16P& p, int batch, hipStream_t stream) {
     auto kfn = k_gemm16<TMW, TNW, WM, WN, NST>;
     static bool attr_done = false;
     if (!attr_done) { if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
+    vh_g_gemm16_last_pick[vh_g_gemm16_nlaunch++ & 1] = TMW * 1000 + TNW * 100 + WN * 10 + NST;      // varhip_gemm16_last_pick: what runs, from this instantiation's own arguments
     hipLaunchKernelGGL(kfn, dim3(p.tilesM * p.tilesN, 1, batch), dim3(64 * WM * WN), lds, stream, p);
     return vh_launch_status();
 }
@@ -686,6 +688,7 @@ static int run_gemm16(Gemm16P& p, int batch, hipStream_t stream, bool qkv, bool 
     }
     const char* A0 = (const char*)p.A; char* O0 = (char*)p.out; const char* R0 = (const char*)p.resid;
     int rc = 0;
+    vh_g_gemm16_nlaunch = 0; vh_g_gemm16_last_pick[0] = vh_g_gemm16_last_pick[1] = 0;      // (a refused call never gets here)
     for (int i = 0; i < nseg && !rc; ++i) {
         const int m0 = seg[i].m0, rows = seg[i].rows, pick = seg[i].pick;
         p.m_base = m0; p.M = rows;

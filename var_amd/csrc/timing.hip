@@ -50,6 +50,8 @@ int vh_g_force_tile16 = -1;
 int vh_g_gemm16_persist = [] { const char* e = getenv("VARHIP_GEMM16_PERSIST"); return e ? (atoi(e) != 0) : 1; }();
 int vh_g_gemm16_deep = [] { const char* e = getenv("VARHIP_GEMM16_DEEP"); return e ? (atoi(e) != 0) : 1; }();       // 0: the 2-stage 64-row tiles only
 int vh_g_conv16_force_wm = 0;
+int vh_g_gemm16_last_pick[2] = {0, 0};      // the kernels of the latest 16-bit GEMM call's launches, written by launch16 / launch16p (varhip_gemm16_last_pick)
+int vh_g_gemm16_nlaunch = 0;                // launches that call has made so far
 int vh_g_conv16_last_pick = -1;      // the instantiation of the latest dispatch_conv16 of either flavour (varhip_conv16_last_pick)
 
 extern "C" {
@@ -58,6 +60,10 @@ extern "C" {
 int varhip_gemm16_force_tile(int tile) { vh_g_force_tile16 = (tile >= 0 && tile <= 3) ? tile : -1; return 0; }
 // 0 = whole 256x256 tiles on k_gemm16<8,4,2,4> (one workgroup per tile), 1 (default) = on the persistent k_gemm16p
 int varhip_gemm16_persistent(int on) { vh_g_gemm16_persist = on ? 1 : 0; return 0; }
+// tests: runtime setter of the switch VARHIP_GEMM16_DEEP seeds (0: the two-stage 64-row kernels k_gemm16<2,2> / <2,4>, 1: the three- and four-stage ones)
+int varhip_gemm16_deep(int on) { vh_g_gemm16_deep = on ? 1 : 0; return 0; }
+// tests: the kernel of launch i (0 or 1) of the latest 16-bit GEMM call of either flavour (include/var_hip.h has the packing); 0: it made no such launch
+int varhip_gemm16_last_pick(int i) { return (i == 0 || i == 1) ? vh_g_gemm16_last_pick[i] : 0; }
 // 0: by size; 2 / 4 / 8: force the 128-pixel / 256-pixel / halo-patch conv kernel (tests, tools/bench_kernels.py)
 int varhip_conv16_force_tile(int wm) { vh_g_conv16_force_wm = (wm == 2 || wm == 4 || wm == 8) ? wm : 0; return 0; }
 // tests: the kernel instantiation the latest 16-bit convolution of either flavour was dispatched to (include/var_hip.h has the packing); -1 before the first

@@ -29,6 +29,8 @@ class _Lib:
         so.varhip_conv16_force_tile.argtypes = [ctypes.c_int]; so.varhip_conv16_force_tile.restype = ctypes.c_int
         so.varhip_conv16_last_pick.argtypes = []; so.varhip_conv16_last_pick.restype = ctypes.c_int
         so.varhip_gemm16_persistent.argtypes = [ctypes.c_int]; so.varhip_gemm16_persistent.restype = ctypes.c_int
+        so.varhip_gemm16_deep.argtypes = [ctypes.c_int]; so.varhip_gemm16_deep.restype = ctypes.c_int
+        so.varhip_gemm16_last_pick.argtypes = [ctypes.c_int]; so.varhip_gemm16_last_pick.restype = ctypes.c_int
         so.varhip_sampler_force_walk.argtypes = [ctypes.c_int]; so.varhip_sampler_force_walk.restype = ctypes.c_int
         so.varhip_gemm_force_tile.argtypes = [ctypes.c_int]; so.varhip_gemm_force_tile.restype = ctypes.c_int
         so.varhip_gemm_qkv_force_tile.argtypes = [ctypes.c_int]; so.varhip_gemm_qkv_force_tile.restype = ctypes.c_int
