@@ -351,6 +351,25 @@ int varhip_token_score_f32(const float* logits, const int64_t* gt, int64_t ld_gt
                            int with_uncond, float ca, float cb, int mode, int param, float thr, const float* dist, int64_t ld_dist,
                            float* out, int64_t ld_out_img, int64_t ld_out_cls, varhip_stream_t stream);
 
+/* ---- the distance-probability profile (VAR.distance_profile; fork var_analysis.py:352-425 plot_dist_kde: the (K, L, V) softmax, the gathered
+ * (K, L, V) distances and the subsampled (d, p) pairs; :694-732 and :798-818: their mean probability per distance bin) -----------------------
+ * One scale of one pass: the row layout, uncond rows, gt addressing and CFG combine of varhip_token_score_f32.  Per element v of a row whose
+ * gt lies in [0, V):  p_v = vm_exp(z_v - m) / s in fp32 with m = max z and s = sum exp(z - m) of varhip_token_score_f32's row pass (the
+ * exponential and the denominator of its mode 3 with param == 0; one correctly rounded division per element);  d_v = dist[gt * ld_dist + v].
+ * The element is in bin b iff edges[b] <= d_v < edges[b + 1] and p_v > min_prob, every comparison in fp32: an element in no bin, a NaN d_v or
+ * a NaN p_v adds nothing; a gt outside [0, V) is never dereferenced and its row adds nothing.  edges: nbins + 1 fp32 values, ascending (the
+ * caller checks; the last may be +inf).  The call ADDS into
+ *   count[i * ld_img + c * ld_cls + b]   the number of elements in the bin,
+ *   mass_q[i * ld_img + c * ld_cls + b]  the sum over them of (int64)rint((double)p_v * 2^48)  (fixed point: a scale's cell stays <= l * 2^48),
+ * with integer atomics only (LDS per workgroup, then 64-bit global adds of the non-zero bins): the sums do not depend on the order of
+ * execution.  The caller zeroes both arrays once.
+ * NULL operands, nbins outside [1, 256], ld_cls < nbins, ld_img < classes * ld_cls, ld_gt < l, ld_dist < V, V outside (0, 2^24], min_prob NaN,
+ * negative or >= 1, images / classes / l < 1: VARHIP_EINVAL. */
+int varhip_dist_profile_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V,
+                            int with_uncond, float ca, float cb, const float* dist, int64_t ld_dist,
+                            const float* edges, int nbins, float min_prob,
+                            int64_t* mass_q, int64_t* count, int64_t ld_img, int64_t ld_cls, varhip_stream_t stream);
+
 /* ---- the pruning step of zero-shot classification (VAR.classify) ---------------------------------------------------------------------
  * One workgroup per image i.  Every candidate c < cand adds its stage's per-token scores to its float64 running total, one plain addition
  * per token in ascending token order:  totals[i * cand + c] += (double)tokens[i * ld_img + c * ld_cls + t],  t = t0 .. t1-1  (t1 == t0: the

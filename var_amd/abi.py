@@ -76,6 +76,7 @@ SIGNATURES_HIP_ONLY = {
     'token_loglik_f32':  [P, P, L, I, I, I, I, I, F, F, P, L, L],       # pinned against float64 log_softmax (tests/test_likelihood_gpu.py)
     'code_dist_f32':     [P, I, I, P],                                  # pinned against neighbor_table_f32 (tests/test_token_scores_gpu.py)
     'token_score_f32':   [P, P, L, I, I, I, I, I, F, F, I, I, F, P, L, P, L, L],   # pinned against float64 (tests/test_token_scores_gpu.py)
+    'dist_profile_f32':  [P, P, L, I, I, I, I, I, F, F, P, L, P, I, F, P, P, L, L],   # pinned against float64 (tests/test_distance_profile_gpu.py)
     'conv3x3_wino_nhwc_f32': [P, P, P, P, P, P, I, I, I, I, I],      # pinned against float64 and the direct conv (tests/test_winograd_gpu.py)
     'class_select_f32':  [P, L, L, I, I, I, I, P, I, P],             # pinned against a numpy lexsort of the rule (tests/test_classify_gpu.py)
     'cfg_argmax_f32':    [P, P, P, L, P, I, I, I, D],                # pinned against cfg_sample_f32(top_k=1) (tests/test_generative_gpu.py)

@@ -52,6 +52,38 @@ struct TsRow {
     const float *lc, *lu;
     float ca, cb;
     int V, lane;
+    // fills z (NV > 0) and gives the row's max m and exponential sum s (every lane gets them): statement for statement the row pass of
+    // k_token_score below, which keeps its own inline copy so that its instantiations compile to what they were before this member existed
+    __device__ __forceinline__ void load_max_sum(float& m, float& s) {
+        m = -INFINITY; s = 0.f;
+        if constexpr (NV > 0) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const int e = j * 256 + 4 * lane;
+                if (e < V) {
+                    const f32x4 c = *(const f32x4*)(lc + e);
+                    if constexpr (CFG) { const f32x4 u = *(const f32x4*)(lu + e); const f32x4 a = ca * c; const f32x4 b = cb * u; z[j] = a - b; }
+                    else z[j] = c;
+                } else {
+                    z[j] = (f32x4)(-INFINITY);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NV; ++j) m = fmaxf(m, fmaxf(fmaxf(z[j][0], z[j][1]), fmaxf(z[j][2], z[j][3])));
+            m = vh_wave_max(m);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const f32x2 e0 = vh_exp_pair(f32x2{z[j][0] - m, z[j][1] - m});
+                const f32x2 e1 = vh_exp_pair(f32x2{z[j][2] - m, z[j][3] - m});
+                s = ((s + e0[0]) + e0[1]) + (e1[0] + e1[1]);
+            }
+        } else {
+            for (int v = lane; v < V; v += 64) m = fmaxf(m, ts_z<CFG>(lc, lu, v, ca, cb));
+            m = vh_wave_max(m);
+            for (int v = lane; v < V; v += 64) s = s + vm_exp(ts_z<CFG>(lc, lu, v, ca, cb) - m);
+        }
+        s = vh_wave_sum(s);
+    }
     // f(z_v, v) for every element v of this lane
     template <typename F> __device__ __forceinline__ void each(F f) const {
         if constexpr (NV > 0) {
@@ -268,5 +300,111 @@ extern "C" int varhip_token_score_f32(const float* logits, const int64_t* gt, in
     if (mode == 1) ts_dispatch<1>(vec, cfg, grid, st, logits, gt, ld_gt, images, classes, l, V, ca, cb, param, thr, dist, ld_dist, out, ld_out_img, ld_out_cls);
     else if (mode == 2) ts_dispatch<2>(vec, cfg, grid, st, logits, gt, ld_gt, images, classes, l, V, ca, cb, param, thr, dist, ld_dist, out, ld_out_img, ld_out_cls);
     else ts_dispatch<3>(vec, cfg, grid, st, logits, gt, ld_gt, images, classes, l, V, ca, cb, param, thr, dist, ld_dist, out, ld_out_img, ld_out_cls);
+    return vh_launch_status();
+}
+
+// ---- distance-probability profile (VAR.distance_profile; fork var_analysis.py:352-425 plot_dist_kde's (distance, probability) pairs, binned
+// at :694-732 / :798-818) ---------------------------------------------------------------------------------------------------------------------
+// Per element v of a scored row: p_v = vm_exp(z_v - m) / s (m, s: TsRow::load_max_sum, the row pass of k_token_score; the exponential and the
+// denominator are those of mode 3 with param == 0, which divides its sum of vm_exp(z_v - m) * d_v by s: here each term is divided, one correctly
+// rounded fp32 division), d_v = dist[gt][v]; bin b iff edges[b] <= d_v < edges[b + 1] and p_v > min_prob (fp32 compares: a NaN is in no bin).
+// A workgroup owns one (image, class) and DP_CHUNK consecutive tokens of the scale, its four waves take them in turn (a wave without a token
+// only meets the barriers).  Edges and one histogram (uint32 counts, uint64 fixed-point mass) live in LDS; every element costs a binary search
+// over the edges and two LDS integer atomics; after the barrier the non-zero bins go out as 64-bit global integer atomics.  Integer sums only:
+// the result does not depend on the order of execution.
+#define DP_CHUNK 8
+#define DP_MAXBINS 256
+
+template <int NV, bool CFG>
+__global__ void __launch_bounds__(256) k_dist_profile(const float* __restrict__ logits, const int64_t* __restrict__ gt, int64_t ld_gt,
+                                                      int images, int classes, int l, int V, float ca, float cb,
+                                                      const float* __restrict__ dist, int64_t ld_dist, const float* __restrict__ edges,
+                                                      int nbins, int top, float min_prob, unsigned long long* __restrict__ mass_q,
+                                                      unsigned long long* __restrict__ count, int64_t ld_img, int64_t ld_cls) {
+    __shared__ float s_edge[DP_MAXBINS + 1];
+    __shared__ unsigned s_cnt[DP_MAXBINS];
+    __shared__ unsigned long long s_mass[DP_MAXBINS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int chunks = (l + DP_CHUNK - 1) / DP_CHUNK;
+    // workgroup -> (image, class, chunk), the chunk fastest
+    const int64_t ic = blockIdx.x / chunks;
+    const int t0 = (int)(blockIdx.x - ic * chunks) * DP_CHUNK;
+    const int img = (int)(ic / classes), k = (int)(ic - (int64_t)img * classes);
+    const int ne = nbins + 1;
+    for (int i = threadIdx.x; i < ne; i += 256) s_edge[i] = edges[i];
+    for (int i = threadIdx.x; i < nbins; i += 256) { s_cnt[i] = 0u; s_mass[i] = 0ull; }
+    __syncthreads();
+    const int t1 = min(t0 + DP_CHUNK, l);
+    for (int t = t0 + wave; t < t1; t += 4) {                               // (wave-uniform)
+        const int64_t g = gt[(int64_t)img * ld_gt + t];
+        if (g < 0 || g >= V) continue;                                      // never dereferenced, contributes nothing (the host API rejects it)
+        TsRow<NV, CFG> row;
+        row.lc = logits + (((int64_t)img * classes + k) * l + t) * V;
+        row.lu = logits + (((int64_t)images * classes + img) * l + t) * V;
+        row.ca = ca; row.cb = cb; row.V = V; row.lane = lane;
+        float m, s;
+        row.load_max_sum(m, s);
+        m = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(m)));     // as k_token_score: no second copy of the row kept alive
+        row.each_d(dist + g * ld_dist, [&](float x, float d, int) {
+            const float p = vm_exp(x - m) / s;
+            // pos = |{i : edges[i] <= d}| by binary search (edges ascending; `top` = the largest power of two <= ne); a NaN d leaves pos = 0
+            int pos = 0;
+            for (int step = top; step > 0; step >>= 1) {
+                const int c = pos + step;
+                if (c <= ne && s_edge[c - 1] <= d) pos = c;
+            }
+            if (pos >= 1 && pos <= nbins && p > min_prob) {                 // pos == ne: d at or above the last edge
+                atomicAdd(&s_cnt[pos - 1], 1u);
+                atomicAdd(&s_mass[pos - 1], (unsigned long long)__double2ll_rn((double)p * 281474976710656.0));     // rint(p * 2^48)
+            }
+        });
+    }
+    __syncthreads();
+    unsigned long long* mo = mass_q + (int64_t)img * ld_img + (int64_t)k * ld_cls;
+    unsigned long long* co = count + (int64_t)img * ld_img + (int64_t)k * ld_cls;
+    for (int i = threadIdx.x; i < nbins; i += 256) {
+        const unsigned c = s_cnt[i];
+        if (c) {
+            atomicAdd(co + i, (unsigned long long)c);
+            const unsigned long long q = s_mass[i];
+            if (q) atomicAdd(mo + i, q);
+        }
+    }
+}
+
+template <int NV>
+static void dp_launch(bool cfg, dim3 grid, hipStream_t st, const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l,
+                      int V, float ca, float cb, const float* dist, int64_t ld_dist, const float* edges, int nbins, int top, float min_prob,
+                      int64_t* mass_q, int64_t* count, int64_t ld_img, int64_t ld_cls) {
+    if (cfg) hipLaunchKernelGGL((k_dist_profile<NV, true>), grid, dim3(256), 0, st, logits, gt, ld_gt, images, classes, l, V, ca, cb, dist, ld_dist,
+                                edges, nbins, top, min_prob, (unsigned long long*)mass_q, (unsigned long long*)count, ld_img, ld_cls);
+    else hipLaunchKernelGGL((k_dist_profile<NV, false>), grid, dim3(256), 0, st, logits, gt, ld_gt, images, classes, l, V, ca, cb, dist, ld_dist,
+                            edges, nbins, top, min_prob, (unsigned long long*)mass_q, (unsigned long long*)count, ld_img, ld_cls);
+}
+
+extern "C" int varhip_dist_profile_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V,
+                                       int with_uncond, float ca, float cb, const float* dist, int64_t ld_dist,
+                                       const float* edges, int nbins, float min_prob,
+                                       int64_t* mass_q, int64_t* count, int64_t ld_img, int64_t ld_cls, varhip_stream_t stream) {
+    if (!logits || !gt || !dist || !edges || !mass_q || !count || images <= 0 || classes <= 0 || l <= 0 || V <= 0 || V > (1 << 24) ||
+        nbins < 1 || nbins > DP_MAXBINS || ld_gt < l || ld_dist < V || ld_cls < nbins || ld_img < (int64_t)classes * ld_cls ||
+        !(min_prob >= 0.f && min_prob < 1.f))                               // (NaN fails both)
+        return VARHIP_EINVAL;
+    const int64_t rows = (int64_t)images * classes * l;
+    const int64_t blocks = (int64_t)images * classes * ((l + DP_CHUNK - 1) / DP_CHUNK);
+    if (blocks > 0x7fffffff) return VARHIP_EINVAL;
+    int top = 1;
+    while (top * 2 <= nbins + 1) top *= 2;
+    const hipStream_t st = (hipStream_t)stream;
+    // the alignment conditions of varhip_token_score_f32's distance modes
+    const bool vec = V % 4 == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)dist & 15) == 0 && ld_dist % 4 == 0;
+    // bytes: as varhip_token_score_f32's mode 3 (the rows, the uncond rows, one distance-table row per scored row)
+    const double bytes = 4.0 * V * (double)(2 * rows + (with_uncond ? (int64_t)images * l : 0)) + 8.0 * rows;
+    VhScope sc(VH_FAM_SAMPLER, st, 0, bytes);
+    const dim3 grid((unsigned)blocks);
+    const bool cfg = with_uncond != 0;
+    if (vec && V <= 1024) dp_launch<4>(cfg, grid, st, logits, gt, ld_gt, images, classes, l, V, ca, cb, dist, ld_dist, edges, nbins, top, min_prob, mass_q, count, ld_img, ld_cls);
+    else if (vec && V <= 4096) dp_launch<16>(cfg, grid, st, logits, gt, ld_gt, images, classes, l, V, ca, cb, dist, ld_dist, edges, nbins, top, min_prob, mass_q, count, ld_img, ld_cls);
+    else dp_launch<0>(cfg, grid, st, logits, gt, ld_gt, images, classes, l, V, ca, cb, dist, ld_dist, edges, nbins, top, min_prob, mass_q, count, ld_img, ld_cls);
     return vh_launch_status();
 }

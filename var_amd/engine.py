@@ -783,8 +783,8 @@ class EncoderEngine(DecoderEngine):
 AUTOCAST_PRECISION = {torch.float16: 'f16', torch.bfloat16: 'bf16'}
 
 
-# score -> mode of varhip_token_score_f32 (0: varhip_token_loglik_f32)
-_SCORE_MODES = {'log_prob': 0, 'group_smoothed': 1, 'neighbor_max': 2, 'expected_distance': 3}
+# score -> mode of varhip_token_score_f32 (0: varhip_token_loglik_f32; 4: varhip_dist_profile_f32, which fills histograms instead of token scores)
+_SCORE_MODES = {'log_prob': 0, 'group_smoothed': 1, 'neighbor_max': 2, 'expected_distance': 3, 'distance_profile': 4}
 
 
 class SamplingEngine:
@@ -1397,6 +1397,21 @@ class SamplingEngine:
         already validated by the caller."""
         return self._score_passes(gt_tokens, labels, cfg, max_rows, score)
 
+    @torch.no_grad()
+    def distance_profile(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, edges: torch.Tensor, min_prob: float):
+        """VAR.distance_profile on the HIP path -> (mass_q, count), two (N, K, S, B) int64 arrays: as token_scores, with each scale's logits
+        reduced behind the head by varhip_dist_profile_f32 into that scale's histograms (zeroed here, once per call).  edges: (B + 1,) fp32,
+        min_prob: an fp32 value, both already validated by the caller."""
+        sc = self._score_setup(gt_tokens, labels, cfg, ('distance_profile',))
+        dev = sc['gt'].device
+        sc['edges'] = edges.to(dev, torch.float32).contiguous()
+        sc['min_prob'] = float(min_prob)
+        N, K = labels.shape
+        S, B = len(self.var.patch_nums), edges.numel() - 1
+        out = (torch.zeros(N, K, S, B, dtype=torch.int64, device=dev), torch.zeros(N, K, S, B, dtype=torch.int64, device=dev))
+        self._score_stage(sc, sc['lab'], S - 1, -1, max_rows, out)
+        return out
+
     def _score_passes(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, score: tuple) -> torch.Tensor:
         """the pass loop of token_log_likelihood / token_scores: one stage through the last scale over every candidate"""
         sc = self._score_setup(gt_tokens, labels, cfg, score)
@@ -1420,7 +1435,7 @@ class SamplingEngine:
             sc['thr'] = float(score[1])
         elif score[0] == 'expected_distance':
             sc['param'] = int(score[1])
-        if score[0] in ('neighbor_max', 'expected_distance'):
+        if score[0] in ('neighbor_max', 'expected_distance', 'distance_profile'):
             sc['dist'] = self.code_distance_table()
             self._wait_ready()
         sc['gt'] = gt = gt_tokens.to(dev, torch.int64).contiguous()
@@ -1434,13 +1449,18 @@ class SamplingEngine:
     def _score_stage(self, sc: dict, lab_all: torch.Tensor, last: int, done: int, max_rows: int, out: torch.Tensor):
         """one stage: the rows of labels lab_all (N, K) through scale `last`, packed into passes of at most max_rows rows:
         images_in_pass x (classes_in_pass + [cfg > 0]), the unconditional row of every image of a pass (label num_classes) after its class rows.
-        Scales <= `done` only rebuild the KV caches; each later scale's logits are reduced by the scoring kernel into out (N, K, >= L_e)."""
+        Scales <= `done` only rebuild the KV caches; each later scale's logits are reduced by the scoring kernel into out (N, K, >= L_e), in
+        the distance_profile mode added by varhip_dist_profile_f32 into scale si of out = (mass_q, count), two (N, K, S, B) int64 arrays."""
         var = self.var
         dev = lab_all.device
         N, K = lab_all.shape
         L, V = var.L, var.V
-        Lo = out.shape[2]
         u, mode, t32, gt = sc['u'], sc['mode'], sc['t32'], sc['gt']
+        if mode == 4:
+            mass, count = out
+            SB, B = mass.shape[2] * mass.shape[3], mass.shape[3]
+        else:
+            Lo = out.shape[2]
         if K + u <= max_rows:
             ipp, kpp = max(1, max_rows // (K + u)), K            # whole images per pass
         else:
@@ -1462,6 +1482,9 @@ class SamplingEngine:
                 if mode == 0:
                     hip.call('token_loglik_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
                              out[i0:, k0:, cur:], K * Lo, Lo)
+                elif mode == 4:
+                    hip.call('dist_profile_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t), sc['dist'], V,
+                             sc['edges'], B, sc['min_prob'], mass[i0:, k0:, si], count[i0:, k0:, si], K * SB, SB)
                 else:
                     hip.call('token_score_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
                              mode, sc['param'], sc['thr'], sc['dist'], V, out[i0:, k0:, cur:], K * Lo, Lo)

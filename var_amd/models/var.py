@@ -186,6 +186,65 @@ def token_eval_torch(z: torch.Tensor, gt: torch.Tensor):
     return nll, smooth, z.argmax(-1), ahead.sum(-1).to(torch.int32)
 
 
+MASS_ONE = float(2 ** 48)            # the fixed point of the probability mass: q_v = rint(p_v * 2^48)
+
+
+class DistanceProfile:
+    """VAR.distance_profile's result: per image n, candidate class k, scale s and distance bin b (edges[b] <= d < edges[b + 1]) the codes v of
+    every token's row with d(gt, v) in the bin and p_v > min_prob, on the model's device:
+      count_NKSB   (N, K, S, B) int64: how many (token, code) pairs fall in the bin
+      mass_q_NKSB  (N, K, S, B) int64: the sum of their q_v = rint(p_v * 2^48), p_v the fp32 softmax probability: integer sums, the same bits
+                   whatever the packing, the class order or the run; a cell is at most pn_s^2 * 2^48 <= 2^58
+      mass_NKSB    (N, K, S, B) float64: mass_q * 2^-48, the probability mass in the bin
+      edges (B + 1,) fp32, min_prob float (the fp32 value used), patch_nums: the scales the result covers
+    mean_prob() is the curve the fork plots (var_analysis.py:694-732, :798-818): the mean probability of the pairs of a bin."""
+    __slots__ = ('count_NKSB', 'mass_q_NKSB', 'edges', 'min_prob', 'patch_nums')
+
+    def __init__(self, count_NKSB, mass_q_NKSB, edges, min_prob, patch_nums):
+        self.count_NKSB, self.mass_q_NKSB, self.edges = count_NKSB, mass_q_NKSB, edges
+        self.min_prob, self.patch_nums = float(min_prob), tuple(patch_nums)
+
+    @property
+    def mass_NKSB(self) -> torch.Tensor:
+        return self.mass_q_NKSB.double() / MASS_ONE
+
+    def mean_prob(self, over_images: bool = False) -> torch.Tensor:
+        """mass / count in float64, NaN where count == 0: (N, K, S, B), or (K, S, B) with over_images=True (both summed over N first)"""
+        mass, count = self.mass_NKSB, self.count_NKSB.double()
+        if over_images:
+            mass, count = mass.sum(0), count.sum(0)
+        return torch.where(count > 0, mass / count, torch.full_like(mass, math.nan))
+
+    def centers(self) -> torch.Tensor:
+        """(B,) float64 bin centres (edges[b] + edges[b + 1]) / 2 (inf for a last bin that reaches +inf)"""
+        e = self.edges.double()
+        return (e[:-1] + e[1:]) / 2
+
+    def __repr__(self):
+        N, K, S, B = self.count_NKSB.shape
+        return f'DistanceProfile(images={N}, classes={K}, scales={S}, bins={B}, min_prob={self.min_prob})'
+
+
+def distance_profile_torch(z: torch.Tensor, gt: torch.Tensor, dist: torch.Tensor, edges: torch.Tensor, min_prob: float):
+    """VAR.distance_profile's definitions in PyTorch for one scale of one image.  z: (K, l, V) fp32 logits of the image's K class rows, gt:
+    (l,) tokens, dist: (l, V) fp32 distance rows of the gt codes, edges: (B + 1,) fp32 ascending, min_prob: an fp32 value
+    -> (count (K, B) int64, mass_q (K, B) int64).  p = softmax(z) in fp32; a pair is in bin b iff edges[b] <= d < edges[b + 1] and
+    p > min_prob (a NaN is in no bin); a token outside [0, V) contributes nothing."""
+    K, l, V = z.shape
+    B = edges.numel() - 1
+    edges = edges.to(z.device, torch.float32)
+    p = torch.softmax(z.float(), dim=-1)
+    d = dist.to(torch.float32).unsqueeze(0).expand(K, l, V).contiguous()
+    b = torch.bucketize(d, edges, right=True) - 1                       # |{i : edges[i] <= d}| - 1
+    ok = (b >= 0) & (b < B) & ~torch.isnan(d) & (p > torch.tensor(min_prob, dtype=torch.float32, device=z.device))
+    ok = ok & ((gt >= 0) & (gt < V)).view(1, l, 1)
+    q = torch.where(ok, torch.round(p.double() * MASS_ONE), torch.zeros((), dtype=torch.float64, device=z.device)).to(torch.int64)
+    cell = (torch.arange(K, device=z.device).view(K, 1, 1) * B + b.clamp(0, B - 1))[ok]
+    count = torch.zeros(K * B, dtype=torch.int64, device=z.device).index_add_(0, cell, torch.ones_like(cell))
+    mass = torch.zeros(K * B, dtype=torch.int64, device=z.device).index_add_(0, cell, q[ok])
+    return count.view(K, B), mass.view(K, B)
+
+
 GENERATIVE_FEATURES = ('vae_post', 'vae_fhat')
 
 
@@ -605,6 +664,56 @@ class VAR(nn.Module):
             d = code_distance_rows(cb, g) if score != 'group_smoothed' else None
             out.append(token_score_torch(z.float(), g, desc, d))
         return torch.stack(out, 0)
+
+    @torch.no_grad()
+    def distance_profile(self, gt_tokens, label, edges, cfg: float = 0.0, max_rows: int = 64, *, min_prob: float = 0.0) -> DistanceProfile:
+        """The distance-probability profile of the teacher-forced distributions -> DistanceProfile (histograms; see there).
+
+        Replaces the fork's var_analysis.py:352-425 (plot_dist_kde: the (K, L, V) softmax, the gathered (K, L, V) codebook distances and the
+        (d, p) pairs it subsamples to max_points) and the binning of those pairs at :694-732 / :798-818: for every ground-truth token, each
+        code's probability p_v is paired with its codebook distance d(gt, v), and the pairs are reduced to a count and a probability mass per
+        image, candidate class, scale and distance bin.  Every pair is counted: the curves are exact, not a random subsample.
+        gt_tokens, label, cfg and max_rows mean exactly what they mean in token_scores (same validation, packing and guided z).  edges: B + 1
+        fp32 values, 1 <= B <= 256, strictly increasing, edges[0] >= 0, the last may be +inf; bin b is edges[b] <= d < edges[b + 1].
+        min_prob (finite, in [0, 1)): only pairs with p_v > min_prob count (the fork's `probs > 1e-10` style cut; 0 keeps every p_v > 0).
+        d is the direct-form distance table of token_scores; p_v the fp32 softmax; the mass is summed in fixed point (2^-48), so the result is
+        bit-equal across max_rows, packing, class order and repeated calls.  A bad edges or min_prob raises ValueError.
+        On the HIP path (the conditions of token_log_likelihood) each scale's logits are reduced by varhip_dist_profile_f32 behind the head: no
+        (rows, L, V) tensor is made.  Elsewhere distance_profile_torch runs on the per-image logits, at most max_rows class rows at a time."""
+        gt, lab, cfg = self._scoring_args(gt_tokens, label, cfg, max_rows)
+        e32, min_prob = self._profile_args(edges, min_prob)
+        dev = gt.device
+        N, K = lab.shape
+        if self._scoring_on_hip(gt):
+            mass, count = self.engine().distance_profile(gt, lab, cfg, int(max_rows), e32, min_prob)
+            return DistanceProfile(count, mass, e32.to(dev), min_prob, self.patch_nums)
+        nsc = len(self.patch_nums)
+        B = e32.numel() - 1
+        cb = self.vae_proxy[0].quantize.embedding.weight.detach().float()
+        count = torch.zeros(N, K, nsc, B, dtype=torch.int64, device=dev)
+        mass = torch.zeros(N, K, nsc, B, dtype=torch.int64, device=dev)
+        for i, z in self._teacher_forced_torch(gt, lab, cfg, max_rows):
+            d = code_distance_rows(cb, gt[i, :z.shape[1]])
+            for si, (b, e) in enumerate(self.begin_ends):
+                for k0 in range(0, K, int(max_rows)):
+                    c, m = distance_profile_torch(z[k0:k0 + max_rows, b:e].float(), gt[i, b:e], d[b:e], e32, min_prob)
+                    count[i, k0:k0 + max_rows, si], mass[i, k0:k0 + max_rows, si] = c, m
+        return DistanceProfile(count, mass, e32.to(dev), min_prob, self.patch_nums)
+
+    def _profile_args(self, edges, min_prob):
+        """validation of distance_profile's edges and min_prob -> ((B + 1,) fp32 CPU tensor, the fp32 value of min_prob as a float)"""
+        try:
+            e = torch.as_tensor(edges).detach().to('cpu', torch.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError('edges must be a 1-D ascending sequence or tensor of numbers') from None
+        if e.dim() != 1 or not 2 <= e.numel() <= 257:
+            raise ValueError('edges must be 1-D with B + 1 entries, 1 <= B <= 256')
+        if bool(torch.isnan(e).any()) or float(e[0]) < 0 or not bool((e[1:] > e[:-1]).all()):
+            raise ValueError('edges must be strictly increasing in fp32, without NaN, with edges[0] >= 0 (the last may be +inf)')
+        if isinstance(min_prob, bool) or not isinstance(min_prob, (int, float, np.integer, np.floating)) or not math.isfinite(float(min_prob)) \
+                or not 0.0 <= float(np.float32(min_prob)) < 1.0:
+            raise ValueError('min_prob must be a finite number in [0, 1)')
+        return e.contiguous(), float(np.float32(min_prob))
 
     def _score_desc(self, score, group, threshold, top_k) -> tuple:
         """validation of token_scores' score and its parameter -> the engine's score descriptor (mode, parameter)"""
