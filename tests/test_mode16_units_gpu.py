@@ -1,6 +1,6 @@
 """The 16-bit mode's pieces that run on every 16-bit step, each as a unit on a real MI355X, in both flavours (f16, bf16): the AdaLN block
 composite (varhip_adaln_block_*), the batched GEMM (varhip_gemm_nt_* with batch > 1: the products of the VAE's attention) and the VAE
-AttnBlock (DecoderEngine.attnblock16).  LayerNorm + modulate with a 16-bit output is pinned in test_kernels_gpu.test_ln_modulate_exact.
+AttnBlock (the 16-bit op set's attnblock: DecoderEngine.ops16(flavour).attnblock).  LayerNorm + modulate with a 16-bit output is pinned in test_kernels_gpu.test_ln_modulate_exact.
 
 Every tolerance is stated from the rounding points of the computation it checks:
   ACC  the fp32 accumulation of a product in another order than the reference's: at most 2e-6 * sum_k |a_k||w_k| (K <= 9216);
@@ -188,7 +188,7 @@ RUNS = [(-1, 1), (0, 1), (1, 1), (2, 1), (2, 0), (3, 1)]
 
 def _batched_operands(case, B, dt, g):
     """(A, lda, W, ldw, bias, out_f16, M, N, K, batch, sA, sW, sO, ldo): flat operand buffers, every slice with its own data.
-    'scores' / 'vt' / 'pv' are the three batched products of DecoderEngine.attnblock16 at HW = 256, C = 640, with its exact arguments."""
+    'scores' / 'vt' / 'pv' are the three batched products of the 16-bit attnblock (engine._Ops16) at HW = 256, C = 640, with its exact arguments."""
     HW, C = 256, 640
     r16 = lambda *s, sc=1.0: (torch.randn(*s, generator=g) * sc).to(dt).cuda()
     if case == 'scores':              # q . k^T: both operands inside the [B*HW, 2C] q|k projection, fp32 out
@@ -272,7 +272,7 @@ def test_gemm16_batched_rejects_resid_and_gamma():
 
 # ---------------------------------------------------------------------------------------------------------------------
 def _attnblock_ref(x, wqkv, bqkv, wp, bp, gam, bet, dt, U):
-    """AttnBlock.forward (basic_vae.py:73-85) in float64 on channels-last x [B, H, W, C], and the bar of attnblock16 against it (see
+    """AttnBlock.forward (basic_vae.py:73-85) in float64 on channels-last x [B, H, W, C], and the bar of the 16-bit attnblock against it (see
     test_attnblock16_against_float64) -> (ref [B, HW, C], bar)"""
     wqkv, wp, bqkv, bp, gam, bet = (t.double() for t in (wqkv, wp, bqkv, bp, gam, bet))
     B, Hh, Ww, C = x.shape
@@ -308,10 +308,10 @@ def _attnblock_ref(x, wqkv, bqkv, wp, bp, gam, bet, dt, U):
 @pytest.mark.parametrize('fl', ['f16', 'bf16'])
 @pytest.mark.parametrize('pre', ['decoder.mid.attn_1', 'decoder.up.4.attn.1'])
 def test_attnblock16_against_float64(fl, pre):
-    """DecoderEngine.attnblock16 on the d16 VAE's weights at its 16 x 16 x 640 attention, on a fresh 16-bit input (GroupNorm statistics from a
+    """DecoderEngine.ops16(flavour).attnblock on the d16 VAE's weights at its 16 x 16 x 640 attention, on a fresh 16-bit input (GroupNorm statistics from a
     statistics pass), against a float64 restatement of AttnBlock.forward (basic_vae.py:73-85) with the same 16-bit weights and fp32 biases / affine.
 
-    Rounding points of attnblock16: the GroupNorm output, the q|k projection, V^T, the probabilities, p.V and the output are 16-bit; scores and
+    Rounding points of the 16-bit attnblock: the GroupNorm output, the q|k projection, V^T, the probabilities, p.V and the output are 16-bit; scores and
     softmax are fp32.  A worst-case chain through the softmax says nothing here: the scores are unnormalised (sum |q||k| / sqrt(C) ~ 16), and
     ACC and U summed in the worst case over every path reach the size of the signal.  The bar is therefore a root-sum-square one: every 16-bit
     rounding is an independent error of variance (U |v|)^2 / 3, every product's accumulation one of standard deviation ACC sum |a||w| (the
@@ -325,7 +325,7 @@ def test_attnblock16_against_float64(fl, pre):
     z, meta = util.load_case('d16_full')
     vae, var = _models(meta)
     eng = vae._decoder_engine()
-    eng.refresh(); eng._ensure16(fl)
+    eng.refresh(); ops = eng.ops16(fl)
     dt, U = FLAV[fl]
     B, Hh, C = 2, 16, 640
     HW = Hh * Hh
@@ -334,12 +334,12 @@ def test_attnblock16_against_float64(fl, pre):
     x = x64[:B].contiguous()
     with torch.inference_mode():
         eng._gn_part = None
-        y = eng.attnblock16(x, pre, B, Hh, Hh).clone()
+        y = ops.attnblock(x, pre, B, Hh, Hh).clone()
         eng._gn_part = None
-        y64 = eng.attnblock16(x64, pre, 64, Hh, Hh)
+        y64 = ops.attnblock(x64, pre, 64, Hh, Hh)
     assert torch.equal(y64[:B], y), f'B = 64 vs B = 2: {int((y64[:B] != y).sum())} elements differ'
 
     D = lambda t: t.double()
-    ref, bar = _attnblock_ref(x, eng.w16[pre + '.qkv.weight'], eng.w[pre + '.qkv.bias'], eng.w16[pre + '.proj_out.weight'],
+    ref, bar = _attnblock_ref(x, ops.w16[pre + '.qkv.weight'], eng.w[pre + '.qkv.bias'], ops.w16[pre + '.proj_out.weight'],
                               eng.w[pre + '.proj_out.bias'], eng.w[pre + '.norm.weight'], eng.w[pre + '.norm.bias'], dt, U)
     _ratio(f'{fl} attnblock16 {pre}', (D(y).view(B, HW, C) - ref).abs(), bar)

@@ -105,20 +105,13 @@ def _chk(t: torch.Tensor, name: str) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
-class _VaeOps:
-    """channels-last building blocks shared by the decoder and encoder engines (reference basic_vae.py:18-92)"""
+class _Engine:
+    """what every engine does with its packed weight copies (`w`, keyed on `_sig`): announce them to other streams, retire them, drop them"""
 
-    PREFIXES = ()
-
-    def __init__(self, vae):
-        self.vae = vae
+    def __init__(self):
         self._sig = None
-        self.w: Dict[str, torch.Tensor] = {}
-        self._gn_part = None            # (tensor, partial sums, blocks per sample) left by the last conv for the GroupNorm after it
+        self.w: dict = {}
         self._ready = None              # event recorded behind the kernels that built the packed copies (they run on whichever stream called first)
-
-    def _signature(self):
-        return _signature(self.vae.parameters())
 
     def _built(self):
         """packed copies were just (re)built on the current stream: calls arriving on OTHER streams wait for this event before they read them"""
@@ -135,22 +128,100 @@ class _VaeOps:
         if self.w and torch.cuda.is_available():
             torch.cuda.synchronize()
 
-    def _stats_from(self, x, B, HW, fn_full):
-        """(mean, rstd) per (sample, group) of a channels-last map: folded from the producing conv's per-block partial sums when it left them for
-        exactly this tensor, else by a statistics pass (`fn_full`) over x"""
-        Cc = x.shape[-1]
-        stats = torch.empty((B, 32, 2), dtype=torch.float32, device=x.device)
-        pend, self._gn_part = self._gn_part, None
-        if pend is not None and pend[0].data_ptr() == x.data_ptr() and pend[0].numel() == x.numel() and tuple(pend[1].shape) == (B, pend[2], Cc, 2):
-            hip.call('gn_stats_part_f32', pend[1], stats, B, pend[2], HW, Cc, 32, 1e-6)
-        else:
-            scratch = torch.empty(hip.gn_scratch_elems(B, HW, Cc, 32), dtype=torch.float64, device=x.device)
-            hip.call(fn_full, x, stats, scratch, B, HW, Cc, 32, 1e-6)
-        return stats
-
     def invalidate(self):
         """drop the packed weight copies: the next call re-reads the module's parameters"""
         self._sig = None
+
+
+# ---- the quantizer's tables, as QuantizerEngine and SamplingEngine both keep them (each its own copy, under its own signature) ----------
+def _pack_quantizer(quant):
+    """(codebook [V][Cvae], [(Phi kernel [Cout][3][3][Cin], bias, resi_ratio), ...]) of a VectorQuantizer2"""
+    return (_chk(quant.embedding.weight.detach(), 'codebook'),
+            [(_chk(p.weight.detach(), 'phi').permute(0, 2, 3, 1).contiguous(), _chk(p.bias.detach(), 'phi'), float(p.resi_ratio))
+             for p in quant.quant_resi.phis()])
+
+
+def _tap_tables(cache: dict, pn: int, P: int, dev):
+    """the bicubic tap tables pn -> P on the device, built once per pn in `cache` (one cache per P); (None, None) at pn == P: nothing to resample"""
+    if pn == P:
+        return None, None
+    if pn not in cache:
+        ti, tw = bicubic_taps(pn, P)
+        cache[pn] = (torch.from_numpy(ti).to(dev), torch.from_numpy(tw).to(dev))
+    return cache[pn]
+
+
+def _scale_tables(taps: dict, phi: list, si: int, S: int, pn: int, P: int, dev):
+    """(ti, tw, pw, pb, ratio): what the quantizer step of scale si (pn x pn of S scales, the last P x P) takes besides its tokens"""
+    return _tap_tables(taps, pn, P, dev) + phi[phi_index(si, S, len(phi))]
+
+
+# ---- the two VAE graphs: (kind, key) steps, read by the walk that runs them (_VaeOps._run) and by the decoder's FLOP counters --------------
+def _decoder_graph(w: dict, nlev: int):
+    """post_quant_conv, then Decoder.forward (reference basic_vae.py:163-226); attention blocks where the weight table `w` has them"""
+    yield 'conv', 'post_quant_conv'
+    yield 'conv', 'decoder.conv_in'
+    yield 'res', 'decoder.mid.block_1'
+    yield 'attn', 'decoder.mid.attn_1'
+    yield 'res', 'decoder.mid.block_2'
+    for lev in reversed(range(nlev)):
+        for ib in range(3):
+            yield 'res', f'decoder.up.{lev}.block.{ib}'
+            if f'decoder.up.{lev}.attn.{ib}.norm.weight' in w:
+                yield 'attn', f'decoder.up.{lev}.attn.{ib}'
+        if lev != 0:
+            yield 'up', f'decoder.up.{lev}.upsample.conv'
+    yield 'tail', 'decoder'                                      # norm_out -> swish -> conv_out -> clamp
+
+
+def _encoder_graph(w: dict, nlev: int):
+    """Encoder.forward (reference basic_vae.py:99-160); quant_conv follows it in EncoderEngine.encode"""
+    yield 'conv', 'encoder.conv_in'
+    for lev in range(nlev):
+        for ib in range(2):
+            yield 'res', f'encoder.down.{lev}.block.{ib}'
+            if f'encoder.down.{lev}.attn.{ib}.norm.weight' in w:
+                yield 'attn', f'encoder.down.{lev}.attn.{ib}'
+        if lev != nlev - 1:
+            yield 'down', f'encoder.down.{lev}.downsample.conv'
+    yield 'res', 'encoder.mid.block_1'
+    yield 'attn', 'encoder.mid.attn_1'
+    yield 'res', 'encoder.mid.block_2'
+    yield 'norm_conv', 'encoder'                                 # norm_out -> swish -> conv_out
+
+
+_NORM_FIRST = ('res', 'norm_conv', 'tail')                      # the steps that open with a GroupNorm of their input
+
+
+class _VaeOps(_Engine):
+    """What the decoder and encoder engines share: the packed weights, the walk over a VAE graph, and the fp32 set of channels-last building
+    blocks (reference basic_vae.py:18-92).  `_Ops16` is the same set of blocks in 16-bit arithmetic; a call picks one of the two and walks."""
+
+    PREFIXES = ()
+    LEVELS = ''                     # prefix of the per-level weights: the highest index under it gives nlev
+    # convs whose result a GroupNorm reads next but which run without the partial-sum epilogue in fp32: the encoder's conv_in has always run on
+    # the plain kernel (the 16-bit one does leave partials), and its first ResnetBlock takes a statistics pass
+    PLAIN_CONVS = ('encoder.conv_in',)
+    fuse_gn = os.environ.get('VARHIP_FUSE_GN', '1') != '0'      # 16-bit blocks; False (tests, A/B runs): every GroupNorm + SiLU as its own pass in front of the conv (the same bits)
+
+    def __init__(self, vae):
+        super().__init__()
+        self.vae = vae
+        self._gn_part = None            # (tensor, partial sums, blocks per sample) left by the last conv for the GroupNorm after it
+
+    def _signature(self):
+        return _signature(self.vae.parameters())
+
+    def refresh(self):
+        sig = self._signature()
+        if sig == self._sig:
+            return
+        self._retire()
+        self.w = self._derive(self._pack())
+        self.w16s = {}                       # {'f16' | 'bf16': 16-bit copies}: made by ops16() the first time such a call runs on these weights
+        self.nlev = 1 + max(int(k.split('.')[2]) for k in self.w if k.startswith(self.LEVELS))
+        self._sig = sig
+        self._built()
 
     def _pack(self):
         """our copies of the weights this engine uses: 3x3 kernels re-laid [Cout][3][3][Cin] (Cin zero-padded to a multiple of 32),
@@ -173,98 +244,91 @@ class _VaeOps:
                 w[k] = v
         return w
 
+    def _derive(self, w):
+        """kernels derived from the packed ones (the decoder has some)"""
+        return w
 
-# Winograd F(2x2,3x3) filter transform (Lavin & Gray 2016): U = G g G^T per (output, input) channel pair
-_WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
-
-
-def wino_filter(w: torch.Tensor) -> torch.Tensor:
-    """[Cout][3][3][Cin] fp32 kernel -> U = G g G^T in float64, rounded once to fp32 and laid out [16][Cin/16][Cout][16] (xi = 4 i + j
-    of the 4x4 transform, input-channel tile, output channel, input channel in the tile) for varhip_conv3x3_wino_nhwc_f32"""
-    co, _, _, ci = w.shape
-    G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
-    u = torch.einsum('ik,jl,oklc->ijoc', G, G, w.double()).float()                      # [4][4][Cout][Cin]
-    return u.reshape(16, co, ci // 16, 16).permute(0, 2, 1, 3).contiguous()
-
-
-class DecoderEngine(_VaeOps):
-    """VQVAE.fhat_to_img on HIP kernels (reference vqvae.py:62-63, basic_vae.py:163-226)."""
-
-    PREFIXES = ('decoder.', 'post_quant_conv.')
-    # default precision of the VQVAE's own entry points (fhat_to_img, idxBl_to_img, ...): 'f32' unless the VQVAE's owner asks for 'f16'
-    # here.  The sampling loop does NOT change it: SamplingEngine passes its own precision with every decode_nhwc call, so two VARs
-    # sharing one VQVAE, or a VAR in the 16-bit mode next to direct VQVAE calls, never fight over a mode flag.
-    precision = 'f32'
-    unfused_tail = False         # tests: run norm_out / conv_out of the decoder as two launches
-    # The ResnetBlock convolutions (stride 1, 3x3) as fused Winograd F(2x2,3x3) (winograd.hip) where wino_ok() holds; False (tests, A/B runs):
-    # every conv on the direct implicit-GEMM kernel.  VARHIP_WINOGRAD=0 sets the default for a whole process.
-    winograd = os.environ.get('VARHIP_WINOGRAD', '1') != '0'
-    WINO_MIN_HW = 16 * 16        # smallest map that takes it (DESIGN.md §13: 1.63-1.72x faster than the direct kernel at every decoder level)
-    # the precision flops_per_image_executed counts when not given one: that of the last decode_nhwc, or the one the owning SamplingEngine was
-    # last set to (SamplingEngine.set_precision), whichever came later; None: `precision`.  Only an f32 decode runs the Winograd kernel.
-    flops_precision = None
-
-    def set_precision(self, precision: str):
-        if precision not in PRECISIONS:
-            raise ValueError(f"precision must be one of {PRECISIONS}")
-        self.precision = precision
-
-    def refresh(self):
-        sig = self._signature()
-        if sig == self._sig:
-            return
-        self._retire()
-        w = self._pack()
-        for k in [k for k in w if k.endswith('.upsample.conv.weight')]:        # Upsample2x convs: pre-summed 2x2 phase weights
-            cout, _, _, cin = w[k].shape
-            wp = torch.empty(4, cout, 2, 2, cin, dtype=torch.float32, device=w[k].device)
-            hip.call('upconv_pack_f32', w[k], wp, cin, cout)
-            w[k[:-len('weight')] + 'phase'] = wp
-        for k in [k for k in w if k.endswith(('.conv1.weight', '.conv2.weight'))]:   # ResnetBlock convs: Winograd filter transforms
-            w[k[:-len('weight')] + 'wino'] = wino_filter(w[k])
-        self.w = w
-        self.w16s = {}                       # {'f16' | 'bf16': 16-bit copies}: made by _ensure16() the first time such a decode runs on these weights
-        self.nlev = 1 + max(int(k.split('.')[2]) for k in w if k.startswith('decoder.up.'))
-        self._sig = sig
-        self._built()
-
-    def _ensure16(self, prec):
-        """16-bit copies of every conv kernel (3x3, phase, 1x1 shortcut, attention projections) next to the fp32 ones; biases and GroupNorm affine
-        stay fp32.  Selects them (self.w16) and the flavour's entry-point suffix / dtype for the decode that follows."""
+    def ops16(self, prec):
+        """the 16-bit blocks for ONE call in flavour `prec`, over 16-bit copies of every conv kernel (3x3, phase, 1x1 shortcut, attention
+        projections) made the first time the flavour runs on these weights; biases and GroupNorm affine stay fp32"""
         if prec not in self.w16s:
             self._wait_ready()
             self.w16s[prec] = {k: v.to(DT16[prec]).contiguous() for k, v in self.w.items()
                                if (k.endswith('.weight') or k.endswith('.phase')) and v.dim() >= 2 and '.norm' not in k}
             self._built()
-        self.w16, self.sfx, self.dt16 = self.w16s[prec], prec, DT16[prec]
+        return _Ops16(self, prec, self.w16s[prec])
 
-    # -- building blocks ---------------------------------------------------------------------------------------------
-    def _part_buffer(self, B, nblk, Cout, dev):
-        """scratch for the GroupNorm partials a conv leaves behind; remembered together with the tensor they describe"""
-        return torch.empty((B, nblk, Cout, 2), dtype=torch.float64, device=dev)
+    def _run(self, ops, graph, h, B, Hh, Ww, **tail):
+        """execute a VAE graph on the blocks of `ops` (this engine: fp32; an _Ops16: 16 bits).  A conv is asked for GroupNorm partials when the
+        step behind it opens with a GroupNorm; none outlive the walk."""
+        steps = list(graph)
+        self._gn_part = None
+        for (kind, key), (nxt, _) in zip(steps, steps[1:] + [(None, None)]):
+            if kind == 'conv':
+                h = ops.conv3(h, key, B, Hh, Ww, stats=nxt in _NORM_FIRST)
+            elif kind == 'res':
+                h = ops.resblock(h, key, B, Hh, Ww)
+            elif kind == 'attn':
+                h = ops.attnblock(h, key, B, Hh, Ww)
+            elif kind == 'up':
+                Hh, Ww = 2 * Hh, 2 * Ww
+                h = ops.upsample(h, key, B, Hh, Ww)
+            elif kind == 'down':
+                Hh, Ww = Hh // 2, Ww // 2
+                h = ops.downsample(h, key, B, Hh, Ww)
+            elif kind == 'norm_conv':
+                h = ops.norm_conv(h, key + '.norm_out', key + '.conv_out', B, Hh, Ww)
+            else:
+                h = ops.tail(h, key, B, Hh, Ww, **tail)
+        self._gn_part = None
+        return h
 
-    def conv3(self, x, key, B, Hh, Ww, up2=0, resid=None, out_mode=0, stats=False):
+    # -- GroupNorm statistics handed from a conv to the norm behind it ------------------------------------------------------------------
+    def _leave_partials(self, out, B, nblk):
+        """`out` is about to be written by a conv whose epilogue also emits per-block channel sums, nblk blocks per sample (0: not for this
+        shape) -> the buffer they go to (None at 0), remembered together with the tensor they describe for the GroupNorm that reads it next.
+        Holding `out` keeps its address from being recycled before then."""
+        self._gn_part = None
+        if not nblk:
+            return None
+        part = torch.empty((B, nblk, out.shape[-1], 2), dtype=torch.float64, device=out.device)
+        self._gn_part = (out, part, nblk)
+        return part
+
+    def _stats_from(self, x, B, HW, fn_full):
+        """(mean, rstd) per (sample, group) of a channels-last map: folded from the producing conv's per-block partial sums when it left them for
+        exactly this tensor, else by a statistics pass (`fn_full`) over x"""
+        Cc = x.shape[-1]
+        stats = torch.empty((B, 32, 2), dtype=torch.float32, device=x.device)
+        pend, self._gn_part = self._gn_part, None
+        if pend is not None and pend[0].data_ptr() == x.data_ptr() and pend[0].numel() == x.numel() and tuple(pend[1].shape) == (B, pend[2], Cc, 2):
+            hip.call('gn_stats_part_f32', pend[1], stats, B, pend[2], HW, Cc, 32, 1e-6)
+        else:
+            scratch = torch.empty(hip.gn_scratch_elems(B, HW, Cc, 32), dtype=torch.float64, device=x.device)
+            hip.call(fn_full, x, stats, scratch, B, HW, Cc, 32, 1e-6)
+        return stats
+
+    # -- the fp32 building blocks --------------------------------------------------------------------------------------------------------
+    def _wino(self, key, Hh, Ww, Cin, Cout):
+        """the Winograd-transformed kernel of conv `key` where that path takes this shape, else None (only the decoder engine keeps any)"""
+        return None
+
+    def conv3(self, x, key, B, Hh, Ww, resid=None, out_mode=0, stats=False):
         """stats=True: the result feeds a GroupNorm next — the conv epilogue also emits per-block channel sums (when the shape
         allows), which gn() then uses instead of a statistics pass over the tensor."""
         wt = self.w[key + '.weight']
         Cout, Cin = wt.shape[0], wt.shape[3]
         out = torch.empty((B, Cout, Hh, Ww) if out_mode else (B, Hh, Ww, Cout), dtype=torch.float32, device=x.device)
-        nblk = hip.conv_gn_blocks(Hh, Ww, Cout) if (stats and out_mode == 0) else 0
-        if up2 == 0 and out_mode == 0 and self.winograd and (key + '.wino') in self.w and self.wino_ok(Hh, Ww, Cin, Cout):
-            part = self._part_buffer(B, nblk, Cout, x.device) if nblk else None
-            hip.call('conv3x3_wino_nhwc_f32', x, self.w[key + '.wino'], self.w[key + '.bias'], resid, out, part, B, Hh, Ww, Cin, Cout)
-            if nblk: self._gn_part = (out, part, nblk)
+        nblk = hip.conv_gn_blocks(Hh, Ww, Cout) if (stats and out_mode == 0 and key not in self.PLAIN_CONVS) else 0
+        wino = self._wino(key, Hh, Ww, Cin, Cout) if out_mode == 0 else None
+        part = self._leave_partials(out, B, nblk)
+        if wino is not None:
+            hip.call('conv3x3_wino_nhwc_f32', x, wino, self.w[key + '.bias'], resid, out, part, B, Hh, Ww, Cin, Cout)
         elif nblk:
-            part = self._part_buffer(B, nblk, Cout, x.device)
-            hip.call('conv3x3_gn_nhwc_f32', x, wt, self.w[key + '.bias'], resid, out, part, B, Hh, Ww, Cin, Cout, up2)
-            self._gn_part = (out, part, nblk)              # holds `out` so its address cannot be recycled before the next gn()
+            hip.call('conv3x3_gn_nhwc_f32', x, wt, self.w[key + '.bias'], resid, out, part, B, Hh, Ww, Cin, Cout, 0)      # (0: no nearest-2x in front)
         else:
-            hip.call('conv3x3_nhwc_f32', x, wt, self.w[key + '.bias'], resid, out, B, Hh, Ww, Cin, Cout, up2, out_mode)
+            hip.call('conv3x3_nhwc_f32', x, wt, self.w[key + '.bias'], resid, out, B, Hh, Ww, Cin, Cout, 0, out_mode)
         return out
-
-    def wino_ok(self, Hh, Ww, Cin, Cout):
-        """the shape rule of the Winograd path: maps of at least WINO_MIN_HW pixels in whole 16 x 16 patches, channels in multiples of 32"""
-        return Hh * Ww >= self.WINO_MIN_HW and Hh % 16 == 0 and Ww % 16 == 0 and Cin % 32 == 0 and Cout % 32 == 0
 
     def gn_stats(self, x, B, HW):
         return self._stats_from(x, B, HW, 'gn_stats_f32')
@@ -275,21 +339,9 @@ class DecoderEngine(_VaeOps):
         hip.call('gn_apply_f32', x, stats, self.w[key + '.weight'], self.w[key + '.bias'], out, B, HW, x.shape[-1], 32, int(silu))
         return out
 
-    def tail(self, h, B, Hh, Ww, denorm, clamp=True):
-        """norm_out -> swish -> conv_out -> clamp (-> (x + 1) / 2) (basic_vae.py:224-226, vqvae.py:63, var.py:190): one pass over the map
-        (varhip_gn_silu_conv_out_f32) where it tiles into 8 x 32 patches, else GroupNorm apply + conv — the same bits either way.
-        clamp=False: conv_out's value as it is (out_mode 3; vqvae.py:59, VQVAE.forward)"""
-        wt = self.w['decoder.conv_out.weight']
-        Cout, Cin = wt.shape[0], wt.shape[3]
-        mode = 3 if not clamp else (1 if denorm else 2)
-        if Hh % 8 == 0 and Ww % 32 == 0 and Cin % 32 == 0 and Cout <= 4 and (10 * 34 * 36 + 4 * Cin) * 4 <= 64 * 1024 and not self.unfused_tail:
-            stats = self.gn_stats(h, B, Hh * Ww)
-            out = torch.empty((B, Cout, Hh, Ww), dtype=torch.float32, device=h.device)
-            hip.call('gn_silu_conv_out_f32', h, stats, self.w['decoder.norm_out.weight'], self.w['decoder.norm_out.bias'], wt,
-                     self.w['decoder.conv_out.bias'], out, B, Hh, Ww, Cin, Cout, 32, mode)
-            return out
-        h = self.gn(h, 'decoder.norm_out', B, Hh * Ww, True)
-        return self.conv3(h, 'decoder.conv_out', B, Hh, Ww, out_mode=mode)
+    def norm_conv(self, x, nkey, ckey, B, Hh, Ww):
+        """conv(swish(norm(x))) (basic_vae.py:57-60) as two passes; no partials: what follows it (the encoder's conv_out) is no GroupNorm"""
+        return self.conv3(self.gn(x, nkey, B, Hh * Ww, True), ckey, B, Hh, Ww)
 
     def lin(self, x2d, key, resid=None):
         wt = self.w[key + '.weight']
@@ -326,135 +378,94 @@ class DecoderEngine(_VaeOps):
         hip.call('gemm_nt_f32', p, HW, vt, HW, None, o, Cc, HW, Cc, HW, EPI_NONE, None, 0, None, 0, 1, 0, B, HW * HW, Cc * HW, HW * Cc)
         return self.lin(o, pre + '.proj_out', resid=x.view(B * HW, Cc)).view(B, Hh, Ww, Cc)
 
-    def flops_per_image_reference(self, P: int) -> float:
-        """FLOPs (2/MAC) of one decode as the REFERENCE computes it (9-tap upsample convs; SURVEY.md §8d: 393.7 G at P=16, ch=160)"""
-        self.refresh()
-        w = self.w
-        def c3(key, hw): co, _, _, ci = w[key + '.weight'].shape; return 2.0 * hw * co * 9 * ci
-        def c1(key, hw): co, ci = w[key + '.weight'].shape; return 2.0 * hw * co * ci
-        def res(pre, hw): return c3(pre + '.conv1', hw) + c3(pre + '.conv2', hw) + (c1(pre + '.nin_shortcut', hw) if (pre + '.nin_shortcut.weight') in w else 0.0)
-        def att(pre, hw): c = w[pre + '.proj_out.weight'].shape[0]; return c1(pre + '.qkv', hw) + c1(pre + '.proj_out', hw) + 2.0 * 2 * hw * hw * c
-        hw = P * P
-        f = c3('post_quant_conv', hw) + c3('decoder.conv_in', hw) + res('decoder.mid.block_1', hw) + att('decoder.mid.attn_1', hw) + res('decoder.mid.block_2', hw)
-        for lev in reversed(range(self.nlev)):
-            for ib in range(3):
-                f += res(f'decoder.up.{lev}.block.{ib}', hw)
-                if f'decoder.up.{lev}.attn.{ib}.norm.weight' in w: f += att(f'decoder.up.{lev}.attn.{ib}', hw)
-            if lev != 0:
-                hw *= 4; f += c3(f'decoder.up.{lev}.upsample.conv', hw)
-        return f + c3('decoder.conv_out', hw)
 
-    def flops_per_image_executed(self, P: int, precision: Optional[str] = None) -> float:
-        """FLOPs the kernels execute for one decode in `precision` (None: `flops_precision`): as flops_per_image_reference, with the Upsample2x
-        convolutions in their folded four-phase form (4 taps per output pixel instead of 9) and, in an f32 decode, the ResnetBlock convolutions
-        that take the Winograd path at 16 multiplies per 2x2 output tile (4 per output pixel instead of 9; the 16-bit decode has no such path)"""
-        prec = precision or self.flops_precision or self.precision
-        f = self.flops_per_image_reference(P)
-        hw, side = P * P, P
-        def wino(pre, hw, side):
-            d = 0.0
-            for c in ('.conv1', '.conv2'):
-                co, _, _, ci = self.w[pre + c + '.weight'].shape
-                if prec == 'f32' and self.winograd and self.wino_ok(side, side, ci, co): d += 2.0 * hw * co * 5 * ci
-            return d
-        f -= wino('decoder.mid.block_1', hw, side) + wino('decoder.mid.block_2', hw, side)
-        for lev in reversed(range(self.nlev)):
-            for ib in range(3):
-                f -= wino(f'decoder.up.{lev}.block.{ib}', hw, side)
-            if lev != 0:
-                hw *= 4; side *= 2
-                co, _, _, ci = self.w[f'decoder.up.{lev}.upsample.conv.weight'].shape
-                f -= 2.0 * hw * co * 5 * ci
-        return f
+def _tail_mode(denorm, clamp):
+    """out_mode of the decoder's last conv: 1 clamp and (x + 1) / 2, 2 clamp to [-1, 1], 3 the value as it is"""
+    return 3 if not clamp else (1 if denorm else 2)
 
-    # -- the 16-bit throughput mode: fp16 activations, conv16.hip / rowops16.hip ----------------------------------------
-    def conv3_16(self, x, key, B, Hh, Ww, resid=None, out_mode=0, stats=False):
+
+class _Ops16:
+    """The building blocks of _VaeOps on 16-bit activations and conv weights with fp32 accumulation (conv16.hip, rowops16.hip, conv16s2.hip):
+    the same methods, for the same walk.  One object per call, made by `_VaeOps.ops16` from a flavour and the engine's weight copies of that
+    flavour, so a call's precision is nobody's state but its own.  `fl` ('f16' | 'bf16') is the flavour and the suffix of its entry points, `dt`
+    its storage type, `w16` the 16-bit kernels; biases and GroupNorm affine are the engine's fp32 ones (`w`), and GroupNorm partials are handed
+    over through the engine like the fp32 ones."""
+
+    def __init__(self, eng: _VaeOps, fl: str, w16: dict):
+        self.eng, self.w, self.w16, self.fl, self.dt = eng, eng.w, w16, fl, DT16[fl]
+
+    def _to16(self, x32, shape=None):
+        y = torch.empty(x32.shape if shape is None else shape, dtype=self.dt, device=x32.device)
+        hip.call('cast_f32_to_' + self.fl, x32, y, y.numel())
+        return y
+
+    def _to32(self, x16):
+        y = torch.empty(x16.shape, dtype=torch.float32, device=x16.device)
+        hip.call(f'cast_{self.fl}_to_f32', x16, y, y.numel())
+        return y
+
+    def conv3(self, x, key, B, Hh, Ww, resid=None, out_mode=0, stats=False):
         wt = self.w16[key + '.weight']
         Cout, Cin = wt.shape[0], wt.shape[3]
-        out = torch.empty((B, Cout, Hh, Ww), dtype=torch.float32, device=x.device) if out_mode else torch.empty((B, Hh, Ww, Cout), dtype=self.dt16, device=x.device)
+        out = torch.empty((B, Cout, Hh, Ww), dtype=torch.float32, device=x.device) if out_mode else torch.empty((B, Hh, Ww, Cout), dtype=self.dt, device=x.device)
         nblk = hip.conv_gn_blocks(Hh, Ww, Cout) if (stats and out_mode == 0 and Cout % 4 == 0) else 0
-        part = self._part_buffer(B, nblk, Cout, x.device) if nblk else None
-        hip.call('conv3x3_nhwc_' + self.sfx, x, wt, self.w[key + '.bias'], resid, out, part, B, Hh, Ww, Cin, Cout, out_mode)
-        if nblk: self._gn_part = (out, part, nblk)
+        part = self.eng._leave_partials(out, B, nblk)
+        hip.call('conv3x3_nhwc_' + self.fl, x, wt, self.w[key + '.bias'], resid, out, part, B, Hh, Ww, Cin, Cout, out_mode)
         return out
 
-    def gn_stats16(self, x, B, HW):
-        return self._stats_from(x, B, HW, 'gn_stats_' + self.sfx)
+    def gn_stats(self, x, B, HW):
+        return self.eng._stats_from(x, B, HW, 'gn_stats_' + self.fl)
 
-    def gn16(self, x, key, B, HW, silu):
-        stats = self.gn_stats16(x, B, HW)
+    def gn(self, x, key, B, HW, silu):
+        stats = self.gn_stats(x, B, HW)
         out = torch.empty_like(x)
-        hip.call('gn_apply_' + self.sfx, x, stats, self.w[key + '.weight'], self.w[key + '.bias'], out, B, HW, x.shape[-1], 32, int(silu))
+        hip.call('gn_apply_' + self.fl, x, stats, self.w[key + '.weight'], self.w[key + '.bias'], out, B, HW, x.shape[-1], 32, int(silu))
         return out
 
-    def tail16(self, h, B, Hh, Ww, denorm):
-        """norm_out -> swish -> conv_out -> clamp (-> (x + 1) / 2) (basic_vae.py:224-226, vqvae.py:63, var.py:190): one pass over the map
-        (varhip_gn_silu_conv_out_*) where it tiles into 8 x 32 patches, else GroupNorm apply + conv — the same bits either way"""
-        wt = self.w16['decoder.conv_out.weight']
-        Cout, Cin = wt.shape[0], wt.shape[3]
-        if Hh % 8 == 0 and Ww % 32 == 0 and Cin % 32 == 0 and Cout <= 16 and (2 * 22 * 1024 + Cout * 9 * Cin * 2 + 16 + 8 * Cin) <= 64 * 1024 and not self.unfused_tail:
-            stats = self.gn_stats16(h, B, Hh * Ww)
-            out = torch.empty((B, Cout, Hh, Ww), dtype=torch.float32, device=h.device)
-            hip.call('gn_silu_conv_out_' + self.sfx, h, stats, self.w['decoder.norm_out.weight'], self.w['decoder.norm_out.bias'], wt,
-                     self.w['decoder.conv_out.bias'], out, B, Hh, Ww, Cin, Cout, 32, 1 if denorm else 2)
-            return out
-        h = self.gn16(h, 'decoder.norm_out', B, Hh * Ww, True)
-        return self.conv3_16(h, 'decoder.conv_out', B, Hh, Ww, out_mode=1 if denorm else 2)
-
-    fuse_gn = os.environ.get('VARHIP_FUSE_GN', '1') != '0'      # False (tests, A/B runs): every GroupNorm + SiLU as its own pass in front of the conv (the same bits)
-
-    def gnconv3_16(self, x, nkey, ckey, B, Hh, Ww, resid=None):
-        """conv(swish(norm(x))) (basic_vae.py:57-60): one launch where the halo-patch conv can normalise its own input patch, else apply pass + conv"""
+    def norm_conv(self, x, nkey, ckey, B, Hh, Ww, resid=None):
+        """conv(swish(norm(x))) (basic_vae.py:57-60): one launch where the halo-patch conv can normalise its own input patch, else apply pass + conv.
+        Always leaves partials: its callers are ResnetBlocks (after the encoder's conv_out nobody reads them, and the walk drops them)"""
         wt = self.w16[ckey + '.weight']
         Cout, Cin = wt.shape[0], wt.shape[3]
-        if not (self.fuse_gn and hip.conv16_gn_fusable(B, Hh, Ww, Cin, Cout)):
-            return self.conv3_16(self.gn16(x, nkey, B, Hh * Ww, True), ckey, B, Hh, Ww, resid=resid, stats=True)
-        stats = self.gn_stats16(x, B, Hh * Ww)
-        out = torch.empty((B, Hh, Ww, Cout), dtype=self.dt16, device=x.device)
-        nblk = hip.conv_gn_blocks(Hh, Ww, Cout) if Cout % 4 == 0 else 0
-        part = self._part_buffer(B, nblk, Cout, x.device) if nblk else None
+        if not (self.eng.fuse_gn and hip.conv16_gn_fusable(B, Hh, Ww, Cin, Cout)):
+            return self.conv3(self.gn(x, nkey, B, Hh * Ww, True), ckey, B, Hh, Ww, resid=resid, stats=True)
+        stats = self.gn_stats(x, B, Hh * Ww)
+        out = torch.empty((B, Hh, Ww, Cout), dtype=self.dt, device=x.device)
+        part = self.eng._leave_partials(out, B, hip.conv_gn_blocks(Hh, Ww, Cout) if Cout % 4 == 0 else 0)
         table = torch.empty((B, 2, Cin), dtype=torch.float32, device=x.device)
         hip.call('gn_scale_shift_f32', stats, self.w[nkey + '.weight'], self.w[nkey + '.bias'], table, B, Cin, 32)
-        hip.call('gnconv3x3_nhwc_' + self.sfx, x, table, 1, wt, self.w[ckey + '.bias'], resid, out, part, B, Hh, Ww, Cin, Cout)
-        if nblk: self._gn_part = (out, part, nblk)
+        hip.call('gnconv3x3_nhwc_' + self.fl, x, table, 1, wt, self.w[ckey + '.bias'], resid, out, part, B, Hh, Ww, Cin, Cout)
         return out
 
-    def resblock16(self, x, pre, B, Hh, Ww):
+    def resblock(self, x, pre, B, Hh, Ww):
         HW = Hh * Ww
-        h = self.gnconv3_16(x, pre + '.norm1', pre + '.conv1', B, Hh, Ww)
+        h = self.norm_conv(x, pre + '.norm1', pre + '.conv1', B, Hh, Ww)
         sc = x
         if (pre + '.nin_shortcut.weight') in self.w16 and self.w16[pre + '.nin_shortcut.weight'].shape[1] % 64:
             # (the encoder's 160 -> 320 shortcut: the 16-bit GEMM contracts 64 at a time) the fp32 GEMM between two casts
-            x32 = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-            hip.call(f'cast_{self.sfx}_to_f32', x, x32, x.numel())
-            sc32 = self.lin(x32.view(B * HW, -1), pre + '.nin_shortcut')
-            sc = torch.empty((B, Hh, Ww, sc32.shape[1]), dtype=self.dt16, device=x.device)
-            hip.call('cast_f32_to_' + self.sfx, sc32, sc, sc.numel())
+            sc32 = self.eng.lin(self._to32(x).view(B * HW, -1), pre + '.nin_shortcut')
+            sc = self._to16(sc32, (B, Hh, Ww, sc32.shape[1]))
         elif (pre + '.nin_shortcut.weight') in self.w16:              # 1x1 conv == fp16 GEMM over the pixels
             wt = self.w16[pre + '.nin_shortcut.weight']
             N, K = wt.shape
-            sc = torch.empty((B, Hh, Ww, N), dtype=self.dt16, device=x.device)
-            hip.call('gemm_nt_' + self.sfx, x, K, wt, K, self.w[pre + '.nin_shortcut.bias'], sc, N, 1, B * HW, N, K, EPI_NONE, None, 0, 0, None, 0, 1, 1, 0, 0, 0)
-        return self.gnconv3_16(h, pre + '.norm2', pre + '.conv2', B, Hh, Ww, resid=sc)
+            sc = torch.empty((B, Hh, Ww, N), dtype=self.dt, device=x.device)
+            hip.call('gemm_nt_' + self.fl, x, K, wt, K, self.w[pre + '.nin_shortcut.bias'], sc, N, 1, B * HW, N, K, EPI_NONE, None, 0, 0, None, 0, 1, 1, 0, 0, 0)
+        return self.norm_conv(h, pre + '.norm2', pre + '.conv2', B, Hh, Ww, resid=sc)
 
-    def attnblock16(self, x, pre, B, Hh, Ww):
+    def attnblock(self, x, pre, B, Hh, Ww):
         """AttnBlock (basic_vae.py:73-92) on fp16 activations: the five products (q/k projection, V^T projection, q.k^T, p.v, proj_out + residual)
         on the f16 MFMA GEMM with fp32 accumulation; scores and softmax in fp32, the probabilities rounded to fp16 for p.v"""
         HW, Cc = Hh * Ww, x.shape[-1]
         dev = x.device
-        f16 = self.dt16
+        f16 = self.dt
         if Cc % 64 or HW % 64:                     # (tiny test configurations: the f16 GEMM contracts 64 at a time) fp32 attention between two casts
-            x32 = torch.empty(x.shape, dtype=torch.float32, device=dev)
-            hip.call(f'cast_{self.sfx}_to_f32', x, x32, x.numel())
-            self._gn_part = None
-            y32 = self.attnblock(x32, pre, B, Hh, Ww)
-            y = torch.empty(x.shape, dtype=f16, device=dev)
-            hip.call('cast_f32_to_' + self.sfx, y32, y, y.numel())
-            return y
-        xn = self.gn16(x, pre + '.norm', B, HW, False).view(B * HW, Cc)
+            x32 = self._to32(x)
+            self.eng._gn_part = None
+            return self._to16(self.eng.attnblock(x32, pre, B, Hh, Ww))
+        xn = self.gn(x, pre + '.norm', B, HW, False).view(B * HW, Cc)
         wqkv, bqkv = self.w16[pre + '.qkv.weight'], self.w[pre + '.qkv.bias']
         g16 = lambda A, lda, W, ldw, bias, out, ldo, o16, M, N, K, epi=EPI_NONE, resid=None, ldr=0, r16=0, batch=1, sA=0, sW=0, sO=0: \
-            hip.call('gemm_nt_' + self.sfx, A, lda, W, ldw, bias, out, ldo, o16, M, N, K, epi, resid, ldr, r16, None, 0, 1, batch, sA, sW, sO)
+            hip.call('gemm_nt_' + self.fl, A, lda, W, ldw, bias, out, ldo, o16, M, N, K, epi, resid, ldr, r16, None, 0, 1, batch, sA, sW, sO)
         qk = torch.empty((B * HW, 2 * Cc), dtype=f16, device=dev)
         g16(xn, Cc, wqkv, Cc, bqkv, qk, 2 * Cc, 1, B * HW, 2 * Cc, Cc)
         # V^T[b][c][j] WITHOUT its bias: the GEMM's bias is per column and here c is the row.  The rows of p sum to one, so the bias is added
@@ -465,40 +476,159 @@ class DecoderEngine(_VaeOps):
         g16(qk, 2 * Cc, qk[:, Cc:], 2 * Cc, None, s, HW, 0, HW, HW, Cc, batch=B, sA=HW * 2 * Cc, sW=HW * 2 * Cc, sO=HW * HW)
         p32 = torch.empty_like(s)
         hip.call('softmax_rows_f32', s, p32, B * HW, HW, float(np.float32(int(Cc) ** (-0.5))))
-        p = torch.empty((B, HW, HW), dtype=f16, device=dev)
-        hip.call('cast_f32_to_' + self.sfx, p32, p, p.numel())
+        p = self._to16(p32)
         o = torch.empty((B * HW, Cc), dtype=f16, device=dev)
         g16(p, HW, vt, HW, bqkv[2 * Cc:], o, Cc, 1, HW, Cc, HW, batch=B, sA=HW * HW, sW=Cc * HW, sO=HW * Cc)
         y = torch.empty((B, Hh, Ww, Cc), dtype=f16, device=dev)
         g16(o, Cc, self.w16[pre + '.proj_out.weight'], Cc, self.w[pre + '.proj_out.bias'], y, Cc, 1, B * HW, Cc, Cc, epi=EPI_RESID, resid=x, ldr=Cc, r16=1)
         return y
 
-    def _decode16(self, f_hat: torch.Tensor, denorm: bool) -> torch.Tensor:
-        B, P = f_hat.shape[0], f_hat.shape[1]
-        Hh = Ww = P
-        x = torch.empty(f_hat.shape, dtype=self.dt16, device=f_hat.device)
-        hip.call('cast_f32_to_' + self.sfx, f_hat.contiguous(), x, x.numel())
-        h = self.conv3_16(x, 'post_quant_conv', B, Hh, Ww)
-        h = self.conv3_16(h, 'decoder.conv_in', B, Hh, Ww, stats=True)
-        h = self.resblock16(h, 'decoder.mid.block_1', B, Hh, Ww)
-        h = self.attnblock16(h, 'decoder.mid.attn_1', B, Hh, Ww)
-        h = self.resblock16(h, 'decoder.mid.block_2', B, Hh, Ww)
-        for lev in reversed(range(self.nlev)):
-            for ib in range(3):
-                h = self.resblock16(h, f'decoder.up.{lev}.block.{ib}', B, Hh, Ww)
-                if f'decoder.up.{lev}.attn.{ib}.norm.weight' in self.w:
-                    h = self.attnblock16(h, f'decoder.up.{lev}.attn.{ib}', B, Hh, Ww)
-            if lev != 0:
-                Hh, Ww = 2 * Hh, 2 * Ww
-                key = f'decoder.up.{lev}.upsample.conv'
-                wp = self.w16[key + '.phase']
-                up = torch.empty((B, Hh, Ww, wp.shape[1]), dtype=self.dt16, device=h.device)
-                nblk = hip.conv_gn_blocks(Hh, Ww, wp.shape[1], phase=True)
-                part = self._part_buffer(B, nblk, wp.shape[1], h.device) if nblk else None
-                hip.call('upconv_phase_' + self.sfx, h, wp, self.w[key + '.bias'], up, part, B, Hh, Ww, wp.shape[4], wp.shape[1])
-                self._gn_part = (up, part, nblk) if nblk else None
-                h = up
-        return self.tail16(h, B, Hh, Ww, denorm)
+    def upsample(self, h, key, B, Hh, Ww):
+        """Upsample2x onto an Hh x Ww map, as DecoderEngine.upsample; one entry point with or without partials"""
+        wp = self.w16[key + '.phase']
+        up = torch.empty((B, Hh, Ww, wp.shape[1]), dtype=self.dt, device=h.device)
+        part = self.eng._leave_partials(up, B, hip.conv_gn_blocks(Hh, Ww, wp.shape[1], phase=True))
+        hip.call('upconv_phase_' + self.fl, h, wp, self.w[key + '.bias'], up, part, B, Hh, Ww, wp.shape[4], wp.shape[1])
+        return up
+
+    def downsample(self, h, key, B, Hh, Ww):
+        """Downsample2x onto an Hh x Ww map (conv16s2.hip)"""
+        wt = self.w16[key + '.weight']
+        out = torch.empty((B, Hh, Ww, wt.shape[0]), dtype=self.dt, device=h.device)
+        self.eng._leave_partials(out, B, 0)
+        hip.call('conv3x3_s2_nhwc_' + self.fl, h, wt, self.w[key + '.bias'], out, B, Hh, Ww, wt.shape[3], wt.shape[0])
+        return out
+
+    def tail(self, h, key, B, Hh, Ww, denorm, clamp=True):
+        """DecoderEngine.tail on a 16-bit map (varhip_gn_silu_conv_out_*); there is no unclamped form (decode_nhwc refuses it)"""
+        wt = self.w16[key + '.conv_out.weight']
+        Cout, Cin = wt.shape[0], wt.shape[3]
+        mode = _tail_mode(denorm, True)
+        if Hh % 8 == 0 and Ww % 32 == 0 and Cin % 32 == 0 and Cout <= 16 and (2 * 22 * 1024 + Cout * 9 * Cin * 2 + 16 + 8 * Cin) <= 64 * 1024 and not self.eng.unfused_tail:
+            stats = self.gn_stats(h, B, Hh * Ww)
+            out = torch.empty((B, Cout, Hh, Ww), dtype=torch.float32, device=h.device)
+            hip.call('gn_silu_conv_out_' + self.fl, h, stats, self.w[key + '.norm_out.weight'], self.w[key + '.norm_out.bias'], wt,
+                     self.w[key + '.conv_out.bias'], out, B, Hh, Ww, Cin, Cout, 32, mode)
+            return out
+        h = self.gn(h, key + '.norm_out', B, Hh * Ww, True)
+        return self.conv3(h, key + '.conv_out', B, Hh, Ww, out_mode=mode)
+
+
+# Winograd F(2x2,3x3) filter transform (Lavin & Gray 2016): U = G g G^T per (output, input) channel pair
+_WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+
+
+def wino_filter(w: torch.Tensor) -> torch.Tensor:
+    """[Cout][3][3][Cin] fp32 kernel -> U = G g G^T in float64, rounded once to fp32 and laid out [16][Cin/16][Cout][16] (xi = 4 i + j
+    of the 4x4 transform, input-channel tile, output channel, input channel in the tile) for varhip_conv3x3_wino_nhwc_f32"""
+    co, _, _, ci = w.shape
+    G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
+    u = torch.einsum('ik,jl,oklc->ijoc', G, G, w.double()).float()                      # [4][4][Cout][Cin]
+    return u.reshape(16, co, ci // 16, 16).permute(0, 2, 1, 3).contiguous()
+
+
+class DecoderEngine(_VaeOps):
+    """VQVAE.fhat_to_img on HIP kernels (reference vqvae.py:62-63, basic_vae.py:163-226)."""
+
+    PREFIXES = ('decoder.', 'post_quant_conv.')
+    LEVELS = 'decoder.up.'
+    # default precision of the VQVAE's own entry points (fhat_to_img, idxBl_to_img, ...): 'f32' unless the VQVAE's owner asks for 'f16'
+    # here.  The sampling loop does NOT change it: SamplingEngine passes its own precision with every decode_nhwc call, so two VARs
+    # sharing one VQVAE, or a VAR in the 16-bit mode next to direct VQVAE calls, never fight over a mode flag.
+    precision = 'f32'
+    unfused_tail = False         # tests: run norm_out / conv_out of the decoder as two launches
+    # The ResnetBlock convolutions (stride 1, 3x3) as fused Winograd F(2x2,3x3) (winograd.hip) where wino_ok() holds; False (tests, A/B runs):
+    # every conv on the direct implicit-GEMM kernel.  VARHIP_WINOGRAD=0 sets the default for a whole process.
+    winograd = os.environ.get('VARHIP_WINOGRAD', '1') != '0'
+    WINO_MIN_HW = 16 * 16        # smallest map that takes it (DESIGN.md §13: 1.63-1.72x faster than the direct kernel at every decoder level)
+    # the precision flops_per_image_executed counts when not given one: that of the last decode_nhwc, or the one the owning SamplingEngine was
+    # last set to (SamplingEngine.set_precision), whichever came later; None: `precision`.  Only an f32 decode runs the Winograd kernel.
+    flops_precision = None
+
+    def set_precision(self, precision: str):
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}")
+        self.precision = precision
+
+    def _derive(self, w):
+        for k in [k for k in w if k.endswith('.upsample.conv.weight')]:        # Upsample2x convs: pre-summed 2x2 phase weights
+            cout, _, _, cin = w[k].shape
+            wp = torch.empty(4, cout, 2, 2, cin, dtype=torch.float32, device=w[k].device)
+            hip.call('upconv_pack_f32', w[k], wp, cin, cout)
+            w[k[:-len('weight')] + 'phase'] = wp
+        for k in [k for k in w if k.endswith(('.conv1.weight', '.conv2.weight'))]:   # ResnetBlock convs: Winograd filter transforms
+            w[k[:-len('weight')] + 'wino'] = wino_filter(w[k])
+        return w
+
+    # -- the fp32 blocks only a decoder has ------------------------------------------------------------------------------------------
+    def wino_ok(self, Hh, Ww, Cin, Cout):
+        """the shape rule of the Winograd path: maps of at least WINO_MIN_HW pixels in whole 16 x 16 patches, channels in multiples of 32"""
+        return Hh * Ww >= self.WINO_MIN_HW and Hh % 16 == 0 and Ww % 16 == 0 and Cin % 32 == 0 and Cout % 32 == 0
+
+    def _wino(self, key, Hh, Ww, Cin, Cout):
+        return self.w.get(key + '.wino') if self.winograd and self.wino_ok(Hh, Ww, Cin, Cout) else None
+
+    def upsample(self, h, key, B, Hh, Ww):
+        """Upsample2x onto an Hh x Ww map: nearest 2x + conv3x3, as 4 phase convs on the low-res map.  Its result is normalised by the next
+        level's first ResnetBlock: the partials where the shape has them"""
+        wp = self.w[key + '.phase']
+        up = torch.empty((B, Hh, Ww, wp.shape[1]), dtype=torch.float32, device=h.device)
+        part = self._leave_partials(up, B, hip.conv_gn_blocks(Hh, Ww, wp.shape[1], phase=True))
+        if part is not None:
+            hip.call('upconv_phase_gn_f32', h, wp, self.w[key + '.bias'], up, part, B, Hh, Ww, wp.shape[4], wp.shape[1])
+        else:
+            hip.call('upconv_phase_f32', h, wp, self.w[key + '.bias'], up, B, Hh, Ww, wp.shape[4], wp.shape[1])
+        return up
+
+    def tail(self, h, key, B, Hh, Ww, denorm, clamp=True):
+        """norm_out -> swish -> conv_out -> clamp (-> (x + 1) / 2) (basic_vae.py:224-226, vqvae.py:63, var.py:190): one pass over the map
+        (varhip_gn_silu_conv_out_f32) where it tiles into 8 x 32 patches, else GroupNorm apply + conv — the same bits either way.
+        clamp=False: conv_out's value as it is (out_mode 3; vqvae.py:59, VQVAE.forward)"""
+        wt = self.w[key + '.conv_out.weight']
+        Cout, Cin = wt.shape[0], wt.shape[3]
+        mode = _tail_mode(denorm, clamp)
+        if Hh % 8 == 0 and Ww % 32 == 0 and Cin % 32 == 0 and Cout <= 4 and (10 * 34 * 36 + 4 * Cin) * 4 <= 64 * 1024 and not self.unfused_tail:
+            stats = self.gn_stats(h, B, Hh * Ww)
+            out = torch.empty((B, Cout, Hh, Ww), dtype=torch.float32, device=h.device)
+            hip.call('gn_silu_conv_out_f32', h, stats, self.w[key + '.norm_out.weight'], self.w[key + '.norm_out.bias'], wt,
+                     self.w[key + '.conv_out.bias'], out, B, Hh, Ww, Cin, Cout, 32, mode)
+            return out
+        h = self.gn(h, key + '.norm_out', B, Hh * Ww, True)
+        return self.conv3(h, key + '.conv_out', B, Hh, Ww, out_mode=mode)
+
+    # -- model arithmetic (for bench.py's roofline) ------------------------------------------------------------------------------------
+    def _flops(self, P: int, prec: Optional[str]) -> float:
+        """2 FLOPs per MAC summed over the decoder graph at a P x P f_hat.  prec None: every 3x3 conv at its 9 taps; else what a decode in
+        `prec` executes (see flops_per_image_executed)"""
+        self.refresh()
+        w, f, hw, side = self.w, 0.0, P * P, P
+        def c3(key, taps=9): co, _, _, ci = w[key + '.weight'].shape; return 2.0 * hw * co * taps * ci
+        def c1(key): co, ci = w[key + '.weight'].shape; return 2.0 * hw * co * ci
+        def res_taps(key): co, _, _, ci = w[key + '.weight'].shape; return 4 if prec == 'f32' and self.winograd and self.wino_ok(side, side, ci, co) else 9
+        for kind, key in _decoder_graph(w, self.nlev):
+            if kind == 'conv':
+                f += c3(key)
+            elif kind == 'res':
+                f += c3(key + '.conv1', res_taps(key + '.conv1')) + c3(key + '.conv2', res_taps(key + '.conv2'))
+                if (key + '.nin_shortcut.weight') in w: f += c1(key + '.nin_shortcut')
+            elif kind == 'attn':
+                f += c1(key + '.qkv') + c1(key + '.proj_out') + 2.0 * 2 * hw * hw * w[key + '.proj_out.weight'].shape[0]
+            elif kind == 'up':
+                hw *= 4; side *= 2
+                f += c3(key, 9 if prec is None else 4)
+            else:
+                f += c3(key + '.conv_out')
+        return f
+
+    def flops_per_image_reference(self, P: int) -> float:
+        """FLOPs (2/MAC) of one decode as the REFERENCE computes it (9-tap upsample convs; SURVEY.md §8d: 393.7 G at P=16, ch=160)"""
+        return self._flops(P, None)
+
+    def flops_per_image_executed(self, P: int, precision: Optional[str] = None) -> float:
+        """FLOPs the kernels execute for one decode in `precision` (None: `flops_precision`): as flops_per_image_reference, with the Upsample2x
+        convolutions in their folded four-phase form (4 taps per output pixel instead of 9) and, in an f32 decode, the ResnetBlock convolutions
+        that take the Winograd path at 16 multiplies per 2x2 output tile (4 per output pixel instead of 9; the 16-bit decode has no such path)"""
+        return self._flops(P, precision or self.flops_precision or self.precision)
 
     def decode_nhwc(self, f_hat: torch.Tensor, denorm: bool = True, precision: Optional[str] = None, clamp: bool = True) -> torch.Tensor:
         """[B,P,P,Cvae] channels-last -> [B,3,16P,16P]; denorm=True: in [0,1] (clamp and (x+1)/2 fused into the last conv, what
@@ -510,65 +640,30 @@ class DecoderEngine(_VaeOps):
         if not clamp and prec != 'f32':
             raise hip.VarHipError('decode_nhwc(clamp=False) is the fp32 decoder only')
         self.flops_precision = prec
-        if prec != 'f32':
-            self._ensure16(prec)
-            self._wait_ready()
-            return self._decode16(f_hat, denorm)
+        ops = self if prec == 'f32' else self.ops16(prec)
         self._wait_ready()
         B, P = f_hat.shape[0], f_hat.shape[1]
-        Hh = Ww = P
-        h = self.conv3(f_hat, 'post_quant_conv', B, Hh, Ww)
-        h = self.conv3(h, 'decoder.conv_in', B, Hh, Ww, stats=True)
-        h = self.resblock(h, 'decoder.mid.block_1', B, Hh, Ww)
-        h = self.attnblock(h, 'decoder.mid.attn_1', B, Hh, Ww)
-        h = self.resblock(h, 'decoder.mid.block_2', B, Hh, Ww)
-        for lev in reversed(range(self.nlev)):
-            for ib in range(3):
-                h = self.resblock(h, f'decoder.up.{lev}.block.{ib}', B, Hh, Ww)
-                if f'decoder.up.{lev}.attn.{ib}.norm.weight' in self.w:
-                    h = self.attnblock(h, f'decoder.up.{lev}.attn.{ib}', B, Hh, Ww)
-            if lev != 0:                                             # Upsample2x: nearest 2x + conv3x3, as 4 phase convs on the low-res map
-                Hh, Ww = 2 * Hh, 2 * Ww
-                key = f'decoder.up.{lev}.upsample.conv'
-                wp = self.w[key + '.phase']
-                up = torch.empty((B, Hh, Ww, wp.shape[1]), dtype=torch.float32, device=h.device)
-                nblk = hip.conv_gn_blocks(Hh, Ww, wp.shape[1], phase=True)
-                if nblk:                                             # its result is normalised by the next level's first ResnetBlock
-                    part = self._part_buffer(B, nblk, wp.shape[1], h.device)
-                    hip.call('upconv_phase_gn_f32', h, wp, self.w[key + '.bias'], up, part, B, Hh, Ww, wp.shape[4], wp.shape[1])
-                    self._gn_part = (up, part, nblk)
-                else:
-                    hip.call('upconv_phase_f32', h, wp, self.w[key + '.bias'], up, B, Hh, Ww, wp.shape[4], wp.shape[1])
-                h = up
-        return self.tail(h, B, Hh, Ww, denorm, clamp)
+        h = f_hat if prec == 'f32' else ops._to16(f_hat.contiguous())
+        return self._run(ops, _decoder_graph(self.w, self.nlev), h, B, P, P, denorm=denorm, clamp=clamp)
 
 
-class QuantizerEngine:
+class QuantizerEngine(_Engine):
     """Encode-side methods of VectorQuantizer2 on HIP: f_to_idxBl_or_fhat (quant.py:135-166) and idxBl_to_var_input (quant.py:169-184)"""
 
     def __init__(self, quant):
+        super().__init__()
         self.quant = quant
-        self._sig = None
 
     def refresh(self):
-        q = self.quant
-        sig = _signature(q.parameters())
+        sig = _signature(self.quant.parameters())
         if sig == self._sig:
             return
-        self.codebook = _chk(q.embedding.weight.detach(), 'codebook')
-        self.phi = [(_chk(p.weight.detach(), 'phi').permute(0, 2, 3, 1).contiguous(), _chk(p.bias.detach(), 'phi'), float(p.resi_ratio))
-                    for p in q.quant_resi.phis()]
-        self._taps = {}
+        self.codebook, self.phi = _pack_quantizer(self.quant)
+        self._taps = {}                      # {P: {pn: tap tables}}: the scales are the caller's, call by call
         self._sig = sig
 
-    def invalidate(self):
-        self._sig = None
-
-    def taps(self, pn, P, dev):
-        if (pn, P) not in self._taps:
-            ti, tw = bicubic_taps(pn, P)
-            self._taps[(pn, P)] = (torch.from_numpy(ti).to(dev), torch.from_numpy(tw).to(dev))
-        return self._taps[(pn, P)]
+    def tables(self, si, S, pn, P, dev):
+        return _scale_tables(self._taps.setdefault(P, {}), self.phi, si, S, pn, P, dev)
 
     @torch.no_grad()
     def quantize(self, f_nhwc: torch.Tensor, to_fhat: bool, patch_nums, last_fhat: bool = False, stats: Optional[dict] = None):
@@ -597,8 +692,7 @@ class QuantizerEngine:
             idx = torch.empty(B * pn * pn, dtype=torch.int64, device=dev)
             # argmin |z - e|^2, or argmax cos(z, e) when using_znorm (quant.py:151-157)
             hip.call('nearest_code_cos_f32' if self.quant.using_znorm else 'nearest_code_f32', z, self.codebook, idx, B * pn * pn, self.codebook.shape[0], Cv)
-            ti, tw = self.taps(pn, P, dev) if pn != P else (None, None)
-            pw, pb, ratio = self.phi[phi_index(si, S, len(self.phi))]
+            ti, tw, pw, pb, ratio = self.tables(si, S, pn, P, dev)
             hip.call('quant_residual_f32', idx, self.codebook, ti, tw, pw, pb, ratio, up, f_hat, f_rest, B, pn, P, Cv)
             if stats is not None:
                 hip.call('vq_scale_stats_f32', f_hat, f_nhwc, f_hat.numel(), idx, B * pn * pn, V, stats['hits_SV'][si], scratch,
@@ -638,8 +732,7 @@ class QuantizerEngine:
         up = torch.empty_like(f_hat)
         outs = []
         for si, pn in enumerate(patch_nums):
-            ti, tw = self.taps(pn, P, dev) if pn != P else (None, None)
-            pw, pb, ratio = self.phi[phi_index(si, S, len(self.phi))]
+            ti, tw, pw, pb, ratio = self.tables(si, S, pn, P, dev)
             if from_tokens:
                 hip.call('quant_accum_f32', items[si].to(dev, torch.int64).contiguous(), self.codebook, ti, tw, pw, pb, ratio, up, f_hat, B, pn, P, Cv)
             else:
@@ -665,8 +758,7 @@ class QuantizerEngine:
         cur = 0
         for si in range(S - 1):
             pn, pq = patch_nums[si], patch_nums[si + 1]
-            ti, tw = self.taps(pn, P, dev) if pn != P else (None, None)
-            pw, pb, ratio = self.phi[phi_index(si, S, len(self.phi))]
+            ti, tw, pw, pb, ratio = self.tables(si, S, pn, P, dev)
             hip.call('quant_accum_f32', idx_list[si].to(torch.int64).contiguous(), self.codebook, ti, tw, pw, pb, ratio, up, f_hat, B, pn, P, Cv)
             pooled = torch.empty((B, pq * pq, Cv), dtype=torch.float32, device=dev)
             hip.call('area_pool_f32', f_hat, pooled, B, P, pq, Cv)
@@ -675,109 +767,41 @@ class QuantizerEngine:
         return out
 
 
-class EncoderEngine(DecoderEngine):
-    """Encoder + quant_conv on HIP (reference vqvae.py:65-75 img_to_*: basic_vae.py:99-160).  Inherits the channels-last conv /
-    GroupNorm / attention building blocks of DecoderEngine."""
+
+class EncoderEngine(_VaeOps):
+    """Encoder + quant_conv on HIP (reference vqvae.py:65-75 img_to_*: basic_vae.py:99-160)."""
 
     PREFIXES = ('encoder.', 'quant_conv.')
+    LEVELS = 'encoder.down.'
+    precision = 'f32'            # what encode() runs in when not told: there is no mode to set, a 16-bit encode is asked for per call
+    last_precision = None        # the precision the last encode() ran in ('f32' | 'f16' | 'bf16')
 
-    def refresh(self):
-        sig = self._signature()
-        if sig == self._sig:
-            return
-        self._retire()
-        self.w = self._pack()
-        self.w16s = {}                       # 16-bit copies per flavour, made by _ensure16() when an encode(precision='f16' | 'bf16') first runs
-        self.nlev = 1 + max(int(k.split('.')[2]) for k in self.w if k.startswith('encoder.down.'))
-        self._sig = sig
-        self._built()
-
-    def conv_s2(self, x, key, B, Hh, Ww):
+    def downsample(self, x, key, B, Hh, Ww):
+        """Downsample2x onto an Hh x Ww map: the stride-2 conv over the map padded right and below (basic_vae.py:41-42)"""
         wt = self.w[key + '.weight']
         Cout, Cin = wt.shape[0], wt.shape[3]
         out = torch.empty((B, Hh, Ww, Cout), dtype=torch.float32, device=x.device)
         hip.call('conv3x3_s2_nhwc_f32', x, wt, self.w[key + '.bias'], out, B, Hh, Ww, Cin, Cout)
         return out
 
-    last_precision = None        # the precision the last encode() ran in ('f32' | 'f16' | 'bf16')
-    conv_in16 = True             # the 16-bit encoder's conv_in on the 16-bit conv (padded image rounded to 16 bits); False (A/B runs): fp32 conv + cast
-
     @torch.no_grad()
     def encode(self, img: torch.Tensor, precision: Optional[str] = None) -> torch.Tensor:
         """img (B,3,H,W) fp32 in [-1,1] -> f (B, H/16, W/16, Cvae) fp32 channels-last == quant_conv(encoder(img)).
-        precision: None or 'f32' — the fp32 encoder; 'f16' / 'bf16' — the 16-bit encoder (_encode16) for THIS call"""
+        precision: None or 'f32' — the fp32 encoder; 'f16' / 'bf16' — for THIS call the encoder on 16-bit activations and conv weights with
+        fp32 accumulation: the image is rounded to 16 bits once, after its channels are zero-padded to conv_in's 32.  quant_conv runs in fp32
+        on the cast conv_out map either way, so f (what the quantizer and the feature distance read) is fp32."""
         if precision not in (None,) + PRECISIONS:
             raise ValueError(f"precision must be None or one of {PRECISIONS}")
         self.refresh()
-        self.last_precision = precision or 'f32'
-        if precision in DT16:
-            self._ensure16(precision)
-            self._wait_ready()
-            return self._encode16(img)
+        prec = self.last_precision = precision or self.precision
+        ops = self if prec == 'f32' else self.ops16(prec)
         self._wait_ready()
         B, Ci, Hh, Ww = img.shape
         cin_pad = self.w['encoder.conv_in.weight'].shape[3]
         x = torch.empty((B, Hh, Ww, cin_pad), dtype=torch.float32, device=img.device)
         hip.call('nchw_to_nhwc_pad_f32', img.contiguous(), x, B, Ci, Hh * Ww, cin_pad)
-        h = self.conv3(x, 'encoder.conv_in', B, Hh, Ww)
-        for lev in range(self.nlev):
-            for ib in range(2):
-                h = self.resblock(h, f'encoder.down.{lev}.block.{ib}', B, Hh, Ww)
-                if f'encoder.down.{lev}.attn.{ib}.norm.weight' in self.w:
-                    h = self.attnblock(h, f'encoder.down.{lev}.attn.{ib}', B, Hh, Ww)
-            if lev != self.nlev - 1:
-                Hh, Ww = Hh // 2, Ww // 2
-                h = self.conv_s2(h, f'encoder.down.{lev}.downsample.conv', B, Hh, Ww)
-        h = self.resblock(h, 'encoder.mid.block_1', B, Hh, Ww)
-        h = self.attnblock(h, 'encoder.mid.attn_1', B, Hh, Ww)
-        h = self.resblock(h, 'encoder.mid.block_2', B, Hh, Ww)
-        h = self.conv3(self.gn(h, 'encoder.norm_out', B, Hh * Ww, True), 'encoder.conv_out', B, Hh, Ww)
-        return self.conv3(h, 'quant_conv', B, Hh, Ww)
-
-    def _to16(self, x32):
-        y = torch.empty(x32.shape, dtype=self.dt16, device=x32.device)
-        hip.call('cast_f32_to_' + self.sfx, x32, y, y.numel())
-        return y
-
-    def _to32(self, x16):
-        y = torch.empty(x16.shape, dtype=torch.float32, device=x16.device)
-        hip.call(f'cast_{self.sfx}_to_f32', x16, y, y.numel())
-        return y
-
-    def _encode16(self, img: torch.Tensor) -> torch.Tensor:
-        """the encoder on 16-bit activations and conv weights with fp32 accumulation (conv16.hip, rowops16.hip, the 16-bit AttnBlock of the
-        decoder, conv16s2.hip for Downsample2x): the image is rounded to 16 bits once, after its channels are zero-padded to conv_in's 32
-        (conv_in16 False: conv_in in fp32, its output cast).  quant_conv runs in fp32 on the cast conv_out map, so f (what the quantizer and
-        the feature distance read) is fp32 as in the fp32 encoder."""
-        B, Ci, Hh, Ww = img.shape
-        cin_pad = self.w['encoder.conv_in.weight'].shape[3]
-        x = torch.empty((B, Hh, Ww, cin_pad), dtype=torch.float32, device=img.device)
-        hip.call('nchw_to_nhwc_pad_f32', img.contiguous(), x, B, Ci, Hh * Ww, cin_pad)
-        self._gn_part = None
-        if self.conv_in16:
-            h = self.conv3_16(self._to16(x), 'encoder.conv_in', B, Hh, Ww, stats=True)
-        else:
-            h = self._to16(self.conv3(x, 'encoder.conv_in', B, Hh, Ww))
-        for lev in range(self.nlev):
-            for ib in range(2):
-                h = self.resblock16(h, f'encoder.down.{lev}.block.{ib}', B, Hh, Ww)
-                if f'encoder.down.{lev}.attn.{ib}.norm.weight' in self.w:
-                    h = self.attnblock16(h, f'encoder.down.{lev}.attn.{ib}', B, Hh, Ww)
-            if lev != self.nlev - 1:
-                Hh, Ww = Hh // 2, Ww // 2
-                key = f'encoder.down.{lev}.downsample.conv'
-                wt = self.w16[key + '.weight']
-                out = torch.empty((B, Hh, Ww, wt.shape[0]), dtype=self.dt16, device=h.device)
-                self._gn_part = None
-                hip.call('conv3x3_s2_nhwc_' + self.sfx, h, wt, self.w[key + '.bias'], out, B, Hh, Ww, wt.shape[3], wt.shape[0])
-                h = out
-        h = self.resblock16(h, 'encoder.mid.block_1', B, Hh, Ww)
-        h = self.attnblock16(h, 'encoder.mid.attn_1', B, Hh, Ww)
-        h = self.resblock16(h, 'encoder.mid.block_2', B, Hh, Ww)
-        h = self.gnconv3_16(h, 'encoder.norm_out', 'encoder.conv_out', B, Hh, Ww)
-        self._gn_part = None
-        return self.conv3(self._to32(h), 'quant_conv', B, Hh, Ww)
-
+        h = self._run(ops, _encoder_graph(self.w, self.nlev), x if prec == 'f32' else ops._to16(x), B, Hh, Ww)
+        return self.conv3(h if prec == 'f32' else ops._to32(h), 'quant_conv', B, h.shape[1], h.shape[2])
 
 
 AUTOCAST_PRECISION = {torch.float16: 'f16', torch.bfloat16: 'bf16'}
@@ -787,19 +811,20 @@ AUTOCAST_PRECISION = {torch.float16: 'f16', torch.bfloat16: 'bf16'}
 _SCORE_MODES = {'log_prob': 0, 'group_smoothed': 1, 'neighbor_max': 2, 'expected_distance': 3, 'distance_profile': 4}
 
 
-class SamplingEngine:
+class SamplingEngine(_Engine):
     """The AR loop of VAR.autoregressive_infer_cfg on HIP kernels.  One engine per VAR module; calls on different HIP streams may be in flight
     together (per-stream workspaces), the host side is not thread-safe."""
 
     MAX_WORKSPACES = 6          # buffer sets kept alive per engine (workspace(): one per (batch size, stream, precision) in use)
+    # all blocks' ada_lin weights are packed into one GEMM operand up to this many bytes; beyond it (the weight rows would leave the GEMM's 32-bit
+    # request offsets) every block projects its own
+    ADA_PACKED_MAX_BYTES = 3.5e9
 
     def __init__(self, var):
+        super().__init__()
         self.var = var
-        self._sig = None
-        self.w: dict = {}
         self._ws: Dict[tuple, dict] = {}            # (batch size, HIP stream, precision) -> buffers of a call
         self._ws_tf: Dict[tuple, dict] = {}         # the same for teacher_forced_logits
-        self._ready = None                          # event behind the kernels that built the derived weight copies (see _VaeOps._built)
         self._labels_ok = None                      # (the last label tensor whose range was checked, its version counter, address, length): one host sync saved per repeated call
 
         self.policy = 'auto' if os.environ.get('VARHIP_FOLLOW_AUTOCAST', '0') not in ('', '0') else 'f32'      # what set_precision() was given: 'f32' | 'f16' | 'bf16' | 'auto' (follow the caller's torch.autocast)
@@ -817,8 +842,7 @@ class SamplingEngine:
             return
         if var.C != 64 * var.num_heads:
             raise hip.VarHipError(f'the HIP attention kernels are built for head_dim 64, got embed_dim {var.C} / {var.num_heads} heads')
-        if self.w and torch.cuda.is_available():
-            torch.cuda.synchronize()         # weights changed: other streams may still read the old derived copies that are dropped below (rare: checkpoint load, EMA swap)
+        self._retire()
         dev = var.pos_start.device
         w = {}
         g = lambda t, n: _chk(t.detach(), n)
@@ -846,7 +870,7 @@ class SamplingEngine:
             blocks.append(d)
         w['blocks'] = blocks
         w['b16'], w['head_w16'] = {}, {}     # {'f16' | 'bf16': ...} 16-bit copies of the GEMM weights, made by _ensure16() when such a call first needs them
-        if not var.shared_aln and var.depth * 6 * C * C * 4 < 3.5e9:          # (beyond: the weight rows would leave the GEMM's 32-bit request offsets)
+        if not var.shared_aln and var.depth * 6 * C * C * 4 < self.ADA_PACKED_MAX_BYTES:
             # all blocks' ada_lin projections as ONE GEMM per call (N = depth * 6C): sixteen launches of 192 workgroups each were bound by one
             # workgroup's K loop (29 us each at d16).  The packed copy (0.4 GB fp32 at d16, 2.65 GB at d30; rebuilt when weights change) is the only
             # copy the engine holds: the per-block path is not used beside it
@@ -855,24 +879,16 @@ class SamplingEngine:
         elif not var.shared_aln:
             for d, b in zip(blocks, var.blocks):
                 d['ada_w'], d['ada_b'] = g(b.ada_lin[1].weight, 'ada_lin'), g(b.ada_lin[1].bias, 'ada_lin')
-        w['codebook'] = g(quant.embedding.weight, 'codebook')
+        w['codebook'], w['phi'] = _pack_quantizer(quant)
         w['codebook_T'] = w['codebook'].t().contiguous()          # [Cvae][V]: "probabilities @ codebook" as an NT GEMM (more_smooth)
-        phis = list(quant.quant_resi.phis())
-        w['phi'] = [(g(p.weight, 'phi').permute(0, 2, 3, 1).contiguous(), g(p.bias, 'phi'), float(p.resi_ratio)) for p in phis]
-        w['taps'] = {}
-        P = var.patch_nums[-1]
+        w['taps'] = {}                                            # {pn: tap tables} of every scale, uploaded here: behind the event of _built()
         for pn in var.patch_nums:
-            if pn != P:
-                ti, tw = bicubic_taps(pn, P)
-                w['taps'][pn] = (torch.from_numpy(ti).to(dev), torch.from_numpy(tw).to(dev))
+            _tap_tables(w['taps'], pn, var.patch_nums[-1], dev)
         self.w = w
         self._sig = sig
         self._labels_ok = None
         self._built()
         self._ensure16()
-
-    _built = _VaeOps._built
-    _wait_ready = _VaeOps._wait_ready
 
     def _ensure16(self):
         """16-bit copies of the four GEMM weights of every block and of the head (round-to-nearest-even, once per weight change and flavour), kept
@@ -882,7 +898,7 @@ class SamplingEngine:
             return
         self._wait_ready()
         dt = DT16[prec]
-        self.w['b16'][prec] = [{k + '16': d[k].to(dt).contiguous() for k in ('qkv_w', 'proj_w', 'fc1_w', 'fc2_w')} for d in self.w['blocks']]
+        self.w['b16'][prec] = [{k: d[k].to(dt).contiguous() for k in ('qkv_w', 'proj_w', 'fc1_w', 'fc2_w')} for d in self.w['blocks']]
         self.w['head_w16'][prec] = self.w['head_w'].to(dt).contiguous()
         self._built()
 
@@ -913,7 +929,7 @@ class SamplingEngine:
 
     def invalidate(self):
         """forget the packed weight copies of the sampling loop and of the decoder (call after editing parameters through `.data`)"""
-        self._sig = None
+        super().invalidate()
         self.dec.invalidate()
 
     # -- workspaces --------------------------------------------------------------------------------------------------
@@ -996,28 +1012,47 @@ class SamplingEngine:
         var = self.var
         C = var.C
         Lmax = var.L if Lmax is None else Lmax
-        if self.precision != 'f32':
-            b16 = self.w['b16'][self.precision][bi]
-            hip.call('adaln_block_' + self.precision, x, x2, ws['xn'], ws['q'], ws['att'], ws['hid'], ws['ada_view'][bi][0], ws['ada_view'][bi][1],
-                     b16['qkv_w16'], blk['qkv_b'], blk['smul'], blk['plain_scale'], int(blk['l2']), b16['proj_w16'], blk['proj_b'],
-                     b16['fc1_w16'], blk['fc1_b'], b16['fc2_w16'], blk['fc2_b'], ws['kc'][bi], ws['vc'][bi],
-                     rows, l, C, var.num_heads, blk['fc1_w'].shape[0], cur, Lmax, var.norm_eps)
-            return
-        hip.call('adaln_block_f32', x, x2, ws['xn'], ws['q'], ws['att'], ws['hid'], ws['ada_view'][bi][0], ws['ada_view'][bi][1],
-                 blk['qkv_w'], blk['qkv_b'], blk['smul'], blk['plain_scale'], int(blk['l2']), blk['proj_w'], blk['proj_b'],
-                 blk['fc1_w'], blk['fc1_b'], blk['fc2_w'], blk['fc2_b'], ws['kc'][bi], ws['vc'][bi],
+        prec = self.precision
+        gw = blk if prec == 'f32' else self.w['b16'][prec][bi]          # the four GEMM weights in the call's arithmetic; everything else is fp32
+        hip.call('adaln_block_' + prec, x, x2, ws['xn'], ws['q'], ws['att'], ws['hid'], ws['ada_view'][bi][0], ws['ada_view'][bi][1],
+                 gw['qkv_w'], blk['qkv_b'], blk['smul'], blk['plain_scale'], int(blk['l2']), gw['proj_w'], blk['proj_b'],
+                 gw['fc1_w'], blk['fc1_b'], gw['fc2_w'], blk['fc2_b'], ws['kc'][bi], ws['vc'][bi],
                  rows, l, C, var.num_heads, blk['fc1_w'].shape[0], cur, Lmax, var.norm_eps)
 
     def head(self, x, hn, xn, logits, M, l):
         """get_logits (var.py:118-124): AdaLNBeforeHead (LayerNorm + scale/shift) then the vocabulary projection -> fp32 logits"""
         var, w = self.var, self.w
         C, V = var.C, var.V
-        if self.precision != 'f32':
-            hip.call(f'ln_modulate_{self.precision}out', x, hn, 2 * C, hn[:, C:], 2 * C, xn, M, C, l, var.norm_eps)
-            hip.call('gemm_nt_' + self.precision, xn, C, w['head_w16'][self.precision], C, w['head_b'], logits, V, 0, M, V, C, EPI_NONE, None, 0, 0, None, 0, 1, 1, 0, 0, 0)
-        else:
-            hip.call('ln_modulate_f32', x, hn, 2 * C, hn[:, C:], 2 * C, xn, M, C, l, var.norm_eps)
+        prec = self.precision
+        hip.call('ln_modulate_f32' if prec == 'f32' else f'ln_modulate_{prec}out', x, hn, 2 * C, hn[:, C:], 2 * C, xn, M, C, l, var.norm_eps)
+        if prec == 'f32':
             self.gemm(xn, w['head_w'], w['head_b'], logits, M)
+        else:                                                            # (the 16-bit GEMM's own argument list: fp32 output, no residual)
+            hip.call('gemm_nt_' + prec, xn, C, w['head_w16'][prec], C, w['head_b'], logits, V, 0, M, V, C, EPI_NONE, None, 0, 0, None, 0, 1, 1, 0, 0, 0)
+
+    def _prologue(self, ws, labels, rows):
+        """what a pass computes once, before its scales (var.py:151-157): the level + position embedding, the first map and the condition of
+        every label (first_map_f32 also writes each label's unconditional twin), and from SiLU(condition) the AdaLN parameters of every
+        block and of the head, for `rows` rows (sampling: the 2B rows of the CFG pairs; teacher forcing: the labels' own R).  Leaves
+        ws['ada_view'][block] = (that block's 6C parameters per row, their row stride)"""
+        var, w = self.var, self.w
+        C, D6 = var.C, var.depth * 6 * var.C
+        hip.call('lvl_pos_f32', w['lvl_embed'], w['lvl_1L'], w['pos_1LC'], ws['lvl_pos'], var.L, C)
+        hip.call('first_map_f32', w['class_emb'], labels, var.num_classes, w['pos_start'], ws['lvl_pos'], ws['cond'], ws['x'], labels.numel(), C, var.first_l)
+        hip.call('silu_f32', ws['cond'], ws['cond_silu'], rows * C)
+        if var.shared_aln:
+            self.gemm(ws['cond_silu'], w['sal_w'], w['sal_b'], ws['shared'], rows)
+            for bi, blk in enumerate(w['blocks']):
+                hip.call('add_bcast_f32', blk['gss'], ws['shared'], ws['ada'][bi], rows, 6 * C)
+            ws['ada_view'] = [(ws['ada'][bi], 6 * C) for bi in range(var.depth)]
+        else:
+            ws['ada_view'] = [(ws['ada'][:, bi * 6 * C:], D6) for bi in range(var.depth)]          # row b: [block 0: 6C | block 1: 6C | ...]
+            if 'ada_w_all' in w:
+                self.gemm(ws['cond_silu'], w['ada_w_all'], w['ada_b_all'], ws['ada'], rows)
+            else:
+                for (view, _), blk in zip(ws['ada_view'], w['blocks']):
+                    hip.call('gemm_nt_f32', ws['cond_silu'], C, blk['ada_w'], C, blk['ada_b'], view, D6, rows, 6 * C, C, EPI_NONE, None, 0, None, 0, 1, 0, 1, 0, 0, 0)
+        self.gemm(ws['cond_silu'], w['hn_w'], w['hn_b'], ws['hn'], rows)
 
     def qkv(self, xn, blk, ws, bi, rows, l, cur):
         """mat_qkv + q/k normalisation + KV-cache append in one launch (basic_var.py:93-109)."""
@@ -1130,27 +1165,8 @@ class SamplingEngine:
             sm_ll = torch.zeros((), dtype=torch.float32, device=dev)
             sm_dl = torch.zeros((), dtype=torch.float32, device=dev)
 
-        # prologue (var.py:151-157)
-        hip.call('lvl_pos_f32', w['lvl_embed'], w['lvl_1L'], w['pos_1LC'], ws['lvl_pos'], var.L, C)
-        hip.call('first_map_f32', w['class_emb'], label_B, var.num_classes, w['pos_start'], ws['lvl_pos'], ws['cond'], ws['x'], B, C, var.first_l)
-        hip.call('silu_f32', ws['cond'], ws['cond_silu'], B2 * C)
         ws['f_hat'].zero_()
-        # AdaLN parameters of every block, once per call
-        if var.shared_aln:
-            self.gemm(ws['cond_silu'], w['sal_w'], w['sal_b'], ws['shared'], B2)
-        if var.shared_aln:
-            for bi, blk in enumerate(w['blocks']):
-                hip.call('add_bcast_f32', blk['gss'], ws['shared'], ws['ada'][bi], B2, 6 * C)
-            ws['ada_view'] = [(ws['ada'][bi], 6 * C) for bi in range(var.depth)]
-        elif 'ada_w_all' in w:
-            self.gemm(ws['cond_silu'], w['ada_w_all'], w['ada_b_all'], ws['ada'], B2)          # row b: [block 0: 6C | block 1: 6C | ...]
-            ws['ada_view'] = [(ws['ada'][:, bi * 6 * C:], var.depth * 6 * C) for bi in range(var.depth)]
-        else:
-            ws['ada_view'] = [(ws['ada'][:, bi * 6 * C:], var.depth * 6 * C) for bi in range(var.depth)]
-            for bi, blk in enumerate(w['blocks']):
-                hip.call('gemm_nt_f32', ws['cond_silu'], C, blk['ada_w'], C, blk['ada_b'], ws['ada_view'][bi][0], var.depth * 6 * C, B2, 6 * C, C, EPI_NONE,
-                         None, 0, None, 0, 1, 0, 1, 0, 0, 0)
-        self.gemm(ws['cond_silu'], w['hn_w'], w['hn_b'], ws['hn'], B2)
+        self._prologue(ws, label_B, B2)
 
         x, x2 = ws['x'], ws['x2']
         cur = 0
@@ -1227,8 +1243,7 @@ class SamplingEngine:
             elif tokens_out is not None:
                 tokens_out[:, cur - l:cur].copy_(idx.view(B, l))
             # quantizer step (var.py:177-183)
-            ti, tw = w['taps'].get(pn, (None, None))
-            pw, pb, ratio = w['phi'][phi_index(si, S, len(w['phi']))]
+            ti, tw, pw, pb, ratio = _scale_tables(w['taps'], w['phi'], si, S, pn, P, dev)
             if more_smooth and not (ed_gt is not None and skip[si]):
                 # h = gumbel_softmax(filtered logits * (1+ratio), tau) @ codebook, a second Exp(1) fill per scale (var.py:178-180)
                 r_ = si / var.num_stages_minus_1 if var.num_stages_minus_1 > 0 else 0.0
@@ -1346,25 +1361,8 @@ class SamplingEngine:
         the last; ws must reach it): yields (si, cur, l) after the head of each scale si >= head_from has left that scale's fp32 logits in
         ws['lg'][:R * l] (row r, token t at r * l + t); scales below head_from only fill the KV caches"""
         var, w = self.var, self.w
-        C, Cv, L = var.C, var.Cvae, var.L
-        hip.call('lvl_pos_f32', w['lvl_embed'], w['lvl_1L'], w['pos_1LC'], ws['lvl_pos'], L, C)
-        hip.call('first_map_f32', w['class_emb'], lab, var.num_classes, w['pos_start'], ws['lvl_pos'], ws['cond'], ws['x'], R, C, var.first_l)
-        hip.call('silu_f32', ws['cond'], ws['cond_silu'], R * C)
-        if var.shared_aln:
-            self.gemm(ws['cond_silu'], w['sal_w'], w['sal_b'], ws['shared'], R)
-        if var.shared_aln:
-            for bi, blk in enumerate(w['blocks']):
-                hip.call('add_bcast_f32', blk['gss'], ws['shared'], ws['ada'][bi], R, 6 * C)
-            ws['ada_view'] = [(ws['ada'][bi], 6 * C) for bi in range(var.depth)]
-        elif 'ada_w_all' in w:
-            self.gemm(ws['cond_silu'], w['ada_w_all'], w['ada_b_all'], ws['ada'], R)
-            ws['ada_view'] = [(ws['ada'][:, bi * 6 * C:], var.depth * 6 * C) for bi in range(var.depth)]
-        else:
-            ws['ada_view'] = [(ws['ada'][:, bi * 6 * C:], var.depth * 6 * C) for bi in range(var.depth)]
-            for bi, blk in enumerate(w['blocks']):
-                hip.call('gemm_nt_f32', ws['cond_silu'], C, blk['ada_w'], C, blk['ada_b'], ws['ada_view'][bi][0], var.depth * 6 * C, R, 6 * C, C, EPI_NONE,
-                         None, 0, None, 0, 1, 0, 1, 0, 0, 0)
-        self.gemm(ws['cond_silu'], w['hn_w'], w['hn_b'], ws['hn'], R)
+        C, Cv = var.C, var.Cvae
+        self._prologue(ws, lab, R)
         x, x2 = ws['x'], ws['x2']
         cur = 0
         for si, pn in enumerate(var.patch_nums[:(len(var.patch_nums) if last is None else last + 1)]):
