@@ -172,6 +172,34 @@ int varhip_philox4x32_host(const uint32_t ctr[4], const uint32_t key[2], uint32_
 /* the fill's transform alone on the host: out[i] = -vm_log((2 (bits[i] >> 9) + 1) * 2^-24)  (exhaustive tests over the 2^23 values of n) */
 int varhip_exp1_from_bits_host_f32(const uint32_t* bits, int64_t n, float* out);
 
+/* ---- scored sampling (VAR.autoregressive_infer_cfg_scored, VAR.sample_best_of) -----------------------------------------------------------
+ * What the sampler's operands say about the token it drew, one wave per token row r = b * l + j, launched right behind varhip_cfg_sample*_f32
+ * of a scale.  logits: [2B][l][V] as the sampler reads them (conditional rows first); masked: [B*l][V], the sampler's masked_out; idx: [B*l],
+ * its idx_out.  Guidance: the scalar t_cfg, or, where t_rows != NULL, the DEVICE array t_rows[B] (t_cfg is then not read), rounded as the
+ * samplers round it: ca = (float)(1.0 + t), cb = (float)t, z = ca * cond - cb * uncond with each product and the difference rounded to fp32.
+ * Every output is addressed out[b * ld_out + j] (ld_out >= l: a scale writes its slice of a (B, L) tensor; nothing else is written):
+ *   lp_cond   fp32   log_softmax(cond)[idx]: varhip_token_loglik_f32 without guidance on the same row, bit for bit (one piece of device code)
+ *   lp_guided fp32   log_softmax(z)[idx]: varhip_token_loglik_f32 with (ca, cb) on the same rows, bit for bit
+ *   lp_drawn  fp32   log_softmax(masked)[idx]: the distribution the token was drawn from; a -inf entry adds 0 to the sum
+ *   kept      int32  the number of entries of the masked row that are not -inf
+ *   entropy   fp32   -sum_v p_v log p_v of the guided row in nats, 0 * log 0 = 0: (float)((0 - A) / (double)s), A = sum_v (double)e_v * (double)lp_v
+ *                    over the elements with e_v > 0, where m = max z, e_v = vm_exp(z_v - m), s = the row's fp32 sum of exponentials (the one lp_guided
+ *                    uses) and lp_v = (z_v - m) - vm_log(s).  A is accumulated in float64 in ONE order that depends on V alone, the order of
+ *                    varhip_token_eval_f32's `smooth` sum: lane i of 64 adds its elements j * 256 + 4 * i + c in ascending (j, c) order, the
+ *                    lanes by the xor butterfly 32, 16, 8, 4, 2, 1.  Rounded once to fp32.  A guided row holding a NaN: NaN.
+ * An idx outside [0, V) (the -1 varhip_cfg_sample_rows_f32 writes for a refused image) is never dereferenced: the three log-probabilities of
+ * the row are NaN, kept and entropy are still the row's own.  On a row holding a NaN the log-probabilities are what varhip_token_loglik_f32
+ * gives there.  Constraints as the samplers': V % 256 == 0, V <= 8192, logits and masked 16-byte aligned; a NULL operand (t_rows excepted),
+ * B or l < 1 or ld_out < l: VARHIP_EINVAL. */
+int varhip_sample_stats_f32(const float* logits, const float* masked, const int64_t* idx, int B, int l, int V, double t_cfg,
+                            const double* t_rows, float* lp_cond, float* lp_guided, float* lp_drawn, int32_t* kept, float* entropy,
+                            int64_t ld_out, varhip_stream_t stream);
+/* the host twin: plain host code (usable without a GPU), same arguments with host pointers, no alignment constraint.  The same operations in
+ * the same order (vm_exp / vm_log consist of correctly rounded operations only): the kernel's bits. */
+int varhip_sample_stats_host_f32(const float* logits, const float* masked, const int64_t* idx, int B, int l, int V, double t_cfg,
+                                 const double* t_rows, float* lp_cond, float* lp_guided, float* lp_drawn, int32_t* kept, float* entropy,
+                                 int64_t ld_out);
+
 /* ---- multi-scale quantizer step ---------------------------------------------------------------------------
  * Feature maps are kept channels-last: f_hat[B][P][P][Cv].
  * (1) h = codebook[idx] as [B][pn][pn][Cv]                                          (var.py:177,182; quant.py:39)

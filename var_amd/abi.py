@@ -93,6 +93,7 @@ SIGNATURES_HIP_ONLY = {
     'vq_straight_through_f32': [P, P, P, P, I, I, I],                # pinned against (f_hat - f) + f in torch, bit for bit
     'token_eval_f32':    [P, P, L, I, I, I, P, P, P, P, L],             # pinned against float64, torch.argmax and the rank's definition (tests/test_evaluate_gpu.py)
     'eval_reduce_f32':   [P, P, P, P, L, I, P, I, I, P, P, P, P],       # pinned against numpy float64 sums and torch.bincount; begin_S1 is a host array
+    'sample_stats_f32':  [P, P, P, I, I, I, D, P, P, P, P, P, P, L],    # pinned against its host twin, token_loglik_f32 and float64 (tests/test_sample_stats_gpu.py)
 }
 
 # plain host functions of the HIP library (no stream argument, no device pointer, no GPU needed); bound by var_amd/hip.py
@@ -100,6 +101,7 @@ SIGNATURES_HOST = {
     'exp1_philox_host_f32': [P, I, I, I, I, I, P],                   # pinned against a numpy Philox4x32-10 (tests/test_per_image_cpu.py)
     'philox4x32_host':   [P, P, P],                                  # pinned against the Random123 known answers
     'exp1_from_bits_host_f32': [P, L, P],
+    'sample_stats_host_f32': [P, P, P, I, I, I, D, P, P, P, P, P, P, L],   # pinned against float64 (tests/test_sample_stats_cpu.py)
 }
 
 # ... and with bfloat16 storage: one entry point per _f16 entry point, same arguments (include/var_hip.h, "bf16")

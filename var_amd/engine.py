@@ -55,6 +55,10 @@ def per_image_tables(cfg, top_k, top_p, S: int, V: int) -> dict:
     return dict(t=t, top_k=k, top_p=np.asarray([float(x) for x in top_p], dtype=np.float64), cap=int(V if (k == 0).any() else k.max()))
 
 
+# the per-token outputs of varhip_sample_stats_f32 in the order of its arguments (the keys of SamplingEngine.sample's `stats`)
+STATS_FIELDS = ('logp_cond', 'logp_guided', 'logp_drawn', 'kept', 'entropy')
+
+
 def phi_index(si: int, S: int, K: int) -> int:
     """which shared Phi conv serves scale si (reference quant.py:218-226)"""
     ticks = np.linspace(1 / 3 / K, 1 - 1 / 3 / K, K) if K == 4 else np.linspace(1 / 2 / K, 1 - 1 / 2 / K, K)
@@ -1066,7 +1070,8 @@ class SamplingEngine(_Engine):
                noises=None, force_idx: Optional[torch.Tensor] = None, trace: bool = False,
                decode: bool = True, gt_tokens: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
                more_smooth: bool = False, gumbel_noises=None, smooth: Optional[dict] = None, greedy: bool = False,
-               tokens_out: Optional[torch.Tensor] = None, edit: Optional[dict] = None, per_image: Optional[dict] = None) -> torch.Tensor:
+               tokens_out: Optional[torch.Tensor] = None, edit: Optional[dict] = None, per_image: Optional[dict] = None,
+               stats: Optional[dict] = None) -> torch.Tensor:
         """label_B: int64 [B] on the device.  noises: optional per-scale Exp(1) tensors [B*l, V] — a list, or a callable
         (si, l) -> tensor (tests inject the CPU generator's stream; var_amd.multi hands each rank its rows); by default they
         are drawn with `exponential_(generator=rng)` exactly as torch.multinomial (helpers.py:19) would.
@@ -1086,7 +1091,13 @@ class SamplingEngine(_Engine):
         per_image = dict(t=[S, B] float64, top_k=[B] int32, top_p=[B] float64 on the device, cap=int): every image samples with its own
         parameters (varhip_cfg_sample_rows_f32; sample_per_image builds the tables); cfg, top_k and top_p are not read.  gumbel_noises may be
         a callable (si, l) -> tensor like noises.
-        force_idx/trace are test hooks (teacher forcing; keep per-scale logits/tokens/f_hat)."""
+        stats: a dict (VAR.autoregressive_infer_cfg_scored): the sampler leaves its filtered logits in the workspace's `masked` buffer (B * l_max
+        * V * 4 bytes, the one more_smooth uses) and varhip_sample_stats_f32 runs behind it on every scale into the (B, L) tensors
+        stats['logp_cond' | 'logp_guided' | 'logp_drawn' | 'entropy'] (fp32) and stats['kept'] (int32), allocated here unless the caller put
+        contiguous ones there.  One launch per scale and nothing else: the RNG draws, the other kernels and their order are those of the
+        call without it.  Combines with more_smooth and per_image; not with smooth, greedy, gt_tokens / keep_mask or edit, whose kept
+        positions have no drawn distribution.
+        force_idx/trace are test hooks (teacher forcing; keep per-scale logits/tokens/f_hat, with stats also the filtered logits 'masked')."""
         var = self.var
         self.resolve_precision()
         self.refresh()
@@ -1105,6 +1116,8 @@ class SamplingEngine(_Engine):
             raise ValueError('edit does not combine with gt_tokens / keep_mask, smooth sampling or greedy selection')
         if per_image is not None and (greedy or smooth is not None):
             raise ValueError('per-image parameters belong to the sampler: they do not combine with greedy selection or smooth sampling')
+        if stats is not None and (smooth is not None or greedy or gt_tokens is not None or keep_mask is not None or edit is not None):
+            raise ValueError('stats describe sampled tokens: they do not combine with smooth sampling, greedy selection, gt_tokens / keep_mask or edit')
         if tokens_out is not None and (tokens_out.dtype != torch.int64 or tuple(tokens_out.shape) != (B, var.L) or not tokens_out.is_contiguous()):
             raise ValueError(f'tokens_out must be a contiguous int64 ({B}, {var.L}) tensor')
         tr = dict(logits=[], idx=[], f_hat=[], pooled=[]) if trace else None
@@ -1117,6 +1130,17 @@ class SamplingEngine(_Engine):
                 ws['probs'] = torch.empty(B * lmax, V, dtype=torch.float32, device=dev)
                 ws['h'] = torch.empty(B * lmax, Cv, dtype=torch.float32, device=dev)
             masked = ws['masked']
+        if stats is not None:
+            if 'masked' not in ws:
+                ws['masked'] = torch.empty(B * max(p * p for p in var.patch_nums), V, dtype=torch.float32, device=dev)
+            masked = ws['masked']
+            for key in STATS_FIELDS:
+                dt = torch.int32 if key == 'kept' else torch.float32
+                if key not in stats:
+                    stats[key] = torch.empty(B, var.L, dtype=dt, device=dev)
+                sv = stats[key]
+                if sv.dtype != dt or tuple(sv.shape) != (B, var.L) or not sv.is_contiguous() or sv.device != dev:
+                    raise ValueError(f"stats['{key}'] must be a contiguous {dt} ({B}, {var.L}) tensor on the model's device")
         if gt_tokens is not None:
             if keep_mask is None or tuple(keep_mask.shape) != tuple(gt_tokens.shape) or tuple(gt_tokens.shape) != (B, var.L):
                 raise ValueError('Mask shape must match the latent token shape obtained from vae.img_to_idxBl')
@@ -1226,6 +1250,10 @@ class SamplingEngine(_Engine):
                                  per_image['top_p'], int(per_image['cap']))
                     else:
                         hip.call('cfg_sample_f32', ws['logits'], noise, idx, masked, B, l, V, float(t), int(top_k), float(top_p))
+                    if stats is not None:         # the drawn tokens' log-probabilities, kept counts and entropies: this scale's slice of the (B, L) tensors
+                        hip.call('sample_stats_f32', ws['logits'], masked, idx, B, l, V, float(t), per_image['t'][si] if per_image is not None else None,
+                                 *[stats[key][:, cur - l:] for key in STATS_FIELDS], var.L)
+                        if trace: tr.setdefault('masked', []).append(masked[:B * l].clone())
                 if gt is not None and not greedy:                         # torch.where(mask, gt_tokens, sampled) (var.py:326-328)
                     hip.call('token_select_i64', keep_u8[:, cur - l:cur].contiguous(), gt[:, cur - l:cur].contiguous(), idx, idx, B * l)
                 if trace and ed_gt is not None: tr['sampled'].append(idx.view(B, l).clone())
@@ -1283,7 +1311,8 @@ class SamplingEngine(_Engine):
     # -- per-image parameters and seeds (VAR.autoregressive_infer_cfg_per_image) --------------------------------------------
     @torch.no_grad()
     def sample_per_image(self, label_B: torch.Tensor, seeds, cfg, top_k, top_p, more_smooth: bool = False,
-                         tokens_out: Optional[torch.Tensor] = None, trace: bool = False) -> torch.Tensor:
+                         tokens_out: Optional[torch.Tensor] = None, trace: bool = False, decode: bool = True,
+                         stats: Optional[dict] = None) -> torch.Tensor:
         """sample() on a batch of unrelated requests: image b uses seeds[b], cfg[b], top_k[b], top_p[b] (host sequences of length B, already
         validated: VAR.autoregressive_infer_cfg_per_image).  The noise is the project's counter-based stream (varhip_exp1_philox_f32): image
         b's rows depend on (seeds[b], scale, row, column, draw) only, the sampler reads image b's parameters from device tables
@@ -1305,7 +1334,41 @@ class SamplingEngine(_Engine):
                 return out
             return fn
         return self.sample(B, label_B, None, 0.0, 0, 0.0, noises=fill(0), gumbel_noises=fill(1) if more_smooth else None,
-                           more_smooth=more_smooth, tokens_out=tokens_out, trace=trace, per_image=per)
+                           more_smooth=more_smooth, tokens_out=tokens_out, trace=trace, per_image=per, decode=decode, stats=stats)
+
+    # -- best-of-n (VAR.sample_best_of) ---------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample_best_of(self, label_N: torch.Tensor, seeds, cfg, top_k, top_p, n: int, by: str, max_images: int):
+        """N = B * n candidates, candidate c of image b at position b * n + c (labels, seeds and parameters already spread and validated: host
+        sequences of length N).  They run through sample_per_image with decode=False and stats in chunks of at most max_images; every chunk
+        writes its rows of the (N, L) token / stats tensors and its f_hat maps.  varhip_class_select_f32 then adds stats[by] to float64 totals
+        in token order and keeps each image's best candidate (higher total first, NaN below everything, ties by lower index).
+        -> (dict of the B winners' tokens and stats (B, L), their f_hat (B, Cvae, P, P), totals (B, n) float64, choice (B,) int64)."""
+        var = self.var
+        dev = var.pos_start.device
+        N, L, P, Cv = len(seeds), var.L, var.patch_nums[-1], var.Cvae
+        B = N // n
+        if n > self.CLASSIFY_MAX_CAND:
+            raise ValueError(f'sample_best_of takes at most {self.CLASSIFY_MAX_CAND} candidates per image, got {n}')
+        rec = {key: torch.empty(N, L, dtype=torch.int32 if key == 'kept' else torch.float32, device=dev) for key in STATS_FIELDS}
+        rec['tokens'] = torch.empty(N, L, dtype=torch.int64, device=dev)
+        f_all = torch.empty(N, Cv, P, P, dtype=torch.float32, device=dev)
+        for c0 in range(0, N, max_images):
+            c1 = min(N, c0 + max_images)
+            f_all[c0:c1] = self.sample_per_image(label_N[c0:c1], seeds[c0:c1], cfg[c0:c1], top_k[c0:c1], top_p[c0:c1], tokens_out=rec['tokens'][c0:c1],
+                                                 decode=False, stats={key: rec[key][c0:c1] for key in STATS_FIELDS})
+        totals = torch.full((B, n), -0.0, dtype=torch.float64, device=dev)      # (-0.0 + x == x for every x)
+        kept = torch.empty(B, 1, dtype=torch.int32, device=dev)
+        hip.call('class_select_f32', rec[by], n * L, L, B, n, 0, L, totals, 1, kept)
+        choice = kept[:, 0].long()
+        win = torch.arange(B, device=dev) * n + choice
+        return {key: v.index_select(0, win) for key, v in rec.items()}, f_all.index_select(0, win), totals, choice
+
+    @torch.no_grad()
+    def decode_f_hat(self, f_hat: torch.Tensor) -> torch.Tensor:
+        """(B, Cvae, P, P) fp32 as sample(decode=False) returns it -> the images (B, 3, H, W) in [0, 1], by the call's own decoder step"""
+        self.resolve_precision()
+        return self.dec.decode_nhwc(f_hat.permute(0, 2, 3, 1).contiguous(), precision=self.precision)
 
     # -- teacher-forced logits (VAR.forward without autograd) ------------------------------------------------------------
     @torch.no_grad()

@@ -248,6 +248,57 @@ def distance_profile_torch(z: torch.Tensor, gt: torch.Tensor, dist: torch.Tensor
 GENERATIVE_FEATURES = ('vae_post', 'vae_fhat')
 
 
+class SampleRecord:
+    """What a scored sampling call returns (VAR.autoregressive_infer_cfg_scored, ..._per_image_scored, sample_best_of), on the model's device:
+      images       (B, 3, H, W) fp32 in [0, 1], or None (decode=False)
+      tokens       (B, L) int64, the drawn tokens
+      logp_cond    (B, L) fp32: log p(token) under the conditional logits (VAR.token_log_likelihood's value at cfg 0 for the same row)
+      logp_guided  (B, L) fp32: the same under the guided logits (1 + t) * cond - t * uncond, t = cfg * scale / (S - 1)
+      logp_drawn   (B, L) fp32: the same under the distribution the token was drawn from (after top-k / top-p)
+      entropy      (B, L) fp32: the entropy of the guided distribution in nats
+      kept         (B, L) int32: how many codes top-k / top-p left to draw from
+      patch_nums   the scales the L tokens are laid out in
+    The definitions, roundings and summation orders are those of varhip_sample_stats_f32 (include/var_hip.h)."""
+    __slots__ = ('images', 'tokens', 'logp_cond', 'logp_guided', 'logp_drawn', 'entropy', 'kept', 'patch_nums')
+    FIELDS = ('logp_cond', 'logp_guided', 'logp_drawn', 'entropy', 'kept')
+
+    def __init__(self, images, tokens, logp_cond, logp_guided, logp_drawn, entropy, kept, patch_nums):
+        self.images, self.tokens, self.logp_cond, self.logp_guided, self.logp_drawn = images, tokens, logp_cond, logp_guided, logp_drawn
+        self.entropy, self.kept, self.patch_nums = entropy, kept, tuple(patch_nums)
+
+    def _cum(self, field: str) -> np.ndarray:
+        if field not in self.FIELDS:
+            raise ValueError(f'field must be one of {self.FIELDS}, got {field!r}')
+        return np.add.accumulate(getattr(self, field).detach().cpu().numpy().astype(np.float64), axis=1)      # sequential, in token order
+
+    def per_scale(self) -> dict:
+        """{field: (B, S) float64 (a CPU tensor)}: per image and scale the sum over the scale's tokens, added on the host in token order"""
+        out = {}
+        for field in self.FIELDS:
+            x = getattr(self, field).detach().cpu().numpy().astype(np.float64)
+            cols, b = [], 0
+            for pn in self.patch_nums:
+                cols.append(np.add.accumulate(x[:, b:b + pn * pn], axis=1)[:, -1])
+                b += pn * pn
+            out[field] = torch.from_numpy(np.stack(cols, axis=1))
+        return out
+
+    def total(self, field: str) -> torch.Tensor:
+        """(B,) float64 (a CPU tensor): the sum of `field` over an image's L tokens, one addition per token in token order (what sample_best_of
+        ranks by: varhip_class_select_f32 adds in the same order)"""
+        return torch.from_numpy(self._cum(field)[:, -1].copy())
+
+    def __repr__(self):
+        B, L = tuple(self.tokens.shape)
+        tot = lambda f: '[' + ', '.join(f'{v:.2f}' for v in self.total(f).tolist()[:4]) + (', ...' if B > 4 else '') + ']'
+        img = None if self.images is None else tuple(self.images.shape)
+        return (f'SampleRecord(B={B}, L={L}, images={img}, logp_cond={tot("logp_cond")}, logp_guided={tot("logp_guided")}, '
+                f'logp_drawn={tot("logp_drawn")}, mean kept={float(self.kept.float().mean()):.1f})')
+
+
+BEST_OF_FIELDS = ('logp_cond', 'logp_guided', 'logp_drawn')
+
+
 def rule_order(totals: np.ndarray) -> np.ndarray:
     """indices of a 1-D float64 array in VAR.classify's order: higher total first, NaN below everything, equal totals by lower index"""
     nan = np.isnan(totals)
@@ -378,6 +429,93 @@ class VAR(nn.Module):
             label_B = torch.full((B,), fill_value=self.num_classes if label_B < 0 else label_B, device=dev)
         return self.engine().sample(B, label_B.to(dev).long(), rng, cfg, top_k, top_p, more_smooth=bool(more_smooth))
 
+    def _scored_device(self, name: str):
+        dev = self.lvl_1L.device
+        if dev.type != 'cuda':
+            raise RuntimeError(f'VAR.{name}: this build runs the sampling loop on MI355X HIP kernels only; move the model to a '
+                               'CUDA/ROCm device (there is no CPU fallback by design)')
+        return dev
+
+    def _record(self, img, tok, st) -> SampleRecord:
+        return SampleRecord(img, tok, st['logp_cond'], st['logp_guided'], st['logp_drawn'], st['entropy'], st['kept'], self.patch_nums)
+
+    @torch.no_grad()
+    def autoregressive_infer_cfg_scored(self, B: int, label_B: Optional[Union[int, torch.LongTensor]], g_seed: Optional[int] = None, cfg=1.5,
+                                        top_k=0, top_p=0.0, more_smooth=False, decode=True) -> SampleRecord:
+        """autoregressive_infer_cfg that also returns what the sampler knew about every token it drew: a SampleRecord with the tokens, their
+        log-probability under the conditional, the guided and the filtered (actually drawn-from) distribution, the guided entropy and the
+        number of codes top-k / top-p kept.  Same argument handling and RNG consumption as autoregressive_infer_cfg; images and tokens are
+        bit-identical to that call with the same arguments.  The numbers come from one reduction per scale behind the sampler
+        (varhip_sample_stats_f32) on logits that are in memory anyway: no second transformer pass, as token_log_likelihood on the tokens
+        would need.  decode=False skips the decoder (images is None)."""
+        dev = self._scored_device('autoregressive_infer_cfg_scored')
+        if g_seed is None: rng = None
+        else: self.rng.manual_seed(g_seed); rng = self.rng
+        if label_B is None:
+            label_B = torch.multinomial(self.uniform_prob, num_samples=B, replacement=True, generator=rng).reshape(B)
+        elif isinstance(label_B, int):
+            label_B = torch.full((B,), fill_value=self.num_classes if label_B < 0 else label_B, device=dev)
+        tok = torch.empty(B, self.L, dtype=torch.int64, device=dev)
+        st = {}
+        img = self.engine().sample(B, label_B.to(dev).long(), rng, cfg, top_k, top_p, more_smooth=bool(more_smooth), tokens_out=tok,
+                                   decode=bool(decode), stats=st)
+        return self._record(img if decode else None, tok, st)
+
+    @torch.no_grad()
+    def autoregressive_infer_cfg_per_image_scored(self, label_B, g_seeds, cfg=1.5, top_k=0, top_p=0.0, more_smooth=False, decode=True) -> SampleRecord:
+        """autoregressive_infer_cfg_per_image (own seed, cfg, top_k, top_p per image; the project's counter-based noise stream) with the
+        SampleRecord of autoregressive_infer_cfg_scored.  The tokens and every per-token field of image b depend on that request alone, not on
+        what it is batched with (pixels: as for the per-image call, the decoder's kernel choice follows the batch).  HIP path only."""
+        dev = self._scored_device('autoregressive_infer_cfg_per_image_scored')
+        lab, seeds, cfgs, ks, ps = self._per_image_args(label_B, g_seeds, cfg, top_k, top_p)
+        tok = torch.empty(lab.numel(), self.L, dtype=torch.int64, device=dev)
+        st = {}
+        img = self.engine().sample_per_image(lab.to(dev).long(), seeds, cfgs, ks, ps, more_smooth=bool(more_smooth), tokens_out=tok,
+                                             decode=bool(decode), stats=st)
+        return self._record(img if decode else None, tok, st)
+
+    @torch.no_grad()
+    def sample_best_of(self, label_B, g_seeds, n: Optional[int] = None, by: str = 'logp_cond', cfg=1.5, top_k=0, top_p=0.0, max_images: int = 64):
+        """Best-of-n sampling: n candidates per image, ranked by their own likelihood, only the winners decoded.
+          label_B   (B,) integer class ids;  g_seeds (B, n) integers in [0, 2^63), one seed per candidate;  n: optional, must equal g_seeds' width
+          by        'logp_cond' | 'logp_guided' | 'logp_drawn': the SampleRecord field whose sum over the L tokens ranks the candidates
+          cfg, top_k, top_p: a scalar, or B values (one per image, shared by its candidates)
+        -> (images (B, 3, H, W), winners: the SampleRecord of the B chosen candidates, totals (B, n) float64, choice (B,) int64).
+        The B * n candidates run through the per-image path with decode=False in chunks of at most max_images, so a candidate is exactly the
+        request autoregressive_infer_cfg_per_image_scored(label, seed, ...) and does not depend on the chunking; each one's f_hat (Cvae * P * P
+        floats) is kept.  totals[b, c] is the float64 sum of the field in token order; varhip_class_select_f32 picks per image the highest total
+        on the device (NaN below everything, ties to the lower index), and only those B f_hat maps are gathered and decoded: the decoder is
+        the most expensive single stage of a call and runs for 1 of n candidates."""
+        dev = self._scored_device('sample_best_of')
+        if by not in BEST_OF_FIELDS:
+            raise ValueError(f'by must be one of {BEST_OF_FIELDS}, got {by!r}')
+        if isinstance(max_images, bool) or int(max_images) != max_images or max_images < 1:
+            raise ValueError('max_images must be an integer >= 1')
+        sd = g_seeds.detach().cpu().tolist() if isinstance(g_seeds, torch.Tensor) else (g_seeds.tolist() if isinstance(g_seeds, np.ndarray) else g_seeds)
+        lab0 = torch.as_tensor(label_B)
+        if (not isinstance(sd, (list, tuple)) or len(sd) != lab0.numel() or len(sd) < 1 or not all(isinstance(r, (list, tuple)) and len(r) == len(sd[0]) for r in sd)
+                or len(sd[0]) < 1):
+            raise ValueError('g_seeds must be (B, n): one row of n >= 1 seeds per image')
+        B, width = len(sd), len(sd[0])
+        if n is not None and int(n) != width:
+            raise ValueError(f'n = {n} but g_seeds holds {width} seeds per image')
+        n = width
+
+        def spread(x):                                        # one value per image -> one per candidate
+            if isinstance(x, torch.Tensor): x = x.detach().cpu().tolist()
+            elif isinstance(x, np.ndarray): x = x.tolist()
+            if isinstance(x, (list, tuple)):
+                if len(x) != B:
+                    raise ValueError(f'cfg / top_k / top_p must be a scalar or {B} values, got {len(x)}')
+                return [v for v in x for _ in range(n)]
+            return x
+        if lab0.dim() != 1:
+            raise ValueError('label_B must hold B >= 1 integer class ids')
+        lab, seeds, cfgs, ks, ps = self._per_image_args(lab0.repeat_interleave(n), [v for r in sd for v in r], spread(cfg), spread(top_k), spread(top_p))
+        rec, f_hat, totals, choice = self.engine().sample_best_of(lab.to(dev).long(), seeds, cfgs, ks, ps, n, by, int(max_images))
+        img = self.engine().decode_f_hat(f_hat)
+        return img, self._record(img, rec.pop('tokens'), rec), totals, choice
+
     @torch.no_grad()
     def autoregressive_infer_cfg_per_image(self, label_B, g_seeds, cfg=1.5, top_k=0, top_p=0.0, more_smooth=False, return_tokens=False):
         """Sample a batch of unrelated requests: image b is drawn with its own seed g_seeds[b] and its own cfg / top_k / top_p (each a scalar
@@ -391,6 +529,20 @@ class VAR(nn.Module):
         more_smooth is one bool for the batch.  Precision follows set_hip_precision / 'auto' as the plain call does.  On the HIP path (a CUDA /
         ROCm model in eval mode, prog_si < 0) the loop is SamplingEngine.sample_per_image; elsewhere (a CPU model, train mode, prog_si >= 0)
         the same stream comes from the library's host twin and the loop runs in PyTorch, image by image."""
+        lab, seeds, cfgs, ks, ps = self._per_image_args(label_B, g_seeds, cfg, top_k, top_p)
+        B = lab.numel()
+        dev = self.lvl_1L.device
+        lab = lab.to(dev).long()
+        if dev.type == 'cuda' and not self.training and self.prog_si < 0:
+            tok = torch.empty(B, self.L, dtype=torch.int64, device=dev) if return_tokens else None
+            img = self.engine().sample_per_image(lab, seeds, cfgs, ks, ps, more_smooth=bool(more_smooth), tokens_out=tok)
+            return (img, tok) if return_tokens else img
+        self.engine()._check_labels(lab)
+        img, tok = self._per_image_torch(lab, seeds, cfgs, ks, ps, bool(more_smooth))
+        return (img, tok) if return_tokens else img
+
+    def _per_image_args(self, label_B, g_seeds, cfg, top_k, top_p):
+        """the argument handling of the per-image calls -> (labels (B,) integer tensor, seeds, cfgs, top_ks, top_ps: lists of B values)"""
         lab = torch.as_tensor(label_B)
         if lab.dim() != 1 or lab.numel() < 1 or lab.dtype.is_floating_point or lab.dtype.is_complex or lab.dtype == torch.bool:
             raise ValueError('label_B must hold B >= 1 integer class ids')
@@ -428,15 +580,7 @@ class VAR(nn.Module):
             raise ValueError(f'top_k must lie in [0, {self.V}]')
         if not all(0.0 <= p <= 1.0 for p in ps):                 # (NaN fails the comparison)
             raise ValueError('top_p must lie in [0, 1]')
-        dev = self.lvl_1L.device
-        lab = lab.to(dev).long()
-        if dev.type == 'cuda' and not self.training and self.prog_si < 0:
-            tok = torch.empty(B, self.L, dtype=torch.int64, device=dev) if return_tokens else None
-            img = self.engine().sample_per_image(lab, seeds, cfgs, ks, ps, more_smooth=bool(more_smooth), tokens_out=tok)
-            return (img, tok) if return_tokens else img
-        self.engine()._check_labels(lab)
-        img, tok = self._per_image_torch(lab, seeds, cfgs, ks, ps, bool(more_smooth))
-        return (img, tok) if return_tokens else img
+        return lab, seeds, cfgs, ks, ps
 
     def _per_image_torch(self, lab, seeds, cfgs, ks, ps, more_smooth: bool):
         """the PyTorch side of autoregressive_infer_cfg_per_image (reference var.py:126-190, one request at a time): the Exp(1) fills are
