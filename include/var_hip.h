@@ -398,6 +398,43 @@ int varhip_dist_profile_f32(const float* logits, const int64_t* gt, int64_t ld_g
                             const float* edges, int nbins, float min_prob,
                             int64_t* mass_q, int64_t* count, int64_t ld_img, int64_t ld_cls, varhip_stream_t stream);
 
+/* ---- per-pixel class evidence (VAR.evidence_maps; fork create_heatmaps_for_classes of eval_prob.py / var_analysis.py / inpainting.py /
+ * smoothing.py / var_size_analysis.py: per class and scale one bilinear F.interpolate, K full-size maps, matplotlib on the CPU) -----------
+ * scores: per-token class scores, class c of image i at scores[i * ld_img + c * ld_cls + token].  The nscales selected scales are HOST arrays
+ * of nscales entries each: pn (side), begin (first token; begin[s + 1] >= begin[s] + pn[s]^2) and w (weight, fp32).  ax_i: [nscales][size][2]
+ * int32 (i0, i1), ax_l: [nscales][size] fp32 l1 on the device: scale s's axis table of the bilinear resample pn[s] -> size
+ * (align_corners=False; the same table serves rows and columns); indices are clamped into [0, pn[s] - 1] before use.  With l0 = 1 - l1 and
+ * a, b, c, d = the tokens (y.i0, x.i0), (y.i0, x.i1), (y.i1, x.i0), (y.i1, x.i1) of scale s:
+ *   v_s = l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d);   m = (..(0.0f + v_0 * w_0) + v_1 * w_1 ..)
+ * every product, sum and difference one fp32 rounding, no contraction.
+ * varhip_evidence_reduce_f32 writes, over all classes of image i:
+ *   lo[i], hi[i]            min and max of m over classes and pixels
+ *   pred[i][y][x]           the class with the largest m, the lowest index among exact ties
+ *   margin[i][y][x]         largest minus second largest m (+inf when classes == 1)
+ *   area[i][c]              pixels with pred == c (sums to size^2)
+ *   maps[i][c][y][x]        m itself, only when maps != NULL
+ * and nothing else; lo and hi serve as unsigned scratch during the call (integer atomic min / max on an order-preserving encoding), area is
+ * zeroed by the call: no operand needs preparing.  Scores must be finite (a NaN's place in the order is not defined).
+ * varhip_evidence_overlay_u8 recomputes m (it does not read maps) and writes out[i][c][y][x][3] uint8:
+ *   v = (m - lo[i]) / (hi[i] - lo[i]), or m - lo[i] when hi[i] == lo[i];  bin = min((int)(v * 256), 255);  colour = matplotlib's 'jet' entry bin
+ *   as uint8;  g = image[i][ch][y][x] (image_pm1: (g + 1) / 2), g8 = (uint8)clamp(g * 255, 0, 255) in fp32, truncated;
+ *   out = (uint8)clamp(g8 * (1 - alpha) + colour * alpha, 0, 255) in float64 (two products, one sum), truncated.
+ * image: [images][3][size][size] fp32.  out needs 4-byte alignment.
+ * NULL operands (maps excepted), images / classes < 1, images > 65535 (reduce), images * classes >= 2^31 (overlay), nscales outside [1, 16],
+ * pn outside [1, 64], begin negative or overlapping, more than 4096 tokens from the first selected to the last, a NaN weight, ld_cls short of
+ * the last selected token, ld_img < classes * ld_cls, size outside [1, 4096], alpha outside [0, 1], image_pm1 not 0 / 1: VARHIP_EINVAL. */
+int varhip_evidence_reduce_f32(const float* scores, int64_t ld_img, int64_t ld_cls, int images, int classes,
+                               int nscales, const int* pn, const int* begin, const float* w,
+                               const int* ax_i, const float* ax_l, int size,
+                               float* lo, float* hi, int* pred, float* margin, int* area, float* maps, varhip_stream_t stream);
+int varhip_evidence_overlay_u8(const float* scores, int64_t ld_img, int64_t ld_cls, int images, int classes,
+                               int nscales, const int* pn, const int* begin, const float* w,
+                               const int* ax_i, const float* ax_l, int size,
+                               const float* lo, const float* hi, const float* image, int image_pm1, double alpha,
+                               uint8_t* out, varhip_stream_t stream);
+/* the 256 x 3 colour table of varhip_evidence_overlay_u8 (768 bytes); a plain host function */
+int varhip_evidence_jet_host(uint8_t* out);
+
 /* ---- the pruning step of zero-shot classification (VAR.classify) ---------------------------------------------------------------------
  * One workgroup per image i.  Every candidate c < cand adds its stage's per-token scores to its float64 running total, one plain addition
  * per token in ascending token order:  totals[i * cand + c] += (double)tokens[i * ld_img + c * ld_cls + t],  t = t0 .. t1-1  (t1 == t0: the

@@ -94,6 +94,8 @@ SIGNATURES_HIP_ONLY = {
     'token_eval_f32':    [P, P, L, I, I, I, P, P, P, P, L],             # pinned against float64, torch.argmax and the rank's definition (tests/test_evaluate_gpu.py)
     'eval_reduce_f32':   [P, P, P, P, L, I, P, I, I, P, P, P, P],       # pinned against numpy float64 sums and torch.bincount; begin_S1 is a host array
     'sample_stats_f32':  [P, P, P, I, I, I, D, P, P, P, P, P, P, L],    # pinned against its host twin, token_loglik_f32 and float64 (tests/test_sample_stats_gpu.py)
+    'evidence_reduce_f32': [P, L, L, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P],   # pinned bit for bit against evidence_maps_torch (tests/test_evidence_gpu.py); pn, begin, w are host arrays
+    'evidence_overlay_u8': [P, L, L, I, I, I, P, P, P, P, P, I, P, P, P, I, D, P],   # pinned byte for byte against evidence_maps_torch
 }
 
 # plain host functions of the HIP library (no stream argument, no device pointer, no GPU needed); bound by var_amd/hip.py
@@ -102,6 +104,7 @@ SIGNATURES_HOST = {
     'philox4x32_host':   [P, P, P],                                  # pinned against the Random123 known answers
     'exp1_from_bits_host_f32': [P, L, P],
     'sample_stats_host_f32': [P, P, P, I, I, I, D, P, P, P, P, P, P, L],   # pinned against float64 (tests/test_sample_stats_cpu.py)
+    'evidence_jet_host': [P],                                        # pinned against matplotlib's 'jet' (tests/test_evidence_cpu.py)
 }
 
 # ... and with bfloat16 storage: one entry point per _f16 entry point, same arguments (include/var_hip.h, "bf16")

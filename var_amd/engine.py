@@ -155,6 +155,77 @@ def _tap_tables(cache: dict, pn: int, P: int, dev):
     return cache[pn]
 
 
+def bilinear_axis(pn: int, size: int):
+    """(i0, i1, l1): the axis table of F.interpolate(mode='bilinear', align_corners=False) for pn -> size, rows and columns alike (also for
+    size < pn: the same formula, no antialiasing).  Follows ATen's upsample_bilinear2d in fp32: src = max((dst + 0.5) * (pn / size) - 0.5, 0) with
+    the ratio and the product in fp32, i0 = int(src), i1 = min(i0 + 1, pn - 1), l1 = src - i0 (the weight of i1; i0 weighs 1 - l1)."""
+    f = np.float32
+    scale = f(pn) / f(size)
+    src = np.maximum((np.arange(size, dtype=np.float32) + f(0.5)) * scale - f(0.5), f(0))
+    i0 = src.astype(np.int32)
+    i1 = np.minimum(i0 + 1, pn - 1).astype(np.int32)
+    return i0, i1, (src - i0.astype(np.float32)).astype(np.float32)
+
+
+def evidence_scales(patch_nums, scales):
+    """(pn, begin, w) of the selected scales as varhip_evidence_* take them: int32, int32 (first token of the scale) and fp32
+    w_s = float32(pn_s^2 / sum of the selected pn^2), numpy arrays"""
+    begins = np.concatenate([[0], np.cumsum([p * p for p in patch_nums])])
+    pn = np.asarray([patch_nums[s] for s in scales], dtype=np.int32)
+    total = int((pn.astype(np.int64) ** 2).sum())
+    w = np.asarray([np.float32(int(p) * int(p) / total) for p in pn], dtype=np.float32)
+    return pn, np.asarray([begins[s] for s in scales], dtype=np.int32), w
+
+
+# the limits of varhip_evidence_reduce_f32 / varhip_evidence_overlay_u8 (include/var_hip.h)
+EVIDENCE_MAX_SCALES, EVIDENCE_MAX_STAGE, EVIDENCE_MAX_PN, EVIDENCE_MAX_SIZE, EVIDENCE_MAX_IMAGES = 16, 4096, 64, 4096, 65535
+_AXIS_HOST: dict = {}              # (pn, size) -> bilinear_axis(pn, size)
+_AXIS_DEVICE: dict = {}            # (selected pn, size, device) -> (ax_i [ns][size][2] int32, ax_l [ns][size] fp32) on the device
+
+
+def evidence_axis_tables(pns: tuple, size: int, dev):
+    """the axis tables of the selected scales on the device, built on the host once per (pn, size) and uploaded once per (scales, size, device)"""
+    key = (tuple(int(p) for p in pns), int(size), str(dev))
+    if key not in _AXIS_DEVICE:
+        ai = np.empty((len(pns), size, 2), np.int32)
+        al = np.empty((len(pns), size), np.float32)
+        for s, pn in enumerate(key[0]):
+            if (pn, size) not in _AXIS_HOST:
+                _AXIS_HOST[(pn, size)] = bilinear_axis(pn, size)
+            ai[s, :, 0], ai[s, :, 1], al[s] = _AXIS_HOST[(pn, size)]
+        if len(_AXIS_DEVICE) >= 64:
+            _AXIS_DEVICE.clear()
+        _AXIS_DEVICE[key] = (torch.from_numpy(ai).to(dev), torch.from_numpy(al).to(dev))
+    return _AXIS_DEVICE[key]
+
+
+@torch.no_grad()
+def evidence_maps_hip(scores: torch.Tensor, patch_nums, scales, size: int, image, image_pm1: bool, alpha: float, return_maps: bool) -> dict:
+    """VAR.evidence_maps on the HIP path: scores (N, K, L) fp32 contiguous on the GPU, arguments already validated by the caller
+    -> dict(lo, hi, pred, margin, area, maps | None, overlays | None).  Two entry points, no (N, K, size, size) tensor unless asked for."""
+    N, K, L = scores.shape
+    dev = scores.device
+    pn, begin, w = evidence_scales(patch_nums, scales)
+    stage = int(begin[-1]) + int(pn[-1]) ** 2 - int(begin[0])
+    if len(pn) > EVIDENCE_MAX_SCALES or stage > EVIDENCE_MAX_STAGE or int(pn.max()) > EVIDENCE_MAX_PN or N > EVIDENCE_MAX_IMAGES or N * K >= 2 ** 31:
+        raise ValueError(f'evidence_maps on the GPU takes at most {EVIDENCE_MAX_SCALES} scales of side <= {EVIDENCE_MAX_PN} spanning at most '
+                         f'{EVIDENCE_MAX_STAGE} tokens, and at most {EVIDENCE_MAX_IMAGES} images')
+    ax_i, ax_l = evidence_axis_tables(tuple(pn.tolist()), size, dev)
+    host = (torch.from_numpy(pn), torch.from_numpy(begin), torch.from_numpy(w))
+    with torch.cuda.device(dev):
+        out = dict(lo=torch.empty(N, dtype=torch.float32, device=dev), hi=torch.empty(N, dtype=torch.float32, device=dev),
+                   pred=torch.empty(N, size, size, dtype=torch.int32, device=dev), margin=torch.empty(N, size, size, dtype=torch.float32, device=dev),
+                   area=torch.empty(N, K, dtype=torch.int32, device=dev),
+                   maps=torch.empty(N, K, size, size, dtype=torch.float32, device=dev) if return_maps else None, overlays=None)
+        hip.call('evidence_reduce_f32', scores, K * L, L, N, K, len(pn), *host, ax_i, ax_l, size,
+                 out['lo'], out['hi'], out['pred'], out['margin'], out['area'], out['maps'])
+        if image is not None:
+            out['overlays'] = torch.empty(N, K, size, size, 3, dtype=torch.uint8, device=dev)
+            hip.call('evidence_overlay_u8', scores, K * L, L, N, K, len(pn), *host, ax_i, ax_l, size,
+                     out['lo'], out['hi'], image, 1 if image_pm1 else 0, float(alpha), out['overlays'])
+    return out
+
+
 def _scale_tables(taps: dict, phi: list, si: int, S: int, pn: int, P: int, dev):
     """(ti, tw, pw, pb, ratio): what the quantizer step of scale si (pn x pn of S scales, the last P x P) takes besides its tokens"""
     return _tap_tables(taps, pn, P, dev) + phi[phi_index(si, S, len(phi))]

@@ -245,6 +245,144 @@ def distance_profile_torch(z: torch.Tensor, gt: torch.Tensor, dist: torch.Tensor
     return count.view(K, B), mass.view(K, B)
 
 
+class EvidenceMaps:
+    """VAR.evidence_maps' result: where in the image the evidence for each class sits.  With m[n, k, y, x] the map of class k (the selected
+    scales' per-token scores, each resampled bilinearly to size x size and weighted by its share of the selected tokens):
+      lo, hi     (N,) fp32: min and max of m over all classes and pixels of image n (the fork's global normalisation)
+      pred       (N, size, size) int32: the class with the largest m at the pixel, the lowest index among exact ties
+      margin     (N, size, size) fp32: largest minus second largest m (+inf with one class)
+      area       (N, K) int32: pixels won by each class (sums to size^2)
+      maps       (N, K, size, size) fp32 or None (return_maps=True)
+      overlays   (N, K, size, size, 3) uint8 or None (an image was given): the fork's jet overlay of every class map
+      scales, size, patch_nums: what the result covers
+    A (K, L) input gives N = 1."""
+    __slots__ = ('lo', 'hi', 'pred', 'margin', 'area', 'maps', 'overlays', 'scales', 'size', 'patch_nums')
+
+    def __init__(self, lo, hi, pred, margin, area, maps, overlays, scales, size, patch_nums):
+        self.lo, self.hi, self.pred, self.margin, self.area, self.maps, self.overlays = lo, hi, pred, margin, area, maps, overlays
+        self.scales, self.size, self.patch_nums = tuple(scales), int(size), tuple(patch_nums)
+
+    def normalized(self) -> torch.Tensor:
+        """(maps - lo) / (hi - lo) per image in fp32, maps - lo where hi == lo: what the colour table is indexed with (needs return_maps=True)"""
+        if self.maps is None:
+            raise ValueError('normalized() needs the maps: call evidence_maps(..., return_maps=True)')
+        return _evidence_normalize(self.maps, self.lo, self.hi)
+
+    def __repr__(self):
+        N, K = self.area.shape
+        return (f'EvidenceMaps(images={N}, classes={K}, size={self.size}, scales={self.scales}, maps={self.maps is not None}, '
+                f'overlays={self.overlays is not None})')
+
+
+def _evidence_normalize(maps: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
+    rng = (hi - lo).view(-1, 1, 1, 1)
+    v = maps - lo.view(-1, 1, 1, 1)
+    return torch.where(rng != 0, v / rng, v)
+
+
+_JET = []
+
+
+def jet_table() -> torch.Tensor:
+    """(256, 3) uint8: matplotlib's 'jet' as (lut * 255).astype(uint8), the table the overlay kernel holds (read from the library: one copy)"""
+    if not _JET:
+        from .. import hip
+        t = np.zeros(768, np.uint8)
+        hip.call_host('evidence_jet_host', t)
+        _JET.append(torch.from_numpy(t.reshape(256, 3)))
+    return _JET[0]
+
+
+def evidence_maps_torch(scores: torch.Tensor, patch_nums, scales, size: int, image: Optional[torch.Tensor] = None, image_pm1: bool = True,
+                        alpha: float = 0.5, return_maps: bool = False) -> dict:
+    """VAR.evidence_maps' definitions in PyTorch, in the operation order of the kernels: the twin the GPU is held to bit for
+    bit.  scores: (N, K, L) fp32, image: (N, 3, size, size) fp32 or None -> dict(lo, hi, pred, margin, area, maps | None, overlays | None).
+    Every product and sum is its own fp32 operation (separate mul / add calls: nothing here may be fused); the (N, K, size, size) maps are
+    materialised, which is what the kernels avoid."""
+    from ..engine import bilinear_axis, evidence_scales
+    N, K, L = scores.shape
+    dev = scores.device
+    pn, begin, w = evidence_scales(patch_nums, scales)
+    m = torch.zeros(N, K, size, size, dtype=torch.float32, device=dev)
+    one = torch.ones((), dtype=torch.float32, device=dev)
+    for p, b, ws in zip(pn.tolist(), begin.tolist(), w):
+        i0, i1, l1 = (torch.from_numpy(np.ascontiguousarray(t)).to(dev) for t in bilinear_axis(p, size))
+        i0, i1 = i0.long(), i1.long()
+        l0 = torch.sub(one, l1)
+        g = scores[:, :, b:b + p * p].reshape(N, K, p, p)
+        r0, r1 = g[:, :, i0], g[:, :, i1]                                  # (N, K, size, p): the rows y.i0 and y.i1
+        l0x, l1x, l0y, l1y = l0.view(1, 1, 1, -1), l1.view(1, 1, 1, -1), l0.view(1, 1, -1, 1), l1.view(1, 1, -1, 1)
+        top = torch.add(torch.mul(l0x, r0[..., i0]), torch.mul(l1x, r0[..., i1]))
+        bot = torch.add(torch.mul(l0x, r1[..., i0]), torch.mul(l1x, r1[..., i1]))
+        v = torch.add(torch.mul(l0y, top), torch.mul(l1y, bot))
+        m = torch.add(m, torch.mul(v, torch.tensor(ws, dtype=torch.float32, device=dev)))
+    lo, hi = m.amin((1, 2, 3)), m.amax((1, 2, 3))
+    best = m.amax(1)
+    ks = torch.arange(K, device=dev).view(1, K, 1, 1)
+    pred = torch.where(m == best.unsqueeze(1), ks, K - 1).amin(1)          # the lowest index among exact ties (no match: a NaN under check=False)
+    second = m.masked_fill(ks == pred.unsqueeze(1), -math.inf).amax(1)
+    area = torch.stack([torch.bincount(pred[n].reshape(-1), minlength=K) for n in range(N)]).to(torch.int32)
+    out = dict(lo=lo, hi=hi, pred=pred.to(torch.int32), margin=torch.sub(best, second), area=area, maps=m if return_maps else None, overlays=None)
+    if image is not None:
+        jet = jet_table().to(dev)
+        x = image.float()
+        if image_pm1:
+            x = torch.div(torch.add(x, 1.0), 2.0)
+        g8 = torch.mul(x, 255.0).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).double()       # truncated, as numpy's astype
+        over = torch.empty(N, K, size, size, 3, dtype=torch.uint8, device=dev)
+        for n in range(N):
+            v = _evidence_normalize(m[n:n + 1], lo[n:n + 1], hi[n:n + 1])[0]
+            col = jet[torch.mul(v, 256.0).clamp(0, 255).long()].double()                          # min(int(v * 256), 255)
+            o = torch.add(torch.mul(g8[n].unsqueeze(0), 1.0 - float(alpha)), torch.mul(col, float(alpha)))
+            over[n] = o.clamp(0, 255).to(torch.uint8)
+        out['overlays'] = over
+    return out
+
+
+def evidence_maps(scores, patch_nums, *, scales=None, size: int = 256, image=None, image_range: str = 'pm1', alpha: float = 0.5,
+                  return_maps: bool = False, check: bool = True) -> EvidenceMaps:
+    """VAR.evidence_maps for any patch_nums (the method passes the model's): see there."""
+    patch_nums = tuple(int(p) for p in patch_nums)
+    S, L = len(patch_nums), sum(p * p for p in patch_nums)
+    if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.dim() not in (2, 3) or scores.shape[-1] != L \
+            or scores.numel() == 0:
+        raise ValueError(f'scores must be a (N, K, {L}) or (K, {L}) fp32 tensor with N, K >= 1')
+    s3 = scores.detach().reshape(-1, scores.shape[-2], L).contiguous() if scores.dim() == 3 else scores.detach().reshape(1, -1, L).contiguous()
+    N, K = s3.shape[:2]
+    if scales is None:
+        scales = tuple(range(S // 2))
+    try:
+        scales = tuple(scales)
+        ok = all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) for s in scales)
+    except TypeError:
+        ok = False
+    if not ok or len(scales) == 0 or any(not 0 <= s < S for s in scales) or any(b <= a for a, b in zip(scales, scales[1:])):
+        raise ValueError(f'scales must be a non-empty increasing sequence of scale indices in [0, {S})')
+    scales = tuple(int(s) for s in scales)
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or not 1 <= size <= 4096:
+        raise ValueError('size must be an integer in [1, 4096]')
+    size = int(size)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)) or not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError('alpha must be a number in [0, 1]')
+    if image_range not in ('pm1', '01'):
+        raise ValueError("image_range must be 'pm1' (the image is in [-1, 1]) or '01'")
+    if image is not None:
+        if not isinstance(image, torch.Tensor) or not image.is_floating_point() or image.dim() not in (3, 4) \
+                or tuple(image.shape[-3:]) != (3, size, size) or (image.dim() == 4 and image.shape[0] != N) or (image.dim() == 3 and N != 1):
+            raise ValueError(f'image must be a ({N}, 3, {size}, {size}) floating-point tensor' + (f' or (3, {size}, {size})' if N == 1 else ''))
+        image = image.detach().to(s3.device, torch.float32).reshape(N, 3, size, size).contiguous()
+    if check:
+        sel = [s3[:, :, sum(p * p for p in patch_nums[:s]):sum(p * p for p in patch_nums[:s + 1])] for s in scales]
+        if not bool(torch.isfinite(torch.cat(sel, -1) if len(sel) > 1 else sel[0]).all()):
+            raise ValueError('scores of the selected scales must be finite (check=False skips this test: the result is then undefined)')
+    if s3.is_cuda:
+        from ..engine import evidence_maps_hip
+        r = evidence_maps_hip(s3, patch_nums, scales, size, image, image_range == 'pm1', float(alpha), bool(return_maps))
+    else:
+        r = evidence_maps_torch(s3, patch_nums, scales, size, image, image_range == 'pm1', float(alpha), bool(return_maps))
+    return EvidenceMaps(r['lo'], r['hi'], r['pred'], r['margin'], r['area'], r['maps'], r['overlays'], scales, size, patch_nums)
+
+
 GENERATIVE_FEATURES = ('vae_post', 'vae_fhat')
 
 
@@ -843,6 +981,36 @@ class VAR(nn.Module):
                     c, m = distance_profile_torch(z[k0:k0 + max_rows, b:e].float(), gt[i, b:e], d[b:e], e32, min_prob)
                     count[i, k0:k0 + max_rows, si], mass[i, k0:k0 + max_rows, si] = c, m
         return DistanceProfile(count, mass, e32.to(dev), min_prob, self.patch_nums)
+
+    def evidence_maps(self, scores, *, scales=None, size: int = 256, image=None, image_range: str = 'pm1', alpha: float = 0.5,
+                      return_maps: bool = False, check: bool = True) -> EvidenceMaps:
+        """Where in the image the evidence for each class sits -> EvidenceMaps (see there): the spatial read-out of token_log_likelihood /
+        token_scores, whose sum over tokens is all that classify uses.
+
+        Replaces the fork's create_heatmaps_for_classes (eval_prob.py, inpainting.py, smoothing.py, var_analysis.py, var_size_analysis.py,
+        drawn under --plot): a host loop over classes and scales with one F.interpolate each, K full-size maps and matplotlib on the CPU.
+        scores: (N, K, L) or (K, L) fp32 per-token scores, L = sum(pn^2) of the model's patch_nums.  scales: an increasing tuple of scale
+        indices, default the fork's first half range(S // 2).  The map of class k is
+          m[n, k, y, x] = sum over the selected s of  w_s * bilinear_s(scores[n, k, scale s])(y, x),   w_s = float32(pn_s^2 / sum of selected pn^2)
+        with torch's interpolate(mode='bilinear', align_corners=False) from pn_s x pn_s to size x size (no antialiasing below pn_s); the
+        operation order is fixed, so the GPU and the PyTorch route agree bit for bit.
+        image: (N, 3, size, size) or (3, size, size), in [-1, 1] (image_range='pm1') or [0, 1] ('01'): adds `overlays`, per class the jet
+        colouring of (m - lo) / (hi - lo) blended as clip(img8 * (1 - alpha) + colour * alpha, 0, 255) the way the fork does in numpy.  (The
+        fork computes the [-1, 1] -> [0, 1] step and then overwrites it, blending a wrapped image; that is not reproduced.)
+        return_maps=True also returns the (N, K, size, size) maps.  check=True tests the selected scores for non-finite values on the
+        device (one reduction and a host sync); with check=False a non-finite score leaves the result undefined.  Bad arguments raise ValueError.
+        On a GPU tensor two gfx950 kernels do all of it: varhip_evidence_reduce_f32 loops over the classes per pixel tile and never writes
+        the maps unless asked, varhip_evidence_overlay_u8 recomputes and colours them.  A CPU tensor takes evidence_maps_torch."""
+        return evidence_maps(scores, self.patch_nums, scales=scales, size=size, image=image, image_range=image_range, alpha=alpha,
+                             return_maps=return_maps, check=check)
+
+    @torch.no_grad()
+    def class_heatmaps(self, gt_tokens, label, image, score: str = 'log_prob', cfg: float = 0.0, max_rows: int = 64, **kw) -> EvidenceMaps:
+        """token_scores(gt_tokens, label, score, cfg, max_rows) followed by evidence_maps(..., image=image): the fork's --plot in one call.
+        Keyword arguments group / threshold / top_k go to token_scores, the rest (scales, size, image_range, alpha, return_maps, check) to
+        evidence_maps.  No arithmetic of its own."""
+        score_kw = {k: kw.pop(k) for k in ('group', 'threshold', 'top_k') if k in kw}
+        return self.evidence_maps(self.token_scores(gt_tokens, label, score, cfg, max_rows, **score_kw), image=image, **kw)
 
     def _profile_args(self, edges, min_prob):
         """validation of distance_profile's edges and min_prob -> ((B + 1,) fp32 CPU tensor, the fp32 value of min_prob as a float)"""
