@@ -398,6 +398,55 @@ int varhip_dist_profile_f32(const float* logits, const int64_t* gt, int64_t ld_g
                             const float* edges, int nbins, float min_prob,
                             int64_t* mass_q, int64_t* count, int64_t ld_img, int64_t ld_cls, varhip_stream_t stream);
 
+/* ---- per-token mutual information over classes (VAR.class_information) ---------------------------------------------------------------------
+ * I(c ; x_t | x_<t) = H(sum_k pi_k p_k) - sum_k pi_k H(p_k): how much the class changes the prediction at a token, without a label and without
+ * the (K, L, V) softmax tensor.  One scale of one pass: the row layout, uncond rows, gt addressing and CFG combine of varhip_token_loglik_f32;
+ * prior: fp32, class c of image i at prior[i * ld_prior + c] (ld_prior >= classes), used as given (not renormalised).
+ * Row pass (class k of a token):  m = max z, s = sum exp(z - m) exactly as varhip_token_loglik_f32 (rowlse.h), e_v = vm_exp(z_v - m);
+ *   H_k   = the `entropy` of varhip_sample_stats_f32 on that row: (float)((0 - A_k) / (double)s), A_k = sum_{e_v > 0} (double)e_v * (double)lp_v,
+ *           lp_v = (z_v - m) - vm_log(s), float64 in the canonical lane order (lane i of 64: elements j * 256 + 4 * i + c ascending, lanes by the
+ *           xor butterfly).  A row holding a NaN: NaN.  Written to entropy[i * ld_ent_img + k * ld_ent_cls + t].
+ *   p_v   = e_v / s, one correctly rounded fp32 division.
+ *   mix_q[v] += (int64)rint(((double)p_v * (double)pi_k) * 2^48)      (the product of two fp32 values is exact in float64: one rounding)
+ *   hcond_q  += (int64)rint(((double)pi_k * (double)H_k) * 2^40)      (likewise; a NaN row adds nothing and raises the token's flag instead)
+ *   Headroom: sum_k pi_k = 1 within 1e-6 and p_v <= 1 keep mix_q[v] <= 2^48 (1 + 1e-6) + K / 2; H_k <= ln V <= 16.7 (V <= 2^24) keeps hcond_q
+ *   below 2^45.  K <= 2^31: both stay far inside int64.
+ * Finalise (per token, once every class has been added):
+ *   q_v = (float)((double)mix_q[v] * 2^-48);  A = sum_{q_v > 0} (double)q_v * (double)vm_log(q_v) in float64 in ONE order that depends on V
+ *   alone: thread t of 256 adds its elements j * 1024 + 4 * t + c in ascending (j, c) order, the 64 lanes of a wave by the xor butterfly, the
+ *   four waves as ((w0 + w1) + w2) + w3.  (The row sums use the wave order above; the token sum, which has no row pass in front of it, uses all
+ *   four waves of the workgroup.)
+ *   h_mix = (float)(0 - A);  h_cond = (float)(hcond_q * 2^-40);  mi = (float)((0 - A) - hcond_q * 2^-40);  logp_mix = vm_log(q_gt), NaN for a gt
+ *   outside [0, V), which is never dereferenced.  A token whose flag is up (a NaN in any class row): all four are NaN.
+ * Every sum across classes is an integer sum: the four per-token values are the same bits for any order of the classes (prior permuted alike),
+ * any split of the classes into calls and any order of execution.
+ * mix_q == NULL, the on-chip route (V <= 4096): the call holds every class of its tokens; the mixture stays in LDS, the call finalises and
+ *   writes h_mix / h_cond / mi / logp_mix [i * ld_out + t] (ld_out >= l).  hcond_q, nanflag and ld_acc are not read.
+ * mix_q != NULL, a chunk: the call ADDS its classes into mix_q[(i * ld_acc + t) * V + v], hcond_q[i * ld_acc + t] and raises
+ *   nanflag[i * ld_acc + t] (int32, 0 / 1); ld_acc >= l; the caller zeroes the three once and runs varhip_class_mix_finish_f32 after the last
+ *   chunk.  Calls that add into the same token must be ordered on one stream (a workgroup owns its token's sums).  The four outputs are not read.
+ * The register path needs V % 4 == 0 and 16-byte aligned logits (V <= 4096), anything else re-reads the row from memory; V > 4096 is a chunk
+ * only.  NULL operands, images / classes / l < 1, V outside (0, 2^24], ld_gt < l, ld_prior < classes, ld_ent_cls < l, ld_ent_img < classes *
+ * ld_ent_cls, ld_acc < l (chunk), ld_out < l or V > 4096 (on-chip): VARHIP_EINVAL. */
+int varhip_class_mix_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V, int with_uncond,
+                         float ca, float cb, const float* prior, int64_t ld_prior, float* entropy, int64_t ld_ent_img, int64_t ld_ent_cls,
+                         int64_t* mix_q, int64_t* hcond_q, int32_t* nanflag, int64_t ld_acc, float* h_mix, float* h_cond, float* mi,
+                         float* logp_mix, int64_t ld_out, varhip_stream_t stream);
+/* the finalise step alone over the accumulator of chunked calls: images x l tokens, addressed as above */
+int varhip_class_mix_finish_f32(const int64_t* mix_q, const int64_t* hcond_q, const int32_t* nanflag, int64_t ld_acc, const int64_t* gt,
+                                int64_t ld_gt, int images, int l, int V, float* h_mix, float* h_cond, float* mi, float* logp_mix,
+                                int64_t ld_out, varhip_stream_t stream);
+/* the host twins: plain host code (usable without a GPU), same arguments with host pointers.  The same operations in the same order (vm_exp /
+ * vm_log consist of correctly rounded operations only): the kernels' bits for 16-byte aligned logits (the twin takes the register path's order
+ * iff V % 4 == 0 and V <= 4096). */
+int varhip_class_mix_host_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V, int with_uncond,
+                              float ca, float cb, const float* prior, int64_t ld_prior, float* entropy, int64_t ld_ent_img, int64_t ld_ent_cls,
+                              int64_t* mix_q, int64_t* hcond_q, int32_t* nanflag, int64_t ld_acc, float* h_mix, float* h_cond, float* mi,
+                              float* logp_mix, int64_t ld_out);
+int varhip_class_mix_finish_host_f32(const int64_t* mix_q, const int64_t* hcond_q, const int32_t* nanflag, int64_t ld_acc, const int64_t* gt,
+                                     int64_t ld_gt, int images, int l, int V, float* h_mix, float* h_cond, float* mi, float* logp_mix,
+                                     int64_t ld_out);
+
 /* ---- per-pixel class evidence (VAR.evidence_maps; fork create_heatmaps_for_classes of eval_prob.py / var_analysis.py / inpainting.py /
  * smoothing.py / var_size_analysis.py: per class and scale one bilinear F.interpolate, K full-size maps, matplotlib on the CPU) -----------
  * scores: per-token class scores, class c of image i at scores[i * ld_img + c * ld_cls + token].  The nscales selected scales are HOST arrays

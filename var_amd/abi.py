@@ -77,6 +77,8 @@ SIGNATURES_HIP_ONLY = {
     'code_dist_f32':     [P, I, I, P],                                  # pinned against neighbor_table_f32 (tests/test_token_scores_gpu.py)
     'token_score_f32':   [P, P, L, I, I, I, I, I, F, F, I, I, F, P, L, P, L, L],   # pinned against float64 (tests/test_token_scores_gpu.py)
     'dist_profile_f32':  [P, P, L, I, I, I, I, I, F, F, P, L, P, I, F, P, P, L, L],   # pinned against float64 (tests/test_distance_profile_gpu.py)
+    'class_mix_f32':     [P, P, L, I, I, I, I, I, F, F, P, L, P, L, L, P, P, P, L, P, P, P, P, L],   # pinned bit for bit against its host twin (tests/test_class_information_gpu.py)
+    'class_mix_finish_f32': [P, P, P, L, P, L, I, I, I, P, P, P, P, L],
     'conv3x3_wino_nhwc_f32': [P, P, P, P, P, P, I, I, I, I, I],      # pinned against float64 and the direct conv (tests/test_winograd_gpu.py)
     'class_select_f32':  [P, L, L, I, I, I, I, P, I, P],             # pinned against a numpy lexsort of the rule (tests/test_classify_gpu.py)
     'cfg_argmax_f32':    [P, P, P, L, P, I, I, I, D],                # pinned against cfg_sample_f32(top_k=1) (tests/test_generative_gpu.py)
@@ -104,6 +106,8 @@ SIGNATURES_HOST = {
     'philox4x32_host':   [P, P, P],                                  # pinned against the Random123 known answers
     'exp1_from_bits_host_f32': [P, L, P],
     'sample_stats_host_f32': [P, P, P, I, I, I, D, P, P, P, P, P, P, L],   # pinned against float64 (tests/test_sample_stats_cpu.py)
+    'class_mix_host_f32': [P, P, L, I, I, I, I, I, F, F, P, L, P, L, L, P, P, P, L, P, P, P, P, L],   # pinned against float64 (tests/test_class_information_cpu.py)
+    'class_mix_finish_host_f32': [P, P, P, L, P, L, I, I, I, P, P, P, P, L],
     'evidence_jet_host': [P],                                        # pinned against matplotlib's 'jet' (tests/test_evidence_cpu.py)
 }
 

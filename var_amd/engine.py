@@ -882,8 +882,9 @@ class EncoderEngine(_VaeOps):
 AUTOCAST_PRECISION = {torch.float16: 'f16', torch.bfloat16: 'bf16'}
 
 
-# score -> mode of varhip_token_score_f32 (0: varhip_token_loglik_f32; 4: varhip_dist_profile_f32, which fills histograms instead of token scores)
-_SCORE_MODES = {'log_prob': 0, 'group_smoothed': 1, 'neighbor_max': 2, 'expected_distance': 3, 'distance_profile': 4}
+# score -> mode of varhip_token_score_f32 (0: varhip_token_loglik_f32; 4: varhip_dist_profile_f32, which fills histograms instead of token scores;
+# 5: varhip_class_mix_f32, which reduces across the classes of a token)
+_SCORE_MODES = {'log_prob': 0, 'group_smoothed': 1, 'neighbor_max': 2, 'expected_distance': 3, 'distance_profile': 4, 'class_information': 5}
 
 
 class SamplingEngine(_Engine):
@@ -1544,6 +1545,25 @@ class SamplingEngine(_Engine):
         self._score_stage(sc, sc['lab'], S - 1, -1, max_rows, out)
         return out
 
+    CLASS_MIX_LDS_V = 4096             # varhip_class_mix_f32 holds a token's mixture on the chip up to this V
+
+    @torch.no_grad()
+    def class_information(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, prior: torch.Tensor) -> dict:
+        """VAR.class_information on the HIP path -> dict(entropy (N, K, L), h_mix, h_cond, mi, logp_mix (N, L)) fp32: as token_scores, with
+        each scale's logits reduced behind the head by varhip_class_mix_f32.  A pass that holds all K classes of its images finalises in that
+        kernel; otherwise the chunks of an image add into an (L, V) int64 accumulator of the teacher-forced workspace (zeroed once per image)
+        and varhip_class_mix_finish_f32 runs per scale after the last chunk.  prior: (N, K) fp32, already validated by the caller."""
+        sc = self._score_setup(gt_tokens, labels, cfg, ('class_information',))
+        dev = sc['gt'].device
+        N, K = labels.shape
+        L = self.var.L
+        sc['prior'] = prior.to(dev, torch.float32).contiguous()
+        out = dict(entropy=torch.empty(N, K, L, dtype=torch.float32, device=dev))
+        for k in ('h_mix', 'h_cond', 'mi', 'logp_mix'):
+            out[k] = torch.empty(N, L, dtype=torch.float32, device=dev)
+        self._score_stage(sc, sc['lab'], len(self.var.patch_nums) - 1, -1, max_rows, out)
+        return out
+
     def _score_passes(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, score: tuple) -> torch.Tensor:
         """the pass loop of token_log_likelihood / token_scores: one stage through the last scale over every candidate"""
         sc = self._score_setup(gt_tokens, labels, cfg, score)
@@ -1582,7 +1602,8 @@ class SamplingEngine(_Engine):
         """one stage: the rows of labels lab_all (N, K) through scale `last`, packed into passes of at most max_rows rows:
         images_in_pass x (classes_in_pass + [cfg > 0]), the unconditional row of every image of a pass (label num_classes) after its class rows.
         Scales <= `done` only rebuild the KV caches; each later scale's logits are reduced by the scoring kernel into out (N, K, >= L_e), in
-        the distance_profile mode added by varhip_dist_profile_f32 into scale si of out = (mass_q, count), two (N, K, S, B) int64 arrays."""
+        the distance_profile mode added by varhip_dist_profile_f32 into scale si of out = (mass_q, count), two (N, K, S, B) int64 arrays; in
+        the class_information mode reduced across the classes by varhip_class_mix_f32 into out = dict(entropy, h_mix, h_cond, mi, logp_mix)."""
         var = self.var
         dev = lab_all.device
         N, K = lab_all.shape
@@ -1591,6 +1612,8 @@ class SamplingEngine(_Engine):
         if mode == 4:
             mass, count = out
             SB, B = mass.shape[2] * mass.shape[3], mass.shape[3]
+        elif mode == 5:
+            ci = [out[k] for k in ('h_mix', 'h_cond', 'mi', 'logp_mix')]
         else:
             Lo = out.shape[2]
         if K + u <= max_rows:
@@ -1600,6 +1623,13 @@ class SamplingEngine(_Engine):
         passes = [(i0, min(ipp, N - i0), k0, min(kpp, K - k0)) for i0 in range(0, N, ipp) for k0 in range(0, K, kpp)]
         ws = self._tf_workspace(max(ni * (nk + u) for _, ni, _, nk in passes), last)   # sized once: a shorter pass uses a prefix
         xin_img = sc['xin'][:, :var.begin_ends[last][1] - var.first_l]
+        if mode == 5 and (kpp < K or V > self.CLASS_MIX_LDS_V):       # the chunked route: the sums of ipp images leave the chip
+            acc = ws.get('class_mix')
+            if acc is None or acc[1].shape[0] < ipp:
+                acc = ws['class_mix'] = (torch.empty(ipp, L, V, dtype=torch.int64, device=dev), torch.empty(ipp, L, dtype=torch.int64, device=dev),
+                                         torch.empty(ipp, L, dtype=torch.int32, device=dev))
+        else:
+            acc = None
         for i0, ni, k0, nk in passes:
             R = ni * (nk + u)
             rows_img = torch.arange(i0, i0 + ni, device=dev)
@@ -1617,6 +1647,20 @@ class SamplingEngine(_Engine):
                 elif mode == 4:
                     hip.call('dist_profile_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t), sc['dist'], V,
                              sc['edges'], B, sc['min_prob'], mass[i0:, k0:, si], count[i0:, k0:, si], K * SB, SB)
+                elif mode == 5:
+                    ca, cb = float(np.float32(1) + t), float(t)
+                    if acc is None:
+                        hip.call('class_mix_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, ca, cb, sc['prior'][i0:], K, out['entropy'][i0:, :, cur:],
+                                 K * L, L, None, None, None, 0, *[o[i0:, cur:] for o in ci], L)
+                        continue
+                    if k0 == 0 and si == 0:
+                        for a in acc:
+                            a[:ni].zero_()
+                    hip.call('class_mix_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, ca, cb, sc['prior'][i0:, k0:], K,
+                             out['entropy'][i0:, k0:, cur:], K * L, L, acc[0][:, cur:], acc[1][:, cur:], acc[2][:, cur:], L, None, None, None, None, 0)
+                    if k0 + nk == K:
+                        hip.call('class_mix_finish_f32', acc[0][:, cur:], acc[1][:, cur:], acc[2][:, cur:], L, gt[i0:, cur:], L, ni, l, V,
+                                 *[o[i0:, cur:] for o in ci], L)
                 else:
                     hip.call('token_score_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
                              mode, sc['param'], sc['thr'], sc['dist'], V, out[i0:, k0:, cur:], K * Lo, Lo)

@@ -245,6 +245,89 @@ def distance_profile_torch(z: torch.Tensor, gt: torch.Tensor, dist: torch.Tensor
     return count.view(K, B), mass.view(K, B)
 
 
+H_ONE = float(2 ** 40)               # the fixed point of sum_k pi_k H_k: rint(pi_k * H_k * 2^40)
+CLASS_INFO_MAX_CAND = 16384          # candidates per image of VAR.class_information (the cap of classify)
+
+
+class ClassInformation:
+    """VAR.class_information's result: per token, how much the class changes the model's prediction, on the model's device (nats):
+      entropy   (N, K, L) fp32: H(p_k), p_k the softmax of the (guided) logits of class k
+      h_mix     (N, L) fp32: H(sum_k pi_k p_k), the entropy of the mixture over the classes
+      h_cond    (N, L) fp32: sum_k pi_k H(p_k)
+      mi        (N, L) fp32: h_mix - h_cond from the unrounded operands: I(c ; x_t | x_<t), between 0 and H(pi) up to rounding
+      logp_mix  (N, L) fp32: log sum_k pi_k p_k(gt), the model-averaged likelihood of the ground-truth token
+      prior     (N, K) fp32 as used, patch_nums: the scales the result covers
+    The sums over classes are integer sums in fixed point (2^-48 for the mixture, 2^-40 for h_cond): the (N, L) fields are bit-equal across
+    max_rows, packing, class order and repeated calls."""
+    __slots__ = ('entropy', 'h_mix', 'h_cond', 'mi', 'logp_mix', 'prior', 'patch_nums')
+
+    def __init__(self, entropy, h_mix, h_cond, mi, logp_mix, prior, patch_nums):
+        self.entropy, self.h_mix, self.h_cond, self.mi, self.logp_mix, self.prior = entropy, h_mix, h_cond, mi, logp_mix, prior
+        self.patch_nums = tuple(patch_nums)
+
+    def per_scale(self) -> dict:
+        """{'mi_sum', 'mi_mean', 'h_mix_sum', 'h_mix_mean', 'h_cond_sum', 'h_cond_mean'}: (N, S) float64 each, per image and scale the sum and
+        the mean over the scale's tokens"""
+        out = {}
+        for name in ('mi', 'h_mix', 'h_cond'):
+            x, cur, sums = getattr(self, name).double(), 0, []
+            for pn in self.patch_nums:
+                sums.append(x[:, cur:cur + pn * pn].sum(-1))
+                cur += pn * pn
+            out[name + '_sum'] = torch.stack(sums, -1)
+            out[name + '_mean'] = out[name + '_sum'] / torch.tensor([pn * pn for pn in self.patch_nums], dtype=torch.float64, device=x.device)
+        return out
+
+    def mi_map(self, **kw) -> 'EvidenceMaps':
+        """evidence_maps(mi[:, None, :], patch_nums, **kw): where in the image the class information sits (one 'class': the map of mi)"""
+        return evidence_maps(self.mi[:, None, :].contiguous(), self.patch_nums, **kw)
+
+    def __repr__(self):
+        N, K, L = self.entropy.shape
+        return f'ClassInformation(images={N}, classes={K}, tokens={L}, scales={len(self.patch_nums)})'
+
+
+def class_information_torch(z: torch.Tensor, gt: torch.Tensor, prior: torch.Tensor, max_rows: Optional[int] = None):
+    """VAR.class_information's definitions in PyTorch for one scale of one image.  z: (K, l, V) fp32 logits of the image's K class rows (the
+    guided combination when cfg > 0), gt: (l,) tokens, prior: (K,) fp32 -> (entropy (K, l), h_mix, h_cond, mi, logp_mix (l,)) fp32.
+    p_k = softmax(z_k) evaluated in float64 and rounded once to fp32, H_k likewise; the sums over classes are the fixed-point integer sums of
+    include/var_hip.h (rint(p pi 2^48), rint(pi H 2^40)), added max_rows class rows at a time (None: all at once): the result does not depend
+    on max_rows.  A NaN in any class row of a token makes its four per-token values NaN; a token outside [0, V): logp_mix NaN."""
+    K, l, V = z.shape
+    dev = z.device
+    pi = prior.to(dev, torch.float32).double()
+    step = K if max_rows is None else max(1, int(max_rows))
+    mix_q = torch.zeros(l, V, dtype=torch.int64, device=dev)
+    hq = torch.zeros(l, dtype=torch.int64, device=dev)
+    bad = torch.zeros(l, dtype=torch.bool, device=dev)
+    ent = torch.empty(K, l, dtype=torch.float32, device=dev)
+    for k0 in range(0, K, step):
+        zz = z[k0:k0 + step].double()
+        nanrow = torch.isnan(zz).any(-1)                                    # (k, l)
+        lp = torch.log_softmax(zz, dim=-1)
+        p = lp.exp()
+        H = (-(torch.where(p > 0, p * lp, torch.zeros_like(p))).sum(-1)).float()
+        H = torch.where(nanrow, torch.full_like(H, math.nan), H)
+        ent[k0:k0 + step] = H
+        pk = pi[k0:k0 + step]
+        q = torch.round(p.float().double() * pk.view(-1, 1, 1) * MASS_ONE)
+        q = torch.where(nanrow.unsqueeze(-1) | torch.isnan(q), torch.zeros_like(q), q)
+        mix_q += q.to(torch.int64).sum(0)
+        hq += torch.where(nanrow, torch.zeros_like(H, dtype=torch.float64), torch.round(pk.view(-1, 1) * H.double() * H_ONE)).to(torch.int64).sum(0)
+        bad |= nanrow.any(0)
+    qv = (mix_q.double() / MASS_ONE).float()
+    a = torch.where(qv > 0, qv.double() * torch.log(qv).double(), torch.zeros_like(qv, dtype=torch.float64)).sum(-1)
+    hc = hq.double() / H_ONE
+    nan = torch.full((l,), math.nan, dtype=torch.float32, device=dev)
+    valid = (gt >= 0) & (gt < V)
+    qg = qv.gather(-1, torch.where(valid, gt, torch.zeros_like(gt)).view(l, 1)).squeeze(-1)
+    h_mix = torch.where(bad, nan, (0.0 - a).float())
+    h_cond = torch.where(bad, nan, hc.float())
+    mi = torch.where(bad, nan, ((0.0 - a) - hc).float())
+    logp = torch.where(bad | ~valid, nan, torch.log(qg))
+    return ent, h_mix, h_cond, mi, logp
+
+
 class EvidenceMaps:
     """VAR.evidence_maps' result: where in the image the evidence for each class sits.  With m[n, k, y, x] the map of class k (the selected
     scales' per-token scores, each resampled bilinearly to size x size and weighted by its share of the selected tokens):
@@ -981,6 +1064,57 @@ class VAR(nn.Module):
                     c, m = distance_profile_torch(z[k0:k0 + max_rows, b:e].float(), gt[i, b:e], d[b:e], e32, min_prob)
                     count[i, k0:k0 + max_rows, si], mass[i, k0:k0 + max_rows, si] = c, m
         return DistanceProfile(count, mass, e32.to(dev), min_prob, self.patch_nums)
+
+    @torch.no_grad()
+    def class_information(self, gt_tokens, label, cfg: float = 0.0, max_rows: int = 64, *, prior=None) -> ClassInformation:
+        """Per token, how much the class changes the model's prediction -> ClassInformation (see there): the mutual information between the
+        class and the next token under the teacher-forced prefix,
+          I(c ; x_t | x_<t) = H(sum_k pi_k p_k) - sum_k pi_k H(p_k),
+        the expected information a token carries about the class.  It needs no label of the image, lies in [0, H(pi)] and can be compared
+        across scales, images and model depths; its (N, L) map feeds evidence_maps (ClassInformation.mi_map).
+        gt_tokens, label, cfg and max_rows mean exactly what they mean in token_scores (same validation, packing and guided z); at most 16384
+        candidates per image.  prior: None (uniform, 1 / K) or (K,) / (N, K) non-negative finite weights whose rows sum to 1 within 1e-6; they
+        are rounded to fp32 and used as given (not renormalised).  A bad prior raises ValueError.
+        On the HIP path (the conditions of token_log_likelihood) each scale's logits are reduced by varhip_class_mix_f32 behind the head: the
+        (K, L, V) softmax tensor the definition asks for is never made.  When a pass holds all K classes of its images the mixture stays in
+        LDS; otherwise (K + [cfg > 0] > max_rows) the chunks add into an (L, V) int64 accumulator per image and varhip_class_mix_finish_f32
+        finalises each scale.  Elsewhere class_information_torch runs on the per-image logits, at most max_rows class rows at a time."""
+        gt, lab, cfg = self._scoring_args(gt_tokens, label, cfg, max_rows)
+        N, K = lab.shape
+        if K > CLASS_INFO_MAX_CAND:
+            raise ValueError(f'class_information takes at most {CLASS_INFO_MAX_CAND} candidates per image, got {K}')
+        pri = self._prior_arg(prior, N, K).to(gt.device)
+        if self._scoring_on_hip(gt):
+            r = self.engine().class_information(gt, lab, cfg, int(max_rows), pri)
+            return ClassInformation(r['entropy'], r['h_mix'], r['h_cond'], r['mi'], r['logp_mix'], pri, self.patch_nums)
+        dev = gt.device
+        ent = torch.empty(N, K, self.L, dtype=torch.float32, device=dev)
+        per_tok = [torch.empty(N, self.L, dtype=torch.float32, device=dev) for _ in range(4)]
+        for i, z in self._teacher_forced_torch(gt, lab, cfg, max_rows):
+            for b, e in self.begin_ends:
+                r = class_information_torch(z[:, b:e].float(), gt[i, b:e], pri[i], int(max_rows))
+                ent[i, :, b:e] = r[0]
+                for dst, src in zip(per_tok, r[1:]):
+                    dst[i, b:e] = src
+        return ClassInformation(ent, *per_tok, pri, self.patch_nums)
+
+    @staticmethod
+    def _prior_arg(prior, N: int, K: int) -> torch.Tensor:
+        """the prior of class_information -> (N, K) fp32, contiguous, on the CPU or where it was given"""
+        if prior is None:
+            return torch.full((N, K), float(np.float32(1.0 / K)), dtype=torch.float32)
+        try:
+            p = torch.as_tensor(prior)
+        except Exception:
+            raise ValueError(f'prior must be None or ({K},) / ({N}, {K}) numbers') from None
+        if p.dtype == torch.bool or p.is_complex() or p.dim() not in (1, 2) or p.shape[-1] != K or (p.dim() == 2 and p.shape[0] != N):
+            raise ValueError(f'prior must be None or ({K},) / ({N}, {K}) numbers')
+        p64 = p.detach().double()
+        if p64.dim() == 1:
+            p64 = p64.unsqueeze(0).expand(N, K)
+        if not bool(torch.isfinite(p64).all()) or bool((p64 < 0).any()) or bool(((p64.sum(-1) - 1).abs() > 1e-6).any()):
+            raise ValueError('prior must be finite and non-negative and every row must sum to 1 within 1e-6')
+        return p64.float().contiguous()
 
     def evidence_maps(self, scores, *, scales=None, size: int = 256, image=None, image_range: str = 'pm1', alpha: float = 0.5,
                       return_maps: bool = False, check: bool = True) -> EvidenceMaps:
