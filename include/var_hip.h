@@ -447,6 +447,41 @@ int varhip_class_mix_finish_host_f32(const int64_t* mix_q, const int64_t* hcond_
                                      int64_t ld_gt, int images, int l, int V, float* h_mix, float* h_cond, float* mi, float* logp_mix,
                                      int64_t ld_out);
 
+/* ---- attention mass by key scale (VAR.attention_profile) -------------------------------------------------------------------------------------
+ * What the attention of reference basic_var.py:107-117 does with its probability: for every query of the current scale, how much of
+ * softmax_j(q . k_j) falls on the keys of each scale and on the query's own neighbourhood, reduced where the scores are made: the (L, L) matrix
+ * (depth x H x L^2 floats per image) never exists.  q: [B2][l][H*64] as varhip_gemm_qkv_f32 leaves it (normalised and scaled), kcache:
+ * [B2][H][Lmax][64], keys 0 .. curL-1 valid, exactly the operands of varhip_attn_cached_f32.  The queries are the last l = pn^2 positions of the
+ * cache: query t sits at key index curL - l + t, at grid position (t / pn, t % pn).  ends: a HOST array of S1 entries, ends[i] = one past the last
+ * key of key scale i (strictly increasing, ends[0] >= 1, ends[S1-1] == curL, ends[S1-2] == curL - l when S1 > 1): bin i < S1 holds the keys
+ * ends[i-1] <= j < ends[i]; bin S1 ("near") holds the keys j >= curL - l whose grid position is within Chebyshev distance `radius` of the
+ * query's (the query itself included).
+ * Arithmetic contract (what makes the kernel and the host twin bit-equal, per query):
+ *   1. s_j = q . k_j: one fp32 fma chain over the 64 channels in the 4-interleaved order 0,4,1,5,2,6,3,7, 8,12,... of varhip_attn_cached_f32:
+ *      the bits that kernel sees.  Keys >= curL do not exist: whatever the cache holds there has no effect (it is not read).
+ *   2. m = max_j s_j (exact, order-free).
+ *   3. e_j = vm_exp_le0(s_j - m) (include/var_math.h), from the same s_j.
+ *   4. w_j = llrintf(e_j * 2^30): the multiply is by a power of two and exact; w_j <= 2^30, and the maximal key has w = 2^30.
+ *   5. Z = sum_j w_j and W_b = sum_{j in bin b} w_j in 64-bit integers: Z >= 2^30, and curL <= 4096 keeps W <= 2^42.
+ *   6. share_b = ((uint64)W_b << 21) / (uint64)Z, truncating (2^42 * 2^21 = 2^63 fits).  SHARE_ONE = 2^21; the bins b < S1 of a query sum to
+ *      a value in [2^21 - S1, 2^21].
+ *   7. A query with a NaN score — or with a maximum that is not finite, whose s_j - m is NaN at the maximal key — writes -1 to its S1 + 1 tokens
+ *      entries, adds nothing to share_sum and adds 1 to nan_count.
+ *   8. The sums over queries are integer adds (LDS, then one 64-bit global atomic per row, head, bin and workgroup): bit-equal across launch
+ *      geometries and arrival orders.
+ * Outputs: share_sum[b * ld_row + h * ld_head + bin] += sum over the l queries of share_bin, bins 0 .. S1; nan_count[b * H + h] += NaN queries;
+ * the caller zeroes both (a second call adds again).  tokens (NULL: not written): tokens[b * ld_tok_row + h * ld_tok_head + t * (S1 + 1) + bin]
+ * = share_bin of query t, plainly overwritten.  Calls that add into the same sums may run in any order.
+ * VARHIP_EINVAL before any launch: a NULL q / kcache / ends / share_sum / nan_count, a size <= 0, curL > Lmax, curL > 4096, l != pn * pn,
+ * l > curL, S1 outside [1, 16], ends not as above, radius < 0, q or kcache not 16-byte aligned, B2 or H above 65535. */
+int varhip_attn_profile_f32(const float* q, const float* kcache, int B2, int l, int H, int curL, int Lmax, const int32_t* ends, int S1,
+                            int pn, int radius, int64_t* share_sum, int64_t ld_row, int64_t ld_head, int32_t* nan_count,
+                            int32_t* tokens, int64_t ld_tok_row, int64_t ld_tok_head, varhip_stream_t stream);
+/* the host twin: plain host code (no GPU), host pointers, the contract above query by query: the kernel's bits */
+int varhip_attn_profile_host_f32(const float* q, const float* kcache, int B2, int l, int H, int curL, int Lmax, const int32_t* ends, int S1,
+                                 int pn, int radius, int64_t* share_sum, int64_t ld_row, int64_t ld_head, int32_t* nan_count,
+                                 int32_t* tokens, int64_t ld_tok_row, int64_t ld_tok_head);
+
 /* ---- per-pixel class evidence (VAR.evidence_maps; fork create_heatmaps_for_classes of eval_prob.py / var_analysis.py / inpainting.py /
  * smoothing.py / var_size_analysis.py: per class and scale one bilinear F.interpolate, K full-size maps, matplotlib on the CPU) -----------
  * scores: per-token class scores, class c of image i at scores[i * ld_img + c * ld_cls + token].  The nscales selected scales are HOST arrays
@@ -738,8 +773,9 @@ int varhip_cast_bf16_to_f32(const void* in, float* out, int64_t n, varhip_stream
  * 13 conv16_small (every other fp16 conv kernel), 14 attn16; 15 conv_wino (k_conv3x3_wino, the fused Winograd F(2x2,3x3) conv; its FLOPs
  * are the executed multiplies, 16 per 2x2 tile, so it is not priced as a direct conv).  Families 0, 1, 10 and 12 each map to exactly
  * one kernel symbol and 15 to the instantiations of one template (k_conv3x3_wino<residual, partials, 0>), so their averages can be checked
- * against a rocprofv3 kernel trace.  Returns the number of families. */
-#define VARHIP_NFAM 16
+ * against a rocprofv3 kernel trace.  16 attn_profile (k_attn_profile, varhip_attn_profile_f32: FLOPs = both QK^T passes).  Returns the number of
+ * families. */
+#define VARHIP_NFAM 17
 int varhip_timing_enable(int on);
 /* restrict the timing to the families whose bit is set (default: all).  Every timed launch costs two event records on the stream —
  * about 2 % of a sampling call when all ~3000 launches are timed; bench.py times only what its roofline object reports. */

@@ -96,6 +96,7 @@ SIGNATURES_HIP_ONLY = {
     'token_eval_f32':    [P, P, L, I, I, I, P, P, P, P, L],             # pinned against float64, torch.argmax and the rank's definition (tests/test_evaluate_gpu.py)
     'eval_reduce_f32':   [P, P, P, P, L, I, P, I, I, P, P, P, P],       # pinned against numpy float64 sums and torch.bincount; begin_S1 is a host array
     'sample_stats_f32':  [P, P, P, I, I, I, D, P, P, P, P, P, P, L],    # pinned against its host twin, token_loglik_f32 and float64 (tests/test_sample_stats_gpu.py)
+    'attn_profile_f32':  [P, P, I, I, I, I, I, P, I, I, I, P, L, L, P, P, L, L],      # pinned bit for bit against its host twin (tests/test_attention_profile_gpu.py); ends is a host array
     'evidence_reduce_f32': [P, L, L, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P],   # pinned bit for bit against evidence_maps_torch (tests/test_evidence_gpu.py); pn, begin, w are host arrays
     'evidence_overlay_u8': [P, L, L, I, I, I, P, P, P, P, P, I, P, P, P, I, D, P],   # pinned byte for byte against evidence_maps_torch
 }
@@ -108,6 +109,7 @@ SIGNATURES_HOST = {
     'sample_stats_host_f32': [P, P, P, I, I, I, D, P, P, P, P, P, P, L],   # pinned against float64 (tests/test_sample_stats_cpu.py)
     'class_mix_host_f32': [P, P, L, I, I, I, I, I, F, F, P, L, P, L, L, P, P, P, L, P, P, P, P, L],   # pinned against float64 (tests/test_class_information_cpu.py)
     'class_mix_finish_host_f32': [P, P, P, L, P, L, I, I, I, P, P, P, P, L],
+    'attn_profile_host_f32': [P, P, I, I, I, I, I, P, I, I, I, P, L, L, P, P, L, L],   # pinned against float64 (tests/test_attention_profile_cpu.py)
     'evidence_jet_host': [P],                                        # pinned against matplotlib's 'jet' (tests/test_evidence_cpu.py)
 }
 

@@ -61,6 +61,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define VH_FAM_ATTN16 14
 // the fused Winograd F(2x2,3x3) convolution (winograd.hip): FLOPs counted as executed (16 multiplies per 2x2 tile), not as a direct conv
 #define VH_FAM_CONV_WINO 15
+// the attention profile (attnprofile.hip): its own family, so that its time can be read next to k_attn_cached's ("attn")
+#define VH_FAM_ATTN_PROFILE 16
 
 // ---- timing table (timing.cpp) ------------------------------------------------------------------------------------
 int vh_timing_on(int fam);

@@ -1491,10 +1491,12 @@ class SamplingEngine(_Engine):
             self._ws_tf[(R, sid, self.precision, Le)] = ws
         return ws
 
-    def _tf_scales(self, ws: dict, lab: torch.Tensor, xin: Optional[torch.Tensor], R: int, last: Optional[int] = None, head_from: int = 0):
+    def _tf_scales(self, ws: dict, lab: torch.Tensor, xin: Optional[torch.Tensor], R: int, last: Optional[int] = None, head_from: int = 0,
+                   after_block=None):
         """the teacher-forced loop over R rows (labels `lab`, next-scale inputs `xin` (R, >= L_e - first_l, Cvae)) through scale `last` (default:
         the last; ws must reach it): yields (si, cur, l) after the head of each scale si >= head_from has left that scale's fp32 logits in
-        ws['lg'][:R * l] (row r, token t at r * l + t); scales below head_from only fill the KV caches"""
+        ws['lg'][:R * l] (row r, token t at r * l + t); scales below head_from only fill the KV caches.  after_block(bi, si, cur, l), if given,
+        runs right behind every block: ws['q'] then holds that block's queries [R * l][C], normalised and scaled, ws['kc'][bi] the keys 0 .. cur + l - 1"""
         var, w = self.var, self.w
         C, Cv = var.C, var.Cvae
         self._prologue(ws, lab, R)
@@ -1508,6 +1510,8 @@ class SamplingEngine(_Engine):
                 hip.call('word_embed_f32', seg, w['word_w'], w['word_b'], ws['lvl_pos'][cur:], x, R, l, C, Cv)
             for bi, blk in enumerate(w['blocks']):
                 self.block(blk, ws, bi, x, x2, R, l, cur, ws['Lmax'])
+                if after_block is not None:
+                    after_block(bi, si, cur, l)
             if si >= head_from:
                 self.head(x, ws['hn'], ws['xn'], ws['lg'], M, l)
                 yield si, cur, l
@@ -1698,6 +1702,71 @@ class SamplingEngine(_Engine):
         hip.call('eval_reduce_f32', out['nll_BL'], out['smooth_BL'], out['pred_BL'], out['rank_BL'], L, N, begins, S, V,
                  out['nll_S'], out['smooth_S'], out['correct_S'], out['pred_hist_V'])
         return out
+
+    # -- attention mass by key scale (VAR.attention_profile) ----------------------------------------------------------------------------
+    ATTN_PROFILE_MAX_L, ATTN_PROFILE_MAX_S = 4096, 16          # the limits of varhip_attn_profile_f32 (include/var_hip.h)
+
+    @torch.no_grad()
+    def attention_profile(self, gt_tokens: torch.Tensor, label_N: torch.Tensor, radius: int, layers: tuple, max_rows: int,
+                          return_tokens: bool = False, _tap=None) -> dict:
+        """VAR.attention_profile on the HIP path -> dict(share_q (N, D', H, S, S + 1) int64, nan_queries (N, D', H, S) int32, tokens (N, D', H, L,
+        S + 1) int32 or None).  gt_tokens (N, L) int64, label_N (N,) int64, layers: the selected block indices, ascending; all validated by the
+        caller.  The images run teacher-forced in passes of at most max_rows rows, one row per image (no CFG rows); the head is skipped (no
+        logits are needed); behind every selected block of every scale varhip_attn_profile_f32 reduces that block's queries (ws['q']) against
+        its key cache into the (layer, query scale) slice of the outputs, zeroed here once.  The kernel keeps a scale's near bin behind its
+        last key bin (index si + 1); it is moved to index S at the end.  _tap (tests): called after a stream sync with clones of the queries
+        and of the keys 0 .. cur + l - 1 and (bi, si, cur, l) for every launch."""
+        var = self.var
+        if self.resolve_precision() != 'f32':
+            raise ValueError(f'attention_profile runs in f32: the {self.precision} workspaces hold 16-bit queries and keys (set_hip_precision(\'f32\'), '
+                             f'no 16-bit autocast)')
+        self.refresh()
+        self._wait_ready()
+        dev = var.pos_start.device
+        L, S, H = var.L, len(var.patch_nums), var.num_heads
+        if L > self.ATTN_PROFILE_MAX_L or S > self.ATTN_PROFILE_MAX_S:
+            raise ValueError(f'attention_profile takes at most {self.ATTN_PROFILE_MAX_L} tokens and {self.ATTN_PROFILE_MAX_S} scales, got {L} and {S}')
+        gt = gt_tokens.to(dev, torch.int64).contiguous()
+        lab = label_N.to(dev, torch.int64).contiguous()
+        self._check_labels(lab)
+        N, Dn = gt.shape[0], len(layers)
+        slot = {bi: d for d, bi in enumerate(layers)}
+        xin = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in var.begin_ends]).to(dev, torch.float32)
+        share = torch.zeros(N, Dn, H, S, S + 1, dtype=torch.int64, device=dev)
+        nanq = torch.zeros(N, Dn, H, S, dtype=torch.int32, device=dev)
+        tokens = torch.zeros(N, Dn, H, L, S + 1, dtype=torch.int32, device=dev) if return_tokens else None
+        ends = [torch.tensor([e for _, e in var.begin_ends[:si + 1]], dtype=torch.int32) for si in range(S)]      # host arrays: the launcher copies them
+        rpp = min(int(max_rows), N)
+        ws = self._tf_workspace(rpp)                                  # sized once: a shorter last pass uses a prefix
+        for i0 in range(0, N, rpp):
+            R = min(rpp, N - i0)
+            nan_pass = torch.zeros(Dn, S, R, H, dtype=torch.int32, device=dev)      # the kernel's nan_count is dense [row][head]
+
+            def tap(bi, si, cur, l):
+                d = slot.get(bi)
+                if d is None:
+                    return
+                S1, pn = si + 1, var.patch_nums[si]
+                tok = torch.empty(R, H, l, S1 + 1, dtype=torch.int32, device=dev) if return_tokens else None
+                hip.call('attn_profile_f32', ws['q'], ws['kc'][bi], R, l, H, cur + l, ws['Lmax'], ends[si], S1, pn, int(radius),
+                         share[i0:, d, :, si], Dn * H * S * (S + 1), S * (S + 1), nan_pass[d, si], tok, H * l * (S1 + 1), l * (S1 + 1))
+                if return_tokens:
+                    dst = tokens[i0:i0 + R, d, :, cur:cur + l]
+                    dst[..., :S1] = tok[..., :S1]
+                    dst[..., S] = tok[..., S1]
+                    if S1 < S:
+                        dst[..., S1:S] = -(tok[..., :1] < 0).to(torch.int32)           # a NaN query: -1 in every entry
+                if _tap is not None:
+                    torch.cuda.current_stream().synchronize()
+                    _tap(ws['q'][:R * l].clone(), ws['kc'][bi][:R, :, :cur + l].clone(), (bi, si, cur, l))
+
+            for _ in self._tf_scales(ws, lab[i0:i0 + R].contiguous(), xin[i0:i0 + R].contiguous(), R, head_from=S, after_block=tap):
+                pass
+            nanq[i0:i0 + R] = nan_pass.permute(2, 0, 3, 1)
+        for si in range(S - 1):                                       # near bin: from behind the scale's last key bin to index S
+            share[..., si, S] = share[..., si, si + 1]
+            share[..., si, si + 1] = 0
+        return dict(share_q=share, nan_queries=nanq, tokens=tokens)
 
     # -- zero-shot classification with per-scale pruning (VAR.classify) -------------------------------------------------------------
     CLASSIFY_MAX_CAND = 16384          # varhip_class_select_f32 stages a stage's totals in LDS

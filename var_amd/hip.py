@@ -116,7 +116,7 @@ def vq_stats_blocks(n: int) -> int:
 
 
 # ---- timing table --------------------------------------------------------------------------------------------------
-NFAM = 16            # VARHIP_NFAM of include/var_hip.h
+NFAM = 17            # VARHIP_NFAM of include/var_hip.h
 
 
 def timing_enable(on: bool, families=None):

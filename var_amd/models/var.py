@@ -328,6 +328,107 @@ def class_information_torch(z: torch.Tensor, gt: torch.Tensor, prior: torch.Tens
     return ent, h_mix, h_cond, mi, logp
 
 
+SHARE_ONE = 2 ** 21                  # the fixed point of an attention share: floor(W_bin * 2^21 / Z)
+ATTN_W_ONE = float(2 ** 30)          # ... and of a softmax numerator: rint(exp(s - max s) * 2^30)
+
+
+class AttentionProfile:
+    """VAR.attention_profile's result: where the attention of every selected block goes, by scale, on the model's device.
+      share_q      (N, D', H, S, S + 1) int64 [n, d, h, sq, b]: the sum over the pn[sq]^2 queries of scale sq of each query's fixed-point share
+                   (units of 2^-21 = 1 / SHARE_ONE, truncated) on bin b.  Bins 0 .. S-1: the key's scale (0 above sq: block-causal); bin S, "near":
+                   the keys of the query's own scale whose grid position is within Chebyshev distance `radius` of the query's, itself included
+      nan_queries  (N, D', H, S) int32: queries with a NaN score (or no finite maximum); they add nothing to share_q
+      tokens       None, or (N, D', H, L, S + 1) int32 with return_tokens=True: every query's own shares, -1 in every entry of a NaN query
+      layers (the D' block indices), radius, patch_nums
+    Integer sums of integer shares: the same bits whatever the packing (max_rows), the batch neighbours or the call history."""
+    __slots__ = ('share_q', 'nan_queries', 'tokens', 'patch_nums', 'radius', 'layers')
+
+    def __init__(self, share_q, nan_queries, tokens, patch_nums, radius, layers):
+        self.share_q, self.nan_queries, self.tokens = share_q, nan_queries, tokens
+        self.patch_nums, self.radius, self.layers = tuple(patch_nums), int(radius), tuple(layers)
+
+    def _per_unit(self, x: torch.Tensor) -> torch.Tensor:
+        """x (N, D', H, S, ...) int64 sums over a scale's queries -> float64 means over the queries that counted (NaN where none did)"""
+        n = torch.tensor([pn * pn for pn in self.patch_nums], dtype=torch.float64, device=x.device) - self.nan_queries.double()
+        n = n.view(*n.shape, *([1] * (x.dim() - n.dim())))
+        return x.double() / (SHARE_ONE * n)
+
+    def scale_matrix(self) -> torch.Tensor:
+        """(N, D', H, S, S) float64 [.., sq, sk]: the mean share of a query of scale sq on the keys of scale sk; a row sums to 1 up to the
+        truncation (at most S / SHARE_ONE below)"""
+        return self._per_unit(self.share_q[..., :-1])
+
+    def near(self) -> torch.Tensor:
+        """(N, D', H, S) float64: the mean share on the query's own neighbourhood (radius)"""
+        return self._per_unit(self.share_q[..., -1])
+
+    def own_scale(self) -> torch.Tensor:
+        """(N, D', H, S) float64: the mean share on the query's own scale, the diagonal of scale_matrix()"""
+        return self._per_unit(torch.diagonal(self.share_q[..., :-1], dim1=-2, dim2=-1))
+
+    def per_layer(self) -> dict:
+        """{'scale_matrix': (N, D', S, S), 'near': (N, D', S), 'own_scale': (N, D', S)} float64: the means over the heads"""
+        return dict(scale_matrix=self.scale_matrix().mean(2), near=self.near().mean(2), own_scale=self.own_scale().mean(2))
+
+    def __repr__(self):
+        N, D, H, S = self.nan_queries.shape
+        return f'AttentionProfile(images={N}, layers={D}, heads={H}, scales={S}, radius={self.radius})'
+
+
+def attention_profile_torch(var, gt: torch.Tensor, label: torch.Tensor, radius: int, layers: tuple, return_tokens: bool = False):
+    """VAR.attention_profile's definitions in PyTorch on the module stack (CPU models, non-HIP tensors; the arithmetic follows the parameters' dtype).
+    gt (N, L) tokens, label (N,) labels, layers: block indices, ascending -> (share_q, nan_queries, tokens or None) as in AttentionProfile.
+    Per block the modules produce q and k (SelfAttention._heads, then the l2 norm and temperature, or `scale`); the scores take the block-causal
+    mask, and from there float64: w = rint(exp(s - max s) * 2^30), integer sums per key scale and over the near keys, share = floor(W * 2^21 / Z),
+    integer sums over a scale's queries (include/var_hip.h, varhip_attn_profile_f32: the same quantisation, fed by PyTorch's q and k).  One image
+    at a time, so an image's integers do not depend on its batch neighbours."""
+    dev = gt.device
+    N, L, S, H = gt.shape[0], var.L, len(var.patch_nums), var.num_heads
+    dt = var.pos_start.dtype
+    mask = var.attn_bias_for_masking[:, :, :L, :L].to(dt)
+    scale_of = var.lvl_1L[0, :L].to(dev)                                                       # (L,) the scale of every position
+    seg = torch.nn.functional.one_hot(scale_of, S).double()                                    # (L, S) key -> its scale bin
+    pn_of = torch.tensor([pn for pn in var.patch_nums for _ in range(pn * pn)], device=dev)
+    pos = torch.cat([torch.arange(pn * pn, device=dev) for pn in var.patch_nums])
+    py, px = pos // pn_of, pos % pn_of
+    near = ((scale_of[:, None] == scale_of[None, :]) & ((py[:, None] - py[None, :]).abs() <= radius) & ((px[:, None] - px[None, :]).abs() <= radius)).double()
+    slot = {bi: d for d, bi in enumerate(layers)}
+    share = torch.zeros(N, len(layers), H, S, S + 1, dtype=torch.int64, device=dev)
+    nanq = torch.zeros(N, len(layers), H, S, dtype=torch.int32, device=dev)
+    tokens = torch.zeros(N, len(layers), H, L, S + 1, dtype=torch.int32, device=dev) if return_tokens else None
+    for n in range(N):
+        cond = var.class_emb(label[n:n + 1])
+        sos = cond.unsqueeze(1).expand(1, var.first_l, -1) + var.pos_start.expand(1, var.first_l, -1)
+        x_in = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[n:n + 1, b:e] for b, e in var.begin_ends])
+        x = torch.cat((sos, var.word_embed(x_in.to(dt))), dim=1) if L > var.first_l else sos
+        x = x + var.lvl_embed(var.lvl_1L[:, :L].expand(1, -1)) + var.pos_1LC[:, :L]
+        cond_or_gss = var.shared_ada_lin(cond)
+        for bi, blk in enumerate(var.blocks):
+            d = slot.get(bi)
+            if d is not None:
+                at = blk.attn
+                _, _, scale1, _, shift1, _ = blk._six(cond_or_gss)
+                q, k, _ = at._heads(blk.ln_wo_grad(x) * (scale1 + 1) + shift1)
+                if at.attn_l2_norm:
+                    q = torch.nn.functional.normalize(q, dim=-1) * at.scale_mul_1H11.clamp_max(at.max_scale_mul).exp()
+                    k = torch.nn.functional.normalize(k, dim=-1)
+                sc = (q @ k.transpose(-1, -2)) * at.scale + mask                                 # (1, H, L, L) in the modules' dtype
+                sc = sc[0].double()
+                bad = torch.isnan(sc).any(-1) | ~torch.isfinite(sc.max(-1).values)               # (H, L)
+                w = torch.round(torch.exp(sc - sc.max(-1, keepdim=True).values) * ATTN_W_ONE)
+                w = torch.where(torch.isnan(w), torch.zeros_like(w), w)                          # float64 integers <= 2^30: sums below 2^53 are exact
+                Wb = torch.cat((w @ seg, (w * near).sum(-1, keepdim=True)), -1).to(torch.int64)  # (H, L, S + 1)
+                Z = Wb[..., :S].sum(-1, keepdim=True).clamp_min(1)
+                tok = torch.div(Wb << 21, Z, rounding_mode='floor')
+                good = (~bad).to(torch.int64)
+                share[n, d].index_add_(1, scale_of, tok * good.unsqueeze(-1))                    # integer sums over the queries of a scale
+                nanq[n, d].index_add_(1, scale_of, bad.to(torch.int32))
+                if return_tokens:
+                    tokens[n, d] = torch.where(bad.unsqueeze(-1), torch.full_like(tok, -1), tok).to(torch.int32)
+            x = blk(x=x, cond_BD=cond_or_gss, attn_bias=mask)
+    return share, nanq, tokens
+
+
 class EvidenceMaps:
     """VAR.evidence_maps' result: where in the image the evidence for each class sits.  With m[n, k, y, x] the map of class k (the selected
     scales' per-token scores, each resampled bilinearly to size x size and weighted by its share of the selected tokens):
@@ -1097,6 +1198,56 @@ class VAR(nn.Module):
                 for dst, src in zip(per_tok, r[1:]):
                     dst[i, b:e] = src
         return ClassInformation(ent, *per_tok, pri, self.patch_nums)
+
+    @torch.no_grad()
+    def attention_profile(self, gt_tokens, label, *, radius: int = 1, layers=None, max_rows: int = 64, return_tokens: bool = False) -> AttentionProfile:
+        """What the attention layers do with their probability, by scale -> AttentionProfile (integer sums; see there).
+
+        For every selected block, head and query: how much of softmax(q . k) goes to the keys of the query's own scale, how much to each earlier
+        scale, and how much to the query's own neighbourhood (grid positions within Chebyshev distance `radius`).  These are the observations
+        behind KV-cache pruning and scale skipping; taking them from softmax(QK^T) of reference basic_var.py:107-117 needs depth x H x L^2 floats
+        per image.  gt_tokens: (N, L) integer tokens, teacher-forced as in token_log_likelihood; label: an int or (N,) class ids in [0,
+        num_classes] (num_classes: unconditional), one condition per image; layers: None (all blocks) or strictly increasing block indices;
+        radius: an int >= 0; max_rows bounds the images of one transformer pass; return_tokens also keeps every query's own shares.
+        On the HIP path (the conditions of token_log_likelihood; f32 only: under a 16-bit precision ValueError) the blocks run on the KV cache
+        and varhip_attn_profile_f32 reduces each selected block's queries against its key cache right behind it, with the scores of the
+        sampler's attention kernel bit for bit: no (L, L) tensor is made, the head is skipped.  Elsewhere attention_profile_torch runs the module
+        stack with the block-causal mask.  Both apply the same quantisation, so the integers agree up to what the two q / k differ by."""
+        dev = self.lvl_1L.device
+        gt = self._token_shape(gt_tokens)
+        N = gt.shape[0]
+        if isinstance(label, (int, np.integer)) and not isinstance(label, bool):
+            lab = torch.full((N,), int(label), dtype=torch.int64)
+        else:
+            lab = torch.as_tensor(label)
+        if lab.dim() != 1 or lab.shape[0] != N or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
+            raise ValueError(f'label must be an int or (N,) integer class ids, N = {N}')
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or radius < 0:
+            raise ValueError('radius must be an integer >= 0')
+        if isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 1:
+            raise ValueError('max_rows must be an integer >= 1')
+        if layers is None:
+            layers = tuple(range(self.depth))
+        else:
+            try:
+                layers = tuple(layers)
+            except TypeError:
+                raise ValueError('layers must be None or a strictly increasing sequence of block indices') from None
+            if not layers or any(isinstance(b, bool) or not isinstance(b, (int, np.integer)) for b in layers) \
+                    or any(b < 0 or b >= self.depth for b in layers) or any(b1 <= b0 for b0, b1 in zip(layers, layers[1:])):
+                raise ValueError(f'layers must be None or a strictly increasing sequence of block indices in [0, {self.depth})')
+            layers = tuple(int(b) for b in layers)
+        self._token_label_range(gt, lab)
+        gt, lab = gt.to(dev, torch.int64), lab.to(dev, torch.int64)
+        radius = int(radius)
+        r_eff = min(radius, max(self.patch_nums))                  # (beyond the largest grid every radius means the whole scale)
+        if self._scoring_on_hip(gt):
+            r = self.engine().attention_profile(gt, lab, r_eff, layers, int(max_rows), bool(return_tokens))
+            return AttentionProfile(r['share_q'], r['nan_queries'], r['tokens'], self.patch_nums, radius, layers)
+        if self.prog_si >= 0:
+            raise ValueError('attention_profile covers every scale: prog_si must be < 0')
+        share, nanq, tokens = attention_profile_torch(self, gt, lab, r_eff, layers, bool(return_tokens))
+        return AttentionProfile(share, nanq, tokens, self.patch_nums, radius, layers)
 
     @staticmethod
     def _prior_arg(prior, N: int, K: int) -> torch.Tensor:
