@@ -529,6 +529,20 @@ int varhip_evidence_jet_host(uint8_t* out);
 int varhip_class_select_f32(const float* tokens, int64_t ld_img, int64_t ld_cls, int images, int cand, int t0, int t1, double* totals,
                             int keep, int32_t* kept, varhip_stream_t stream);
 
+/* ---- KV-cache row compaction (VAR.sample_best_of_pruned: the survivors of a prune boundary move to a smaller batch) ----
+ * For every buffer i < nbuf:  dst[i][r][h][t][:] = src[i][idx[r]][h][t][:]  for r < rows_out, h < H, t < len, on caches laid out
+ * [rows][H][Lmax][64] as SamplingEngine.workspace allocates kc[bi] / vc[bi]: src[i] has rows_src rows, dst[i] rows_dst, both H heads of Lmax
+ * tokens of 64 elements of elem_bytes (4: the f32 mode, 2: f16 / bf16 caches).  Nothing else is written: tokens t >= len and rows >= rows_out of
+ * dst keep their bytes.  src / dst: HOST arrays of nbuf device pointers (each 16-byte aligned), copied into the kernel's argument block like
+ * varhip_edit_keep_u8's patch_nums: one launch for up to 96 buffers (the K and V caches of 48 blocks; d36 has 72), a longer list is cut into launches
+ * of 96.  idx: a DEVICE array of rows_out int32 source rows, not read by the host; duplicates are allowed, and an entry outside [0, rows_src)
+ * leaves its destination row unwritten.  Plain 16-byte vector loads and stores.
+ * VARHIP_EINVAL before any launch: a NULL or misaligned pointer, nbuf / rows_src / rows_dst / H / Lmax <= 0, elem_bytes other than 2 or 4, len < 0
+ * or > Lmax, rows_out < 0 or > rows_dst, any src range sharing a byte with any dst range (ranges = the whole buffers), a row of more than 2^31
+ * 16-byte vectors.  len == 0 or rows_out == 0: success, nothing launched. */
+int varhip_kv_compact(const void* const* src, void* const* dst, int nbuf, const int32_t* idx, int rows_src, int rows_dst, int rows_out,
+                      int H, int Lmax, int len, int elem_bytes, varhip_stream_t stream);
+
 /* ---- generative zero-shot classification (VAR.classify_generative; reference eval_prob.py:466-516) ------------------------------------------
  * Greedy CFG token selection: what var.py:172-175 + helpers.py:6-19 (fork's `gen` mode calls var.inpainting(top_k=1, top_p=0), var.py:236-364)
  * reduce to without the Exp(1) draw.  Row r = b * l + j of B * l: z = (1+t)*cond - t*uncond, rounded as cfg_sample_f32 rounds it (cond =

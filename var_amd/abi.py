@@ -99,6 +99,7 @@ SIGNATURES_HIP_ONLY = {
     'attn_profile_f32':  [P, P, I, I, I, I, I, P, I, I, I, P, L, L, P, P, L, L],      # pinned bit for bit against its host twin (tests/test_attention_profile_gpu.py); ends is a host array
     'evidence_reduce_f32': [P, L, L, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P],   # pinned bit for bit against evidence_maps_torch (tests/test_evidence_gpu.py); pn, begin, w are host arrays
     'evidence_overlay_u8': [P, L, L, I, I, I, P, P, P, P, P, I, P, P, P, I, D, P],   # pinned byte for byte against evidence_maps_torch
+    'kv_compact':        [P, P, I, P, I, I, I, I, I, I, I],             # pinned byte for byte against numpy's gather (tests/test_kv_compact_gpu.py); src, dst are host arrays of pointers
 }
 
 # plain host functions of the HIP library (no stream argument, no device pointer, no GPU needed); bound by var_amd/hip.py

@@ -901,6 +901,7 @@ class SamplingEngine(_Engine):
         self.var = var
         self._ws: Dict[tuple, dict] = {}            # (batch size, HIP stream, precision) -> buffers of a call
         self._ws_tf: Dict[tuple, dict] = {}         # the same for teacher_forced_logits
+        self._ws_bop: Dict[tuple, dict] = {}        # (capacity, HIP stream, precision, stage) -> buffers of a stage of sample_best_of_pruned
         self._labels_ok = None                      # (the last label tensor whose range was checked, its version counter, address, length): one host sync saved per repeated call
 
         self.policy = 'auto' if os.environ.get('VARHIP_FOLLOW_AUTOCAST', '0') not in ('', '0') else 'f32'      # what set_precision() was given: 'f32' | 'f16' | 'bf16' | 'auto' (follow the caller's torch.autocast)
@@ -1000,8 +1001,8 @@ class SamplingEngine(_Engine):
             self.dec.flops_precision = precision                    # what the decoder's FLOP count describes from now on (bench.py prices each mode)
         if precision != 'auto' and precision != self.precision:
             self.precision = precision
-            self._ws = {k: v for k, v in self._ws.items() if k[2] == precision}          # an explicit switch releases the other modes' buffers (6-11 GB each at d16 / B=64)
-            self._ws_tf = {k: v for k, v in self._ws_tf.items() if k[2] == precision}
+            for cache in ('_ws', '_ws_tf', '_ws_bop'):                                   # an explicit switch releases the other modes' buffers (6-11 GB each at d16 / B=64)
+                setattr(self, cache, {k: v for k, v in getattr(self, cache, {}).items() if k[2] == precision})
 
     def invalidate(self):
         """forget the packed weight copies of the sampling loop and of the decoder (call after editing parameters through `.data`)"""
@@ -1018,6 +1019,12 @@ class SamplingEngine(_Engine):
         dev = self.var.pos_start.device
         if ws is not None and ws['dev'] == dev:
             return ws
+        self._ws = self._evict(self._ws, sid)
+        ws = self._ws[(B, sid, self.precision)] = self._alloc_workspace(B, dev)
+        return ws
+
+    def _alloc_workspace(self, B: int, dev) -> dict:
+        """a fresh buffer set of a sampling call of B images in the current precision (workspace() and _bop_workspace() cache them)"""
         var = self.var
         C, L, H, V, Cv, P = var.C, var.L, var.num_heads, var.V, var.Cvae, var.patch_nums[-1]
         lmax = max(p * p for p in var.patch_nums)
@@ -1025,14 +1032,27 @@ class SamplingEngine(_Engine):
         hid = var.blocks[0].ffn.fc1.weight.shape[0]
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
         act = DT16.get(self.precision, torch.float32)                           # GEMM operands and KV cache; x / x2 / logits stay fp32
-        ws = dict(dev=dev, x=e(M, C), x2=e(M, C), xn=e(M, C, dt=act), q=e(M, C, dt=act), att=e(M, C, dt=act), hid=e(M, hid, dt=act), logits=e(M, V),
-                  idx=e(B * lmax, dt=torch.int64), lvl_pos=e(L, C), cond=e(2 * B, C), cond_silu=e(2 * B, C), hn=e(2 * B, 2 * C),
-                  ada=e(var.depth, 2 * B, 6 * C) if var.shared_aln else e(2 * B, var.depth * 6 * C), shared=e(2 * B, 6 * C) if var.shared_aln else None,
-                  kc=[torch.zeros(2 * B, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
-                  vc=[torch.zeros(2 * B, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
-                  f_hat=e(B, P, P, Cv), up=e(B, P, P, Cv), pooled=e(B * lmax, Cv))
-        self._ws = self._evict(self._ws, sid)
-        self._ws[(B, sid, self.precision)] = ws
+        return dict(dev=dev, x=e(M, C), x2=e(M, C), xn=e(M, C, dt=act), q=e(M, C, dt=act), att=e(M, C, dt=act), hid=e(M, hid, dt=act), logits=e(M, V),
+                    idx=e(B * lmax, dt=torch.int64), lvl_pos=e(L, C), cond=e(2 * B, C), cond_silu=e(2 * B, C), hn=e(2 * B, 2 * C),
+                    ada=e(var.depth, 2 * B, 6 * C) if var.shared_aln else e(2 * B, var.depth * 6 * C), shared=e(2 * B, 6 * C) if var.shared_aln else None,
+                    kc=[torch.zeros(2 * B, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
+                    vc=[torch.zeros(2 * B, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
+                    f_hat=e(B, P, P, Cv), up=e(B, P, P, Cv), pooled=e(B * lmax, Cv))
+
+    def _bop_workspace(self, cap: int, stage: int) -> dict:
+        """the buffer set of stage `stage` of sample_best_of_pruned, for up to `cap` candidates (a chunk of fewer uses a prefix of every buffer:
+        all of them are row-major in the candidate).  A cache of its own, keyed (capacity, HIP stream, precision, stage): one capacity resident per
+        (stream, precision, stage), so the stages evict neither one another nor the plain calls' workspace, and a repeated call allocates nothing."""
+        sid = int(torch.cuda.current_stream().cuda_stream)
+        dev = self.var.pos_start.device
+        key = (cap, sid, self.precision, stage)
+        ws = self._ws_bop.get(key)
+        if ws is None or ws['dev'] != dev:
+            self._ws_bop = {k: v for k, v in self._ws_bop.items() if k[1:] != key[1:]}          # (before allocating: the replaced set is freed first)
+            while len(self._ws_bop) >= 4 * len(self.var.patch_nums):                            # other streams' and precisions' sets, oldest first
+                self._ws_bop.pop(next(iter(self._ws_bop)))
+            ws = self._ws_bop[key] = self._alloc_workspace(cap, dev)
+            ws['masked'] = torch.empty(cap * max(p * p for p in self.var.patch_nums), self.var.V, dtype=torch.float32, device=dev)
         return ws
 
     def _evict(self, cache: dict, sid: int, slot: tuple = ()) -> dict:
@@ -1435,6 +1455,129 @@ class SamplingEngine(_Engine):
         choice = kept[:, 0].long()
         win = torch.arange(B, device=dev) * n + choice
         return {key: v.index_select(0, win) for key, v in rec.items()}, f_all.index_select(0, win), totals, choice
+
+    # -- best-of-n with per-scale pruning (VAR.sample_best_of_pruned) -------------------------------------------------------------------
+    def _bop_scales(self, ws: dict, B: int, first: int, last: int, per: dict, seeds_d: torch.Tensor, stats: dict, tokens: torch.Tensor):
+        """scales first .. last of sample_per_image(stats=..., decode=False) for the B candidates whose state sits in the first rows of ws (its
+        prologue run, ws['x'] holding scale `first`'s input, the caches scales < first): the launches of sample()'s plain per-image branch, scale
+        by scale — blocks, head, Philox fill, varhip_cfg_sample_rows_f32, varhip_sample_stats_f32, quantizer step — and next_map_f32 between
+        the stage's own scales.  Ends behind the quantizer step of `last`: what follows it is the caller's (a prune boundary, or nothing)."""
+        var, w = self.var, self.w
+        dev = ws['dev']
+        C, V, Cv, S, P = var.C, var.V, var.Cvae, len(var.patch_nums), var.patch_nums[-1]
+        x, x2, masked = ws['x'], ws['x2'], ws['masked']
+        for si in range(first, last + 1):
+            pn = var.patch_nums[si]
+            cur, l = var.begin_ends[si][0], pn * pn
+            for bi, blk in enumerate(w['blocks']):
+                self.block(blk, ws, bi, x, x2, 2 * B, l, cur)
+            self.head(x, ws['hn'], ws['xn'], ws['logits'], 2 * B * l, l)
+            idx = ws['idx'][:B * l]
+            noise = torch.empty(B * l, V, dtype=torch.float32, device=dev)
+            hip.call('exp1_philox_f32', seeds_d, B, l, V, si, 0, noise)
+            hip.call('cfg_sample_rows_f32', ws['logits'], noise, idx, masked, B, l, V, per['t'][si], per['top_k'], per['top_p'], int(per['cap']))
+            hip.call('sample_stats_f32', ws['logits'], masked, idx, B, l, V, 0.0, per['t'][si], *[stats[key][:, cur:] for key in STATS_FIELDS], var.L)
+            tokens[:, cur:cur + l].copy_(idx.view(B, l))
+            ti, tw, pw, pb, ratio = _scale_tables(w['taps'], w['phi'], si, S, pn, P, dev)
+            hip.call('quant_accum_f32', idx, w['codebook'], ti, tw, pw, pb, ratio, ws['up'], ws['f_hat'], B, pn, P, Cv)
+            if si != last:
+                hip.call('next_map_f32', ws['f_hat'], w['word_w'], w['word_b'], ws['lvl_pos'][cur + l:], x, ws['pooled'], B, P, var.patch_nums[si + 1], C, Cv)
+
+    @torch.no_grad()
+    def sample_best_of_pruned(self, label_N: torch.Tensor, seeds, cfg, top_k, top_p, n: int, by: str, schedule: list, max_images: int):
+        """sample_best_of that stops sampling a candidate at the scale where it is dropped.  N = B * n candidates, candidate c of image b at
+        position b * n + c (host sequences of length N, already spread and validated; an image's candidates share its label, cfg, top_k and
+        top_p: candidate 0's are read).  schedule: [(scale, m), ...] ascending, each m below the survivor count before it (validated by the caller).
+        One stage per boundary and a final one through the last scale; a stage runs its scales on a workspace of its own batch (_bop_scales).
+        At a boundary behind scale s, after the quantizer step: varhip_class_select_f32 adds stats[by] of the stage's scales to the float64 running
+        totals and keeps each image's best m (sample_best_of's rule); the survivors' seeds and f_hat rows are gathered, varhip_kv_compact moves
+        their conditional and unconditional rows of every block's K and V cache (tokens 0 .. end(s) - 1) into the next stage's workspace in one
+        launch, _prologue rebuilds the condition and AdaLN tables there, and next_map_f32 recomputes scale s + 1's input from the gathered f_hat.
+        Survivor positions stay on the device: the stage batches follow from the schedule alone, and every host table of a chunk is uploaded
+        before its first stage, so nothing waits for the host at a boundary.  Chunks hold max_images // n whole images.
+        -> (dict of every candidate's tokens (int64, -1 past its depth) and stats (NaN / -1 past its depth), each (B, n, L); the winners' f_hat
+        (B, Cvae, P, P); totals (B, n) float64 at each candidate's depth; depth (B, n) int64; choice (B,) int64).
+        self.best_of_work: [(last scale of the stage, candidates per image, candidate row-tokens the transformer ran in it), ...]."""
+        var = self.var
+        N, L, S, V, H = len(seeds), var.L, len(var.patch_nums), var.V, var.num_heads
+        B = N // n
+        if n > self.CLASSIFY_MAX_CAND:
+            raise ValueError(f'sample_best_of_pruned takes at most {self.CLASSIFY_MAX_CAND} candidates per image, got {n}')
+        if n > max_images:
+            raise ValueError(f'max_images = {max_images} holds no whole image of n = {n} candidates')
+        self.resolve_precision()
+        self.refresh()
+        self._wait_ready()
+        dev = var.pos_start.device
+        if label_N.dtype != torch.int64 or label_N.numel() != N:
+            raise ValueError('label_N must be an int64 tensor of B * n labels')
+        self._check_labels(label_N)
+        lab_img = label_N.to(dev).view(B, n)[:, 0].contiguous()
+        stages, first, m = [], 0, n                                 # (first scale, last scale, candidates per image, kept behind it)
+        for s, k in list(schedule) + [(S - 1, 1)]:
+            stages.append((first, s, m, k))
+            first, m = s + 1, k
+        per_chunk = min(B, max_images // n)
+        esz = 4 if self.precision == 'f32' else 2
+        rec = {key: torch.full((B, n, L), -1 if key == 'kept' else float('nan'), dtype=torch.int32 if key == 'kept' else torch.float32, device=dev)
+               for key in STATS_FIELDS}
+        rec['tokens'] = torch.full((B, n, L), -1, dtype=torch.int64, device=dev)
+        totals = torch.empty(B, n, dtype=torch.float64, device=dev)
+        depth = torch.empty(B, n, dtype=torch.int64, device=dev)
+        choice = torch.empty(B, dtype=torch.int64, device=dev)
+        f_win = torch.empty(B, var.patch_nums[-1], var.patch_nums[-1], var.Cvae, dtype=torch.float32, device=dev)
+        work = [[last, m, 0] for _, last, m, _ in stages]
+        for b0 in range(0, B, per_chunk):
+            b1 = min(B, b0 + per_chunk)
+            nb = b1 - b0
+            # every host table of the chunk, uploaded before its first stage: per stage the per-image sampler tables of its nb * m rows
+            pers = []
+            for _, _, m, _ in stages:
+                tab = per_image_tables(*[[v for v in x[b0 * n:b1 * n:n] for _ in range(m)] for x in (cfg, top_k, top_p)], S, V)
+                f64 = torch.from_numpy(np.concatenate((tab['t'].reshape(-1), tab['top_p']))).to(dev)
+                pers.append(dict(t=f64[:S * nb * m].view(S, nb * m), top_p=f64[S * nb * m:], top_k=torch.from_numpy(tab['top_k']).to(dev), cap=tab['cap']))
+            seeds_d = torch.from_numpy(np.asarray(seeds[b0 * n:b1 * n], dtype=np.int64)).to(dev)
+            img = torch.arange(nb, device=dev).view(nb, 1)
+            pos = torch.arange(n, device=dev).expand(nb, n).contiguous()        # the stage's candidates, ascending positions per image
+            tot = torch.full((nb, n), -0.0, dtype=torch.float64, device=dev)     # their running totals (-0.0 + x == x for every x)
+            prev = rows = None
+            for j, (first, last, m, keep) in enumerate(stages):
+                R = nb * m
+                ws = self._bop_workspace(per_chunk * m, j)
+                self._prologue(ws, lab_img[b0:b1].repeat_interleave(m), 2 * R)
+                if j == 0:
+                    ws['f_hat'][:R].zero_()
+                else:
+                    # the boundary's data movement: seeds and f_hat rows by torch gathers, the caches by one varhip_kv_compact launch
+                    # (conditional rows 0 .. R-1 and their unconditional twins behind them, in the old batch and in the new one)
+                    R0 = nb * stages[j - 1][2]
+                    seeds_d = seeds_d.index_select(0, rows)
+                    ws['f_hat'][:R].copy_(prev['f_hat'][:R0].index_select(0, rows))
+                    rows2 = torch.cat((rows, rows + R0)).to(torch.int32)
+                    ptr = lambda bufs: torch.tensor([t.data_ptr() for t in bufs], dtype=torch.int64)      # host arrays: the launcher copies them
+                    hip.call('kv_compact', ptr(prev['kc'] + prev['vc']), ptr(ws['kc'] + ws['vc']), 2 * var.depth, rows2, 2 * R0, ws['kc'][0].shape[0],
+                             2 * R, H, L, var.begin_ends[first][0], esz)
+                    hip.call('next_map_f32', ws['f_hat'], self.w['word_w'], self.w['word_b'], ws['lvl_pos'][var.begin_ends[first][0]:], ws['x'], ws['pooled'],
+                             R, var.patch_nums[-1], var.patch_nums[first], var.C, var.Cvae)
+                st = {key: torch.empty(R, L, dtype=torch.int32 if key == 'kept' else torch.float32, device=dev) for key in STATS_FIELDS}
+                tok = torch.empty(R, L, dtype=torch.int64, device=dev)
+                self._bop_scales(ws, R, first, last, pers[j], seeds_d, st, tok)
+                t0, t1 = var.begin_ends[first][0], var.begin_ends[last][1]
+                rec['tokens'][b0:b1][img, pos, t0:t1] = tok.view(nb, m, L)[:, :, t0:t1]
+                for key in STATS_FIELDS:
+                    rec[key][b0:b1][img, pos, t0:t1] = st[key].view(nb, m, L)[:, :, t0:t1]
+                kept = torch.empty(nb, min(keep, m), dtype=torch.int32, device=dev)
+                hip.call('class_select_f32', st[by], m * L, L, nb, m, t0, t1, tot, keep, kept)
+                totals[b0:b1][img, pos] = tot
+                depth[b0:b1][img, pos] = last
+                work[j][2] += R * (t1 - t0)
+                kept = kept.long()
+                rows = (img * m + kept).view(-1)                                # the survivors' rows in this stage's batch, ascending per image
+                pos, tot, prev = pos.gather(1, kept), tot.gather(1, kept).contiguous(), ws
+            choice[b0:b1] = pos[:, 0]
+            f_win[b0:b1] = prev['f_hat'][:R].index_select(0, rows)
+        self.best_of_work = [tuple(x) for x in work]
+        return rec, f_win.permute(0, 3, 1, 2).contiguous(), totals, depth, choice
 
     @torch.no_grad()
     def decode_f_hat(self, f_hat: torch.Tensor) -> torch.Tensor:

@@ -66,6 +66,41 @@ class ClassifyResult(NamedTuple):
     tokens: torch.Tensor
 
 
+class BestOfResult(NamedTuple):
+    """VAR.sample_best_of_pruned's result: images (B, 3, H, W) or None, winners: the SampleRecord of the B chosen candidates, totals (B, n)
+    float64 each candidate's running total at its depth, depth (B, n) int64 the last scale it was sampled through, choice (B,) int64 the best
+    full-depth candidate, tokens (B, n, L) int64 every candidate's drawn tokens (-1 past its depth)"""
+    images: Optional[torch.Tensor]
+    winners: 'SampleRecord'
+    totals: torch.Tensor
+    depth: torch.Tensor
+    choice: torch.Tensor
+    tokens: torch.Tensor
+
+
+def normalize_keep(keep, S: int, alive: int) -> list:
+    """the `keep` argument of VAR.classify and VAR.sample_best_of_pruned -> [(scale, m), ...] ascending in the scale.  keep: None / {} (no pruning)
+    or {scale: m}, 0 <= scale < S-1, integer m >= 1; `alive` candidates enter.  A boundary that drops nothing (m at or above the survivor count
+    before it) is no boundary and vanishes."""
+    if keep is None:
+        keep = {}
+    if not isinstance(keep, dict):
+        raise ValueError('keep must be None or a dict {scale_index: m}')
+    sched = []
+    for si, m in keep.items():
+        if isinstance(si, bool) or not isinstance(si, (int, np.integer)) or not 0 <= si < S - 1:
+            raise ValueError(f'keep: a boundary must be an integer scale index in [0, {S - 2}], got {si!r}')
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 1:
+            raise ValueError(f'keep: the number of candidates kept must be an integer >= 1, got {m!r}')
+        sched.append((int(si), int(m)))
+    schedule = []
+    for si, m in sorted(sched):
+        if m < alive:                        # a boundary that drops nothing is no boundary
+            schedule.append((si, m))
+            alive = m
+    return schedule
+
+
 class GenerativeResult(NamedTuple):
     """VAR.classify_generative's result: pred (N,) int64 positions into the label row, score (N, K) fp32 -mean|f_in - f_rec|, tokens (N, K, L)
     int64 the reconstructions' tokens (kept prefix + greedy tokens)"""
@@ -839,6 +874,59 @@ class VAR(nn.Module):
         return img, self._record(img, rec.pop('tokens'), rec), totals, choice
 
     @torch.no_grad()
+    def sample_best_of_pruned(self, label_B, g_seeds, keep, n: Optional[int] = None, by: str = 'logp_cond', cfg=1.5, top_k=0, top_p=0.0,
+                              max_images: int = 64, decode: bool = True) -> BestOfResult:
+        """Best-of-n sampling that drops candidates by scale -> BestOfResult(images, winners, totals, depth, choice, tokens).
+        label_B, g_seeds (B, n), n, by, cfg, top_k, top_p and max_images mean what they mean in sample_best_of.  keep: None / {} (no pruning: the
+        result of sample_best_of) or {scale: m}, 0 <= scale < S-1, integer m >= 1, as in classify: behind that scale each image keeps its m best
+        surviving candidates by the running total of `by` (an m at or above the survivor count drops nothing), and the others are sampled no
+        further: a dropped candidate costs no transformer time past its scale, the survivors go on in a smaller batch.  The rule at every
+        boundary and for choice is sample_best_of's: the float64 total in token order, highest first, NaN below everything, ties to the lower
+        index.  Every candidate, through its depth, is bit for bit the request autoregressive_infer_cfg_per_image_scored(label, seed, ...) run
+        alone, whatever it was batched with and whatever max_images is; self.rng is neither read nor advanced.
+          totals (B, n) float64: each candidate's running total at its depth;  depth (B, n) int64: the last scale it was sampled through
+          choice (B,) int64: the best full-depth candidate;  tokens (B, n, L) int64: every candidate's tokens, -1 past its depth
+          winners: the SampleRecord of the B chosen candidates;  images: their decoded images (None with decode=False)
+        Chunks hold max_images // n whole images (n > max_images raises ValueError).  Whether an early total predicts the final rank depends on
+        the weights: that trade-off is the caller's, as with classify's keep.  HIP path only (SamplingEngine.sample_best_of_pruned, DESIGN.md
+        section 30)."""
+        dev = self._scored_device('sample_best_of_pruned')
+        if by not in BEST_OF_FIELDS:
+            raise ValueError(f'by must be one of {BEST_OF_FIELDS}, got {by!r}')
+        if isinstance(max_images, bool) or int(max_images) != max_images or max_images < 1:
+            raise ValueError('max_images must be an integer >= 1')
+        sd = g_seeds.detach().cpu().tolist() if isinstance(g_seeds, torch.Tensor) else (g_seeds.tolist() if isinstance(g_seeds, np.ndarray) else g_seeds)
+        lab0 = torch.as_tensor(label_B)
+        if (not isinstance(sd, (list, tuple)) or len(sd) != lab0.numel() or len(sd) < 1 or not all(isinstance(r, (list, tuple)) and len(r) == len(sd[0]) for r in sd)
+                or len(sd[0]) < 1):
+            raise ValueError('g_seeds must be (B, n): one row of n >= 1 seeds per image')
+        B, width = len(sd), len(sd[0])
+        if n is not None and int(n) != width:
+            raise ValueError(f'n = {n} but g_seeds holds {width} seeds per image')
+        n = width
+
+        def spread(x):                                        # one value per image -> one per candidate
+            if isinstance(x, torch.Tensor): x = x.detach().cpu().tolist()
+            elif isinstance(x, np.ndarray): x = x.tolist()
+            if isinstance(x, (list, tuple)):
+                if len(x) != B:
+                    raise ValueError(f'cfg / top_k / top_p must be a scalar or {B} values, got {len(x)}')
+                return [v for v in x for _ in range(n)]
+            return x
+        if lab0.dim() != 1:
+            raise ValueError('label_B must hold B >= 1 integer class ids')
+        schedule = normalize_keep(keep, len(self.patch_nums), n)
+        if n > max_images:
+            raise ValueError(f'max_images = {max_images} holds no whole image of n = {n} candidates')
+        lab, seeds, cfgs, ks, ps = self._per_image_args(lab0.repeat_interleave(n), [v for r in sd for v in r], spread(cfg), spread(top_k), spread(top_p))
+        eng = self.engine()
+        rec, f_hat, totals, depth, choice = eng.sample_best_of_pruned(lab.to(dev).long(), seeds, cfgs, ks, ps, n, by, schedule, int(max_images))
+        img = eng.decode_f_hat(f_hat) if decode else None
+        pick = choice.view(B, 1, 1).expand(B, 1, self.L)
+        win = {key: v.gather(1, pick)[:, 0] for key, v in rec.items()}
+        return BestOfResult(img, self._record(img, win.pop('tokens'), win), totals, depth, choice, rec['tokens'])
+
+    @torch.no_grad()
     def autoregressive_infer_cfg_per_image(self, label_B, g_seeds, cfg=1.5, top_k=0, top_p=0.0, more_smooth=False, return_tokens=False):
         """Sample a batch of unrelated requests: image b is drawn with its own seed g_seeds[b] and its own cfg / top_k / top_p (each a scalar
         for all, or B values).  Returns (B, 3, H, W) fp32 in [0, 1]; with return_tokens=True also the (B, L) int64 tokens.
@@ -1359,23 +1447,7 @@ class VAR(nn.Module):
         result: identical semantics, without the saving."""
         desc = self._score_desc(score, group, threshold, top_k)
         gt, lab, cfg = self._scoring_args(gt_tokens, label, cfg, max_rows)
-        S = len(self.patch_nums)
-        if keep is None:
-            keep = {}
-        if not isinstance(keep, dict):
-            raise ValueError('keep must be None or a dict {scale_index: m}')
-        sched = []
-        for si, m in keep.items():
-            if isinstance(si, bool) or not isinstance(si, (int, np.integer)) or not 0 <= si < S - 1:
-                raise ValueError(f'keep: a boundary must be an integer scale index in [0, {S - 2}], got {si!r}')
-            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 1:
-                raise ValueError(f'keep: the number of candidates kept must be an integer >= 1, got {m!r}')
-            sched.append((int(si), int(m)))
-        schedule, alive = [], lab.shape[1]
-        for si, m in sorted(sched):
-            if m < alive:                        # a boundary that drops nothing is no boundary
-                schedule.append((si, m))
-                alive = m
+        schedule = normalize_keep(keep, len(self.patch_nums), lab.shape[1])
         if self._scoring_on_hip(gt):
             return ClassifyResult(*self.engine().classify(gt, lab, cfg, int(max_rows), desc, schedule))
         kw = {k: v for k, v in (('group', group), ('threshold', threshold), ('top_k', top_k)) if v is not None}
