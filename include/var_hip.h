@@ -543,6 +543,51 @@ int varhip_class_select_f32(const float* tokens, int64_t ld_img, int64_t ld_cls,
 int varhip_kv_compact(const void* const* src, void* const* dst, int nbuf, const int32_t* idx, int rows_src, int rows_dst, int rows_out,
                       int H, int Lmax, int len, int elem_bytes, varhip_stream_t stream);
 
+/* ---- in-place KV-cache resampling (VAR.sample_smc: dead particles' rows are overwritten by survivors') ----
+ * The in-place counterpart of varhip_kv_compact on nbuf caches laid out [rows][H][Lmax][64] (elements of elem_bytes = 4 or 2).  For every row
+ * r < rows with idx[r] != r:  bufs[i][r][h][t][:] = bufs[i][idx[r]][h][t][:]  for h < H, t < len.  Rows with idx[r] == r are neither read as a
+ * destination nor written; nothing else is written.  The kernel checks what the host cannot (idx is a DEVICE array of rows int32, not read by
+ * the host): a row whose idx[r] lies outside [0, rows), or whose source is not a fixed point (idx[idx[r]] != idx[r]), is left unwritten and
+ * adds 1 to *bad once (a global atomic add; bad: a device int32 the caller zeroes).  Sources are fixed points and destinations are not, so no
+ * row is both read and written: that is the whole in-place argument, and why no second cache set is needed.  bufs: a HOST array of nbuf device
+ * pointers (16-byte aligned), copied into the kernel's argument block; up to 96 per launch, a longer list is cut (only the first launch counts
+ * bad rows).  Plain 16-byte vector loads and stores.
+ * VARHIP_EINVAL before any launch: NULL bufs / idx / bad, a NULL or misaligned buffer, nbuf / H / Lmax <= 0, rows < 0, elem_bytes other than 2
+ * or 4, len < 0 or > Lmax, two buffers sharing a byte (ranges = rows whole rows), a row of more than 2^31 16-byte vectors.
+ * len == 0 or rows == 0: success, nothing launched. */
+int varhip_kv_resample(void* const* bufs, int nbuf, const int32_t* idx, int rows, int H, int Lmax, int len, int elem_bytes,
+                       int32_t* bad, varhip_stream_t stream);
+
+/* ---- the resampling decision of a particle sampler (VAR.sample_smc) ----------------------------------------------
+ * One workgroup per image i < images with n particles.  tokens is addressed as in varhip_class_select_f32: tokens[i*ld_img + c*ld_cls + t].
+ *   logw [images*n] float64, in and out;  seeds [images] device int64, one per image;  anc [images*n] int32 local ancestor indices in [0, n);
+ *   did [images] int32, 1 if the image was resampled;  ess [images] float64, the effective sample size;  logw_seen [images*n] float64 or NULL:
+ *   the log-weights after step 1, before any reset.
+ * float64 with plain IEEE operations in the stated order, no contraction into FMA; varhip_smc_resample_host_f32 (host pointers, no stream)
+ * gives the same bits.
+ *  1. s_c = sum_{t = t0}^{t1-1} (double)tokens[..], ascending t, starting from +0.0;  logw_c = logw_c + beta * s_c.
+ *  2. m = the maximum of the non-NaN logw_c.  Degenerate image (no such c, or m not finite): did = 0, ess = 0, anc = identity, logw as step 1
+ *     left it.
+ *  3. w_c = 0 for a NaN logw_c, otherwise (double)vm_exp((float)(logw_c - m))  (include/var_math.h).
+ *  4. W = sum w_c, Q = sum w_c * w_c, both in ascending c;  ess = W * W / Q.
+ *  5. The image resamples iff ess_frac < 0 (always) or ess < ess_frac * n.  Otherwise did = 0 and anc = identity.
+ *  6. Systematic resampling with one uniform per (image, boundary): u = (2 (x >> 9) + 1) * 2^-24, x = word 0 of Philox4x32-10 with the image's
+ *     seed as the key (split as varhip_exp1_philox_f32 splits it) and the counter (0, 0, scale, 2) (draw index 2: the fills use 0 and 1).
+ *     Thresholds T_j = ((double)j + u) * (W / n), j < n;  C_c = the inclusive cumulative sum of w, ascending, C_{-1} = 0;  offspring
+ *     o_c = #{j : C_{c-1} <= T_j < C_c};  a threshold not below C_{n-1} goes to the last c with w_c > 0.
+ *  7. Survivors stay in place: anc[c] = c wherever o_c >= 1.  The slots with o_c = 0, in ascending order, receive the surplus copies: survivor
+ *     c supplies o_c - 1 of them, survivors taken in ascending order.  Hence anc[anc[c]] == anc[c] for every c.  Every logw_c becomes +0.0,
+ *     did = 1.
+ * n <= 2048 (an image's weights and offspring counts are staged in 40 KiB of LDS).
+ * VARHIP_EINVAL before any launch: images < 1, n < 1 or n > 2048, t0 < 0, t1 < t0, scale < 0, ld_cls < t1 or ld_img < n * ld_cls when t1 > t0,
+ * a NULL operand other than logw_seen (tokens may be NULL when t1 == t0). */
+int varhip_smc_resample_f32(const float* tokens, int64_t ld_img, int64_t ld_cls, int images, int n, int t0, int t1, double beta,
+                            double* logw, const int64_t* seeds, int scale, double ess_frac,
+                            int32_t* anc, int32_t* did, double* ess, double* logw_seen, varhip_stream_t stream);
+int varhip_smc_resample_host_f32(const float* tokens, int64_t ld_img, int64_t ld_cls, int images, int n, int t0, int t1, double beta,
+                                 double* logw, const int64_t* seeds, int scale, double ess_frac,
+                                 int32_t* anc, int32_t* did, double* ess, double* logw_seen);
+
 /* ---- generative zero-shot classification (VAR.classify_generative; reference eval_prob.py:466-516) ------------------------------------------
  * Greedy CFG token selection: what var.py:172-175 + helpers.py:6-19 (fork's `gen` mode calls var.inpainting(top_k=1, top_p=0), var.py:236-364)
  * reduce to without the Exp(1) draw.  Row r = b * l + j of B * l: z = (1+t)*cond - t*uncond, rounded as cfg_sample_f32 rounds it (cond =

@@ -100,6 +100,8 @@ SIGNATURES_HIP_ONLY = {
     'evidence_reduce_f32': [P, L, L, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P],   # pinned bit for bit against evidence_maps_torch (tests/test_evidence_gpu.py); pn, begin, w are host arrays
     'evidence_overlay_u8': [P, L, L, I, I, I, P, P, P, P, P, I, P, P, P, I, D, P],   # pinned byte for byte against evidence_maps_torch
     'kv_compact':        [P, P, I, P, I, I, I, I, I, I, I],             # pinned byte for byte against numpy's gather (tests/test_kv_compact_gpu.py); src, dst are host arrays of pointers
+    'kv_resample':       [P, I, P, I, I, I, I, I, P],                   # pinned byte for byte against numpy's gather on a copy (tests/test_smc_kernels_gpu.py); bufs is a host array of pointers
+    'smc_resample_f32':  [P, L, L, I, I, I, I, D, P, P, I, D, P, P, P, P],   # pinned bit for bit against its host twin (tests/test_smc_kernels_gpu.py)
 }
 
 # plain host functions of the HIP library (no stream argument, no device pointer, no GPU needed); bound by var_amd/hip.py
@@ -111,7 +113,8 @@ SIGNATURES_HOST = {
     'class_mix_host_f32': [P, P, L, I, I, I, I, I, F, F, P, L, P, L, L, P, P, P, L, P, P, P, P, L],   # pinned against float64 (tests/test_class_information_cpu.py)
     'class_mix_finish_host_f32': [P, P, P, L, P, L, I, I, I, P, P, P, P, L],
     'attn_profile_host_f32': [P, P, I, I, I, I, I, P, I, I, I, P, L, L, P, P, L, L],   # pinned against float64 (tests/test_attention_profile_cpu.py)
-    'evidence_jet_host': [P],                                        # pinned against matplotlib's 'jet' (tests/test_evidence_cpu.py)
+    'smc_resample_host_f32': [P, L, L, I, I, I, I, D, P, P, I, D, P, P, P, P],   # pinned against a numpy restatement of the contract (tests/test_smc_resample_cpu.py)
+    'evidence_jet_host': [P],                                       # pinned against matplotlib's 'jet' (tests/test_evidence_cpu.py)
 }
 
 # ... and with bfloat16 storage: one entry point per _f16 entry point, same arguments (include/var_hip.h, "bf16")

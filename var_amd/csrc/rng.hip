@@ -5,21 +5,7 @@
 // or 1) and e = -vm_log(u): include/var_math.h's logarithm is built from correctly rounded operations only, so the kernel and the host twin
 // below (plain host code of this library, same -ffp-contract=off) produce the same bits.  No libm / ocml transcendental is involved.
 #include "common.h"
-
-struct VrPhilox { uint32_t w[4]; };
-
-__host__ __device__ static inline VrPhilox vr_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    VrPhilox o;
-    o.w[0] = c0; o.w[1] = c1; o.w[2] = c2; o.w[3] = c3;
-    return o;
-}
+#include "philox.h"
 
 // 32 random bits -> Exp(1): the top 23 bits n give u = (2n + 1) * 2^-24 in [2^-24, 1 - 2^-24] (2n + 1 < 2^24: the conversion and the scaling
 // are exact), e = -ln u in (0, 16.7]

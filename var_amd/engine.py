@@ -1579,6 +1579,122 @@ class SamplingEngine(_Engine):
         self.best_of_work = [tuple(x) for x in work]
         return rec, f_win.permute(0, 3, 1, 2).contiguous(), totals, depth, choice
 
+    # -- particle resampling at scale boundaries (VAR.sample_smc) -----------------------------------------------------------------------
+    SMC_MAX_PARTICLES = 2048    # varhip_smc_resample_f32 stages an image's weights in LDS
+    smc_reference = False       # test switch: the slow route of sample_smc (ancestors from the host twin, caches gathered out of place by torch)
+
+    @torch.no_grad()
+    def sample_smc(self, label_N: torch.Tensor, seeds, cfg, top_k, top_p, n: int, by: str, resample: list, beta: float, ess_frac: float,
+                   rs_seeds, max_images: int):
+        """n particles per image with resampling behind the scales of `resample` (ascending, below the last scale; validated by the caller).
+        N = B * n particles, particle c of image b at position b * n + c (host sequences of length N, already spread and validated; an image's
+        particles share its label, cfg, top_k and top_p).  rs_seeds: B integers, the key of each image's resampling uniform.
+        One workspace of nb * n rows serves all stages of a chunk (sample_best_of_pruned's first-stage set: no second cache set), _prologue runs
+        once.  A stage runs _bop_scales from the scale after the previous boundary through the next one; behind a boundary scale s, after its
+        quantizer step: (a) varhip_smc_resample_f32 adds beta * (the stage's stats[by]) to the float64 log-weights, decides by the effective
+        sample size and leaves the ancestor table, survivors in place; (b) the table plus the image's row offset, and its copy shifted by R for
+        the unconditional twins, is the row index; (c) ONE varhip_kv_resample launch overwrites the dead rows of every block's K and V cache,
+        tokens 0 .. end(s) - 1, in place; (d) the f_hat rows, the tokens and the statistic rows [:, :end(s)] are gathered by the table, so every
+        slot's record is its lineage's; (e) next_map_f32 recomputes scale s + 1's input from f_hat.  A slot keeps its own seed: a copy diverges
+        from its parent from scale s + 1 on.  Behind the last scale the weights take in the last stage without resampling.  did, anc and the
+        count of refused rows stay on the device until the call ends; a non-zero count raises.  Chunks hold max_images // n whole images.
+        -> dict(tokens, the STATS_FIELDS (each (B * n, L)), f_hat (B * n, Cvae, P, P), log_weights (B, n) f64, ancestors (B, K, n) int64,
+        resampled (B, K) bool, ess (B, K) f64, log_weights_seen (B, K, n) f64).  Under smc_reference self.smc_pre_tokens holds, per boundary,
+        the (B, n, end(s)) tokens before its gather (None otherwise).  self.smc_work: [(last scale of the stage, particle row-tokens the transformer ran), ...]."""
+        var = self.var
+        N, L, S, V, H = len(seeds), var.L, len(var.patch_nums), var.V, var.num_heads
+        B, K = N // n, len(resample)
+        if n > self.SMC_MAX_PARTICLES:
+            raise ValueError(f'sample_smc takes at most {self.SMC_MAX_PARTICLES} particles per image, got {n}')
+        if n > max_images:
+            raise ValueError(f'max_images = {max_images} holds no whole image of n = {n} particles')
+        self.resolve_precision()
+        self.refresh()
+        self._wait_ready()
+        dev = var.pos_start.device
+        if label_N.dtype != torch.int64 or label_N.numel() != N:
+            raise ValueError('label_N must be an int64 tensor of B * n labels')
+        self._check_labels(label_N)
+        lab = label_N.to(dev)
+        P, Cv = var.patch_nums[-1], var.Cvae
+        stages, first = [], 0
+        for s in list(resample) + [S - 1]:
+            stages.append((first, s))
+            first = s + 1
+        per_chunk = min(B, max_images // n)
+        esz = 4 if self.precision == 'f32' else 2
+        ref = bool(self.smc_reference)
+        rec = {key: torch.empty(N, L, dtype=torch.int32 if key == 'kept' else torch.float32, device=dev) for key in STATS_FIELDS}
+        rec['tokens'] = torch.empty(N, L, dtype=torch.int64, device=dev)
+        f_all = torch.empty(N, P, P, Cv, dtype=torch.float32, device=dev)
+        logw = torch.zeros(B, n, dtype=torch.float64, device=dev)
+        # per boundary (and one more set for the weight update behind the last scale), boundary-major so that a chunk's part is contiguous
+        anc = torch.empty(K + 1, B, n, dtype=torch.int32, device=dev)
+        did = torch.empty(K + 1, B, dtype=torch.int32, device=dev)
+        ess = torch.empty(K + 1, B, dtype=torch.float64, device=dev)
+        seen = torch.empty(K + 1, B, n, dtype=torch.float64, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        rs_np = np.asarray(rs_seeds, dtype=np.int64)
+        rs_d = torch.from_numpy(rs_np).to(dev)
+        pre =[[] for _ in range(K)]
+        work = [[last, 0] for _, last in stages]
+        for b0 in range(0, B, per_chunk):
+            b1 = min(B, b0 + per_chunk)
+            nb = b1 - b0
+            R = nb * n
+            tab = per_image_tables(cfg[b0 * n:b1 * n], top_k[b0 * n:b1 * n], top_p[b0 * n:b1 * n], S, V)
+            f64 = torch.from_numpy(np.concatenate((tab['t'].reshape(-1), tab['top_p']))).to(dev)
+            per = dict(t=f64[:S * R].view(S, R), top_p=f64[S * R:], top_k=torch.from_numpy(tab['top_k']).to(dev), cap=tab['cap'])
+            seeds_d = torch.from_numpy(np.asarray(seeds[b0 * n:b1 * n], dtype=np.int64)).to(dev)
+            ws = self._bop_workspace(per_chunk * n, 0)
+            caches = ws['kc'] + ws['vc']
+            ptrs = torch.tensor([t.data_ptr() for t in caches], dtype=torch.int64)          # a host array: the launcher copies it
+            off = (torch.arange(nb, device=dev, dtype=torch.int32) * n).view(nb, 1)
+            self._prologue(ws, lab[b0 * n:b1 * n], 2 * R)
+            ws['f_hat'][:R].zero_()
+            st = {key: rec[key][b0 * n:b1 * n] for key in STATS_FIELDS}
+            tok = rec['tokens'][b0 * n:b1 * n]
+            lw = logw[b0:b1]
+            for j, (first, last) in enumerate(stages):
+                self._bop_scales(ws, R, first, last, per, seeds_d, st, tok)
+                t0, t1 = var.begin_ends[first][0], var.begin_ends[last][1]
+                work[j][1] += R * (t1 - t0)
+                frac = ess_frac if j < K else 0.0               # (behind the last scale: ess >= 1 > 0 * n, the weights are updated and nothing moves)
+                out = (lw, anc[j, b0:b1], did[j, b0:b1], ess[j, b0:b1], seen[j, b0:b1])             # (a)
+                if not ref:
+                    hip.call('smc_resample_f32', st[by], n * L, L, nb, n, t0, t1, float(beta), lw, rs_d[b0:b1], last, frac, *out[1:])
+                else:
+                    h = [x.cpu().numpy() for x in out]
+                    hip.call_host('smc_resample_host_f32', st[by].cpu().numpy(), n * L, L, nb, n, t0, t1, float(beta), h[0], rs_np[b0:b1], last, frac,
+                                  *h[1:])
+                    for x, v in zip(out, h):
+                        x.copy_(torch.from_numpy(v))
+                if j == K:
+                    break
+                rows = (anc[j, b0:b1] + off).view(-1)                                   # (b) the slots' ancestors as rows of the chunk
+                idx = torch.cat((rows, rows + R))
+                if not ref:
+                    hip.call('kv_resample', ptrs, len(caches), idx, 2 * R, H, L, t1, esz, bad)       # (c)
+                else:
+                    pre[j].append(tok[:, :t1].clone().view(nb, n, t1))
+                    for t in caches:
+                        t[:2 * R, :, :t1] = t[:2 * R, :, :t1].clone().index_select(0, idx.long())
+                rows = rows.long()
+                ws['f_hat'][:R].copy_(ws['f_hat'][:R].index_select(0, rows))            # (d)
+                tok[:, :t1] = tok[:, :t1].index_select(0, rows)
+                for key in STATS_FIELDS:
+                    st[key][:, :t1] = st[key][:, :t1].index_select(0, rows)
+                hip.call('next_map_f32', ws['f_hat'], self.w['word_w'], self.w['word_b'], ws['lvl_pos'][t1:], ws['x'], ws['pooled'],
+                         R, P, var.patch_nums[last + 1], var.C, Cv)                      # (e)
+            f_all[b0 * n:b1 * n] = ws['f_hat'][:R]
+        if int(bad.item()) != 0:
+            raise hip.VarHipError(f'sample_smc: varhip_kv_resample refused {int(bad.item())} rows (an ancestor table that is no table of fixed points)')
+        self.smc_work = [tuple(x) for x in work]
+        res = dict(rec, f_hat=f_all.permute(0, 3, 1, 2).contiguous(), log_weights=logw, ancestors=anc[:K].permute(1, 0, 2).long().contiguous(),
+                   resampled=did[:K].t().ne(0).contiguous(), ess=ess[:K].t().contiguous(), log_weights_seen=seen[:K].permute(1, 0, 2).contiguous())
+        self.smc_pre_tokens = [torch.cat(p, 0) for p in pre] if ref else None
+        return res
+
     @torch.no_grad()
     def decode_f_hat(self, f_hat: torch.Tensor) -> torch.Tensor:
         """(B, Cvae, P, P) fp32 as sample(decode=False) returns it -> the images (B, 3, H, W) in [0, 1], by the call's own decoder step"""

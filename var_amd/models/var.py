@@ -78,6 +78,41 @@ class BestOfResult(NamedTuple):
     tokens: torch.Tensor
 
 
+class SMCResult(NamedTuple):
+    """VAR.sample_smc's result (K = len(resample) boundaries): images (B, n, 3, H, W) or None; particles: the SampleRecord of the B * n final
+    particles (row b * n + c), tokens and statistics lineage-consistent; log_weights (B, n) float64, final; ancestors (B, K, n) int64: the slot
+    whose state slot c carries on from each boundary; resampled (B, K) bool; ess (B, K) float64: the effective sample size each boundary saw;
+    log_weights_seen (B, K, n) float64: the log-weights each boundary decided on; patch_nums"""
+    images: Optional[torch.Tensor]
+    particles: 'SampleRecord'
+    log_weights: torch.Tensor
+    ancestors: torch.Tensor
+    resampled: torch.Tensor
+    ess: torch.Tensor
+    log_weights_seen: torch.Tensor
+    patch_nums: tuple
+
+    def best(self) -> torch.Tensor:
+        """(B,) int64: each image's particle of the highest final log-weight by VAR.classify's rule (NaN below everything, ties to the lower index)"""
+        lw = self.log_weights.detach().cpu().numpy()
+        return torch.tensor([int(rule_order(row)[0]) for row in lw], dtype=torch.int64, device=self.log_weights.device)
+
+
+def normalize_resample(resample, S: int) -> list:
+    """the `resample` argument of VAR.sample_smc -> the boundary scales as a list: integer scale indices in [0, S-2] (below the last scale),
+    ascending and unique, validated as normalize_keep validates a scale; an empty sequence is allowed"""
+    if resample is None or isinstance(resample, (str, bytes, dict)) or not hasattr(resample, '__iter__'):
+        raise ValueError('resample must be a sequence of boundary scale indices')
+    out = []
+    for si in resample:
+        if isinstance(si, bool) or not isinstance(si, (int, np.integer)) or not 0 <= si < S - 1:
+            raise ValueError(f'resample: a boundary must be an integer scale index in [0, {S - 2}], got {si!r}')
+        if out and si <= out[-1]:
+            raise ValueError(f'resample: the boundaries must be ascending and unique, got {si!r} after {out[-1]}')
+        out.append(int(si))
+    return out
+
+
 def normalize_keep(keep, S: int, alive: int) -> list:
     """the `keep` argument of VAR.classify and VAR.sample_best_of_pruned -> [(scale, m), ...] ascending in the scale.  keep: None / {} (no pruning)
     or {scale: m}, 0 <= scale < S-1, integer m >= 1; `alive` candidates enter.  A boundary that drops nothing (m at or above the survivor count
@@ -925,6 +960,72 @@ class VAR(nn.Module):
         pick = choice.view(B, 1, 1).expand(B, 1, self.L)
         win = {key: v.gather(1, pick)[:, 0] for key, v in rec.items()}
         return BestOfResult(img, self._record(img, win.pop('tokens'), win), totals, depth, choice, rec['tokens'])
+
+    @torch.no_grad()
+    def sample_smc(self, label_B, g_seeds, resample=(4, 6), n: Optional[int] = None, by: str = 'logp_cond', beta: float = 1.0, ess=0.5,
+                   cfg=1.5, top_k=0, top_p=0.0, max_images: int = 64, decode: bool = True, resample_seeds=None) -> SMCResult:
+        """n particles per image with resampling at scale boundaries (a particle filter over the scales) -> SMCResult.
+        label_B, g_seeds (B, n), n, by, cfg, top_k, top_p and max_images mean what they mean in sample_best_of_pruned.
+          resample   boundary scales, ascending, unique, below the last scale (an empty sequence: no boundary)
+          beta       the weight's inverse temperature (a finite float)
+          ess        a float in (0, 1]: an image resamples behind a boundary when its effective sample size is below ess * n; None: always
+          resample_seeds  (B,) integers in [0, 2^63), the key of each image's resampling uniform; default g_seeds[:, 0]
+        What the particles approximate: every token is drawn from the filtered, guided distribution (cfg, top_k, top_p), which is the proposal;
+        behind a stage a particle's incremental weight is exp(beta * sum of `by` over the stage's tokens).  Behind a boundary scale the weak
+        particles die and the strong ones are copied into their slots (systematic resampling, one uniform per (image, boundary); survivors
+        stay in their own slots; the weights restart at 1), so the call ends with n images per label that share good coarse scales and differ
+        in the fine ones: slot c keeps its own seed g_seeds[b][c], so a copy diverges from its parent from the next scale on, its noise there
+        keyed by (slot seed, scale).  The weighted particles target the proposal tilted by exp(beta * sum `by`); beta = 0 gives equal weights
+        (ess == n: no threshold resamples), a large beta with ess=None tends to "keep the best and refill".  Without a resampling event the
+        particles are bit for bit autoregressive_infer_cfg_per_image_scored on the same labels and seeds, and at beta = 1 log_weights are
+        sample_best_of's totals.  An image's result depends on its own label, seeds and parameters only, not on what it is batched with or on
+        max_images (pixels: as for the per-image call, the decoder's kernel choice follows its batch); self.rng is neither read nor advanced.  The K and V caches are resampled in place (varhip_kv_resample: only the rows that
+        died are copied), so the call needs no second cache set and the late scales run the full batch.  Chunks hold max_images // n whole
+        images (n > max_images raises ValueError).  HIP path only, no more_smooth (SamplingEngine.sample_smc)."""
+        dev = self._scored_device('sample_smc')
+        if by not in BEST_OF_FIELDS:
+            raise ValueError(f'by must be one of {BEST_OF_FIELDS}, got {by!r}')
+        if isinstance(max_images, bool) or int(max_images) != max_images or max_images < 1:
+            raise ValueError('max_images must be an integer >= 1')
+        if ess is not None and (isinstance(ess, bool) or not isinstance(ess, (int, float, np.integer, np.floating)) or not 0.0 < float(ess) <= 1.0):
+            raise ValueError(f'ess must be None (always resample) or a float in (0, 1], got {ess!r}')
+        if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)) or not math.isfinite(float(beta)):
+            raise ValueError(f'beta must be a finite float, got {beta!r}')
+        bounds = normalize_resample(resample, len(self.patch_nums))
+        sd = g_seeds.detach().cpu().tolist() if isinstance(g_seeds, torch.Tensor) else (g_seeds.tolist() if isinstance(g_seeds, np.ndarray) else g_seeds)
+        lab0 = torch.as_tensor(label_B)
+        if (not isinstance(sd, (list, tuple)) or len(sd) != lab0.numel() or len(sd) < 1 or not all(isinstance(r, (list, tuple)) and len(r) == len(sd[0]) for r in sd)
+                or len(sd[0]) < 1):
+            raise ValueError('g_seeds must be (B, n): one row of n >= 1 seeds per image')
+        B, width = len(sd), len(sd[0])
+        if n is not None and int(n) != width:
+            raise ValueError(f'n = {n} but g_seeds holds {width} seeds per image')
+        n = width
+
+        def spread(x):                                        # one value per image -> one per particle
+            if isinstance(x, torch.Tensor): x = x.detach().cpu().tolist()
+            elif isinstance(x, np.ndarray): x = x.tolist()
+            if isinstance(x, (list, tuple)):
+                if len(x) != B:
+                    raise ValueError(f'cfg / top_k / top_p must be a scalar or {B} values, got {len(x)}')
+                return [v for v in x for _ in range(n)]
+            return x
+        if lab0.dim() != 1:
+            raise ValueError('label_B must hold B >= 1 integer class ids')
+        if n > max_images:
+            raise ValueError(f'max_images = {max_images} holds no whole image of n = {n} particles')
+        lab, seeds, cfgs, ks, ps = self._per_image_args(lab0.repeat_interleave(n), [v for r in sd for v in r], spread(cfg), spread(top_k), spread(top_p))
+        rs = [r[0] for r in sd] if resample_seeds is None else self._per_image_args(lab0, resample_seeds, 0.0, 0, 0.0)[1]
+        eng = self.engine()
+        res = eng.sample_smc(lab.to(dev).long(), seeds, cfgs, ks, ps, n, by, bounds, float(beta), -1.0 if ess is None else float(ess), rs, int(max_images))
+        img = None
+        if decode:
+            f_hat = res['f_hat']
+            img = torch.cat([eng.decode_f_hat(f_hat[c0:c0 + int(max_images)]) for c0 in range(0, B * n, int(max_images))])
+            img = img.view(B, n, *img.shape[1:])
+        st = {key: res[key] for key in SampleRecord.FIELDS}
+        return SMCResult(img, self._record(None if img is None else img.view(B * n, *img.shape[2:]), res['tokens'], st), res['log_weights'],
+                         res['ancestors'], res['resampled'], res['ess'], res['log_weights_seen'], tuple(self.patch_nums))
 
     @torch.no_grad()
     def autoregressive_infer_cfg_per_image(self, label_B, g_seeds, cfg=1.5, top_k=0, top_p=0.0, more_smooth=False, return_tokens=False):
