@@ -225,6 +225,11 @@ int varhip_gumbel_softmax_f32(const float* x, const float* noise, float* y, int6
  * lvl_pos must already point at row cur_L.  pooled: caller-provided [B][pq*pq][Cv] buffer (intermediate; kept for inspection). */
 int varhip_next_map_f32(const float* f_hat, const float* word_w, const float* word_b, const float* lvl_pos,
                         float* x_out, float* pooled, int B, int P, int pq, int C, int Cv, varhip_stream_t stream);
+/* testing (a host global, no launch): the kernel route of the latest call of this process among the quantizer steps (varhip_quant_accum_f32,
+ * _h_f32, varhip_quant_residual_f32, the _edit_ forms: 1 = the LDS-staged Phi kernel, 2 = the plain one), the word embedding
+ * (varhip_next_map_f32, varhip_word_embed_f32: 4 = the Cv == 32 kernel, 8 = the generic one) and the nearest-code lookups (16 = the MFMA kernel,
+ * 32 = the generic one); 0 before any such call, unchanged by a call that returned VARHIP_EINVAL.  Every route computes the same bits. */
+int varhip_quant_last_route(void);
 
 /* lvl_pos[t][:] = lvl_embed[lvl[t]][:] + pos[t][:]     (var.py:153) */
 int varhip_lvl_pos_f32(const float* lvl_embed, const int64_t* lvl, const float* pos, float* out, int L, int C, varhip_stream_t stream);

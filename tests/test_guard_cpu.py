@@ -297,6 +297,7 @@ NO_DEVICE_POINTER = {                                        # everything else v
     'gemm_last_evec': 'test hook: reports the epilogue switch of the latest dispatch',
     'conv16_last_pick': 'test hook: reports the kernel instantiation of the latest 16-bit convolution',
     'gemm16_deep': 'test hook: kernel choice', 'gemm16_last_pick': 'test hook: reports the kernel instantiations of the latest 16-bit GEMM',
+    'quant_last_route': 'test hook: reports the kernel route of the latest quantizer-step, word-embed or nearest-code call',
 }
 FLAVOURS = ('f16', 'bf16')
 

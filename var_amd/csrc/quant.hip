@@ -33,6 +33,12 @@ __global__ void k_gather_up(const int64_t* __restrict__ idx, const float* __rest
     up[i] = o;
 }
 
+// test hook (varhip_quant_last_route, include/var_hip.h): the kernel route of the latest quantizer-step, word-embed or nearest-code call.
+// It is written next to each dispatch decision and read by nothing in the library.
+enum { QR_PHI_LDS = 1, QR_PHI_PLAIN = 2, QR_WE32 = 4, QR_WE_ANY = 8, QR_NC_MFMA = 16, QR_NC_ANY = 32 };
+static int vh_g_quant_last_route = 0;
+extern "C" int varhip_quant_last_route(void) { return vh_g_quant_last_route; }
+
 __global__ void k_phi_accum(const float* __restrict__ up, const float* __restrict__ phi_w, const float* __restrict__ phi_b, float ratio, float keep,
                             float* __restrict__ f_hat, int B, int P, int Cv) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       // [B][P][P][Cv] over co
@@ -92,6 +98,7 @@ static bool launch_phi_accum(const float* up, const float* phi_w, const float* p
     static bool attr_done = false;
     if (!attr_done) { (void)hipFuncSetAttribute((const void*)k_phi_accum_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); attr_done = true; }
     hipLaunchKernelGGL(k_phi_accum_lds, dim3(P, B), dim3(256), lds, s, up, phi_w, phi_b, ratio, 1.0f - ratio, f_hat, f_rest, P, Cv);
+    vh_g_quant_last_route = QR_PHI_LDS;
     return true;
 }
 
@@ -100,6 +107,7 @@ void vh_quant_phi_accum(const float* up, const float* phi_w, const float* phi_b,
     if (!launch_phi_accum(up, phi_w, phi_b, ratio, f_hat, nullptr, B, P, Cv, s)) {
         const unsigned blocks = (unsigned)(((int64_t)B * P * P * Cv + 255) / 256);
         hipLaunchKernelGGL(k_phi_accum, dim3(blocks), dim3(256), 0, s, up, phi_w, phi_b, ratio, 1.0f - ratio, f_hat, B, P, Cv);
+        vh_g_quant_last_route = QR_PHI_PLAIN;
     }
 }
 
@@ -112,8 +120,10 @@ extern "C" int varhip_quant_accum_f32(const int64_t* idx, const float* codebook,
     VhScope sc(VH_FAM_OTHER, (hipStream_t)stream, 2.0 * tot * 9 * Cv, 16.0 * tot);
     const unsigned blocks = (unsigned)((tot + 255) / 256);
     hipLaunchKernelGGL(k_gather_up<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, idx, codebook, tap_idx, tap_w, up, B, pn, P, Cv);
-    if (!launch_phi_accum(up, phi_w, phi_b, ratio, f_hat, nullptr, B, P, Cv, (hipStream_t)stream))
+    if (!launch_phi_accum(up, phi_w, phi_b, ratio, f_hat, nullptr, B, P, Cv, (hipStream_t)stream)) {
         hipLaunchKernelGGL(k_phi_accum, dim3(blocks), dim3(256), 0, (hipStream_t)stream, up, phi_w, phi_b, ratio, 1.0f - ratio, f_hat, B, P, Cv);
+        vh_g_quant_last_route = QR_PHI_PLAIN;
+    }
     return vh_launch_status();
 }
 
@@ -125,8 +135,10 @@ extern "C" int varhip_quant_accum_h_f32(const float* h, const int32_t* tap_idx, 
     VhScope sc(VH_FAM_OTHER, (hipStream_t)stream, 2.0 * tot * 9 * Cv, 16.0 * tot);
     const unsigned blocks = (unsigned)((tot + 255) / 256);
     hipLaunchKernelGGL(k_gather_up<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const int64_t*)nullptr, h, tap_idx, tap_w, up, B, pn, P, Cv);
-    if (!launch_phi_accum(up, phi_w, phi_b, ratio, f_hat, nullptr, B, P, Cv, (hipStream_t)stream))
+    if (!launch_phi_accum(up, phi_w, phi_b, ratio, f_hat, nullptr, B, P, Cv, (hipStream_t)stream)) {
         hipLaunchKernelGGL(k_phi_accum, dim3(blocks), dim3(256), 0, (hipStream_t)stream, up, phi_w, phi_b, ratio, 1.0f - ratio, f_hat, B, P, Cv);
+        vh_g_quant_last_route = QR_PHI_PLAIN;
+    }
     return vh_launch_status();
 }
 
@@ -188,10 +200,13 @@ __global__ void __launch_bounds__(256) k_word_embed32(const float* __restrict__ 
 }
 static void launch_word_embed(const float* pooled, const float* word_w, const float* word_b, const float* lvl_pos, float* x_out, int B, int lq, int C, int Cv, hipStream_t s) {
     const int64_t rows = (int64_t)B * lq, t2 = rows * C;
-    if (Cv == 32 && !(((uintptr_t)word_w) & 15) && (rows + WE_ROWS - 1) / WE_ROWS <= 65535)
+    if (Cv == 32 && !(((uintptr_t)word_w) & 15) && (rows + WE_ROWS - 1) / WE_ROWS <= 65535) {
         hipLaunchKernelGGL(k_word_embed32, dim3((C + 255) / 256, (unsigned)((rows + WE_ROWS - 1) / WE_ROWS)), dim3(256), 0, s, pooled, word_w, word_b, lvl_pos, x_out, rows, lq, C);
-    else
+        vh_g_quant_last_route = QR_WE32;
+    } else {
         hipLaunchKernelGGL(k_word_embed, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, pooled, word_w, word_b, lvl_pos, x_out, B, lq, C, Cv);
+        vh_g_quant_last_route = QR_WE_ANY;
+    }
 }
 
 extern "C" int varhip_next_map_f32(const float* f_hat, const float* word_w, const float* word_b, const float* lvl_pos,
@@ -199,9 +214,8 @@ extern "C" int varhip_next_map_f32(const float* f_hat, const float* word_w, cons
     if (B <= 0 || P <= 0 || pq <= 0 || pq > P || C <= 0 || Cv <= 0 || !pooled) return VARHIP_EINVAL;
     const int lq = pq * pq;
     VhScope sc(VH_FAM_OTHER, (hipStream_t)stream, 2.0 * B * lq * (double)C * Cv, 8.0 * B * lq * (double)C);
-    const int64_t t1 = (int64_t)B * lq * Cv, t2 = (int64_t)B * lq * C;
+    const int64_t t1 = (int64_t)B * lq * Cv;
     hipLaunchKernelGGL(k_area_pool, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f_hat, pooled, B, P, pq, Cv);
-    (void)t2;
     launch_word_embed(pooled, word_w, word_b, lvl_pos, x_out, B, lq, C, Cv, (hipStream_t)stream);
     return vh_launch_status();
 }
@@ -255,8 +269,10 @@ extern "C" int varhip_quant_residual_f32(const int64_t* idx, const float* codebo
     VhScope sc(VH_FAM_OTHER, (hipStream_t)stream, 2.0 * tot * 9 * Cv, 24.0 * tot);
     const unsigned blocks = (unsigned)((tot + 255) / 256);
     hipLaunchKernelGGL(k_gather_up<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, idx, codebook, tap_idx, tap_w, up, B, pn, P, Cv);
-    if (!launch_phi_accum(up, phi_w, phi_b, ratio, f_hat, f_rest, B, P, Cv, (hipStream_t)stream))
+    if (!launch_phi_accum(up, phi_w, phi_b, ratio, f_hat, f_rest, B, P, Cv, (hipStream_t)stream)) {
         hipLaunchKernelGGL(k_phi_accum_rest, dim3(blocks), dim3(256), 0, (hipStream_t)stream, up, phi_w, phi_b, ratio, 1.0f - ratio, f_hat, f_rest, B, P, Cv);
+        vh_g_quant_last_route = QR_PHI_PLAIN;
+    }
     return vh_launch_status();
 }
 
@@ -372,6 +388,7 @@ static int launch_nearest_mfma(const float* z, const float* codebook, int64_t* i
     static bool attr_done = false;
     if (!attr_done) { (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_done = true; }
     hipLaunchKernelGGL(kfn, dim3((unsigned)((N + 127) / 128)), dim3(256), lds, stream, z, codebook, idx_out, N, V);
+    vh_g_quant_last_route = QR_NC_MFMA;
     return vh_launch_status();
 }
 
@@ -411,6 +428,7 @@ extern "C" int varhip_nearest_code_f32(const float* z, const float* codebook, in
     VhScope sc(VH_FAM_OTHER, (hipStream_t)stream, 4.0 * N * (double)V * Cv, 4.0 * ((double)N * Cv + (double)V * Cv) + 8.0 * N);
     if (Cv == 32 && (((uintptr_t)z | (uintptr_t)codebook) & 15) == 0) return launch_nearest_mfma<false>(z, codebook, idx_out, N, V, (hipStream_t)stream);
     hipLaunchKernelGGL(k_nearest_code, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, z, codebook, idx_out, V, Cv);
+    vh_g_quant_last_route = QR_NC_ANY;
     return vh_launch_status();
 }
 
@@ -453,5 +471,6 @@ extern "C" int varhip_nearest_code_cos_f32(const float* z, const float* codebook
     VhScope sc(VH_FAM_OTHER, (hipStream_t)stream, 4.0 * N * (double)V * Cv, 4.0 * ((double)N * Cv + (double)V * Cv) + 8.0 * N);
     if (Cv == 32 && (((uintptr_t)z | (uintptr_t)codebook) & 15) == 0) return launch_nearest_mfma<true>(z, codebook, idx_out, N, V, (hipStream_t)stream);
     hipLaunchKernelGGL(k_nearest_code_cos, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, z, codebook, idx_out, V, Cv);
+    vh_g_quant_last_route = QR_NC_ANY;
     return vh_launch_status();
 }

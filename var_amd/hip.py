@@ -36,6 +36,7 @@ class _Lib:
         so.varhip_gemm_qkv_force_tile.argtypes = [ctypes.c_int]; so.varhip_gemm_qkv_force_tile.restype = ctypes.c_int
         so.varhip_gemm_last_pick.argtypes = []; so.varhip_gemm_last_pick.restype = ctypes.c_int
         so.varhip_gemm_last_evec.argtypes = []; so.varhip_gemm_last_evec.restype = ctypes.c_int
+        so.varhip_quant_last_route.argtypes = []; so.varhip_quant_last_route.restype = ctypes.c_int
         so.varhip_vq_stats_blocks.argtypes = [ctypes.c_int64]; so.varhip_vq_stats_blocks.restype = ctypes.c_int
         self.host = {}
         for name, args in abi.SIGNATURES_HOST.items():
