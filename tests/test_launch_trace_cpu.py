@@ -12,16 +12,22 @@ functions: they choose the paths.
 Per launch the record holds the entry point's name and every argument in order: None, ints, floats as `float.hex`, host arrays by content,
 tensors as (dtype, shape, stride, storage offset, buffer number).  A buffer number is the order in which that storage first appeared in the
 case; the recorder keeps every tensor it saw alive until the case ends, so no address comes back under another tensor and the numbers are
-the dataflow.  What the entry point returns is recorded the same way.  The tensors are real CPU tensors: `_stats_from` compares
+the dataflow.  The host arrays of device pointers that `kv_compact` and `kv_resample` take are recorded as the buffer numbers of the storages
+they point to (the workspaces that own them live in the engine's caches), so the dataflow across a prune or resampling boundary is part of
+the record.  What the entry point returns is recorded the same way.  The tensors are real CPU tensors: `_stats_from` compares
 `data_ptr()`s, and that comparison runs for real.
 
 The one place where the host branches on a kernel's output is `edit_keep_u8` -> `skip`: the recorder fills that output (the first
-KEEP_PREFIX tokens of every row kept), and two cases cover a fully kept first scale and no kept token.
+KEEP_PREFIX tokens of every row kept), and two cases cover a fully kept first scale and no kept token.  Two more outputs become indices
+on the host, and the recorder fills them as well: `class_select_f32` leaves kept[i] = 0 .. keep-1 (every image keeps its first candidates),
+`smc_resample_f32` leaves the identity ancestor table and did = 0 (nothing is resampled; `kv_resample` still runs, and its count of refused
+rows stays 0).  The `smc_reference` route of sample_smc goes through `hip.call_host` and real NumPy: tests/test_smc_gpu.py holds it.
 
 The fixture stores, per case, one line per launch ("name digest-of-its-arguments") and the SHA-256 of the whole record: a failure names the
 first launch that differs.  `python tests/test_launch_trace_cpu.py --write PATH` writes it.  It only drives entry points that keep their
 signature (decode_nhwc, encode, the SamplingEngine and QuantizerEngine methods), so the same file records any revision of engine.py;
-tests/golden/launch_trace.json is the record of the revision before the engines' fp32 / 16-bit paths were folded into one walk each."""
+every case of tests/golden/launch_trace.json is the record of the revision that first had it: the revision before the engines' fp32 /
+16-bit paths were folded into one walk each, and for the stats, best-of and particle cases the one before the samplers shared one scale walk."""
 import contextlib
 import hashlib
 import json
@@ -41,14 +47,17 @@ from var_amd import engine, hip                                             # no
 
 FIXTURE = os.path.join(ROOT, 'tests', 'golden', 'launch_trace.json')
 HOST_ARRAYS = {('edit_keep_u8', 4), ('eval_reduce_f32', 6)}                 # tensor arguments the launcher reads on the host: recorded by content
+POINTER_ARRAYS = {('kv_compact', 0), ('kv_compact', 1), ('kv_resample', 0)}    # host arrays of device addresses: recorded as the buffers they point to
 ADA_ATTR = 'ADA_PACKED_MAX_BYTES'                                           # SamplingEngine: above it the per-block AdaLN projections replace the packed one
 
-# every entry point named in a hip.call of _VaeOps, DecoderEngine, EncoderEngine and of SamplingEngine's prologue, block() and head():
-# the cases below must reach all of them
+# every entry point named in a hip.call of _VaeOps, DecoderEngine, EncoderEngine, of SamplingEngine's prologue, block() and head(), and of
+# the per-image, stats, best-of and particle routes of its sampling walk: the cases below must reach all of them
 MUST_REACH = {
     'conv3x3_nhwc_f32', 'conv3x3_gn_nhwc_f32', 'conv3x3_wino_nhwc_f32', 'conv3x3_s2_nhwc_f32', 'gn_stats_f32', 'gn_stats_part_f32', 'gn_apply_f32',
     'gn_silu_conv_out_f32', 'gemm_nt_f32', 'softmax_rows_f32', 'upconv_phase_f32', 'upconv_phase_gn_f32', 'nchw_to_nhwc_pad_f32', 'gn_scale_shift_f32',
     'lvl_pos_f32', 'first_map_f32', 'silu_f32', 'add_bcast_f32', 'adaln_block_f32', 'ln_modulate_f32',
+    'exp1_philox_f32', 'cfg_sample_rows_f32', 'sample_stats_f32', 'class_select_f32', 'kv_compact', 'kv_resample', 'smc_resample_f32', 'quant_accum_f32',
+    'next_map_f32',
 } | {n + s for s in ('f16', 'bf16') for n in ('conv3x3_nhwc_', 'gn_stats_', 'gn_apply_', 'gn_silu_conv_out_', 'gnconv3x3_nhwc_', 'gemm_nt_', 'upconv_phase_',
                                                 'conv3x3_s2_nhwc_', 'cast_f32_to_', 'adaln_block_')} \
   | {'cast_f16_to_f32', 'cast_bf16_to_f32', 'ln_modulate_f16out', 'ln_modulate_bf16out'}
@@ -65,9 +74,11 @@ class Recorder:
         n = self.bufs.setdefault(t.untyped_storage().data_ptr(), len(self.bufs))
         return ['T', str(t.dtype), list(t.shape), list(t.stride()), int(t.storage_offset()), n]
 
-    def value(self, a, host=False):
+    def value(self, a, host=False, pointers=False):
         if a is None or isinstance(a, str):
             return a
+        if pointers:
+            return ['pointers', [self.bufs.setdefault(p, len(self.bufs)) for p in a.tolist()]]
         if isinstance(a, torch.Tensor):
             return ['host', str(a.dtype), a.tolist()] if host else self.tensor(a)
         if isinstance(a, np.ndarray):
@@ -84,10 +95,15 @@ class Recorder:
 
     def call(self, name, *args, stream=None):
         assert stream is None
-        self.log.append([name] + [self.value(a, (name, i) in HOST_ARRAYS) for i, a in enumerate(args)])
+        self.log.append([name] + [self.value(a, (name, i) in HOST_ARRAYS, (name, i) in POINTER_ARRAYS) for i, a in enumerate(args)])
         if name == 'edit_keep_u8':
             args[-1].zero_()
             args[-1][:, :self.KEEP_PREFIX] = 1
+        if name == 'class_select_f32':                           # kept (images, keep)
+            args[-1][:] = torch.arange(args[-1].shape[1], dtype=args[-1].dtype)
+        if name == 'smc_resample_f32':                           # ..., anc (images, n), did (images,), ess, seen
+            args[-4][:] = torch.arange(args[-4].shape[1], dtype=args[-4].dtype)
+            args[-3].zero_()
 
     def returned(self, out):
         self.log.append(['return', self.value(out)])
@@ -245,6 +261,21 @@ def sampling_cases():
     out['sample_per_image more_smooth'] = record(lambda: eng.sample_per_image(lab, [1, 2], [1.5, 2.0], [900, 0], [0.96, 0.0], more_smooth=True))
     out['sample smooth'] = record(lambda: (plain(smooth=dict(gt=gt, n=4, thr=None)), eng.last_smooth))
     out['sample decode=False'] = record(lambda: plain(decode=False))
+    def scored(fn, **kw):                                        # the call's result and what it left in the caller's stats dict and tensors
+        kw['stats'] = {}
+        return fn(**kw), kw
+    out['sample stats'] = record(lambda: scored(plain))
+    out['sample stats more_smooth'] = record(lambda: scored(plain, more_smooth=True))
+    out['sample_per_image stats decode=False'] = record(lambda: scored(
+        lambda **kw: eng.sample_per_image(lab, [1, 2], [1.5, 2.0], [900, 0], [0.96, 0.0], **kw), decode=False, tokens_out=torch.empty(2, L, dtype=torch.int64)))
+    # two candidates / particles per image: labels, seeds and parameters spread to N = 4 rows as the VAR methods hand them over
+    lab4 = lab.repeat_interleave(2)
+    cand = ([11, 12, 21, 22], [1.5, 1.5, 2.0, 2.0], [900, 900, 0, 0], [0.96, 0.96, 0.0, 0.0])
+    out['sample_best_of two chunks'] = record(lambda: eng.sample_best_of(lab4, *cand, 2, 'logp_cond', 2))
+    for name, max_images in (('one chunk', 4), ('two chunks', 2)):
+        out[f'sample_best_of_pruned {name}'] = record(
+            lambda: (eng.sample_best_of_pruned(lab4, *cand, 2, 'logp_cond', [(0, 1)], max_images), eng.best_of_work))
+        out[f'sample_smc {name}'] = record(lambda: (eng.sample_smc(lab4, *cand, 2, 'logp_cond', [0, 1], 1.0, 0.5, [5, 6], max_images), eng.smc_work))
     labels = torch.tensor([[1, 2, 3], [4, 5, 6]])
     out['token_log_likelihood cfg'] = record(lambda: eng.token_log_likelihood(gt, labels, 1.5, 4))
     out['token_log_likelihood no cfg'] = record(lambda: eng.token_log_likelihood(gt, labels, 0.0, 8))

@@ -16,6 +16,7 @@ from __future__ import annotations
 import math
 import os
 import weakref
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -887,6 +888,25 @@ AUTOCAST_PRECISION = {torch.float16: 'f16', torch.bfloat16: 'bf16'}
 _SCORE_MODES = {'log_prob': 0, 'group_smoothed': 1, 'neighbor_max': 2, 'expected_distance': 3, 'distance_profile': 4, 'class_information': 5}
 
 
+class _Exp1:
+    """One stream of Exp(1) fills [B * l, V] fp32, the one place where the sampling loop gets its noise.  src None: every fill is drawn with
+    `exponential_(generator=rng)` exactly as torch.multinomial (helpers.py:19) would; a callable (si, l) -> tensor (the Philox fill of
+    sample_per_image; var_amd.multi hands each rank its rows; tests inject the CPU generator's stream); a list: one tensor per draw, indexed by
+    the draw count, so a scale that draws nothing (fully kept under inpainting) takes no entry."""
+
+    def __init__(self, src, rng: Optional[torch.Generator], V: int, dev):
+        self.src, self.rng, self.V, self.dev, self.draws = src, rng, V, dev, 0
+
+    def draw(self, B: int, si: int, l: int, use: bool = True) -> Optional[torch.Tensor]:
+        """scale si's fill.  use=False: the draw is spent and not read — the generator advances, a list skips its entry, a callable is not called"""
+        if self.src is None:
+            return torch.empty(B * l, self.V, dtype=torch.float32, device=self.dev).exponential_(1, generator=self.rng)
+        k, self.draws = self.draws, self.draws + 1
+        if not use:
+            return None
+        return (self.src(si, l) if callable(self.src) else self.src[k]).to(self.dev, torch.float32).contiguous()
+
+
 class SamplingEngine(_Engine):
     """The AR loop of VAR.autoregressive_infer_cfg on HIP kernels.  One engine per VAR module; calls on different HIP streams may be in flight
     together (per-stream workspaces), the host side is not thread-safe."""
@@ -1156,6 +1176,210 @@ class SamplingEngine(_Engine):
         hip.call('gemm_qkv_f32', xn, C, blk['qkv_w'], C, blk['qkv_b'], rows * l, C, C, blk['smul'], blk['plain_scale'], int(blk['l2']),
                  ws['q'], ws['kc'][bi], ws['vc'][bi], rows, l, H, cur, self.var.L)
 
+    # -- the sampling walk -------------------------------------------------------------------------------------------
+    def _scales(self, ws: dict, B: int, first: int, last: int, tr: Optional[dict] = None, ev: Optional[list] = None):
+        """the sampling loop over scales first .. last for the B images whose state sits in the first rows of ws (its prologue run, ws['x'] holding
+        scale `first`'s input, the caches the scales below it).  Per scale: the blocks; the scale is yielded (si, pn, l = pn * pn, cur = its first
+        token, r = the stage ratio) and the caller's loop body sets .idx, the int64 [B * l] tokens it chose, and where they apply .soft and .ed;
+        then the quantizer step (_quant_step) and, between the walk's own scales, next_map_f32.  Ends behind the quantizer step of `last`: what
+        follows is the caller's (a prune or resampling boundary, the decoder).  tr: sample()'s trace; ev: its profile_scales events."""
+        var, w = self.var, self.w
+        C, Cv, P = var.C, var.Cvae, var.patch_nums[-1]
+        x, x2 = ws['x'], ws['x2']
+        for si in range(first, last + 1):                                 # var.py:160
+            pn = var.patch_nums[si]
+            r = si / var.num_stages_minus_1 if var.num_stages_minus_1 > 0 else 0.0                  # the stage ratio (var.py:166)
+            sc = SimpleNamespace(si=si, pn=pn, l=pn * pn, cur=var.begin_ends[si][0], r=r, idx=None, soft=None, ed=None)
+            if ev: ev[si].record()
+            for bi, blk in enumerate(w['blocks']):                        # AdaLNSelfAttn.forward, basic_var.py:152-159
+                self.block(blk, ws, bi, x, x2, 2 * B, sc.l, sc.cur)
+            yield sc
+            self._quant_step(ws, B, sc)
+            if tr is not None: tr['f_hat'].append(ws['f_hat'].permute(0, 3, 1, 2).clone())
+            if si != last:
+                pq = var.patch_nums[si + 1]
+                hip.call('next_map_f32', ws['f_hat'], w['word_w'], w['word_b'], ws['lvl_pos'][sc.cur + sc.l:], x, ws['pooled'], B, P, pq, C, Cv)
+                if tr is not None: tr['pooled'].append(ws['pooled'][:B * pq * pq].view(B, pq, pq, Cv).permute(0, 3, 1, 2).clone())
+
+    def _quant_step(self, ws: dict, B: int, sc):
+        """the quantizer step of a scale (var.py:177-183): f_hat += phi(upsample(h)), h = codebook[sc.idx].  sc.soft, an Exp(1) fill [B * l, V]
+        (more_smooth): h = gumbel_softmax(filtered logits * (1 + ratio), tau) @ codebook instead, from the logits the sampler left in
+        ws['masked'] (var.py:178-180).  sc.ed = (tokens, keep, ...) [B, L] of an edit: kept positions take codebook[token] (replace_embedding)."""
+        var, w = self.var, self.w
+        V, Cv, P = var.V, var.Cvae, var.patch_nums[-1]
+        l, cur = sc.l, sc.cur
+        tail = (*_scale_tables(w['taps'], w['phi'], sc.si, len(var.patch_nums), sc.pn, P, ws['dev']), ws['up'], ws['f_hat'], B, sc.pn, P, Cv)
+        kept = () if sc.ed is None else (sc.ed[1][:, cur:], sc.ed[0][:, cur:], var.L, w['codebook'])
+        if sc.soft is not None:
+            hip.call('gumbel_softmax_f32', ws['masked'], sc.soft, ws['probs'], B * l, V, float(1 + sc.r), float(max(0.27 * (1 - sc.r * 0.95), 0.005)))
+            self.gemm(ws['probs'], w['codebook_T'], None, ws['h'], B * l)
+            hip.call('quant_accum_h_edit_f32' if kept else 'quant_accum_h_f32', ws['h'], *kept, *tail)
+        elif kept:                                                        # codebook[keep ? token : sampled]
+            hip.call('quant_accum_edit_f32', sc.idx, *kept, *tail)
+        else:
+            hip.call('quant_accum_f32', sc.idx, w['codebook'], *tail)
+
+    # -- the choosers: each leaves a scale's tokens, int64 [B * l] -------------------------------------------------------------------
+    def _logits(self, ws: dict, B: int, sc, tr: Optional[dict]):
+        """get_logits (var.py:118-124): AdaLNBeforeHead + head over the scale's 2B * l rows, into ws['logits']"""
+        self.head(ws['x'], ws['hn'], ws['xn'], ws['logits'], 2 * B * sc.l, sc.l)
+        if tr is not None: tr['logits'].append(ws['logits'][:2 * B * sc.l].view(2 * B, sc.l, self.var.V).clone())
+
+    def _sampled(self, ws: dict, B: int, sc, noise: '_Exp1', masked: Optional[torch.Tensor], t: float = 0.0, top_k: int = 0, top_p: float = 0.0,
+                 per: Optional[dict] = None, stats: Optional[dict] = None, tr: Optional[dict] = None) -> torch.Tensor:
+        """CFG + top-k/top-p + multinomial (var.py:172-175) with one fill of `noise`.  per = dict(t=[S, B] float64, top_k=[B] int32, top_p=[B] float64
+        on the device, cap=int): every image samples with its own parameters (varhip_cfg_sample_rows_f32), and t, top_k and top_p are not read.
+        masked: None, or [>= B * l, V] fp32 that receives the filtered logits.  stats: the (B, L) tensors of STATS_FIELDS; varhip_sample_stats_f32
+        runs behind the sampler into this scale's slice of them (the drawn tokens' log-probabilities, kept counts and entropies)."""
+        var = self.var
+        l, cur, V = sc.l, sc.cur, var.V
+        self._logits(ws, B, sc, tr)
+        idx = ws['idx'][:B * l]
+        fill = noise.draw(B, sc.si, l)
+        if per is not None:
+            hip.call('cfg_sample_rows_f32', ws['logits'], fill, idx, masked, B, l, V, per['t'][sc.si], per['top_k'], per['top_p'], int(per['cap']))
+        else:
+            hip.call('cfg_sample_f32', ws['logits'], fill, idx, masked, B, l, V, float(t), int(top_k), float(top_p))
+        if stats is not None:
+            hip.call('sample_stats_f32', ws['logits'], masked, idx, B, l, V, float(t), per['t'][sc.si] if per is not None else None,
+                     *[stats[key][:, cur:] for key in STATS_FIELDS], var.L)
+            if tr is not None: tr.setdefault('masked', []).append(masked[:B * l].clone())
+        return idx
+
+    def _greedy(self, ws: dict, B: int, sc, t: float, inp: Optional[tuple], tr: Optional[dict]) -> torch.Tensor:
+        """CFG + argmax: the lowest index of the CFG logits' maximum (varhip_cfg_argmax_f32) — cfg_sample_f32 with top_k=1 on every row without an
+        exact tie at its maximum; no sampler, no Exp(1) draw.  inp = (tokens, keep, ...) [B, L] of inpainting: the keep mask is fused in."""
+        l, cur = sc.l, sc.cur
+        self._logits(ws, B, sc, tr)
+        idx = ws['idx'][:B * l]
+        mask = (None, None, 0) if inp is None else (inp[1][:, cur:], inp[0][:, cur:], self.var.L)
+        hip.call('cfg_argmax_f32', ws['logits'], *mask, idx, B, l, self.var.V, float(t))
+        return idx
+
+    def _smooth_select(self, ws: dict, B: int, sc, sm: dict, t: float, masked: Optional[torch.Tensor], tr: Optional[dict]) -> torch.Tensor:
+        """neighbour-candidate selection instead of sampling (var.py:484-537, fork): no sampler, no Exp(1) draw, every position takes the most
+        likely of the nearest codebook neighbours of its ground-truth token (sm: _smooth_setup); `masked` receives the CFG logits.  The two
+        log-likelihoods accumulate in sm['ll'] and sm['dl']."""
+        l, cur, r, n, thr = sc.l, sc.cur, sc.r, sm['n'], sm['thr']
+        self._logits(ws, B, sc, tr)
+        idx = ws['idx'][:B * l]
+        hip.call('smooth_select_f32', ws['logits'], sm['gt'][:, cur:cur + l].contiguous(), sm['nbr_idx'], sm['nbr_dist'], n, 1 + int((n - 1) * r),
+                 int(thr is not None), float(thr if thr is not None else 0.0), float(r), B, l, self.var.V, float(t),
+                 idx, sm['val'], sm['dlp'], masked)
+        # var.py:537: new_tensor(max_vals) has the tokens' dtype, so every value is truncated to an integer before the sum
+        sm['ll'] = sm['ll'] + sm['val'][:B * l].to(torch.int64).sum()
+        sm['dl'] = sm['dl'] + sm['dlp'][:B * l].sum()
+        return idx
+
+    def _edit_kept(self, B: int, sc, tokens: torch.Tensor, noise: '_Exp1', gumbel: Optional['_Exp1']) -> torch.Tensor:
+        """an edit's scale whose tokens are all kept: no head, no sampler, no gumbel softmax, but the scale's fills are drawn as the notebook's
+        loop draws them (it samples, then replaces), so the RNG stream stays that of a plain call; its tokens go to the plain quantizer step"""
+        noise.draw(B, sc.si, sc.l, use=False)
+        if gumbel is not None:
+            gumbel.draw(B, sc.si, sc.l, use=False)
+        return tokens[:, sc.cur:sc.cur + sc.l].contiguous().view(-1)
+
+    def _publish(self, B: int, sc, idx: torch.Tensor, kept: bool, inp: Optional[tuple], ed: Optional[tuple], force_idx: Optional[torch.Tensor],
+                 tokens_out: Optional[torch.Tensor], tr: Optional[dict]) -> torch.Tensor:
+        """what happens to a scale's chosen tokens `idx` before the quantizer step -> the tokens that step takes.  kept: every token of the scale
+        was kept (nothing was chosen).  inp = (tokens, keep, ...) of inpainting whose chooser did not apply the mask itself:
+        torch.where(mask, gt_tokens, sampled) (var.py:326-328), in place.  force_idx (B, L): teacher forcing, replaces the tokens.  ed = (tokens,
+        keep, ...) of an edit: the replacement happens inside the quantizer step, the final tokens are only materialised for the caller
+        (tokens_out, trace).  The trace's 'idx' holds the final tokens, under edit its 'sampled' the chooser's (None on fully kept scales)."""
+        l, cur = sc.l, sc.cur
+        if inp is not None and not kept:
+            hip.call('token_select_i64', inp[1][:, cur:cur + l].contiguous(), inp[0][:, cur:cur + l].contiguous(), idx, idx, B * l)
+        if tr is not None:
+            if kept: tr['logits'].append(None)
+            if ed is not None: tr['sampled'].append(None if kept else idx.view(B, l).clone())
+            if ed is None or kept: tr['idx'].append(idx.view(B, l).clone())
+        if force_idx is not None:
+            idx = force_idx[:, cur:cur + l].to(idx.device, torch.int64).contiguous().view(-1)
+        fin = idx.view(B, l)
+        if ed is not None and not kept and (tokens_out is not None or tr is not None):
+            fin = torch.empty(B, l, dtype=torch.int64, device=idx.device)
+            hip.call('token_select_i64', ed[1][:, cur:cur + l].contiguous(), ed[0][:, cur:cur + l].contiguous(), idx, fin, B * l)
+            if tr is not None: tr['idx'].append(fin.clone())
+        if tokens_out is not None:
+            tokens_out[:, cur:cur + l].copy_(fin)
+        return idx
+
+    # -- the modes of sample(): argument checks and device preparation, each run only when its argument is given --------------------
+    def _masked(self, ws: dict, B: int, soft: bool) -> torch.Tensor:
+        """the workspace's buffer for the sampler's filtered logits (B * l_max * V * 4 bytes: more_smooth and stats share it), made on first use;
+        soft: with it the gumbel-softmax probabilities and their embedding of more_smooth"""
+        var = self.var
+        for key, cols in (('masked', var.V), ('probs', var.V), ('h', var.Cvae))[:3 if soft else 1]:
+            if key not in ws:
+                ws[key] = torch.empty(B * max(p * p for p in var.patch_nums), cols, dtype=torch.float32, device=ws['dev'])
+        return ws['masked']
+
+    def _stats_setup(self, B: int, stats: dict, dev):
+        """stats: the (B, L) tensors of STATS_FIELDS, allocated here unless the caller put contiguous ones there"""
+        var = self.var
+        for key in STATS_FIELDS:
+            dt = torch.int32 if key == 'kept' else torch.float32
+            if key not in stats:
+                stats[key] = torch.empty(B, var.L, dtype=dt, device=dev)
+            sv = stats[key]
+            if sv.dtype != dt or tuple(sv.shape) != (B, var.L) or not sv.is_contiguous() or sv.device != dev:
+                raise ValueError(f"stats['{key}'] must be a contiguous {dt} ({B}, {var.L}) tensor on the model's device")
+
+    def _inpaint_setup(self, B: int, gt_tokens: torch.Tensor, keep_mask: Optional[torch.Tensor], more_smooth: bool, dev) -> tuple:
+        """VAR.inpainting (var.py:236-364, fork): kept positions take the given token, the others are chosen; a scale whose tokens are all kept
+        skips the head, the sampler and the RNG draw, as the reference does -> (tokens int64, keep uint8, both [B, L] on the device; per scale:
+        is every token kept)"""
+        var = self.var
+        if keep_mask is None or tuple(keep_mask.shape) != tuple(gt_tokens.shape) or tuple(gt_tokens.shape) != (B, var.L):
+            raise ValueError('Mask shape must match the latent token shape obtained from vae.img_to_idxBl')
+        gt = gt_tokens.to(dev, torch.int64).contiguous()
+        if int(gt.min()) < 0 or int(gt.max()) >= var.V:
+            raise ValueError(f'gt_tokens must lie in [0, {var.V})')
+        keep = keep_mask.to(dev).bool()
+        skip = torch.stack([keep[:, b0:e0].all() for b0, e0 in var.begin_ends]).tolist()      # one host sync for all scales
+        if more_smooth and any(skip):
+            # var.py:312-341 (fork): on a fully kept scale the reference feeds the gumbel softmax the PREVIOUS scale's logits
+            # (a NameError on the first scale, a shape error afterwards) — there is no behaviour to reproduce
+            raise NotImplementedError('inpainting(more_smooth=True) with a fully kept scale: undefined in the reference (it reads logits it did not compute)')
+        return gt, keep.to(torch.uint8).contiguous(), skip
+
+    def _edit_setup(self, B: int, edit: dict, dev) -> tuple:
+        """VAR.autoregressive_infer_cfg_with_mask (demo_zero_shot_edit.ipynb cell 2): the mask is resized to every scale on the device
+        (varhip_edit_keep_u8); kept positions take codebook[token] in the quantizer step (varhip_quant_accum[_h]_edit_f32).  Unlike inpainting
+        every scale draws its Exp(1) fill, and with more_smooth its gumbel fill (_edit_kept) -> (tokens int64, keep uint8, both [B, L] on the
+        device; per scale: is every token kept)"""
+        var = self.var
+        tokens, mask = edit['tokens'], edit['mask']
+        if tokens.dtype != torch.int64 or tuple(tokens.shape) != (B, var.L):
+            raise ValueError(f'edit tokens must be an int64 ({B}, {var.L}) tensor')
+        if mask.dtype != torch.float32 or mask.dim() != 3 or mask.shape[0] not in (1, B) or min(mask.shape[1:]) < 1:
+            raise ValueError(f'edit mask must be a float32 (1 or {B}, h, w) tensor')
+        tokens = tokens.to(dev).contiguous()
+        if int(tokens.min()) < 0 or int(tokens.max()) >= var.V:
+            raise ValueError(f'edit tokens must lie in [0, {var.V})')
+        mask = mask.to(dev).contiguous()
+        keep = torch.empty(B, var.L, dtype=torch.uint8, device=dev)
+        pns = torch.tensor(var.patch_nums, dtype=torch.int32)               # a host array: the launcher copies it into the kernel's arguments
+        hip.call('edit_keep_u8', mask, mask.shape[0], mask.shape[1], mask.shape[2], pns, len(var.patch_nums), B, keep)
+        skip = torch.stack([keep[:, b0:e0].all() for b0, e0 in var.begin_ends]).tolist()      # one host sync for all scales
+        return tokens, keep, skip
+
+    def _smooth_setup(self, B: int, smooth: dict, dev) -> dict:
+        """VAR.smooth_sampling (var.py:367-572, fork): the ground-truth tokens, the table of every code's n nearest codes, the per-position
+        outputs of varhip_smooth_select_f32 and the two accumulated log-likelihoods (_smooth_select adds every scale's)"""
+        var = self.var
+        gt = smooth['gt'].to(dev, torch.int64).contiguous()
+        n = int(smooth['n'])
+        if tuple(gt.shape) != (B, var.L) or int(gt.min()) < 0 or int(gt.max()) >= var.V:
+            raise ValueError(f'gt_tokens must be (B, L) token ids in [0, {var.V})')
+        if not 1 <= n <= var.V:
+            raise ValueError(f'n must lie in [1, {var.V}]')
+        nbr_idx, nbr_dist = self.neighbor_table(n)
+        rows = B * max(p * p for p in var.patch_nums)
+        return dict(gt=gt, n=n, thr=smooth.get('thr'), nbr_idx=nbr_idx, nbr_dist=nbr_dist,
+                    val=torch.empty(rows, dtype=torch.float32, device=dev), dlp=torch.empty(rows, dtype=torch.float32, device=dev),
+                    ll=torch.zeros((), dtype=torch.float32, device=dev), dl=torch.zeros((), dtype=torch.float32, device=dev))
+
     # -- the loop ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def sample(self, B: int, label_B: torch.Tensor, rng: Optional[torch.Generator], cfg: float, top_k: int, top_p: float,
@@ -1166,38 +1390,26 @@ class SamplingEngine(_Engine):
                stats: Optional[dict] = None) -> torch.Tensor:
         """label_B: int64 [B] on the device.  noises: optional per-scale Exp(1) tensors [B*l, V] — a list, or a callable
         (si, l) -> tensor (tests inject the CPU generator's stream; var_amd.multi hands each rank its rows); by default they
-        are drawn with `exponential_(generator=rng)` exactly as torch.multinomial (helpers.py:19) would.
-        gt_tokens/keep_mask [B, L]: VAR.inpainting (var.py:236-364, fork) — kept positions take the given token, the others are
-        sampled; a scale whose tokens are all kept skips the head, the sampler and the RNG draw, as the reference does.
-        smooth = dict(gt=[B, L] tokens, n=int, thr=float|None): VAR.smooth_sampling (var.py:367-572, fork) — no sampler, no Exp(1)
-        draw: every position takes the most likely of the nearest codebook neighbours of its ground-truth token; the two
-        accumulated log-likelihoods are left in self.last_smooth.
-        greedy=True: no sampler and no Exp(1) draw (rng, noises, top_k and top_p are not read): every sampled position takes the lowest index
-        of the CFG logits' maximum (varhip_cfg_argmax_f32, the keep mask fused in) — cfg_sample_f32 with top_k=1 on every row without an
-        exact tie at its maximum.  tokens_out: optional int64 [B, L] on the device, receives every scale's tokens (kept and chosen).
-        edit = dict(tokens=[B, L] int64, mask=[Bm, h, w] fp32, Bm in {1, B}): VAR.autoregressive_infer_cfg_with_mask (demo_zero_shot_edit.ipynb
-        cell 2) — the mask is resized to every scale on the device (varhip_edit_keep_u8), kept positions take codebook[token] in the quantizer
-        step (varhip_quant_accum[_h]_edit_f32).  Unlike inpainting every scale draws its Exp(1) fill (and with more_smooth its gumbel fill), so
-        the RNG stream is that of a plain call; a fully kept scale draws them and skips the head, the sampler and the gumbel softmax.  The
-        trace's 'idx' holds the final tokens, its 'sampled' the sampler's (None on fully kept scales).
+        are drawn with `exponential_(generator=rng)` exactly as torch.multinomial (helpers.py:19) would (_Exp1).  gumbel_noises: the same for
+        the second fill per scale that more_smooth draws.
+        gt_tokens/keep_mask [B, L]: VAR.inpainting (_inpaint_setup).  edit = dict(tokens=[B, L] int64, mask=[Bm, h, w] fp32, Bm in {1, B}):
+        VAR.autoregressive_infer_cfg_with_mask (_edit_setup).  smooth = dict(gt=[B, L] tokens, n=int, thr=float|None): VAR.smooth_sampling
+        (_smooth_setup); the two accumulated log-likelihoods are left in self.last_smooth.
+        greedy=True: every chosen position takes the argmax of the CFG logits (_greedy); rng, noises, top_k and top_p are not read.
+        tokens_out: optional int64 [B, L] on the device, receives every scale's tokens (kept and chosen).
         per_image = dict(t=[S, B] float64, top_k=[B] int32, top_p=[B] float64 on the device, cap=int): every image samples with its own
-        parameters (varhip_cfg_sample_rows_f32; sample_per_image builds the tables); cfg, top_k and top_p are not read.  gumbel_noises may be
-        a callable (si, l) -> tensor like noises.
-        stats: a dict (VAR.autoregressive_infer_cfg_scored): the sampler leaves its filtered logits in the workspace's `masked` buffer (B * l_max
-        * V * 4 bytes, the one more_smooth uses) and varhip_sample_stats_f32 runs behind it on every scale into the (B, L) tensors
-        stats['logp_cond' | 'logp_guided' | 'logp_drawn' | 'entropy'] (fp32) and stats['kept'] (int32), allocated here unless the caller put
-        contiguous ones there.  One launch per scale and nothing else: the RNG draws, the other kernels and their order are those of the
-        call without it.  Combines with more_smooth and per_image; not with smooth, greedy, gt_tokens / keep_mask or edit, whose kept
-        positions have no drawn distribution.
+        parameters (sample_per_image builds the tables); cfg, top_k and top_p are not read.
+        stats: a dict (VAR.autoregressive_infer_cfg_scored), receives the (B, L) tensors stats['logp_cond' | 'logp_guided' | 'logp_drawn' |
+        'entropy'] (fp32) and stats['kept'] (int32).  One launch per scale and nothing else (_sampled): the RNG draws, the other kernels and
+        their order are those of the call without it.  Combines with more_smooth and per_image; not with smooth, greedy, gt_tokens /
+        keep_mask or edit, whose kept positions have no drawn distribution.
         force_idx/trace are test hooks (teacher forcing; keep per-scale logits/tokens/f_hat, with stats also the filtered logits 'masked')."""
         var = self.var
         self.resolve_precision()
         self.refresh()
         self._wait_ready()
-        w, ws = self.w, self.workspace(B)
-        dev = ws['dev']
-        C, H, V, Cv, S = var.C, var.num_heads, var.V, var.Cvae, len(var.patch_nums)
-        P, B2 = var.patch_nums[-1], 2 * B
+        ws = self.workspace(B)
+        dev, S = ws['dev'], len(var.patch_nums)
         if label_B.dtype != torch.int64 or label_B.numel() != B:
             raise ValueError('label_B must be an int64 tensor of B labels')
         self._check_labels(label_B)
@@ -1213,184 +1425,42 @@ class SamplingEngine(_Engine):
         if tokens_out is not None and (tokens_out.dtype != torch.int64 or tuple(tokens_out.shape) != (B, var.L) or not tokens_out.is_contiguous()):
             raise ValueError(f'tokens_out must be a contiguous int64 ({B}, {var.L}) tensor')
         tr = dict(logits=[], idx=[], f_hat=[], pooled=[]) if trace else None
-        gt = keep_u8 = skip = masked = None
-        draws = 0
-        if more_smooth:
-            lmax = max(p * p for p in var.patch_nums)
-            if 'probs' not in ws:
-                ws['masked'] = torch.empty(B * lmax, V, dtype=torch.float32, device=dev)
-                ws['probs'] = torch.empty(B * lmax, V, dtype=torch.float32, device=dev)
-                ws['h'] = torch.empty(B * lmax, Cv, dtype=torch.float32, device=dev)
-            masked = ws['masked']
+        masked = self._masked(ws, B, more_smooth) if more_smooth or stats is not None else None
         if stats is not None:
-            if 'masked' not in ws:
-                ws['masked'] = torch.empty(B * max(p * p for p in var.patch_nums), V, dtype=torch.float32, device=dev)
-            masked = ws['masked']
-            for key in STATS_FIELDS:
-                dt = torch.int32 if key == 'kept' else torch.float32
-                if key not in stats:
-                    stats[key] = torch.empty(B, var.L, dtype=dt, device=dev)
-                sv = stats[key]
-                if sv.dtype != dt or tuple(sv.shape) != (B, var.L) or not sv.is_contiguous() or sv.device != dev:
-                    raise ValueError(f"stats['{key}'] must be a contiguous {dt} ({B}, {var.L}) tensor on the model's device")
-        if gt_tokens is not None:
-            if keep_mask is None or tuple(keep_mask.shape) != tuple(gt_tokens.shape) or tuple(gt_tokens.shape) != (B, var.L):
-                raise ValueError('Mask shape must match the latent token shape obtained from vae.img_to_idxBl')
-            gt = gt_tokens.to(dev, torch.int64).contiguous()
-            if int(gt.min()) < 0 or int(gt.max()) >= V:
-                raise ValueError(f'gt_tokens must lie in [0, {V})')
-            keep = keep_mask.to(dev).bool()
-            keep_u8 = keep.to(torch.uint8).contiguous()
-            skip = torch.stack([keep[:, b0:e0].all() for b0, e0 in var.begin_ends]).tolist()      # one host sync for all scales
-            if more_smooth and any(skip):
-                # var.py:312-341 (fork): on a fully kept scale the reference feeds the gumbel softmax the PREVIOUS scale's logits
-                # (a NameError on the first scale, a shape error afterwards) — there is no behaviour to reproduce
-                raise NotImplementedError('inpainting(more_smooth=True) with a fully kept scale: undefined in the reference (it reads logits it did not compute)')
-
-        ed_gt = ed_keep = None
-        if edit is not None:
-            ed_gt, ed_mask = edit['tokens'], edit['mask']
-            if ed_gt.dtype != torch.int64 or tuple(ed_gt.shape) != (B, var.L):
-                raise ValueError(f'edit tokens must be an int64 ({B}, {var.L}) tensor')
-            if ed_mask.dtype != torch.float32 or ed_mask.dim() != 3 or ed_mask.shape[0] not in (1, B) or min(ed_mask.shape[1:]) < 1:
-                raise ValueError(f'edit mask must be a float32 (1 or {B}, h, w) tensor')
-            ed_gt = ed_gt.to(dev).contiguous()
-            if int(ed_gt.min()) < 0 or int(ed_gt.max()) >= V:
-                raise ValueError(f'edit tokens must lie in [0, {V})')
-            ed_mask = ed_mask.to(dev).contiguous()
-            ed_keep = torch.empty(B, var.L, dtype=torch.uint8, device=dev)
-            pns = torch.tensor(var.patch_nums, dtype=torch.int32)               # a host array: the launcher copies it into the kernel's arguments
-            hip.call('edit_keep_u8', ed_mask, ed_mask.shape[0], ed_mask.shape[1], ed_mask.shape[2], pns, S, B, ed_keep)
-            skip = torch.stack([ed_keep[:, b0:e0].all() for b0, e0 in var.begin_ends]).tolist()      # one host sync for all scales
-            if trace: tr['sampled'] = []
-
-        sm_gt = sm_ll = sm_dl = None
-        if smooth is not None:
-            if gt_tokens is not None:
-                raise ValueError('smooth sampling and inpainting are separate entry points')
-            sm_gt = smooth['gt'].to(dev, torch.int64).contiguous()
-            sm_n, sm_thr = int(smooth['n']), smooth.get('thr')
-            if tuple(sm_gt.shape) != (B, var.L) or int(sm_gt.min()) < 0 or int(sm_gt.max()) >= V:
-                raise ValueError(f'gt_tokens must be (B, L) token ids in [0, {V})')
-            if not 1 <= sm_n <= V:
-                raise ValueError(f'n must lie in [1, {V}]')
-            nbr_idx, nbr_dist = self.neighbor_table(sm_n)
-            lmax = max(p * p for p in var.patch_nums)
-            sm_val = torch.empty(B * lmax, dtype=torch.float32, device=dev)
-            sm_dlp = torch.empty(B * lmax, dtype=torch.float32, device=dev)
-            sm_ll = torch.zeros((), dtype=torch.float32, device=dev)
-            sm_dl = torch.zeros((), dtype=torch.float32, device=dev)
+            self._stats_setup(B, stats, dev)
+        inp = self._inpaint_setup(B, gt_tokens, keep_mask, more_smooth, dev) if gt_tokens is not None else None
+        ed = self._edit_setup(B, edit, dev) if edit is not None else None
+        if ed is not None and trace: tr['sampled'] = []
+        if smooth is not None and gt_tokens is not None:
+            raise ValueError('smooth sampling and inpainting are separate entry points')
+        sm = self._smooth_setup(B, smooth, dev) if smooth is not None else None
+        skip = (inp or ed or (None, None, None))[2]
+        noise = _Exp1(noises, rng, var.V, dev)
+        gumbel = _Exp1(gumbel_noises, rng, var.V, dev) if more_smooth else None
 
         ws['f_hat'].zero_()
-        self._prologue(ws, label_B, B2)
-
-        x, x2 = ws['x'], ws['x2']
-        cur = 0
+        self._prologue(ws, label_B, 2 * B)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(S + 2)] if getattr(self, 'profile_scales', False) else None
-        for si, pn in enumerate(var.patch_nums):                          # var.py:160
-            l = pn * pn
-            M = B2 * l
-            if ev: ev[si].record()
-            for bi, blk in enumerate(w['blocks']):                        # AdaLNSelfAttn.forward, basic_var.py:152-159
-                self.block(blk, ws, bi, x, x2, B2, l, cur)
-            cur += l
-            if skip is not None and skip[si] and ed_gt is not None:
-                # edit, every token of this scale is kept: no head, no sampler, no gumbel softmax, but the scale's fills are drawn as the
-                # notebook's loop draws them (it samples, then replaces), and its tokens go to the plain quantizer step below
-                if noises is not None:
-                    draws += 1
-                else:
-                    torch.empty(B * l, V, dtype=torch.float32, device=dev).exponential_(1, generator=rng)
-                if more_smooth and gumbel_noises is None:
-                    torch.empty(B * l, V, dtype=torch.float32, device=dev).exponential_(generator=rng)
-                idx = ed_gt[:, cur - l:cur].contiguous().view(-1)
-                if trace: tr['logits'].append(None); tr['sampled'].append(None); tr['idx'].append(idx.view(B, l).clone())
-            elif skip is not None and skip[si]:
-                # inpainting, every token of this scale is kept: no head, no sampling, no RNG draw (var.py:312-313, fork)
-                idx = gt[:, cur - l:cur].contiguous().view(-1)
-                if trace: tr['logits'].append(None); tr['idx'].append(idx.view(B, l).clone())
+        for sc in self._scales(ws, B, 0, S - 1, tr, ev):
+            t = cfg * sc.r if S > 1 else 0.0
+            kept = skip is not None and skip[sc.si]
+            if kept and ed is not None:
+                idx = self._edit_kept(B, sc, ed[0], noise, gumbel)
+            elif kept:        # inpainting, every token of this scale is kept: no head, no sampling, no RNG draw (var.py:312-313, fork)
+                idx = inp[0][:, sc.cur:sc.cur + sc.l].contiguous().view(-1)
+            elif sm is not None:
+                idx = self._smooth_select(ws, B, sc, sm, t, masked, tr)
+            elif greedy:
+                idx = self._greedy(ws, B, sc, t, inp, tr)
             else:
-                # get_logits (var.py:118-124): AdaLNBeforeHead + head
-                self.head(x, ws['hn'], ws['xn'], ws['logits'], M, l)
-                if trace: tr['logits'].append(ws['logits'][:M].view(B2, l, V).clone())
-                t = cfg * (si / var.num_stages_minus_1) if var.num_stages_minus_1 > 0 else 0.0
-                idx = ws['idx'][:B * l]
-                if sm_gt is not None:
-                    # neighbour-candidate selection instead of sampling (var.py:484-537, fork); `masked` receives the CFG logits
-                    r_ = si / var.num_stages_minus_1 if var.num_stages_minus_1 > 0 else 0.0
-                    hip.call('smooth_select_f32', ws['logits'], sm_gt[:, cur - l:cur].contiguous(), nbr_idx, nbr_dist, sm_n, 1 + int((sm_n - 1) * r_),
-                             int(sm_thr is not None), float(sm_thr if sm_thr is not None else 0.0), float(r_), B, l, V, float(t),
-                             idx, sm_val, sm_dlp, masked)
-                    # var.py:537: new_tensor(max_vals) has the tokens' dtype, so every value is truncated to an integer before the sum
-                    sm_ll = sm_ll + sm_val[:B * l].to(torch.int64).sum()
-                    sm_dl = sm_dl + sm_dlp[:B * l].sum()
-                elif greedy:
-                    # CFG + argmax, the keep mask fused in (what top_k=1 + multinomial select on rows without a tie)
-                    if gt is not None:
-                        hip.call('cfg_argmax_f32', ws['logits'], keep_u8[:, cur - l:], gt[:, cur - l:], var.L, idx, B, l, V, float(t))
-                    else:
-                        hip.call('cfg_argmax_f32', ws['logits'], None, None, 0, idx, B, l, V, float(t))
-                else:
-                    # CFG + top-k/top-p + multinomial (var.py:172-175)
-                    if noises is not None:        # a list is indexed by draw count: skipped (fully kept) scales draw nothing
-                        noise = (noises(si, l) if callable(noises) else noises[draws]).to(dev, torch.float32).contiguous()
-                        draws += 1
-                    else:
-                        noise = torch.empty(B * l, V, dtype=torch.float32, device=dev).exponential_(1, generator=rng)
-                    if per_image is not None:
-                        hip.call('cfg_sample_rows_f32', ws['logits'], noise, idx, masked, B, l, V, per_image['t'][si], per_image['top_k'],
-                                 per_image['top_p'], int(per_image['cap']))
-                    else:
-                        hip.call('cfg_sample_f32', ws['logits'], noise, idx, masked, B, l, V, float(t), int(top_k), float(top_p))
-                    if stats is not None:         # the drawn tokens' log-probabilities, kept counts and entropies: this scale's slice of the (B, L) tensors
-                        hip.call('sample_stats_f32', ws['logits'], masked, idx, B, l, V, float(t), per_image['t'][si] if per_image is not None else None,
-                                 *[stats[key][:, cur - l:] for key in STATS_FIELDS], var.L)
-                        if trace: tr.setdefault('masked', []).append(masked[:B * l].clone())
-                if gt is not None and not greedy:                         # torch.where(mask, gt_tokens, sampled) (var.py:326-328)
-                    hip.call('token_select_i64', keep_u8[:, cur - l:cur].contiguous(), gt[:, cur - l:cur].contiguous(), idx, idx, B * l)
-                if trace and ed_gt is not None: tr['sampled'].append(idx.view(B, l).clone())
-                if trace and ed_gt is None: tr['idx'].append(idx.view(B, l).clone())
-            if force_idx is not None:
-                idx = force_idx[:, cur - l:cur].to(dev, torch.int64).contiguous().view(-1)
-            # edit on a scale that is not fully kept: the replacement happens inside the quantizer step; the final tokens are only
-            # materialised for the caller (tokens_out, trace)
-            ed_step = ed_gt is not None and not skip[si]
-            if ed_step and (tokens_out is not None or trace):
-                fin = torch.empty(B, l, dtype=torch.int64, device=dev)
-                hip.call('token_select_i64', ed_keep[:, cur - l:cur].contiguous(), ed_gt[:, cur - l:cur].contiguous(), idx, fin, B * l)
-                if trace: tr['idx'].append(fin.clone())
-                if tokens_out is not None: tokens_out[:, cur - l:cur].copy_(fin)
-            elif tokens_out is not None:
-                tokens_out[:, cur - l:cur].copy_(idx.view(B, l))
-            # quantizer step (var.py:177-183)
-            ti, tw, pw, pb, ratio = _scale_tables(w['taps'], w['phi'], si, S, pn, P, dev)
-            if more_smooth and not (ed_gt is not None and skip[si]):
-                # h = gumbel_softmax(filtered logits * (1+ratio), tau) @ codebook, a second Exp(1) fill per scale (var.py:178-180)
-                r_ = si / var.num_stages_minus_1 if var.num_stages_minus_1 > 0 else 0.0
-                gum_t = max(0.27 * (1 - r_ * 0.95), 0.005)
-                if gumbel_noises is not None:
-                    gn = (gumbel_noises(si, l) if callable(gumbel_noises) else gumbel_noises[si]).to(dev, torch.float32).contiguous()
-                else:
-                    gn = torch.empty(B * l, V, dtype=torch.float32, device=dev).exponential_(generator=rng)
-                hip.call('gumbel_softmax_f32', masked, gn, ws['probs'], B * l, V, float(1 + r_), float(gum_t))
-                self.gemm(ws['probs'], w['codebook_T'], None, ws['h'], B * l)
-                if ed_step:               # h_BChw = codebook[gt] where kept, else the gumbel-softmax embedding (replace_embedding)
-                    hip.call('quant_accum_h_edit_f32', ws['h'], ed_keep[:, cur - l:], ed_gt[:, cur - l:], var.L, w['codebook'], ti, tw, pw, pb, ratio,
-                             ws['up'], ws['f_hat'], B, pn, P, Cv)
-                else:
-                    hip.call('quant_accum_h_f32', ws['h'], ti, tw, pw, pb, ratio, ws['up'], ws['f_hat'], B, pn, P, Cv)
-            elif ed_step:                 # codebook[keep ? gt : sampled]
-                hip.call('quant_accum_edit_f32', idx, ed_keep[:, cur - l:], ed_gt[:, cur - l:], var.L, w['codebook'], ti, tw, pw, pb, ratio,
-                         ws['up'], ws['f_hat'], B, pn, P, Cv)
-            else:
-                hip.call('quant_accum_f32', idx, w['codebook'], ti, tw, pw, pb, ratio, ws['up'], ws['f_hat'], B, pn, P, Cv)
-            if trace: tr['f_hat'].append(ws['f_hat'].permute(0, 3, 1, 2).clone())
-            if si != S - 1:
-                pq = var.patch_nums[si + 1]
-                hip.call('next_map_f32', ws['f_hat'], w['word_w'], w['word_b'], ws['lvl_pos'][cur:], x, ws['pooled'], B, P, pq, C, Cv)
-                if trace: tr['pooled'].append(ws['pooled'][:B * pq * pq].view(B, pq, pq, Cv).permute(0, 3, 1, 2).clone())
+                idx = self._sampled(ws, B, sc, noise, masked, t, top_k, top_p, per_image, stats, tr)
+            sc.idx = self._publish(B, sc, idx, kept, None if greedy else inp, ed, force_idx, tokens_out, tr)
+            if not kept:              # (a fully kept scale takes the plain quantizer step: under more_smooth it is an edit's, _inpaint_setup refuses its own)
+                sc.ed = ed
+                if more_smooth:
+                    sc.soft = gumbel.draw(B, sc.si, sc.l)
         self.last_trace = tr
-        self.last_smooth = (sm_ll, sm_dl) if sm_gt is not None else None
+        self.last_smooth = (sm['ll'], sm['dl']) if sm is not None else None
         if not decode:
             return ws['f_hat'].permute(0, 3, 1, 2).contiguous()
         if ev: ev[S].record()
@@ -1410,23 +1480,53 @@ class SamplingEngine(_Engine):
         b's rows depend on (seeds[b], scale, row, column, draw) only, the sampler reads image b's parameters from device tables
         (varhip_cfg_sample_rows_f32) — so a request's tokens do not depend on what it is batched with.  The tables are built and uploaded once,
         outside the scale loop; per scale: one fill launch, one sampler launch (and the draw-1 fill under more_smooth)."""
-        var = self.var
-        B, S, V = len(seeds), len(var.patch_nums), var.V
-        dev = var.pos_start.device
-        tab = per_image_tables(cfg, top_k, top_p, S, V)
-        # one upload: [S*B t | B top_p] float64, then the two integer tables
-        f64 = torch.from_numpy(np.concatenate((tab['t'].reshape(-1), tab['top_p']))).to(dev, non_blocking=False)
-        per = dict(t=f64[:S * B].view(S, B), top_p=f64[S * B:], top_k=torch.from_numpy(tab['top_k']).to(dev), cap=tab['cap'])
-        seeds_d = torch.from_numpy(np.asarray(seeds, dtype=np.int64)).to(dev)
-
-        def fill(draw):
-            def fn(si, l):
-                out = torch.empty(B * l, V, dtype=torch.float32, device=dev)
-                hip.call('exp1_philox_f32', seeds_d, B, l, V, si, draw, out)
-                return out
-            return fn
-        return self.sample(B, label_B, None, 0.0, 0, 0.0, noises=fill(0), gumbel_noises=fill(1) if more_smooth else None,
+        per, seeds_d = self._per_image_upload(cfg, top_k, top_p, seeds)
+        return self.sample(len(seeds), label_B, None, 0.0, 0, 0.0, noises=self._philox(seeds_d, 0), gumbel_noises=self._philox(seeds_d, 1) if more_smooth else None,
                            more_smooth=more_smooth, tokens_out=tokens_out, trace=trace, per_image=per, decode=decode, stats=stats)
+
+    def _per_image_upload(self, cfg, top_k, top_p, seeds=None) -> tuple:
+        """the device side of per-row sampler parameters (host sequences of one length R) -> (sample()'s `per_image` dict, the int64 [R] seeds on
+        the device or None)"""
+        var = self.var
+        R, S, dev = len(cfg), len(var.patch_nums), var.pos_start.device
+        tab = per_image_tables(cfg, top_k, top_p, S, var.V)
+        # one upload: [S*R t | R top_p] float64, then the two integer tables
+        f64 = torch.from_numpy(np.concatenate((tab['t'].reshape(-1), tab['top_p']))).to(dev)
+        per = dict(t=f64[:S * R].view(S, R), top_p=f64[S * R:], top_k=torch.from_numpy(tab['top_k']).to(dev), cap=tab['cap'])
+        return per, None if seeds is None else torch.from_numpy(np.asarray(seeds, dtype=np.int64)).to(dev)
+
+    def _philox(self, seeds_d: torch.Tensor, draw: int):
+        """the project's counter-based Exp(1) stream as a noise source of _Exp1: (si, l) -> the fill [R * l, V] of draw `draw` (0: the sampler's,
+        1: the gumbel softmax's) of scale si, row r keyed by seeds_d[r] (varhip_exp1_philox_f32)"""
+        R, V = seeds_d.numel(), self.var.V
+
+        def fill(si, l):
+            out = torch.empty(R * l, V, dtype=torch.float32, device=seeds_d.device)
+            hip.call('exp1_philox_f32', seeds_d, R, l, V, si, draw, out)
+            return out
+        return fill
+
+    def _begin_rows(self, who: str, what: str, label_N: torch.Tensor, N: int, n: int, most: int, max_images: int):
+        """how a call over N = B * n rows, n `what` per image, opens: its limits, the call's precision and weights, the labels' check -> the device"""
+        if n > most:
+            raise ValueError(f'{who} takes at most {most} {what} per image, got {n}')
+        if n > max_images:
+            raise ValueError(f'max_images = {max_images} holds no whole image of n = {n} {what}')
+        self.resolve_precision()
+        self.refresh()
+        self._wait_ready()
+        if label_N.dtype != torch.int64 or label_N.numel() != N:
+            raise ValueError('label_N must be an int64 tensor of B * n labels')
+        self._check_labels(label_N)
+        return self.var.pos_start.device
+
+    def _scored_scales(self, ws: dict, R: int, first: int, last: int, per: dict, seeds_d: torch.Tensor, stats: dict, tokens: torch.Tensor):
+        """scales first .. last of sample_per_image(stats=..., decode=False, tokens_out=tokens) for the R rows whose state sits in ws (_scales): the
+        stages of sample_best_of_pruned and sample_smc.  ws['masked'] takes the filtered logits."""
+        noise = _Exp1(self._philox(seeds_d, 0), None, self.var.V, ws['dev'])
+        for sc in self._scales(ws, R, first, last):
+            sc.idx = self._sampled(ws, R, sc, noise, ws['masked'], per=per, stats=stats)
+            tokens[:, sc.cur:sc.cur + sc.l].copy_(sc.idx.view(R, sc.l))
 
     # -- best-of-n (VAR.sample_best_of) ---------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -1457,38 +1557,12 @@ class SamplingEngine(_Engine):
         return {key: v.index_select(0, win) for key, v in rec.items()}, f_all.index_select(0, win), totals, choice
 
     # -- best-of-n with per-scale pruning (VAR.sample_best_of_pruned) -------------------------------------------------------------------
-    def _bop_scales(self, ws: dict, B: int, first: int, last: int, per: dict, seeds_d: torch.Tensor, stats: dict, tokens: torch.Tensor):
-        """scales first .. last of sample_per_image(stats=..., decode=False) for the B candidates whose state sits in the first rows of ws (its
-        prologue run, ws['x'] holding scale `first`'s input, the caches scales < first): the launches of sample()'s plain per-image branch, scale
-        by scale — blocks, head, Philox fill, varhip_cfg_sample_rows_f32, varhip_sample_stats_f32, quantizer step — and next_map_f32 between
-        the stage's own scales.  Ends behind the quantizer step of `last`: what follows it is the caller's (a prune boundary, or nothing)."""
-        var, w = self.var, self.w
-        dev = ws['dev']
-        C, V, Cv, S, P = var.C, var.V, var.Cvae, len(var.patch_nums), var.patch_nums[-1]
-        x, x2, masked = ws['x'], ws['x2'], ws['masked']
-        for si in range(first, last + 1):
-            pn = var.patch_nums[si]
-            cur, l = var.begin_ends[si][0], pn * pn
-            for bi, blk in enumerate(w['blocks']):
-                self.block(blk, ws, bi, x, x2, 2 * B, l, cur)
-            self.head(x, ws['hn'], ws['xn'], ws['logits'], 2 * B * l, l)
-            idx = ws['idx'][:B * l]
-            noise = torch.empty(B * l, V, dtype=torch.float32, device=dev)
-            hip.call('exp1_philox_f32', seeds_d, B, l, V, si, 0, noise)
-            hip.call('cfg_sample_rows_f32', ws['logits'], noise, idx, masked, B, l, V, per['t'][si], per['top_k'], per['top_p'], int(per['cap']))
-            hip.call('sample_stats_f32', ws['logits'], masked, idx, B, l, V, 0.0, per['t'][si], *[stats[key][:, cur:] for key in STATS_FIELDS], var.L)
-            tokens[:, cur:cur + l].copy_(idx.view(B, l))
-            ti, tw, pw, pb, ratio = _scale_tables(w['taps'], w['phi'], si, S, pn, P, dev)
-            hip.call('quant_accum_f32', idx, w['codebook'], ti, tw, pw, pb, ratio, ws['up'], ws['f_hat'], B, pn, P, Cv)
-            if si != last:
-                hip.call('next_map_f32', ws['f_hat'], w['word_w'], w['word_b'], ws['lvl_pos'][cur + l:], x, ws['pooled'], B, P, var.patch_nums[si + 1], C, Cv)
-
     @torch.no_grad()
     def sample_best_of_pruned(self, label_N: torch.Tensor, seeds, cfg, top_k, top_p, n: int, by: str, schedule: list, max_images: int):
         """sample_best_of that stops sampling a candidate at the scale where it is dropped.  N = B * n candidates, candidate c of image b at
         position b * n + c (host sequences of length N, already spread and validated; an image's candidates share its label, cfg, top_k and
         top_p: candidate 0's are read).  schedule: [(scale, m), ...] ascending, each m below the survivor count before it (validated by the caller).
-        One stage per boundary and a final one through the last scale; a stage runs its scales on a workspace of its own batch (_bop_scales).
+        One stage per boundary and a final one through the last scale; a stage runs its scales on a workspace of its own batch (_scored_scales).
         At a boundary behind scale s, after the quantizer step: varhip_class_select_f32 adds stats[by] of the stage's scales to the float64 running
         totals and keeps each image's best m (sample_best_of's rule); the survivors' seeds and f_hat rows are gathered, varhip_kv_compact moves
         their conditional and unconditional rows of every block's K and V cache (tokens 0 .. end(s) - 1) into the next stage's workspace in one
@@ -1501,17 +1575,7 @@ class SamplingEngine(_Engine):
         var = self.var
         N, L, S, V, H = len(seeds), var.L, len(var.patch_nums), var.V, var.num_heads
         B = N // n
-        if n > self.CLASSIFY_MAX_CAND:
-            raise ValueError(f'sample_best_of_pruned takes at most {self.CLASSIFY_MAX_CAND} candidates per image, got {n}')
-        if n > max_images:
-            raise ValueError(f'max_images = {max_images} holds no whole image of n = {n} candidates')
-        self.resolve_precision()
-        self.refresh()
-        self._wait_ready()
-        dev = var.pos_start.device
-        if label_N.dtype != torch.int64 or label_N.numel() != N:
-            raise ValueError('label_N must be an int64 tensor of B * n labels')
-        self._check_labels(label_N)
+        dev = self._begin_rows('sample_best_of_pruned', 'candidates', label_N, N, n, self.CLASSIFY_MAX_CAND, max_images)
         lab_img = label_N.to(dev).view(B, n)[:, 0].contiguous()
         stages, first, m = [], 0, n                                 # (first scale, last scale, candidates per image, kept behind it)
         for s, k in list(schedule) + [(S - 1, 1)]:
@@ -1531,11 +1595,7 @@ class SamplingEngine(_Engine):
             b1 = min(B, b0 + per_chunk)
             nb = b1 - b0
             # every host table of the chunk, uploaded before its first stage: per stage the per-image sampler tables of its nb * m rows
-            pers = []
-            for _, _, m, _ in stages:
-                tab = per_image_tables(*[[v for v in x[b0 * n:b1 * n:n] for _ in range(m)] for x in (cfg, top_k, top_p)], S, V)
-                f64 = torch.from_numpy(np.concatenate((tab['t'].reshape(-1), tab['top_p']))).to(dev)
-                pers.append(dict(t=f64[:S * nb * m].view(S, nb * m), top_p=f64[S * nb * m:], top_k=torch.from_numpy(tab['top_k']).to(dev), cap=tab['cap']))
+            pers = [self._per_image_upload(*[[v for v in x[b0 * n:b1 * n:n] for _ in range(m)] for x in (cfg, top_k, top_p)])[0] for _, _, m, _ in stages]
             seeds_d = torch.from_numpy(np.asarray(seeds[b0 * n:b1 * n], dtype=np.int64)).to(dev)
             img = torch.arange(nb, device=dev).view(nb, 1)
             pos = torch.arange(n, device=dev).expand(nb, n).contiguous()        # the stage's candidates, ascending positions per image
@@ -1561,7 +1621,7 @@ class SamplingEngine(_Engine):
                              R, var.patch_nums[-1], var.patch_nums[first], var.C, var.Cvae)
                 st = {key: torch.empty(R, L, dtype=torch.int32 if key == 'kept' else torch.float32, device=dev) for key in STATS_FIELDS}
                 tok = torch.empty(R, L, dtype=torch.int64, device=dev)
-                self._bop_scales(ws, R, first, last, pers[j], seeds_d, st, tok)
+                self._scored_scales(ws, R, first, last, pers[j], seeds_d, st, tok)
                 t0, t1 = var.begin_ends[first][0], var.begin_ends[last][1]
                 rec['tokens'][b0:b1][img, pos, t0:t1] = tok.view(nb, m, L)[:, :, t0:t1]
                 for key in STATS_FIELDS:
@@ -1590,7 +1650,7 @@ class SamplingEngine(_Engine):
         N = B * n particles, particle c of image b at position b * n + c (host sequences of length N, already spread and validated; an image's
         particles share its label, cfg, top_k and top_p).  rs_seeds: B integers, the key of each image's resampling uniform.
         One workspace of nb * n rows serves all stages of a chunk (sample_best_of_pruned's first-stage set: no second cache set), _prologue runs
-        once.  A stage runs _bop_scales from the scale after the previous boundary through the next one; behind a boundary scale s, after its
+        once.  A stage runs _scored_scales from the scale after the previous boundary through the next one; behind a boundary scale s, after its
         quantizer step: (a) varhip_smc_resample_f32 adds beta * (the stage's stats[by]) to the float64 log-weights, decides by the effective
         sample size and leaves the ancestor table, survivors in place; (b) the table plus the image's row offset, and its copy shifted by R for
         the unconditional twins, is the row index; (c) ONE varhip_kv_resample launch overwrites the dead rows of every block's K and V cache,
@@ -1604,17 +1664,7 @@ class SamplingEngine(_Engine):
         var = self.var
         N, L, S, V, H = len(seeds), var.L, len(var.patch_nums), var.V, var.num_heads
         B, K = N // n, len(resample)
-        if n > self.SMC_MAX_PARTICLES:
-            raise ValueError(f'sample_smc takes at most {self.SMC_MAX_PARTICLES} particles per image, got {n}')
-        if n > max_images:
-            raise ValueError(f'max_images = {max_images} holds no whole image of n = {n} particles')
-        self.resolve_precision()
-        self.refresh()
-        self._wait_ready()
-        dev = var.pos_start.device
-        if label_N.dtype != torch.int64 or label_N.numel() != N:
-            raise ValueError('label_N must be an int64 tensor of B * n labels')
-        self._check_labels(label_N)
+        dev = self._begin_rows('sample_smc', 'particles', label_N, N, n, self.SMC_MAX_PARTICLES, max_images)
         lab = label_N.to(dev)
         P, Cv = var.patch_nums[-1], var.Cvae
         stages, first = [], 0
@@ -1642,10 +1692,7 @@ class SamplingEngine(_Engine):
             b1 = min(B, b0 + per_chunk)
             nb = b1 - b0
             R = nb * n
-            tab = per_image_tables(cfg[b0 * n:b1 * n], top_k[b0 * n:b1 * n], top_p[b0 * n:b1 * n], S, V)
-            f64 = torch.from_numpy(np.concatenate((tab['t'].reshape(-1), tab['top_p']))).to(dev)
-            per = dict(t=f64[:S * R].view(S, R), top_p=f64[S * R:], top_k=torch.from_numpy(tab['top_k']).to(dev), cap=tab['cap'])
-            seeds_d = torch.from_numpy(np.asarray(seeds[b0 * n:b1 * n], dtype=np.int64)).to(dev)
+            per, seeds_d = self._per_image_upload(*[x[b0 * n:b1 * n] for x in (cfg, top_k, top_p, seeds)])
             ws = self._bop_workspace(per_chunk * n, 0)
             caches = ws['kc'] + ws['vc']
             ptrs = torch.tensor([t.data_ptr() for t in caches], dtype=torch.int64)          # a host array: the launcher copies it
@@ -1656,7 +1703,7 @@ class SamplingEngine(_Engine):
             tok = rec['tokens'][b0 * n:b1 * n]
             lw = logw[b0:b1]
             for j, (first, last) in enumerate(stages):
-                self._bop_scales(ws, R, first, last, per, seeds_d, st, tok)
+                self._scored_scales(ws, R, first, last, per, seeds_d, st, tok)
                 t0, t1 = var.begin_ends[first][0], var.begin_ends[last][1]
                 work[j][1] += R * (t1 - t0)
                 frac = ess_frac if j < K else 0.0               # (behind the last scale: ess >= 1 > 0 * n, the weights are updated and nothing moves)
