@@ -152,6 +152,7 @@ int varhip_sampler_force_walk(int on);
  * top_k[b] == 0; the host holds the table it uploads, so it passes the number.  An image whose top_k is outside [0, V] or needs more than
  * top_k_cap gets idx_out = -1 on its rows and leaves masked_out alone (no LDS is touched).  Constraints as varhip_cfg_sample_f32, and
  * 1 <= top_k_cap <= V: VARHIP_EINVAL otherwise. */
+/* pinned against varhip_cfg_sample_f32 per image (tests/test_per_image_gpu.py) */
 int varhip_cfg_sample_rows_f32(const float* logits, const float* noise, int64_t* idx_out, float* masked_out, int B, int l, int V,
                                const double* t_cfg, const int32_t* top_k, const double* top_p, int top_k_cap, varhip_stream_t stream);
 
@@ -164,10 +165,13 @@ int varhip_cfg_sample_rows_f32(const float* logits, const float* noise, int64_t*
  * fp32 and lies in [2^-24, 1 - 2^-24]; vm_log (include/var_math.h) consists of correctly rounded operations only, so the kernel and the
  * host twin give the same bits.  This is the project's own stream, not torch's.  seeds: DEVICE int64 [B] (the host twin: host pointers);
  * out 16-byte aligned (the kernel stores 16 bytes per lane).  V % 4 != 0, B or l < 1, scale or draw < 0, a misaligned out: VARHIP_EINVAL. */
+/* pinned against its host twin below (tests/test_per_image_gpu.py) */
 int varhip_exp1_philox_f32(const int64_t* seeds, int B, int l, int V, int scale, int draw, float* out, varhip_stream_t stream);
 /* the host twin: plain host code (usable without a GPU), same arguments with host pointers, no alignment constraint */
+/* pinned against a numpy Philox4x32-10 (tests/test_per_image_cpu.py) */
 int varhip_exp1_philox_host_f32(const int64_t* seeds, int B, int l, int V, int scale, int draw, float* out);
 /* one Philox4x32-10 block on the host (known-answer tests of the integer stage against the published vectors) */
+/* pinned against the Random123 known answers (tests/test_per_image_cpu.py) */
 int varhip_philox4x32_host(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 /* the fill's transform alone on the host: out[i] = -vm_log((2 (bits[i] >> 9) + 1) * 2^-24)  (exhaustive tests over the 2^23 values of n) */
 int varhip_exp1_from_bits_host_f32(const uint32_t* bits, int64_t n, float* out);
@@ -191,11 +195,13 @@ int varhip_exp1_from_bits_host_f32(const uint32_t* bits, int64_t n, float* out);
  * the row are NaN, kept and entropy are still the row's own.  On a row holding a NaN the log-probabilities are what varhip_token_loglik_f32
  * gives there.  Constraints as the samplers': V % 256 == 0, V <= 8192, logits and masked 16-byte aligned; a NULL operand (t_rows excepted),
  * B or l < 1 or ld_out < l: VARHIP_EINVAL. */
+/* pinned against its host twin, varhip_token_loglik_f32 and float64 (tests/test_sample_stats_gpu.py) */
 int varhip_sample_stats_f32(const float* logits, const float* masked, const int64_t* idx, int B, int l, int V, double t_cfg,
                             const double* t_rows, float* lp_cond, float* lp_guided, float* lp_drawn, int32_t* kept, float* entropy,
                             int64_t ld_out, varhip_stream_t stream);
 /* the host twin: plain host code (usable without a GPU), same arguments with host pointers, no alignment constraint.  The same operations in
  * the same order (vm_exp / vm_log consist of correctly rounded operations only): the kernel's bits. */
+/* pinned against float64 (tests/test_sample_stats_cpu.py) */
 int varhip_sample_stats_host_f32(const float* logits, const float* masked, const int64_t* idx, int B, int l, int V, double t_cfg,
                                  const double* t_rows, float* lp_cond, float* lp_guided, float* lp_drawn, int32_t* kept, float* entropy,
                                  int64_t ld_out);
@@ -313,6 +319,7 @@ int varhip_gn_stats_part_f32(const double* gn_part, float* stats, int B, int nbl
  * varhip_conv3x3_gn_nhwc_f32 with the same block count H*W/128, but block 2 t + h is the 8-row half h (0 upper, 1 lower) of the t-th
  * 16 x 16 patch of the image in row-major patch order.  Needs H % 16 == 0, W % 16 == 0, Cin % 32 == 0, Cout % 32 == 0, 16-byte
  * aligned pointers; else VARHIP_EINVAL.  Results do not depend on B or on the image's position in the batch. */
+/* pinned against float64 and the direct conv (tests/test_winograd_gpu.py) */
 int varhip_conv3x3_wino_nhwc_f32(const float* in, const float* u, const float* bias, const float* resid, float* out, double* gn_part,
                                  int B, int H, int W, int Cin, int Cout, varhip_stream_t stream);
 int varhip_conv3x3_s2_nhwc_f32(const float* in, const float* w, const float* bias, float* out,
@@ -321,6 +328,7 @@ int varhip_conv3x3_s2_nhwc_f32(const float* in, const float* w, const float* bia
  * varhip_conv3x3_s2_nhwc_f32 on 16-bit operands (in [B][2H][2W][Cin], w [Cout][3][3][Cin]), fp32 accumulation on the 16-bit MFMA, + bias
  * (fp32), rounded once to the storage type: out [B][H][W][Cout].  Needs Cin % 32 == 0, Cout % 16 == 0, 16-byte aligned in / w, 8-byte
  * aligned out; else VARHIP_EINVAL.  "f16" / "bf16": the two storage types (elem16.h). */
+/* pinned against a CPU twin (tests/test_generative_gpu.py) */
 int varhip_conv3x3_s2_nhwc_f16(const void* in, const void* w, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
                                varhip_stream_t stream);
 int varhip_conv3x3_s2_nhwc_bf16(const void* in, const void* w, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
@@ -362,6 +370,7 @@ int varhip_smooth_select_f32(const float* logits, const int64_t* gt, const int32
  * ca = fl32(1 + t), cb = t, t = fl32(fl32(cfg) * fl32(si / (S-1)))), else z = logits.  gt: the pass's tokens at the scale's offset,
  * gt[i * ld_gt + t] (a token outside [0, V) scores NaN and is never read); out[i * ld_out_img + c * ld_out_cls + t] = (z_gt - max z) - log(sum exp(z - max z)).
  * Not bit-identical to torch.log_softmax (another summation order): within a few ulps of the log-sum-exp of a float64 evaluation. */
+/* pinned against float64 log_softmax (tests/test_likelihood_gpu.py) */
 int varhip_token_loglik_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V,
                             int with_uncond, float ca, float cb, float* out, int64_t ld_out_img, int64_t ld_out_cls, varhip_stream_t stream);
 
@@ -370,6 +379,7 @@ int varhip_token_loglik_f32(const float* logits, const int64_t* gt, int64_t ld_g
  * The codebook distance table: out[v * V + u] = sqrt(sum_c (cb[v][c] - cb[u][c])^2) with the arithmetic of varhip_neighbor_table_f32 (one fma
  * chain over the channels in channel order, then sqrt): every entry equals that table's distance for the same pair bit for bit; the table is
  * exactly symmetric with a zero diagonal.  codebook: [V][D], 1 <= V <= 65535; out: [V][V]. */
+/* pinned against varhip_neighbor_table_f32 (tests/test_token_scores_gpu.py) */
 int varhip_code_dist_f32(const float* codebook, int V, int D, float* out, varhip_stream_t stream);
 /* One scale of one pass of teacher-forced scoring: the pass layout, gt / out addressing and CFG combine of varhip_token_loglik_f32, and
  * p = softmax(z) per row, codes ordered by z descending with ties by ascending code index:
@@ -380,6 +390,7 @@ int varhip_code_dist_f32(const float* codebook, int V, int D, float* out, varhip
  *          with their p renormalised to sum to 1                                                                   (var_analysis.py:252-258)
  * dist: [>= V rows][ld_dist] (modes 2 and 3; the table of varhip_code_dist_f32, ld_dist >= V), may be NULL in mode 1.  V <= 2^24.
  * Bad sizes, an unknown mode or a parameter out of its range: VARHIP_EINVAL. */
+/* pinned against float64 (tests/test_token_scores_gpu.py) */
 int varhip_token_score_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V,
                            int with_uncond, float ca, float cb, int mode, int param, float thr, const float* dist, int64_t ld_dist,
                            float* out, int64_t ld_out_img, int64_t ld_out_cls, varhip_stream_t stream);
@@ -398,6 +409,7 @@ int varhip_token_score_f32(const float* logits, const int64_t* gt, int64_t ld_gt
  * execution.  The caller zeroes both arrays once.
  * NULL operands, nbins outside [1, 256], ld_cls < nbins, ld_img < classes * ld_cls, ld_gt < l, ld_dist < V, V outside (0, 2^24], min_prob NaN,
  * negative or >= 1, images / classes / l < 1: VARHIP_EINVAL. */
+/* pinned against float64 (tests/test_distance_profile_gpu.py) */
 int varhip_dist_profile_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V,
                             int with_uncond, float ca, float cb, const float* dist, int64_t ld_dist,
                             const float* edges, int nbins, float min_prob,
@@ -433,6 +445,7 @@ int varhip_dist_profile_f32(const float* logits, const int64_t* gt, int64_t ld_g
  * The register path needs V % 4 == 0 and 16-byte aligned logits (V <= 4096), anything else re-reads the row from memory; V > 4096 is a chunk
  * only.  NULL operands, images / classes / l < 1, V outside (0, 2^24], ld_gt < l, ld_prior < classes, ld_ent_cls < l, ld_ent_img < classes *
  * ld_ent_cls, ld_acc < l (chunk), ld_out < l or V > 4096 (on-chip): VARHIP_EINVAL. */
+/* pinned bit for bit against its host twin (tests/test_class_information_gpu.py) */
 int varhip_class_mix_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V, int with_uncond,
                          float ca, float cb, const float* prior, int64_t ld_prior, float* entropy, int64_t ld_ent_img, int64_t ld_ent_cls,
                          int64_t* mix_q, int64_t* hcond_q, int32_t* nanflag, int64_t ld_acc, float* h_mix, float* h_cond, float* mi,
@@ -444,6 +457,7 @@ int varhip_class_mix_finish_f32(const int64_t* mix_q, const int64_t* hcond_q, co
 /* the host twins: plain host code (usable without a GPU), same arguments with host pointers.  The same operations in the same order (vm_exp /
  * vm_log consist of correctly rounded operations only): the kernels' bits for 16-byte aligned logits (the twin takes the register path's order
  * iff V % 4 == 0 and V <= 4096). */
+/* pinned against float64 (tests/test_class_information_cpu.py) */
 int varhip_class_mix_host_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int images, int classes, int l, int V, int with_uncond,
                               float ca, float cb, const float* prior, int64_t ld_prior, float* entropy, int64_t ld_ent_img, int64_t ld_ent_cls,
                               int64_t* mix_q, int64_t* hcond_q, int32_t* nanflag, int64_t ld_acc, float* h_mix, float* h_cond, float* mi,
@@ -479,10 +493,12 @@ int varhip_class_mix_finish_host_f32(const int64_t* mix_q, const int64_t* hcond_
  * = share_bin of query t, plainly overwritten.  Calls that add into the same sums may run in any order.
  * VARHIP_EINVAL before any launch: a NULL q / kcache / ends / share_sum / nan_count, a size <= 0, curL > Lmax, curL > 4096, l != pn * pn,
  * l > curL, S1 outside [1, 16], ends not as above, radius < 0, q or kcache not 16-byte aligned, B2 or H above 65535. */
+/* pinned bit for bit against its host twin (tests/test_attention_profile_gpu.py) */
 int varhip_attn_profile_f32(const float* q, const float* kcache, int B2, int l, int H, int curL, int Lmax, const int32_t* ends, int S1,
                             int pn, int radius, int64_t* share_sum, int64_t ld_row, int64_t ld_head, int32_t* nan_count,
                             int32_t* tokens, int64_t ld_tok_row, int64_t ld_tok_head, varhip_stream_t stream);
 /* the host twin: plain host code (no GPU), host pointers, the contract above query by query: the kernel's bits */
+/* pinned against float64 (tests/test_attention_profile_cpu.py) */
 int varhip_attn_profile_host_f32(const float* q, const float* kcache, int B2, int l, int H, int curL, int Lmax, const int32_t* ends, int S1,
                                  int pn, int radius, int64_t* share_sum, int64_t ld_row, int64_t ld_head, int32_t* nan_count,
                                  int32_t* tokens, int64_t ld_tok_row, int64_t ld_tok_head);
@@ -512,16 +528,19 @@ int varhip_attn_profile_host_f32(const float* q, const float* kcache, int B2, in
  * NULL operands (maps excepted), images / classes < 1, images > 65535 (reduce), images * classes >= 2^31 (overlay), nscales outside [1, 16],
  * pn outside [1, 64], begin negative or overlapping, more than 4096 tokens from the first selected to the last, a NaN weight, ld_cls short of
  * the last selected token, ld_img < classes * ld_cls, size outside [1, 4096], alpha outside [0, 1], image_pm1 not 0 / 1: VARHIP_EINVAL. */
+/* pinned bit for bit against evidence_maps_torch (tests/test_evidence_gpu.py) */
 int varhip_evidence_reduce_f32(const float* scores, int64_t ld_img, int64_t ld_cls, int images, int classes,
                                int nscales, const int* pn, const int* begin, const float* w,
                                const int* ax_i, const float* ax_l, int size,
                                float* lo, float* hi, int* pred, float* margin, int* area, float* maps, varhip_stream_t stream);
+/* pinned byte for byte against evidence_maps_torch (tests/test_evidence_gpu.py) */
 int varhip_evidence_overlay_u8(const float* scores, int64_t ld_img, int64_t ld_cls, int images, int classes,
                                int nscales, const int* pn, const int* begin, const float* w,
                                const int* ax_i, const float* ax_l, int size,
                                const float* lo, const float* hi, const float* image, int image_pm1, double alpha,
                                uint8_t* out, varhip_stream_t stream);
 /* the 256 x 3 colour table of varhip_evidence_overlay_u8 (768 bytes); a plain host function */
+/* pinned against matplotlib's 'jet' (tests/test_evidence_cpu.py) */
 int varhip_evidence_jet_host(uint8_t* out);
 
 /* ---- the pruning step of zero-shot classification (VAR.classify) ---------------------------------------------------------------------
@@ -531,6 +550,7 @@ int varhip_evidence_jet_host(uint8_t* out);
  * below everything (-inf included), equal totals (+0 / -0, NaN / NaN) by lower index; the min(keep, cand) best indices are written to
  * kept[i * min(keep, cand) + j] in ascending index order.  keep = 1 gives the argmax of the rule.  cand <= 16384 (the totals are staged in
  * LDS); a larger cand, keep < 1, t1 < t0 or ld_cls < t1 / ld_img < cand * ld_cls with t1 > t0: VARHIP_EINVAL. */
+/* pinned against a numpy lexsort of the rule (tests/test_classify_gpu.py) */
 int varhip_class_select_f32(const float* tokens, int64_t ld_img, int64_t ld_cls, int images, int cand, int t0, int t1, double* totals,
                             int keep, int32_t* kept, varhip_stream_t stream);
 
@@ -545,6 +565,7 @@ int varhip_class_select_f32(const float* tokens, int64_t ld_img, int64_t ld_cls,
  * VARHIP_EINVAL before any launch: a NULL or misaligned pointer, nbuf / rows_src / rows_dst / H / Lmax <= 0, elem_bytes other than 2 or 4, len < 0
  * or > Lmax, rows_out < 0 or > rows_dst, any src range sharing a byte with any dst range (ranges = the whole buffers), a row of more than 2^31
  * 16-byte vectors.  len == 0 or rows_out == 0: success, nothing launched. */
+/* pinned byte for byte against numpy's gather (tests/test_kv_compact_gpu.py) */
 int varhip_kv_compact(const void* const* src, void* const* dst, int nbuf, const int32_t* idx, int rows_src, int rows_dst, int rows_out,
                       int H, int Lmax, int len, int elem_bytes, varhip_stream_t stream);
 
@@ -560,6 +581,7 @@ int varhip_kv_compact(const void* const* src, void* const* dst, int nbuf, const 
  * VARHIP_EINVAL before any launch: NULL bufs / idx / bad, a NULL or misaligned buffer, nbuf / H / Lmax <= 0, rows < 0, elem_bytes other than 2
  * or 4, len < 0 or > Lmax, two buffers sharing a byte (ranges = rows whole rows), a row of more than 2^31 16-byte vectors.
  * len == 0 or rows == 0: success, nothing launched. */
+/* pinned byte for byte against numpy's gather on a copy (tests/test_smc_kernels_gpu.py) */
 int varhip_kv_resample(void* const* bufs, int nbuf, const int32_t* idx, int rows, int H, int Lmax, int len, int elem_bytes,
                        int32_t* bad, varhip_stream_t stream);
 
@@ -586,9 +608,11 @@ int varhip_kv_resample(void* const* bufs, int nbuf, const int32_t* idx, int rows
  * n <= 2048 (an image's weights and offspring counts are staged in 40 KiB of LDS).
  * VARHIP_EINVAL before any launch: images < 1, n < 1 or n > 2048, t0 < 0, t1 < t0, scale < 0, ld_cls < t1 or ld_img < n * ld_cls when t1 > t0,
  * a NULL operand other than logw_seen (tokens may be NULL when t1 == t0). */
+/* pinned bit for bit against its host twin (tests/test_smc_kernels_gpu.py) */
 int varhip_smc_resample_f32(const float* tokens, int64_t ld_img, int64_t ld_cls, int images, int n, int t0, int t1, double beta,
                             double* logw, const int64_t* seeds, int scale, double ess_frac,
                             int32_t* anc, int32_t* did, double* ess, double* logw_seen, varhip_stream_t stream);
+/* pinned against a numpy restatement of the contract (tests/test_smc_resample_cpu.py) */
 int varhip_smc_resample_host_f32(const float* tokens, int64_t ld_img, int64_t ld_cls, int images, int n, int t0, int t1, double beta,
                                  double* logw, const int64_t* seeds, int scale, double ess_frac,
                                  int32_t* anc, int32_t* did, double* ess, double* logw_seen);
@@ -600,6 +624,7 @@ int varhip_smc_resample_host_f32(const float* tokens, int64_t ld_img, int64_t ld
  * (torch.argmax).  keep != NULL fuses torch.where(mask, gt_tokens, sampled) (var.py:326-328, fork): keep[b * ld_keep + j] != 0 writes
  * gt[b * ld_keep + j] and reads no logits.  Equal to cfg_sample_f32(top_k=1, top_p=0) (+ token_select_i64) on every row without an exact tie
  * at its maximum.  Bad sizes, keep without gt or ld_keep < l: VARHIP_EINVAL. */
+/* pinned against varhip_cfg_sample_f32(top_k=1) (tests/test_generative_gpu.py) */
 int varhip_cfg_argmax_f32(const float* logits, const uint8_t* keep, const int64_t* gt, int64_t ld_keep, int64_t* idx_out,
                           int B, int l, int V, double t_cfg, varhip_stream_t stream);
 
@@ -607,6 +632,7 @@ int varhip_cfg_argmax_f32(const float* logits, const uint8_t* keep, const int64_
  * score[r] = -(float)(sum_d |f_in[img[r] * D + d] - f_rec[r * D + d]| / D), the |.| in fp32 and the sum in float64 in one fixed order (thread t
  * of 256 adds d = t, t+256, ... ascending; the 256 partials by a pairwise tree), so a row's score does not depend on the rows beside it.
  * D < 1 or rows < 0: VARHIP_EINVAL. */
+/* pinned against the torch L1 (tests/test_generative_gpu.py) */
 int varhip_feature_l1_f32(const float* f_in, const float* f_rec, const int64_t* img, int64_t rows, int64_t D, float* score,
                           varhip_stream_t stream);
 
@@ -616,17 +642,20 @@ int varhip_feature_l1_f32(const float* f_in, const float* f_rec, const int64_t* 
  * patch_nums: a HOST array of S int32 (1 <= S <= 32), L = sum pn^2, keep_out: [B][L] uint8.  upsample_bilinear2d's fp32 arithmetic: scale = (float)h / pn,
  * src = max(fma(scale, d + 0.5f, -0.5f), 0), i0 = (int)src, i1 = i0 + (i0 < h - 1), l1 = src - i0, l0 = 1 - l1, then
  * v = l0h * (l0w * x00 + l1w * x01) + l1h * (l0w * x10 + l1w * x11), each operation rounded.  Bad sizes: VARHIP_EINVAL. */
+/* pinned against F.interpolate > 0.5 and the reference's maps (tests/test_edit_gpu.py) */
 int varhip_edit_keep_u8(const float* mask, int Bm, int h, int w, const int32_t* patch_nums, int S, int B, uint8_t* keep_out, varhip_stream_t stream);
 
 /* varhip_quant_accum_f32 with replace_embedding fused in: position j of row b takes codebook[gt[b * ld_gt + j]] where keep[b * ld_gt + j] != 0,
  * else codebook[idx[b * pn * pn + j]].  keep / gt point at the scale's first token of a [B][ld_gt] map, ld_gt >= pn * pn.  Bitwise equal to
  * varhip_token_select_i64 into idx followed by varhip_quant_accum_f32.  Bad sizes, NULL keep or gt: VARHIP_EINVAL. */
+/* pinned against varhip_token_select_i64 + varhip_quant_accum_f32 (tests/test_edit_gpu.py) */
 int varhip_quant_accum_edit_f32(const int64_t* idx, const uint8_t* keep, const int64_t* gt, int64_t ld_gt, const float* codebook,
                                 const int32_t* tap_idx, const float* tap_w, const float* phi_w, const float* phi_b, float ratio,
                                 float* up, float* f_hat, int B, int pn, int P, int Cv, varhip_stream_t stream);
 
 /* the more_smooth flavour: kept positions read codebook[gt[b * ld_gt + j]], the others h[b * pn * pn + j] ([B][pn*pn][Cv], the gumbel-softmax
  * embedding); bitwise equal to overwriting the kept rows of h and calling varhip_quant_accum_h_f32. */
+/* pinned against an overwrite of h + varhip_quant_accum_h_f32 (tests/test_edit_gpu.py) */
 int varhip_quant_accum_h_edit_f32(const float* h, const uint8_t* keep, const int64_t* gt, int64_t ld_gt, const float* codebook,
                                   const int32_t* tap_idx, const float* tap_w, const float* phi_w, const float* phi_b, float ratio,
                                   float* up, float* f_hat, int B, int pn, int P, int Cv, varhip_stream_t stream);
@@ -653,14 +682,17 @@ int varhip_nearest_code_cos_f32(const float* z, const float* codebook, int64_t* 
  * scratch: >= VARHIP_VQ_STATS_MAX_BLOCKS doubles.  n < 1, V < 1, n_idx < 0 or > 2^26, a NULL operand: VARHIP_EINVAL. */
 #define VARHIP_VQ_STATS_MAX_BLOCKS 1024
 int varhip_vq_stats_blocks(int64_t n);
+/* pinned against torch.bincount and a numpy float64 sum (tests/test_vae_forward_gpu.py) */
 int varhip_vq_scale_stats_f32(const float* f_hat, const float* f, int64_t n, const int64_t* idx, int64_t n_idx, int V, int64_t* hits,
                               double* scratch, double* sum_out, float* mse_out, int32_t* bad, varhip_stream_t stream);
 /* quant.py:95,97: acc = 0; per scale in order acc = acc + (mse_S[si] * beta + mse_S[si]); *out = acc * (float)(1.0 / S).  fp32, every
  * operation rounded on its own (no contraction), beta as the fp32 value of the module's float. */
+/* pinned against the fp32 sequence in torch (tests/test_vae_forward_gpu.py) */
 int varhip_vq_loss_combine_f32(const float* mse_S, int S, float beta, float* out, varhip_stream_t stream);
 /* quant.py:98 `(f_hat.data - f_no_grad).add_(f_BChw)`: v = (f_hat - f) + f per element in fp32, two roundings (not bit-equal to f_hat).
  * f_hat, f: [B][HW][C] channels-last; out_nhwc (nullable) the same layout, out_nchw (nullable) [B][C][HW], both written in the one pass;
  * at least one of them.  Bad sizes: VARHIP_EINVAL. */
+/* pinned against (f_hat - f) + f in torch, bit for bit (tests/test_vae_forward_gpu.py) */
 int varhip_vq_straight_through_f32(const float* f_hat, const float* f, float* out_nhwc, float* out_nchw, int B, int HW, int C,
                                    varhip_stream_t stream);
 
@@ -679,6 +711,7 @@ int varhip_vq_straight_through_f32(const float* f_hat, const float* f, float* ou
  * On a row holding a NaN, nll is what varhip_token_loglik_f32 gives there (NaN when z_gt is the NaN; otherwise its register path drops the NaN
  * element from the exponential sum and its scalar path propagates it) and smooth is NaN.
  * Bad sizes (R, l, V < 1, ld_gt < l, ld_out < l) or a NULL operand: VARHIP_EINVAL. */
+/* pinned against float64, torch.argmax and the rank's definition (tests/test_evaluate_gpu.py) */
 int varhip_token_eval_f32(const float* logits, const int64_t* gt, int64_t ld_gt, int R, int l, int V, float* nll, float* smooth,
                           int64_t* pred, int32_t* rank, int64_t ld_out, varhip_stream_t stream);
 /* Once per call, over the [N][ld] per-token arrays varhip_token_eval_f32 filled; begin_S1: a HOST array of S + 1 int32 token offsets, begin[0] = 0,
@@ -689,6 +722,7 @@ int varhip_token_eval_f32(const float* logits, const int64_t* gt, int64_t ld_gt,
  *   correct_S[s] = |{tokens with rank == 0}| (int64; an out-of-range gt has rank -1 and never counts).
  * pred_hist_V[v] += |{tokens with pred == v}| (int64, the caller zeroes it; replaces trainer.py:140 bincount): integer atomics only, in LDS
  * first for V <= 8192; a pred outside [0, V) is not counted.  N * L <= 2^26.  Bad sizes or a NULL operand: VARHIP_EINVAL. */
+/* pinned against numpy float64 sums and torch.bincount (tests/test_evaluate_gpu.py) */
 int varhip_eval_reduce_f32(const float* nll, const float* smooth, const int64_t* pred, const int32_t* rank, int64_t ld, int N,
                            const int32_t* begin_S1, int S, int V, double* nll_S, double* smooth_S, int64_t* correct_S,
                            int64_t* pred_hist_V, varhip_stream_t stream);

@@ -1,11 +1,10 @@
 """VAR.autoregressive_infer_cfg_with_mask without a GPU: argument checks (ValueError before the device check), the CPU model's RuntimeError,
 models.var.get_edit_mask against hand-written boxes, the reference fixtures' self-consistency (tools/gen_golden_edit.py), and the new C ABI
-entries (include/var_hip.h against var_amd/abi.py)."""
+entries (their table, the Makefile, the notebook cell the header cites)."""
 import contextlib
 import io
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -155,24 +154,11 @@ def test_lambda_half_fixture_exercises_the_edge(golden_dir):
     assert k13[6, 0] == 1 and k13[0, 6] == 1 and k13[5, 5] == 0
 
 
-def _decls(header):
-    out = {}
-    for m in re.finditer(r'\bint\s+varhip_(\w+)\s*\(([^;]*?)\)\s*;', header, re.S):
-        out[m.group(1)] = [a.strip() for a in m.group(2).split(',')]
-    return out
-
-
 def test_new_entry_points_in_header_and_abi_with_matching_argument_lists():
+    """(the argument lists themselves: tests/test_abi_cpu.py, for every declaration of the header)"""
     from var_amd import abi
-    import ctypes as C
     header = open(os.path.join(ROOT, 'include', 'var_hip.h')).read()
-    decl = _decls(header)
-    kind = lambda a: ('P' if '*' in a else 'L' if 'int64_t' in a else 'F' if a.startswith('float') else 'D' if a.startswith('double') else 'I')
-    ct = {C.c_void_p: 'P', C.c_int: 'I', C.c_int64: 'L', C.c_float: 'F', C.c_double: 'D'}
     for name in ('edit_keep_u8', 'quant_accum_edit_f32', 'quant_accum_h_edit_f32'):
-        assert name in decl and name in abi.SIGNATURES_HIP_ONLY, name
-        args = decl[name]
-        assert args[-1].endswith('stream')
-        assert [kind(a) for a in args[:-1]] == [ct[t] for t in abi.SIGNATURES_HIP_ONLY[name]], name
+        assert name in abi.SIGNATURES_HIP_ONLY, name
     assert 'edit.hip' in open(os.path.join(ROOT, 'var_amd', 'csrc', 'Makefile')).read().split('SRCS16')[0]
     assert 'demo_zero_shot_edit.ipynb cell 2' in header

@@ -6,7 +6,6 @@ import io
 import json
 import math
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -123,12 +122,9 @@ def test_fixture_is_self_consistent(golden_dir):
 
 
 def test_new_abi_entries_declared_and_exported():
-    txt = open(os.path.join(ROOT, 'include', 'var_hip.h')).read()
-    declared = set(re.findall(r'\b(varhip_\w+)\s*\(', txt))
     new = {'varhip_cfg_argmax_f32', 'varhip_feature_l1_f32'}
-    assert new <= declared
     from var_amd import abi
-    assert {n[len('varhip_'):] for n in new} <= set(abi.SIGNATURES_HIP_ONLY)
+    assert {n[len('varhip_'):] for n in new} <= set(abi.SIGNATURES_HIP_ONLY) <= set(abi.DECLS)     # (the tables against the header: tests/test_abi_cpu.py)
     so_path = os.path.join(ROOT, 'var_amd', 'libvar_hip.so')
     if not os.path.exists(so_path):
         subprocess.check_call(['make', '-C', os.path.join(ROOT, 'var_amd', 'csrc'), '-j8'], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)

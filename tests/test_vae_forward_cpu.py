@@ -1,11 +1,9 @@
 """VQVAE.forward / VectorQuantizer2.forward and their forward_stats without a GPU: the PyTorch branch against the reference's
 own outputs (tests/golden/vaefwd_*.npz, tools/gen_golden_vae_forward.py), its autograd wiring, the usages without a process group, the EMA
 schedule under the package's dist flag, and the ABI of the new entry points."""
-import ctypes
 import glob
 import json
 import os
-import re
 import tempfile
 
 import numpy as np
@@ -183,26 +181,12 @@ def test_half_input_is_cast_and_cpu_never_takes_hip():
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------------
-NEW = {'vq_scale_stats_f32': 11, 'vq_loss_combine_f32': 4, 'vq_straight_through_f32': 7}
-
-
 def test_abi_of_the_new_entry_points():
+    """(the argument lists: tests/test_abi_cpu.py, for every declaration of the header)"""
     from var_amd import abi, hip
     hdr = open(os.path.join(ROOT, 'include', 'var_hip.h')).read()
-    so = ctypes.CDLL(os.path.join(ROOT, 'var_amd', 'libvar_hip.so'))
-    P, L, I, F = abi.P, abi.L, abi.I, abi.F
-    want = {'vq_scale_stats_f32': [P, P, L, P, L, I, P, P, P, P, P], 'vq_loss_combine_f32': [P, I, F, P], 'vq_straight_through_f32': [P, P, P, P, I, I, I]}
-    for name, nargs in NEW.items():
-        assert abi.SIGNATURES_HIP_ONLY[name] == want[name] and len(want[name]) == nargs
-        m = re.search(r'int varhip_%s\(([^;]*?)\);' % name, hdr, re.S)
-        assert m, name
-        params = [p.strip() for p in m.group(1).split(',')]
-        assert len(params) == nargs + 1 and params[-1] == 'varhip_stream_t stream', (name, params)
-        for p, ct in zip(params, want[name]):                       # pointer / int64 / int / float, argument by argument
-            kind = P if '*' in p else L if p.startswith('int64_t') else F if p.startswith('float') else I
-            assert kind is ct, (name, p)
-        assert hasattr(so, 'varhip_' + name) and name in hip.lib().fn
-    assert hasattr(so, 'varhip_vq_stats_blocks')
+    for name in ('vq_scale_stats_f32', 'vq_loss_combine_f32', 'vq_straight_through_f32'):
+        assert name in abi.SIGNATURES_HIP_ONLY and name in hip.lib().fn
     assert hip.vq_stats_blocks(1) == 1 and hip.vq_stats_blocks(4097) == 2 and hip.vq_stats_blocks(1 << 30) == hip.VQ_STATS_MAX_BLOCKS
     assert f'#define VARHIP_VQ_STATS_MAX_BLOCKS {hip.VQ_STATS_MAX_BLOCKS}' in hdr
     # each new entry cites the reference lines it replaces

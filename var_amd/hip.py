@@ -20,29 +20,7 @@ class _Lib:
                               f'(or `make -C var_amd/csrc`). There is no CPU/PyTorch fallback for the sampling path.')
         self.so = ctypes.CDLL(LIB_PATH)
         self.fn = abi.bind(self.so, 'varhip_', with_stream=True)
-        so = self.so
-        so.varhip_timing_enable.argtypes = [ctypes.c_int]; so.varhip_timing_enable.restype = ctypes.c_int
-        so.varhip_timing_reset.argtypes = []; so.varhip_timing_reset.restype = ctypes.c_int
-        so.varhip_timing_read.argtypes = [ctypes.c_void_p] * 4; so.varhip_timing_read.restype = ctypes.c_int
-        so.varhip_timing_name.argtypes = [ctypes.c_int]; so.varhip_timing_name.restype = ctypes.c_char_p
-        so.varhip_gemm16_force_tile.argtypes = [ctypes.c_int]; so.varhip_gemm16_force_tile.restype = ctypes.c_int
-        so.varhip_conv16_force_tile.argtypes = [ctypes.c_int]; so.varhip_conv16_force_tile.restype = ctypes.c_int
-        so.varhip_conv16_last_pick.argtypes = []; so.varhip_conv16_last_pick.restype = ctypes.c_int
-        so.varhip_gemm16_persistent.argtypes = [ctypes.c_int]; so.varhip_gemm16_persistent.restype = ctypes.c_int
-        so.varhip_gemm16_deep.argtypes = [ctypes.c_int]; so.varhip_gemm16_deep.restype = ctypes.c_int
-        so.varhip_gemm16_last_pick.argtypes = [ctypes.c_int]; so.varhip_gemm16_last_pick.restype = ctypes.c_int
-        so.varhip_sampler_force_walk.argtypes = [ctypes.c_int]; so.varhip_sampler_force_walk.restype = ctypes.c_int
-        so.varhip_gemm_force_tile.argtypes = [ctypes.c_int]; so.varhip_gemm_force_tile.restype = ctypes.c_int
-        so.varhip_gemm_qkv_force_tile.argtypes = [ctypes.c_int]; so.varhip_gemm_qkv_force_tile.restype = ctypes.c_int
-        so.varhip_gemm_last_pick.argtypes = []; so.varhip_gemm_last_pick.restype = ctypes.c_int
-        so.varhip_gemm_last_evec.argtypes = []; so.varhip_gemm_last_evec.restype = ctypes.c_int
-        so.varhip_quant_last_route.argtypes = []; so.varhip_quant_last_route.restype = ctypes.c_int
-        so.varhip_vq_stats_blocks.argtypes = [ctypes.c_int64]; so.varhip_vq_stats_blocks.restype = ctypes.c_int
-        self.host = {}
-        for name, args in abi.SIGNATURES_HOST.items():
-            fn = getattr(so, 'varhip_' + name)
-            fn.argtypes = list(args); fn.restype = ctypes.c_int
-            self.host[name] = fn
+        self.host = {name: getattr(self.so, 'varhip_' + name) for name in abi.SIGNATURES_HOST}      # bound by abi.bind with the rest
 
     def version(self) -> str:
         return self.fn['version']().decode()
@@ -108,7 +86,7 @@ def conv16_gn_fusable(B, H, W, Cin, Cout) -> bool:
     return bool(lib().fn['conv16_gn_fusable'](B, H, W, Cin, Cout))
 
 
-VQ_STATS_MAX_BLOCKS = 1024      # VARHIP_VQ_STATS_MAX_BLOCKS of include/var_hip.h: doubles of scratch varhip_vq_scale_stats_f32 takes
+VQ_STATS_MAX_BLOCKS = abi.CONSTANTS['VQ_STATS_MAX_BLOCKS']      # VARHIP_VQ_STATS_MAX_BLOCKS of include/var_hip.h: doubles of scratch varhip_vq_scale_stats_f32 takes
 
 
 def vq_stats_blocks(n: int) -> int:
@@ -117,7 +95,7 @@ def vq_stats_blocks(n: int) -> int:
 
 
 # ---- timing table --------------------------------------------------------------------------------------------------
-NFAM = 17            # VARHIP_NFAM of include/var_hip.h
+NFAM = abi.CONSTANTS['NFAM']            # VARHIP_NFAM of include/var_hip.h
 
 
 def timing_enable(on: bool, families=None):
