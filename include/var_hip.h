@@ -206,6 +206,64 @@ int varhip_sample_stats_host_f32(const float* logits, const float* masked, const
                                  const double* t_rows, float* lp_cond, float* lp_guided, float* lp_drawn, int32_t* kept, float* entropy,
                                  int64_t ld_out);
 
+/* ---- lossless token coding (VAR.compress / VAR.decompress) -------------------------------------------------------------------------------
+ * The model as the probability source of a range coder.  A decoder must rebuild every table its encoder used to the last bit, on another
+ * batch and in another call order, so the table is defined by exact integer operations on the row's exponentials:
+ * THE TABLE.  Row r = b * l + j of a scale's [2B][l][V] logits (conditional rows first) becomes F[V], positive integers that sum to exactly
+ * 2^PB, PB = VARCODEC_PB.  With the guidance t (the scalar t_cfg, or the DEVICE array t_rows[B] where t_rows != NULL):
+ *   z_v = ca * cond_v - cb * uncond_v,  ca = (float)(1.0 + t), cb = (float)t, each product and the difference rounded to fp32 (as
+ *         varhip_cfg_sample_f32 and varhip_token_loglik_f32 form it)
+ *   m   = max_v z_v;  e_v = vm_exp(z_v - m)  (include/var_math.h; a -inf entry gives e_v = 0, the maximum gives e_v = 1)
+ *   i_v = (uint64)floor((double)e_v * 2^32)                              exact in double, i_v <= 2^32
+ *   I   = sum_v i_v                                                      an exact integer sum (< 2^46 for V <= 8192): order does not matter
+ *   K   = 2^PB - V;  q_v = (i_v * K) / I                                 unsigned 64-bit integer division, the product is below 2^57
+ *   D   = K - sum_v q_v                                                  0 <= D < V
+ *   F_v = 1 + q_v, and the lowest index v* with z_v == m also takes D;   C_v = sum_{u < v} F_u, the exclusive prefix in index order
+ * Nothing above depends on who computes it or in what order: any implementation of these lines gives the same F.  A row that holds a NaN, or
+ * whose maximum is +inf or -inf (no finite entry), is REFUSED: nothing is coded from it.
+ * Addressing: gt, pair_out and flag_out share the row stride ld >= l (a scale's slice of (B, L) tensors): gt[b * ld + j], flag_out[b * ld + j],
+ * pair_out[2 * (b * ld + j) + {0, 1}].  Outputs:
+ *   cum_out  (may be NULL) uint32 [B*l][V], dense: the INCLUSIVE cumulative table C_v + F_v (its last entry is 2^PB); a refused row is all 0,
+ *            a table in which no slot has an owner
+ *   pair_out (NULL exactly when gt is NULL) (C_g, F_g) of the row's token g = gt[b * ld + j]; (0, 0) on a refused row or a g outside [0, V)
+ *   flag_out int32, written for every row: 0, 1 = the row was refused, 2 = g lies outside [0, V) (never dereferenced)
+ * cum_out and pair_out must not both be NULL.  Constraints as the samplers': V % 256 == 0, V <= 8192, logits (and cum_out) 16-byte aligned,
+ * B, l >= 1, ld >= l; anything else: VARHIP_EINVAL before any launch.  One wave per row, four rows per workgroup. */
+#define VARCODEC_PB 24
+/* pinned against its host twin bit for bit (tests/test_codec_kernels_gpu.py) */
+int varhip_code_table_f32(const float* logits, int B, int l, int V, double t_cfg, const double* t_rows, const int64_t* gt, int64_t ld,
+                          uint32_t* cum_out, uint32_t* pair_out, int32_t* flag_out, varhip_stream_t stream);
+/* the host twin: plain host code, host pointers (t_rows too), no alignment constraint; the same integers by the definition above */
+/* pinned against the Python-integer restatement of the definition in tests/codecref.py (tests/test_codec_cpu.py) */
+int varhip_code_table_host_f32(const float* logits, int B, int l, int V, double t_cfg, const double* t_rows, const int64_t* gt, int64_t ld,
+                               uint32_t* cum_out, uint32_t* pair_out, int32_t* flag_out);
+/* THE CODER: rANS with a 64-bit state x in [2^31, 2^63) and 32-bit words.
+ *   encoding (C, F):  if x >= ((2^31 >> PB) << 32) * F: emit the low 32 bits of x, x >>= 32.  Then x = ((x / F) << PB) + x % F + C.
+ *   Symbols are encoded in REVERSE token order from x = 2^31.  The stream: the final state as two words (high word first), then the emitted
+ *   words in reverse order of emission, so the decoder reads forward.
+ *   decoding:  slot = x & (2^PB - 1); s = the symbol with C_s <= slot < C_s + F_s; x = F_s * (x >> PB) + slot - C_s; if x < 2^31:
+ *   x = x << 32 | next word.  After the last token of a complete stream x == 2^31 and every word has been read: the integrity check.
+ * varhip_rans_encode_host: pairs = n (C, F) pairs in token order; words_out[cap] receives the stream, *nwords_out its length (<= n + 2).
+ * n < 0, a NULL pointer, a pair with F == 0 or C + F > 2^PB, or a stream longer than cap: VARHIP_EINVAL. */
+int varhip_rans_encode_host(const uint32_t* pairs, int64_t n, uint32_t* words_out, int64_t cap, int64_t* nwords_out);
+/* varhip_rans_decode_u32: the l tokens of one scale for each of B images from cum = the scale's cum_out [B*l][V]; one wave per image, serial
+ * over its tokens, the 64 lanes searching a row in two dependent rounds (lane i reads entry (V / 64) * i + V / 64 - 1, a ballot picks the
+ * segment, the lanes then read inside it).  Image b's stream is words[word_off[b] .. word_off[b] + nwords[b]) (DEVICE arrays), words_total
+ * the length of `words`.  state: uint32 [B][4] = (x low, x high, words consumed, started), carried between the scales of a call: all zero
+ * before the first scale (the kernel then reads the stream's two state words), the end check reads it after the last.  err_out int32 [B],
+ * zero before the first scale, sticky: 1 = a read past the image's words, 2 = a slot no symbol owns (a refused row's table), 3 = the image's
+ * word range does not lie inside `words`.  From the token at which an error is found on, the image's tokens are -1 (idx_out int64 [B*l]), in
+ * this and every later scale; a token whose symbol was found before a refill ran past the end is still written.  Every read of `words` is
+ * checked against the image's nwords and every loop is bounded by l and V: never by data.  V % 256 == 0, V <= 8192, B, l >= 1, words_total
+ * >= 0, no NULL pointer; anything else: VARHIP_EINVAL. */
+/* pinned against its host twin (tests/test_codec_kernels_gpu.py) */
+int varhip_rans_decode_u32(const uint32_t* cum, int l, int V, const uint32_t* words, int64_t words_total, const int64_t* word_off,
+                           const int64_t* nwords, uint32_t* state, int64_t* idx_out, int32_t* err_out, int B, varhip_stream_t stream);
+/* the host twin: the same search and the same state transitions on host pointers */
+/* pinned against the Python-integer coder of tests/codecref.py (tests/test_codec_cpu.py) */
+int varhip_rans_decode_host(const uint32_t* cum, int l, int V, const uint32_t* words, int64_t words_total, const int64_t* word_off,
+                            const int64_t* nwords, uint32_t* state, int64_t* idx_out, int32_t* err_out, int B);
+
 /* ---- multi-scale quantizer step ---------------------------------------------------------------------------
  * Feature maps are kept channels-last: f_hat[B][P][P][Cv].
  * (1) h = codebook[idx] as [B][pn][pn][Cv]                                          (var.py:177,182; quant.py:39)

@@ -99,6 +99,8 @@ SIGNATURES_HOST = {k: d[1] for k, d in DECLS.items() if not d[2] and P in d[1] a
 
 EPI_NONE, EPI_GELU, EPI_RESID = CONSTANTS['EPI_NONE'], CONSTANTS['EPI_GELU'], CONSTANTS['EPI_RESID']
 EINVAL = CONSTANTS['EINVAL']
+with open(HEADER) as _f:
+    CODEC_PB = int(re.search(r'^#define VARCODEC_PB (\d+)$', _f.read(), re.M).group(1))      # precision bits of the coding tables (codec.hip)
 
 
 def bind(lib, prefix: str, with_stream: bool):

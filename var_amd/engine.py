@@ -1742,6 +1742,91 @@ class SamplingEngine(_Engine):
         self.smc_pre_tokens = [torch.cat(p, 0) for p in pre] if ref else None
         return res
 
+    # -- lossless token coding (VAR.compress / VAR.decompress) -----------------------------------------------------------------
+    def _codec_begin(self, who: str, B: int, label_B: torch.Tensor) -> tuple:
+        """what code_tokens and decode_tokens share in front of the walk: f32 or ValueError (a stream written in one arithmetic cannot be read
+        in another), the call's workspace, the checked labels -> (ws, labels on the device)"""
+        if self.resolve_precision() != 'f32':
+            raise ValueError(f'{who} runs in f32: a stream coded with {self.precision} tables could not be read in any other arithmetic '
+                             f'(set_hip_precision(\'f32\'), no 16-bit autocast)')
+        self.refresh()
+        self._wait_ready()
+        ws = self.workspace(B)
+        if label_B.dtype != torch.int64 or label_B.numel() != B:
+            raise ValueError('label_B must be an int64 tensor of B labels')
+        self._check_labels(label_B)
+        return ws, label_B.to(ws['dev']).contiguous()
+
+    @torch.no_grad()
+    def code_tokens(self, gt_tokens: torch.Tensor, label_B: torch.Tensor, cfg: float, last: int) -> tuple:
+        """the encoder's half of VAR.compress: sample()'s walk over scales 0 .. last on 2B rows with the tokens given, and behind every scale's
+        head varhip_code_table_f32 with gt: the (C, F) of every token under the table of its row, guidance t = cfg * si / (S - 1) as sample()
+        forms it.  gt_tokens (B, L) int64 in [0, V) on the device, label_B (B,) int64.  One device-to-host copy after the walk
+        -> (pairs (B, L, 2) uint32, flags (B, L) int32: varhip_code_table_f32's, both numpy; rows past scale `last` are zero)."""
+        var = self.var
+        B = gt_tokens.shape[0]
+        ws, label_B = self._codec_begin('compress', B, label_B)
+        dev, S = ws['dev'], len(var.patch_nums)
+        gt = gt_tokens.to(dev, torch.int64).contiguous()
+        out = torch.zeros(B, var.L, 3, dtype=torch.int32, device=dev)          # (C, F, flag) per token: one copy back
+        pairs, flags = torch.zeros(B, var.L, 2, dtype=torch.int32, device=dev), torch.zeros(B, var.L, dtype=torch.int32, device=dev)
+        ws['f_hat'].zero_()
+        self._prologue(ws, label_B, 2 * B)
+        for sc in self._scales(ws, B, 0, last):
+            t = cfg * sc.r if S > 1 else 0.0
+            self._logits(ws, B, sc, None)
+            hip.call('code_table_f32', ws['logits'], B, sc.l, var.V, float(t), None, gt[:, sc.cur:], var.L, None, pairs[:, sc.cur:], flags[:, sc.cur:])
+            sc.idx = gt[:, sc.cur:sc.cur + sc.l].contiguous().view(-1)
+        out[:, :, :2] = pairs
+        out[:, :, 2] = flags
+        host = out.cpu().numpy()
+        return np.ascontiguousarray(host[:, :, :2]).view(np.uint32), np.ascontiguousarray(host[:, :, 2])
+
+    @torch.no_grad()
+    def decode_tokens(self, words: np.ndarray, word_off: np.ndarray, nwords: np.ndarray, label_B: torch.Tensor, cfg: float, last: int,
+                      fill: Optional[float], decode: bool) -> tuple:
+        """the decoder's half of VAR.decompress: the same walk with the bitstream as the chooser.  Per coded scale: the head,
+        varhip_code_table_f32 with cum_out = ws['masked'] (the buffer _masked provides), varhip_rans_decode_u32 into ws['idx']; the quantizer
+        step and next_map as in sampling.  words: uint32, all images' streams back to back, image b's at word_off[b] with nwords[b] words
+        (int64); uploaded once before the walk.  Scales past `last`: not run (fill None; their tokens stay -1), or chosen by _greedy with
+        guidance fill * si / (S - 1).  No host synchronisation inside the walk: the coder's state, err and the tables' flags come back in one
+        copy when it ends.  A token of -1 (an image in error) reaches the quantizer step as code 0; the caller raises for that image.
+        -> (tokens (B, L) int64 on the device, images or None, state (B, 4) uint32, err (B,) int32, refused (B,) int32: rows of the image
+        whose table was refused; the last three numpy)"""
+        var = self.var
+        B = int(nwords.shape[0])
+        ws, label_B = self._codec_begin('decompress', B, label_B)
+        dev, S, V = ws['dev'], len(var.patch_nums), var.V
+        cum = self._masked(ws, B, False)
+        words_d = torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(dev) if words.size else torch.zeros(1, dtype=torch.int32, device=dev)
+        off_d = torch.from_numpy(np.ascontiguousarray(word_off, np.int64)).to(dev)
+        nw_d = torch.from_numpy(np.ascontiguousarray(nwords, np.int64)).to(dev)
+        st = torch.zeros(B, 6, dtype=torch.int32, device=dev)                  # the coder's state (4 words), err, refused rows: one copy back
+        state, err = st[:, :4].contiguous(), st[:, 4].contiguous()
+        flags = torch.zeros(B, var.L, dtype=torch.int32, device=dev)
+        tokens = torch.full((B, var.L), -1, dtype=torch.int64, device=dev)
+        ws['f_hat'].zero_()
+        self._prologue(ws, label_B, 2 * B)
+        for sc in self._scales(ws, B, 0, last if fill is None else S - 1):
+            if sc.si <= last:
+                t = cfg * sc.r if S > 1 else 0.0
+                self._logits(ws, B, sc, None)
+                idx = ws['idx'][:B * sc.l]
+                hip.call('code_table_f32', ws['logits'], B, sc.l, V, float(t), None, None, var.L, cum, None, flags[:, sc.cur:])
+                hip.call('rans_decode_u32', cum, sc.l, V, words_d, int(words.size), off_d, nw_d, state, idx, err, B)
+                tokens[:, sc.cur:sc.cur + sc.l].copy_(idx.view(B, sc.l))
+                idx.clamp_(min=0)
+            else:
+                idx = self._greedy(ws, B, sc, fill * sc.r if S > 1 else 0.0, None, None)
+                tokens[:, sc.cur:sc.cur + sc.l].copy_(idx.view(B, sc.l))
+            sc.idx = idx
+        img = self.dec.decode_nhwc(ws['f_hat'], precision=self.precision) if decode else None
+        st[:, :4] = state
+        st[:, 4] = err
+        st[:, 5] = flags.ne(0).sum(1)
+        host = st.cpu().numpy()
+        return tokens, img, np.ascontiguousarray(host[:, :4]).view(np.uint32), np.ascontiguousarray(host[:, 4]), np.ascontiguousarray(host[:, 5])
+
     @torch.no_grad()
     def decode_f_hat(self, f_hat: torch.Tensor) -> torch.Tensor:
         """(B, Cvae, P, P) fp32 as sample(decode=False) returns it -> the images (B, 3, H, W) in [0, 1], by the call's own decoder step"""

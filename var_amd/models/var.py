@@ -728,6 +728,68 @@ def get_edit_mask(patch_nums, y0: float, x0: float, y1: float, x1: float, device
     return 1 - m if inpainting else m
 
 
+class VarCodecError(Exception):
+    """a blob that VAR.decompress could not turn back into its tokens.  .image: the blob's index in the call; .check: 'bounds' (the decoder
+    read past the stream's words or met a slot no symbol owns), 'end' (after the last token the coder's state is not 2^31 or words are left
+    over), 'hash' (the tokens' hash differs from the header's) or 'table' (a logits row of the model was refused: NaN or no finite maximum).
+    Decoding with other weights than the encoder's ends here too, as a rule at 'end'."""
+    def __init__(self, image: int, check: str, detail: str):
+        super().__init__(f'decompress: image {image} failed the {check} check: {detail}')
+        self.image, self.check = image, check
+
+
+class CompressResult(NamedTuple):
+    """VAR.compress: blobs[b] the self-describing byte string of image b, nbytes (B,) int64 their lengths, ideal_bits (B, S)
+    float64: per scale sum log2(2^PB / F_token) of the coded tokens under the integer tables (0 for scales not coded)"""
+    blobs: list
+    nbytes: torch.Tensor
+    ideal_bits: torch.Tensor
+    patch_nums: tuple
+
+
+class DecompressResult(NamedTuple):
+    """VAR.decompress: tokens (B, L) int64 (-1 past the coded scales unless they were completed), images (B, 3, H, W) in [0, 1] or None,
+    labels (B,) int64 from the blobs, scales: the index of the last coded scale"""
+    tokens: torch.Tensor
+    images: Optional[torch.Tensor]
+    labels: torch.Tensor
+    scales: int
+
+
+CODEC_MAGIC, CODEC_VERSION = b'VARC', 1
+_CODEC_HEAD = '<4sHBBIHHiIdQI'          # magic, version, PB, S, V, scales coded, 0, label, 0, cfg, token hash, word count; then S x uint16 patch_nums
+
+
+def codec_token_hash(tok: np.ndarray) -> int:
+    """64-bit hash of a token sequence: sum_i (tok_i + 1) * M^(n - i) mod 2^64, M = 0x9E3779B97F4A7C15 (odd: every position counts)"""
+    tok = np.asarray(tok, np.int64).astype(np.uint64) + np.uint64(1)
+    with np.errstate(over='ignore'):
+        pw = np.cumprod(np.full(tok.shape[0], 0x9E3779B97F4A7C15, np.uint64))[::-1]
+        return int((tok * pw).sum(dtype=np.uint64))
+
+
+def codec_pack(words: np.ndarray, label: int, cfg: float, V: int, patch_nums, coded: int, tok_hash: int, pb: int) -> bytes:
+    import struct
+    head = struct.pack(_CODEC_HEAD, CODEC_MAGIC, CODEC_VERSION, pb, len(patch_nums), V, coded, 0, int(label), 0, float(cfg), tok_hash, int(words.shape[0]))
+    return head + struct.pack(f'<{len(patch_nums)}H', *patch_nums) + np.asarray(words, '<u4').tobytes()
+
+
+def codec_unpack(blob: bytes) -> dict:
+    """the header and words of one blob; ValueError on anything that is no blob of this version"""
+    import struct
+    n0 = struct.calcsize(_CODEC_HEAD)
+    if not isinstance(blob, (bytes, bytearray, memoryview)) or len(blob) < n0:
+        raise ValueError('decompress: a blob is a bytes object made by VAR.compress')
+    blob = bytes(blob)
+    magic, ver, pb, S, V, coded, _, label, _, cfg, th, nw = struct.unpack_from(_CODEC_HEAD, blob)
+    if magic != CODEC_MAGIC or ver != CODEC_VERSION:
+        raise ValueError(f'decompress: not a VAR token blob of version {CODEC_VERSION}')
+    if len(blob) != n0 + 2 * S + 4 * nw:
+        raise ValueError(f'decompress: the blob holds {len(blob)} bytes, its header announces {n0 + 2 * S + 4 * nw}')
+    pns = struct.unpack_from(f'<{S}H', blob, n0)
+    return dict(pb=pb, V=V, coded=coded, label=label, cfg=cfg, hash=th, patch_nums=tuple(pns), words=np.frombuffer(blob, '<u4', nw, n0 + 2 * S))
+
+
 class SharedAdaLin(nn.Linear):
     def forward(self, cond_BD):
         return super().forward(cond_BD).view(-1, 1, 6, self.weight.shape[0] // 6)
@@ -1695,6 +1757,99 @@ class VAR(nn.Module):
             raise ValueError(f'max_rows must be an integer >= {1 + (cfg > 0)} (the class rows of a pass plus the unconditional row with cfg > 0)')
         self._token_label_range(gt, lab)
         return gt.to(dev, torch.int64), lab.to(dev, torch.int64), cfg
+
+    # ---- lossless token coding --------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def compress(self, gt_tokens, label_B, cfg: float = 0.0, scales: Optional[int] = None) -> CompressResult:
+        """Code the tokens of B images losslessly with this model as the probability source: image b's blob is about -log2 p(tokens | label,
+        coarser scales) bits long plus a 44 + 2 S byte header.  gt_tokens: (B, L) integer ids, or the list vae.img_to_idxBl returns; label_B:
+        an int or (B,) class ids in [0, num_classes]; cfg: the guidance of the coding distribution (t = cfg * si / (S - 1) per scale, as in
+        sampling; 0 = the conditional model); scales = s: only scales 0 .. s are coded (decompress can complete the rest greedily).
+        The walk is sample()'s on 2B rows with the tokens given; per scale varhip_code_table_f32 turns every logits row into an integer
+        frequency table (include/var_hip.h) and leaves the token's (C, F); the rANS coder runs on the host.  A blob does not depend on what it
+        was batched with, nor on the calls made before.  f32 only (ValueError under a 16-bit precision); a CPU model: RuntimeError."""
+        from .. import abi, hip
+        dev = self._scored_device('compress')
+        gt = self._token_shape(torch.cat(list(gt_tokens), 1) if isinstance(gt_tokens, (list, tuple)) else gt_tokens)
+        B, S = gt.shape[0], len(self.patch_nums)
+        lab = torch.full((B,), int(label_B)) if isinstance(label_B, int) else torch.as_tensor(label_B)
+        if lab.dim() != 1 or lab.shape[0] != B or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
+            raise ValueError(f'label_B must be an int or ({B},) integer class ids')
+        cfg = float(cfg)
+        if not math.isfinite(cfg) or cfg < 0:
+            raise ValueError('cfg must be finite and >= 0')
+        last = S - 1 if scales is None else scales
+        if int(last) != last or not 0 <= last < S:
+            raise ValueError(f'scales must be None or an integer in [0, {S - 1}]')
+        last = int(last)
+        self._token_label_range(gt, lab)
+        pairs, flags = self.engine().code_tokens(gt.to(dev, torch.int64), lab.to(dev, torch.int64), cfg, last)
+        n = self.begin_ends[last][1]
+        if flags[:, :n].any():
+            b, j = (int(v) for v in np.argwhere(flags[:, :n])[0])
+            raise hip.VarHipError(f'compress: the coding table of image {b}, token {j} was refused (a NaN or no finite maximum in its logits row)')
+        tok = gt.cpu().numpy()
+        labs = lab.tolist()
+        blobs, ideal = [], np.zeros((B, S), np.float64)
+        buf, nw = np.empty(n + 2, np.uint32), np.zeros(1, np.int64)
+        for b in range(B):
+            hip.call_host('rans_encode_host', pairs[b], n, buf, n + 2, nw)
+            blobs.append(codec_pack(buf[:int(nw[0])], labs[b], cfg, self.V, self.patch_nums, last + 1, codec_token_hash(tok[b, :n]), abi.CODEC_PB))
+            bits = abi.CODEC_PB - np.log2(pairs[b, :n, 1].astype(np.float64))
+            ideal[b, :last + 1] = [bits[b0:e0].sum() for b0, e0 in self.begin_ends[:last + 1]]
+        return CompressResult(blobs, torch.tensor([len(x) for x in blobs], dtype=torch.int64), torch.from_numpy(ideal), tuple(self.patch_nums))
+
+    @torch.no_grad()
+    def decompress(self, blobs, complete: Optional[str] = None, fill_cfg: float = 1.5, decode: bool = True) -> DecompressResult:
+        """The tokens (and images) back from VAR.compress's blobs, which may carry different labels and come from different compress calls; they
+        must agree on cfg, the coded scales, PB and patch_nums and match this model's V and patch_nums (ValueError otherwise).  Blobs that code
+        scales 0 .. s < S - 1: complete=None leaves the later tokens -1 (the image, if asked for, is the coarse f_hat's), complete='greedy'
+        fills them with the argmax of the guided logits (guidance fill_cfg), the completion inpainting's greedy route gives for that prefix.
+        The walk is sample()'s with the bitstream as the chooser (varhip_rans_decode_u32 behind varhip_code_table_f32), no host
+        synchronisation inside it.  A blob that fails the decoder's bounds check, the end check or the token hash raises VarCodecError naming
+        the image and the check: also what decoding with other weights gives.  f32 only; a CPU model: RuntimeError."""
+        from .. import abi
+        dev = self._scored_device('decompress')
+        if complete not in (None, 'greedy'):
+            raise ValueError("complete must be None or 'greedy'")
+        blobs = list(blobs)
+        if not blobs:
+            raise ValueError('decompress: no blob given')
+        heads = [codec_unpack(x) for x in blobs]
+        h0 = heads[0]
+        for i, h in enumerate(heads):
+            if (h['cfg'], h['coded'], h['pb'], h['patch_nums']) != (h0['cfg'], h0['coded'], h0['pb'], h0['patch_nums']):
+                raise ValueError(f'decompress: blob {i} differs from blob 0 in cfg, coded scales, PB or patch_nums: decode such blobs in separate calls')
+        S = len(self.patch_nums)
+        if h0['patch_nums'] != tuple(self.patch_nums) or h0['V'] != self.V or any(h['V'] != self.V for h in heads):
+            raise ValueError(f"decompress: the blobs were coded for V = {h0['V']}, patch_nums = {h0['patch_nums']}; this model has {self.V}, {tuple(self.patch_nums)}")
+        if h0['pb'] != abi.CODEC_PB or not 1 <= h0['coded'] <= S or not math.isfinite(h0['cfg']) or h0['cfg'] < 0:
+            raise ValueError('decompress: the header names a table precision, scale count or cfg this build does not code with')
+        fill_cfg = float(fill_cfg)
+        if not math.isfinite(fill_cfg) or fill_cfg < 0:
+            raise ValueError('fill_cfg must be finite and >= 0')
+        lab = torch.tensor([h['label'] for h in heads], dtype=torch.int64)
+        if int(lab.min()) < 0 or int(lab.max()) > self.num_classes:
+            raise ValueError(f'labels must lie in [0, {self.num_classes}]')
+        last = h0['coded'] - 1
+        nw = np.array([h['words'].shape[0] for h in heads], np.int64)
+        off = np.concatenate(([0], np.cumsum(nw)[:-1])).astype(np.int64)
+        words = np.concatenate([h['words'] for h in heads]).astype(np.uint32)
+        fill = fill_cfg if complete == 'greedy' and last < S - 1 else None
+        tokens, img, state, err, refused = self.engine().decode_tokens(words, off, nw, lab.to(dev), h0['cfg'], last, fill, bool(decode))
+        tok = tokens.cpu().numpy()
+        n = self.begin_ends[last][1]
+        for i, h in enumerate(heads):
+            x, pos = int(state[i, 0]) | int(state[i, 1]) << 32, int(state[i, 2])
+            if refused[i]:
+                raise VarCodecError(i, 'table', f'{int(refused[i])} logits rows of the model hold a NaN or no finite maximum')
+            if err[i]:
+                raise VarCodecError(i, 'bounds', 'the decoder ' + {1: "read past the stream's last word", 2: 'met a slot that no symbol owns'}.get(int(err[i]), 'was given a word range outside the upload'))
+            if x != 1 << 31 or pos != int(nw[i]):
+                raise VarCodecError(i, 'end', f'after the last token the state is {x:#x} (expected 0x80000000) with {pos} of {int(nw[i])} words read')
+            if codec_token_hash(tok[i, :n]) != h['hash']:
+                raise VarCodecError(i, 'hash', 'the decoded tokens do not hash to the value in the header')
+        return DecompressResult(tokens, img, lab.to(dev), last)
 
     def _token_shape(self, gt_tokens) -> torch.Tensor:
         """the token argument of the scoring calls and of evaluate -> an (N, L) integer tensor, shape and dtype checked"""
