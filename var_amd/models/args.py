@@ -1,0 +1,203 @@
+"""The argument checkers of VAR's public calls (var.py): plain functions without model state.  Each returns the normalised value or raises
+ValueError with the message the caller gives.
+
+The definitions, once:
+  integer   a Python int or a numpy integer, never a bool.  Where a call has always taken a float of integral value (`integral_float`)
+            whatever equals its own int() passes too.
+  float     int, float or a numpy scalar, never a bool, finite; `convert` marks the arguments that have always gone through float()
+            (cfg, fill_cfg, threshold: a str or a 0-d tensor passes).  cfg and fill_cfg, and the per-image cfg / top_p, take a bool
+            too (float(True) = 1.0): they always did, in every call.
+  labels    an integer tensor (no float, complex or bool dtype) of the stated shape, in [0, num_classes] (num_classes: unconditional)
+  tokens    an (N, L) integer tensor in [0, V)
+  per image a scalar for all, or B values as a tensor, an ndarray, a list or a tuple
+The range checks cost one host synchronisation per tensor (one aminmax)."""
+import math
+
+import numpy as np
+import torch
+
+
+def is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+
+def integer(x, msg: str, lo=None, hi=None, integral_float: bool = False) -> int:
+    ok = is_int(x)
+    if not ok and integral_float and not isinstance(x, bool):
+        try:
+            ok = bool(int(x) == x)
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+    if not ok or (lo is not None and x < lo) or (hi is not None and x > hi):
+        raise ValueError(msg)
+    return int(x)
+
+
+def real(x, msg: str, ok=None, convert: bool = False) -> float:
+    """a finite float that satisfies ok(value)"""
+    try:
+        if isinstance(x, bool) or not (convert or isinstance(x, (int, float, np.integer, np.floating))):
+            raise TypeError
+        v = float(x)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(msg) from None
+    if not math.isfinite(v) or (ok is not None and not ok(v)):
+        raise ValueError(msg)
+    return v
+
+
+def as_list(x):
+    """a tensor or ndarray as the (nested) list of its values; anything else as it is"""
+    if isinstance(x, torch.Tensor):
+        return x.detach().cpu().tolist()
+    return x.tolist() if isinstance(x, np.ndarray) else x
+
+
+def per_image(x, name: str, B: int, conv=None, each: int = 1) -> list:
+    """a scalar for all or B values -> a list of B * each values (each: consecutive copies of an image's value), converted by conv"""
+    x = as_list(x)
+    if isinstance(x, (list, tuple)):
+        if len(x) != B:
+            raise ValueError(f'{name} must be a scalar or {B} values, got {len(x)}')
+        vals = [v for v in x for _ in range(each)]
+    else:
+        vals = [x] * (B * each)
+    try:
+        return vals if conv is None else [conv(v) for v in vals]
+    except (TypeError, OverflowError) as e:
+        raise ValueError(f'{name}: {e}') from None
+
+
+def _integral(v) -> int:
+    if isinstance(v, bool) or (isinstance(v, float) and v != int(v)) or not isinstance(v, (int, float, np.integer)):
+        raise ValueError(f'expected an integer, got {v!r}')
+    return int(v)
+
+
+def _integer_tensor(t: torch.Tensor) -> bool:
+    return not (t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool)
+
+
+def labels_1d(label, N, msg: str, scalar: bool = False) -> torch.Tensor:
+    """(N,) integer class ids (N None: one or more); scalar: an int stands for N of them"""
+    lab = torch.full((N,), int(label), dtype=torch.int64) if scalar and is_int(label) else torch.as_tensor(label)
+    if lab.dim() != 1 or lab.numel() != (N if N is not None else max(lab.numel(), 1)) or not _integer_tensor(lab):
+        raise ValueError(msg)
+    return lab
+
+
+def labels_2d(label, N: int, msg: str) -> torch.Tensor:
+    """(K,) for every image or (N, K) integer class ids, K >= 1 -> (N, K)"""
+    lab = torch.as_tensor(label)
+    if lab.dim() == 1:
+        lab = lab.unsqueeze(0).expand(N, -1)
+    if lab.dim() != 2 or lab.shape[0] != N or lab.shape[1] < 1 or not _integer_tensor(lab):
+        raise ValueError(msg)
+    return lab
+
+
+def in_range(t: torch.Tensor, hi: int, msg: str):
+    """every element in [0, hi]: one host synchronisation"""
+    lo, top = torch.stack(torch.aminmax(t)).tolist()
+    if lo < 0 or top > hi:
+        raise ValueError(msg)
+
+
+def token_rows(gt_tokens, L: int) -> torch.Tensor:
+    """the token argument of the scoring calls, of evaluate and of compress -> an (N, L) integer tensor, shape and dtype checked"""
+    gt = torch.as_tensor(gt_tokens)
+    if gt.dim() != 2 or gt.shape[1] != L or gt.shape[0] < 1 or not _integer_tensor(gt):
+        raise ValueError(f'gt_tokens must be an (N, {L}) integer tensor of token ids')
+    return gt
+
+
+def token_label_range(gt: torch.Tensor, lab: torch.Tensor, V: int, num_classes: int):
+    """explicit range checks (one host sync each): a bad token would index past a logits row, a bad label past class_emb"""
+    in_range(gt, V - 1, f'gt_tokens must lie in [0, {V})')
+    in_range(lab, num_classes, f'labels must lie in [0, {num_classes}]')
+
+
+def cfg_arg(cfg, name: str = 'cfg') -> float:
+    """cfg / fill_cfg: whatever float() takes, a bool included (1.0 / 0.0), as in the per-image samplers"""
+    return real(float(cfg) if isinstance(cfg, bool) else cfg, f'{name} must be finite and >= 0', lambda v: v >= 0, convert=True)
+
+
+def sample_args(V: int, label_B, g_seeds, cfg, top_k, top_p):
+    """the argument handling of the per-image calls -> (labels (B,) integer tensor, seeds, cfgs, top_ks, top_ps: lists of B values)"""
+    lab = labels_1d(label_B, None, 'label_B must hold B >= 1 integer class ids')
+    B = lab.numel()
+    if isinstance(g_seeds, (int, np.integer)) or (isinstance(g_seeds, torch.Tensor) and g_seeds.dim() == 0):
+        raise ValueError(f'g_seeds must hold one seed per image ({B} values)')
+    seeds = per_image(g_seeds, 'g_seeds', B, _integral)
+    cfgs, ks, ps = per_image(cfg, 'cfg', B, float), per_image(top_k, 'top_k', B, _integral), per_image(top_p, 'top_p', B, float)
+    if any(sd < 0 or sd >= 1 << 63 for sd in seeds):
+        raise ValueError('g_seeds must lie in [0, 2^63)')
+    if not all(math.isfinite(c) for c in cfgs):
+        raise ValueError('cfg must be finite')
+    if any(k < 0 or k > V for k in ks):
+        raise ValueError(f'top_k must lie in [0, {V}]')
+    if not all(0.0 <= p <= 1.0 for p in ps):                 # (NaN fails the comparison)
+        raise ValueError('top_p must lie in [0, 1]')
+    return lab, seeds, cfgs, ks, ps
+
+
+def candidate_args(V: int, fields, label_B, g_seeds, n, by, cfg, top_k, top_p, max_images, noun=None):
+    """the front end of sample_best_of, sample_best_of_pruned and sample_smc: n candidates (particles) per image, g_seeds (B, n), labels and
+    parameters one per image -> (B, n, and sample_args' result on the B * n rows, the seeds as B rows).  noun: refuse n > max_images"""
+    if by not in fields:
+        raise ValueError(f'by must be one of {fields}, got {by!r}')
+    integer(max_images, 'max_images must be an integer >= 1', 1, integral_float=True)
+    sd = as_list(g_seeds)
+    lab0 = torch.as_tensor(label_B)
+    if (not isinstance(sd, (list, tuple)) or len(sd) != lab0.numel() or len(sd) < 1 or not all(isinstance(r, (list, tuple)) and len(r) == len(sd[0]) for r in sd)
+            or len(sd[0]) < 1):
+        raise ValueError('g_seeds must be (B, n): one row of n >= 1 seeds per image')
+    B, width = len(sd), len(sd[0])
+    try:
+        agree = n is None or (not isinstance(n, bool) and int(n) == width)
+    except (TypeError, ValueError, OverflowError):
+        agree = False
+    if not agree:
+        raise ValueError(f'n = {n} but g_seeds holds {width} seeds per image')
+    n = width
+    if lab0.dim() != 1:
+        raise ValueError('label_B must hold B >= 1 integer class ids')
+    if noun is not None and n > max_images:
+        raise ValueError(f'max_images = {max_images} holds no whole image of n = {n} {noun}')
+    spread = lambda x: per_image(x, 'cfg / top_k / top_p', B, None, n)          # one value per image -> one per candidate
+    return (B, n) + sample_args(V, lab0.repeat_interleave(n), [v for r in sd for v in r], spread(cfg), spread(top_k), spread(top_p)) + (sd,)
+
+
+def _scale_index(si, S: int, what: str) -> int:
+    return integer(si, f'{what}: a boundary must be an integer scale index in [0, {S - 2}], got {si!r}', 0, S - 2)
+
+
+def normalize_resample(resample, S: int) -> list:
+    """the `resample` argument of VAR.sample_smc -> the boundary scales as a list: integer scale indices in [0, S-2] (below the last scale),
+    ascending and unique, validated as normalize_keep validates a scale; an empty sequence is allowed"""
+    if resample is None or isinstance(resample, (str, bytes, dict)) or not hasattr(resample, '__iter__'):
+        raise ValueError('resample must be a sequence of boundary scale indices')
+    out = []
+    for si in resample:
+        _scale_index(si, S, 'resample')
+        if out and si <= out[-1]:
+            raise ValueError(f'resample: the boundaries must be ascending and unique, got {si!r} after {out[-1]}')
+        out.append(int(si))
+    return out
+
+
+def normalize_keep(keep, S: int, alive: int) -> list:
+    """the `keep` argument of VAR.classify and VAR.sample_best_of_pruned -> [(scale, m), ...] ascending in the scale.  keep: None / {} (no pruning)
+    or {scale: m}, 0 <= scale < S-1, integer m >= 1; `alive` candidates enter.  A boundary that drops nothing (m at or above the survivor count
+    before it) is no boundary and vanishes."""
+    if keep is None:
+        keep = {}
+    if not isinstance(keep, dict):
+        raise ValueError('keep must be None or a dict {scale_index: m}')
+    sched = [(_scale_index(si, S, 'keep'), integer(m, f'keep: the number of candidates kept must be an integer >= 1, got {m!r}', 1)) for si, m in keep.items()]
+    schedule = []
+    for si, m in sorted(sched):
+        if m < alive:                        # a boundary that drops nothing is no boundary
+            schedule.append((si, m))
+            alive = m
+    return schedule

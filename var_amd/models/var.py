@@ -13,6 +13,8 @@ import torch
 import torch.nn as nn
 
 from .. import dist
+from . import args as A
+from .args import normalize_keep, normalize_resample     # noqa: F401  (names that tests and tools import from here)
 from .basic_var import AdaLNBeforeHead, AdaLNSelfAttn
 from .helpers import gumbel_softmax_with_rng, sample_with_top_k_top_p_     # noqa: F401  (names the notebooks import from here)
 from .vqvae import VQVAE, VectorQuantizer2
@@ -96,44 +98,6 @@ class SMCResult(NamedTuple):
         """(B,) int64: each image's particle of the highest final log-weight by VAR.classify's rule (NaN below everything, ties to the lower index)"""
         lw = self.log_weights.detach().cpu().numpy()
         return torch.tensor([int(rule_order(row)[0]) for row in lw], dtype=torch.int64, device=self.log_weights.device)
-
-
-def normalize_resample(resample, S: int) -> list:
-    """the `resample` argument of VAR.sample_smc -> the boundary scales as a list: integer scale indices in [0, S-2] (below the last scale),
-    ascending and unique, validated as normalize_keep validates a scale; an empty sequence is allowed"""
-    if resample is None or isinstance(resample, (str, bytes, dict)) or not hasattr(resample, '__iter__'):
-        raise ValueError('resample must be a sequence of boundary scale indices')
-    out = []
-    for si in resample:
-        if isinstance(si, bool) or not isinstance(si, (int, np.integer)) or not 0 <= si < S - 1:
-            raise ValueError(f'resample: a boundary must be an integer scale index in [0, {S - 2}], got {si!r}')
-        if out and si <= out[-1]:
-            raise ValueError(f'resample: the boundaries must be ascending and unique, got {si!r} after {out[-1]}')
-        out.append(int(si))
-    return out
-
-
-def normalize_keep(keep, S: int, alive: int) -> list:
-    """the `keep` argument of VAR.classify and VAR.sample_best_of_pruned -> [(scale, m), ...] ascending in the scale.  keep: None / {} (no pruning)
-    or {scale: m}, 0 <= scale < S-1, integer m >= 1; `alive` candidates enter.  A boundary that drops nothing (m at or above the survivor count
-    before it) is no boundary and vanishes."""
-    if keep is None:
-        keep = {}
-    if not isinstance(keep, dict):
-        raise ValueError('keep must be None or a dict {scale_index: m}')
-    sched = []
-    for si, m in keep.items():
-        if isinstance(si, bool) or not isinstance(si, (int, np.integer)) or not 0 <= si < S - 1:
-            raise ValueError(f'keep: a boundary must be an integer scale index in [0, {S - 2}], got {si!r}')
-        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 1:
-            raise ValueError(f'keep: the number of candidates kept must be an integer >= 1, got {m!r}')
-        sched.append((int(si), int(m)))
-    schedule = []
-    for si, m in sorted(sched):
-        if m < alive:                        # a boundary that drops nothing is no boundary
-            schedule.append((si, m))
-            alive = m
-    return schedule
 
 
 class GenerativeResult(NamedTuple):
@@ -871,24 +835,31 @@ class VAR(nn.Module):
                                  top_k=0, top_p=0.0, more_smooth=False) -> torch.Tensor:
         """Sample B images; returns (B, 3, H, W) in [0, 1].  Same arguments and RNG consumption as the reference
         (var.py:126-190): `g_seed` seeds self.rng, one Exp(1) fill of shape (B*l, V) is drawn per scale."""
+        self._hip_only('autoregressive_infer_cfg')
+        rng, lab = self._rng_and_labels(B, label_B, g_seed, negative_is_uncond=True, seeded_draw=True)
+        return self.engine().sample(B, lab, rng, cfg, top_k, top_p, more_smooth=bool(more_smooth))
+
+    def _hip_only(self, name: str, loop: str = 'sampling loop', how: str = '; move the model to a CUDA/ROCm device (there is no CPU fallback by design)'):
+        """the model's device; a model off the GPU is refused: the sampling calls have no PyTorch implementation"""
         dev = self.lvl_1L.device
         if dev.type != 'cuda':
-            raise RuntimeError('VAR.autoregressive_infer_cfg: this build runs the sampling loop on MI355X HIP kernels only; move the model to a '
-                               'CUDA/ROCm device (there is no CPU fallback by design)')
+            raise RuntimeError(f'VAR.{name}: this build runs the {loop} on MI355X HIP kernels only{how}')
+        return dev
+
+    def _rng_and_labels(self, B, label_B, g_seed, *, negative_is_uncond: bool, seeded_draw: bool, name: str = 'label_B'):
+        """g_seed and label_B of the reference-style sampling calls -> (self.rng seeded with g_seed, or None; (B,) int64 labels on the model's
+        device).  negative_is_uncond: an int label below 0 means num_classes.  seeded_draw: labels for label_B=None are drawn from that rng
+        (autoregressive_infer_cfg*); otherwise from torch's global generator, as the reference's inpainting and smooth_sampling do."""
+        dev = self.lvl_1L.device
         if g_seed is None: rng = None
         else: self.rng.manual_seed(g_seed); rng = self.rng
         if label_B is None:
-            label_B = torch.multinomial(self.uniform_prob, num_samples=B, replacement=True, generator=rng).reshape(B)
-        elif isinstance(label_B, int):
-            label_B = torch.full((B,), fill_value=self.num_classes if label_B < 0 else label_B, device=dev)
-        return self.engine().sample(B, label_B.to(dev).long(), rng, cfg, top_k, top_p, more_smooth=bool(more_smooth))
-
-    def _scored_device(self, name: str):
-        dev = self.lvl_1L.device
-        if dev.type != 'cuda':
-            raise RuntimeError(f'VAR.{name}: this build runs the sampling loop on MI355X HIP kernels only; move the model to a '
-                               'CUDA/ROCm device (there is no CPU fallback by design)')
-        return dev
+            label_B = torch.multinomial(self.uniform_prob, num_samples=B, replacement=True, generator=rng if seeded_draw else None).reshape(B)
+        elif isinstance(label_B, bool):
+            raise ValueError(f'{name} must be None, an int or {B} integer class ids')
+        elif A.is_int(label_B):
+            label_B = torch.full((B,), fill_value=self.num_classes if negative_is_uncond and label_B < 0 else int(label_B), device=dev)
+        return rng, label_B.to(dev).long()
 
     def _record(self, img, tok, st) -> SampleRecord:
         return SampleRecord(img, tok, st['logp_cond'], st['logp_guided'], st['logp_drawn'], st['entropy'], st['kept'], self.patch_nums)
@@ -902,16 +873,11 @@ class VAR(nn.Module):
         bit-identical to that call with the same arguments.  The numbers come from one reduction per scale behind the sampler
         (varhip_sample_stats_f32) on logits that are in memory anyway: no second transformer pass, as token_log_likelihood on the tokens
         would need.  decode=False skips the decoder (images is None)."""
-        dev = self._scored_device('autoregressive_infer_cfg_scored')
-        if g_seed is None: rng = None
-        else: self.rng.manual_seed(g_seed); rng = self.rng
-        if label_B is None:
-            label_B = torch.multinomial(self.uniform_prob, num_samples=B, replacement=True, generator=rng).reshape(B)
-        elif isinstance(label_B, int):
-            label_B = torch.full((B,), fill_value=self.num_classes if label_B < 0 else label_B, device=dev)
+        dev = self._hip_only('autoregressive_infer_cfg_scored')
+        rng, lab = self._rng_and_labels(B, label_B, g_seed, negative_is_uncond=True, seeded_draw=True)
         tok = torch.empty(B, self.L, dtype=torch.int64, device=dev)
         st = {}
-        img = self.engine().sample(B, label_B.to(dev).long(), rng, cfg, top_k, top_p, more_smooth=bool(more_smooth), tokens_out=tok,
+        img = self.engine().sample(B, lab, rng, cfg, top_k, top_p, more_smooth=bool(more_smooth), tokens_out=tok,
                                    decode=bool(decode), stats=st)
         return self._record(img if decode else None, tok, st)
 
@@ -920,7 +886,7 @@ class VAR(nn.Module):
         """autoregressive_infer_cfg_per_image (own seed, cfg, top_k, top_p per image; the project's counter-based noise stream) with the
         SampleRecord of autoregressive_infer_cfg_scored.  The tokens and every per-token field of image b depend on that request alone, not on
         what it is batched with (pixels: as for the per-image call, the decoder's kernel choice follows the batch).  HIP path only."""
-        dev = self._scored_device('autoregressive_infer_cfg_per_image_scored')
+        dev = self._hip_only('autoregressive_infer_cfg_per_image_scored')
         lab, seeds, cfgs, ks, ps = self._per_image_args(label_B, g_seeds, cfg, top_k, top_p)
         tok = torch.empty(lab.numel(), self.L, dtype=torch.int64, device=dev)
         st = {}
@@ -940,32 +906,8 @@ class VAR(nn.Module):
         floats) is kept.  totals[b, c] is the float64 sum of the field in token order; varhip_class_select_f32 picks per image the highest total
         on the device (NaN below everything, ties to the lower index), and only those B f_hat maps are gathered and decoded: the decoder is
         the most expensive single stage of a call and runs for 1 of n candidates."""
-        dev = self._scored_device('sample_best_of')
-        if by not in BEST_OF_FIELDS:
-            raise ValueError(f'by must be one of {BEST_OF_FIELDS}, got {by!r}')
-        if isinstance(max_images, bool) or int(max_images) != max_images or max_images < 1:
-            raise ValueError('max_images must be an integer >= 1')
-        sd = g_seeds.detach().cpu().tolist() if isinstance(g_seeds, torch.Tensor) else (g_seeds.tolist() if isinstance(g_seeds, np.ndarray) else g_seeds)
-        lab0 = torch.as_tensor(label_B)
-        if (not isinstance(sd, (list, tuple)) or len(sd) != lab0.numel() or len(sd) < 1 or not all(isinstance(r, (list, tuple)) and len(r) == len(sd[0]) for r in sd)
-                or len(sd[0]) < 1):
-            raise ValueError('g_seeds must be (B, n): one row of n >= 1 seeds per image')
-        B, width = len(sd), len(sd[0])
-        if n is not None and int(n) != width:
-            raise ValueError(f'n = {n} but g_seeds holds {width} seeds per image')
-        n = width
-
-        def spread(x):                                        # one value per image -> one per candidate
-            if isinstance(x, torch.Tensor): x = x.detach().cpu().tolist()
-            elif isinstance(x, np.ndarray): x = x.tolist()
-            if isinstance(x, (list, tuple)):
-                if len(x) != B:
-                    raise ValueError(f'cfg / top_k / top_p must be a scalar or {B} values, got {len(x)}')
-                return [v for v in x for _ in range(n)]
-            return x
-        if lab0.dim() != 1:
-            raise ValueError('label_B must hold B >= 1 integer class ids')
-        lab, seeds, cfgs, ks, ps = self._per_image_args(lab0.repeat_interleave(n), [v for r in sd for v in r], spread(cfg), spread(top_k), spread(top_p))
+        dev = self._hip_only('sample_best_of')
+        B, n, lab, seeds, cfgs, ks, ps, sd = A.candidate_args(self.V, BEST_OF_FIELDS, label_B, g_seeds, n, by, cfg, top_k, top_p, max_images)
         rec, f_hat, totals, choice = self.engine().sample_best_of(lab.to(dev).long(), seeds, cfgs, ks, ps, n, by, int(max_images))
         img = self.engine().decode_f_hat(f_hat)
         return img, self._record(img, rec.pop('tokens'), rec), totals, choice
@@ -987,35 +929,9 @@ class VAR(nn.Module):
         Chunks hold max_images // n whole images (n > max_images raises ValueError).  Whether an early total predicts the final rank depends on
         the weights: that trade-off is the caller's, as with classify's keep.  HIP path only (SamplingEngine.sample_best_of_pruned, DESIGN.md
         section 30)."""
-        dev = self._scored_device('sample_best_of_pruned')
-        if by not in BEST_OF_FIELDS:
-            raise ValueError(f'by must be one of {BEST_OF_FIELDS}, got {by!r}')
-        if isinstance(max_images, bool) or int(max_images) != max_images or max_images < 1:
-            raise ValueError('max_images must be an integer >= 1')
-        sd = g_seeds.detach().cpu().tolist() if isinstance(g_seeds, torch.Tensor) else (g_seeds.tolist() if isinstance(g_seeds, np.ndarray) else g_seeds)
-        lab0 = torch.as_tensor(label_B)
-        if (not isinstance(sd, (list, tuple)) or len(sd) != lab0.numel() or len(sd) < 1 or not all(isinstance(r, (list, tuple)) and len(r) == len(sd[0]) for r in sd)
-                or len(sd[0]) < 1):
-            raise ValueError('g_seeds must be (B, n): one row of n >= 1 seeds per image')
-        B, width = len(sd), len(sd[0])
-        if n is not None and int(n) != width:
-            raise ValueError(f'n = {n} but g_seeds holds {width} seeds per image')
-        n = width
-
-        def spread(x):                                        # one value per image -> one per candidate
-            if isinstance(x, torch.Tensor): x = x.detach().cpu().tolist()
-            elif isinstance(x, np.ndarray): x = x.tolist()
-            if isinstance(x, (list, tuple)):
-                if len(x) != B:
-                    raise ValueError(f'cfg / top_k / top_p must be a scalar or {B} values, got {len(x)}')
-                return [v for v in x for _ in range(n)]
-            return x
-        if lab0.dim() != 1:
-            raise ValueError('label_B must hold B >= 1 integer class ids')
+        dev = self._hip_only('sample_best_of_pruned')
+        B, n, lab, seeds, cfgs, ks, ps, sd = A.candidate_args(self.V, BEST_OF_FIELDS, label_B, g_seeds, n, by, cfg, top_k, top_p, max_images, 'candidates')
         schedule = normalize_keep(keep, len(self.patch_nums), n)
-        if n > max_images:
-            raise ValueError(f'max_images = {max_images} holds no whole image of n = {n} candidates')
-        lab, seeds, cfgs, ks, ps = self._per_image_args(lab0.repeat_interleave(n), [v for r in sd for v in r], spread(cfg), spread(top_k), spread(top_p))
         eng = self.engine()
         rec, f_hat, totals, depth, choice = eng.sample_best_of_pruned(lab.to(dev).long(), seeds, cfgs, ks, ps, n, by, schedule, int(max_images))
         img = eng.decode_f_hat(f_hat) if decode else None
@@ -1044,39 +960,13 @@ class VAR(nn.Module):
         max_images (pixels: as for the per-image call, the decoder's kernel choice follows its batch); self.rng is neither read nor advanced.  The K and V caches are resampled in place (varhip_kv_resample: only the rows that
         died are copied), so the call needs no second cache set and the late scales run the full batch.  Chunks hold max_images // n whole
         images (n > max_images raises ValueError).  HIP path only, no more_smooth (SamplingEngine.sample_smc)."""
-        dev = self._scored_device('sample_smc')
-        if by not in BEST_OF_FIELDS:
-            raise ValueError(f'by must be one of {BEST_OF_FIELDS}, got {by!r}')
-        if isinstance(max_images, bool) or int(max_images) != max_images or max_images < 1:
-            raise ValueError('max_images must be an integer >= 1')
-        if ess is not None and (isinstance(ess, bool) or not isinstance(ess, (int, float, np.integer, np.floating)) or not 0.0 < float(ess) <= 1.0):
-            raise ValueError(f'ess must be None (always resample) or a float in (0, 1], got {ess!r}')
-        if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)) or not math.isfinite(float(beta)):
-            raise ValueError(f'beta must be a finite float, got {beta!r}')
+        dev = self._hip_only('sample_smc')
+        if ess is not None:
+            A.real(ess, f'ess must be None (always resample) or a float in (0, 1], got {ess!r}', lambda v: 0.0 < v <= 1.0)
+        A.real(beta, f'beta must be a finite float, got {beta!r}')
         bounds = normalize_resample(resample, len(self.patch_nums))
-        sd = g_seeds.detach().cpu().tolist() if isinstance(g_seeds, torch.Tensor) else (g_seeds.tolist() if isinstance(g_seeds, np.ndarray) else g_seeds)
-        lab0 = torch.as_tensor(label_B)
-        if (not isinstance(sd, (list, tuple)) or len(sd) != lab0.numel() or len(sd) < 1 or not all(isinstance(r, (list, tuple)) and len(r) == len(sd[0]) for r in sd)
-                or len(sd[0]) < 1):
-            raise ValueError('g_seeds must be (B, n): one row of n >= 1 seeds per image')
-        B, width = len(sd), len(sd[0])
-        if n is not None and int(n) != width:
-            raise ValueError(f'n = {n} but g_seeds holds {width} seeds per image')
-        n = width
-
-        def spread(x):                                        # one value per image -> one per particle
-            if isinstance(x, torch.Tensor): x = x.detach().cpu().tolist()
-            elif isinstance(x, np.ndarray): x = x.tolist()
-            if isinstance(x, (list, tuple)):
-                if len(x) != B:
-                    raise ValueError(f'cfg / top_k / top_p must be a scalar or {B} values, got {len(x)}')
-                return [v for v in x for _ in range(n)]
-            return x
-        if lab0.dim() != 1:
-            raise ValueError('label_B must hold B >= 1 integer class ids')
-        if n > max_images:
-            raise ValueError(f'max_images = {max_images} holds no whole image of n = {n} particles')
-        lab, seeds, cfgs, ks, ps = self._per_image_args(lab0.repeat_interleave(n), [v for r in sd for v in r], spread(cfg), spread(top_k), spread(top_p))
+        B, n, lab, seeds, cfgs, ks, ps, sd = A.candidate_args(self.V, BEST_OF_FIELDS, label_B, g_seeds, n, by, cfg, top_k, top_p, max_images, 'particles')
+        lab0 = lab[::n]                                        # (lab holds each image's label n times)
         rs = [r[0] for r in sd] if resample_seeds is None else self._per_image_args(lab0, resample_seeds, 0.0, 0, 0.0)[1]
         eng = self.engine()
         res = eng.sample_smc(lab.to(dev).long(), seeds, cfgs, ks, ps, n, by, bounds, float(beta), -1.0 if ess is None else float(ess), rs, int(max_images))
@@ -1116,44 +1006,7 @@ class VAR(nn.Module):
 
     def _per_image_args(self, label_B, g_seeds, cfg, top_k, top_p):
         """the argument handling of the per-image calls -> (labels (B,) integer tensor, seeds, cfgs, top_ks, top_ps: lists of B values)"""
-        lab = torch.as_tensor(label_B)
-        if lab.dim() != 1 or lab.numel() < 1 or lab.dtype.is_floating_point or lab.dtype.is_complex or lab.dtype == torch.bool:
-            raise ValueError('label_B must hold B >= 1 integer class ids')
-        B = lab.numel()
-
-        def per(x, name, conv):
-            if isinstance(x, torch.Tensor):
-                x = x.detach().cpu().tolist()
-            elif isinstance(x, np.ndarray):
-                x = x.tolist()
-            if isinstance(x, (list, tuple)):
-                if len(x) != B:
-                    raise ValueError(f'{name} must be a scalar or {B} values, got {len(x)}')
-                vals = list(x)
-            else:
-                vals = [x] * B
-            try:
-                return [conv(v) for v in vals]
-            except (TypeError, OverflowError) as e:
-                raise ValueError(f'{name}: {e}') from None
-
-        def as_int(v):
-            if isinstance(v, bool) or (isinstance(v, float) and v != int(v)) or not isinstance(v, (int, float, np.integer)):
-                raise ValueError(f'expected an integer, got {v!r}')
-            return int(v)
-        if isinstance(g_seeds, (int, np.integer)) or (isinstance(g_seeds, torch.Tensor) and g_seeds.dim() == 0):
-            raise ValueError(f'g_seeds must hold one seed per image ({B} values)')
-        seeds = per(g_seeds, 'g_seeds', as_int)
-        cfgs, ks, ps = per(cfg, 'cfg', float), per(top_k, 'top_k', as_int), per(top_p, 'top_p', float)
-        if any(sd < 0 or sd >= 1 << 63 for sd in seeds):
-            raise ValueError('g_seeds must lie in [0, 2^63)')
-        if not all(math.isfinite(c) for c in cfgs):
-            raise ValueError('cfg must be finite')
-        if any(k < 0 or k > self.V for k in ks):
-            raise ValueError(f'top_k must lie in [0, {self.V}]')
-        if not all(0.0 <= p <= 1.0 for p in ps):                 # (NaN fails the comparison)
-            raise ValueError('top_p must lie in [0, 1]')
-        return lab, seeds, cfgs, ks, ps
+        return A.sample_args(self.V, label_B, g_seeds, cfg, top_k, top_p)
 
     def _per_image_torch(self, lab, seeds, cfgs, ks, ps, more_smooth: bool):
         """the PyTorch side of autoregressive_infer_cfg_per_image (reference var.py:126-190, one request at a time): the Exp(1) fills are
@@ -1237,18 +1090,10 @@ class VAR(nn.Module):
         mask = self._edit_mask(edit_mask, B)
         if isinstance(label_B, torch.Tensor) and (label_B.dtype.is_floating_point or label_B.dtype == torch.bool or label_B.numel() != B):
             raise ValueError(f'label_B must be None, an int or {B} integer class ids')
-        dev = self.lvl_1L.device
-        if dev.type != 'cuda':
-            raise RuntimeError('VAR.autoregressive_infer_cfg_with_mask: this build runs the editing loop on MI355X HIP kernels only; move the model '
-                               'to a CUDA/ROCm device (there is no CPU fallback by design)')
-        if g_seed is None: rng = None
-        else: self.rng.manual_seed(g_seed); rng = self.rng
-        if label_B is None:
-            label_B = torch.multinomial(self.uniform_prob, num_samples=B, replacement=True, generator=rng).reshape(B)
-        elif isinstance(label_B, int):
-            label_B = torch.full((B,), fill_value=self.num_classes if label_B < 0 else label_B, device=dev)
+        dev = self._hip_only('autoregressive_infer_cfg_with_mask', 'editing loop')
+        rng, lab = self._rng_and_labels(B, label_B, g_seed, negative_is_uncond=True, seeded_draw=True)
         tokens = tokens.to(dev).expand(B, -1).contiguous()
-        return self.engine().sample(B, label_B.to(dev).long().reshape(B), rng, cfg, top_k, top_p, more_smooth=bool(more_smooth),
+        return self.engine().sample(B, lab.reshape(B), rng, cfg, top_k, top_p, more_smooth=bool(more_smooth),
                                     edit=dict(tokens=tokens, mask=mask.to(dev)))
 
     def _edit_tokens(self, toks, B: int) -> torch.Tensor:
@@ -1467,16 +1312,9 @@ class VAR(nn.Module):
         dev = self.lvl_1L.device
         gt = self._token_shape(gt_tokens)
         N = gt.shape[0]
-        if isinstance(label, (int, np.integer)) and not isinstance(label, bool):
-            lab = torch.full((N,), int(label), dtype=torch.int64)
-        else:
-            lab = torch.as_tensor(label)
-        if lab.dim() != 1 or lab.shape[0] != N or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
-            raise ValueError(f'label must be an int or (N,) integer class ids, N = {N}')
-        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or radius < 0:
-            raise ValueError('radius must be an integer >= 0')
-        if isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 1:
-            raise ValueError('max_rows must be an integer >= 1')
+        lab = A.labels_1d(label, N, f'label must be an int or (N,) integer class ids, N = {N}', scalar=True)
+        A.integer(radius, 'radius must be an integer >= 0', 0)
+        A.integer(max_rows, 'max_rows must be an integer >= 1', 1)
         if layers is None:
             layers = tuple(range(self.depth))
         else:
@@ -1484,7 +1322,7 @@ class VAR(nn.Module):
                 layers = tuple(layers)
             except TypeError:
                 raise ValueError('layers must be None or a strictly increasing sequence of block indices') from None
-            if not layers or any(isinstance(b, bool) or not isinstance(b, (int, np.integer)) for b in layers) \
+            if not layers or not all(A.is_int(b) for b in layers) \
                     or any(b < 0 or b >= self.depth for b in layers) or any(b1 <= b0 for b0, b1 in zip(layers, layers[1:])):
                 raise ValueError(f'layers must be None or a strictly increasing sequence of block indices in [0, {self.depth})')
             layers = tuple(int(b) for b in layers)
@@ -1558,9 +1396,7 @@ class VAR(nn.Module):
             raise ValueError('edges must be 1-D with B + 1 entries, 1 <= B <= 256')
         if bool(torch.isnan(e).any()) or float(e[0]) < 0 or not bool((e[1:] > e[:-1]).all()):
             raise ValueError('edges must be strictly increasing in fp32, without NaN, with edges[0] >= 0 (the last may be +inf)')
-        if isinstance(min_prob, bool) or not isinstance(min_prob, (int, float, np.integer, np.floating)) or not math.isfinite(float(min_prob)) \
-                or not 0.0 <= float(np.float32(min_prob)) < 1.0:
-            raise ValueError('min_prob must be a finite number in [0, 1)')
+        A.real(min_prob, 'min_prob must be a finite number in [0, 1)', lambda v: 0.0 <= float(np.float32(v)) < 1.0)
         return e.contiguous(), float(np.float32(min_prob))
 
     def _score_desc(self, score, group, threshold, top_k) -> tuple:
@@ -1573,16 +1409,14 @@ class VAR(nn.Module):
                 raise ValueError(f'{name} is not a parameter of score {score!r}')
         if score == 'group_smoothed':
             group = 50 if group is None else group
-            if isinstance(group, bool) or int(group) != group or group < 1:
-                raise ValueError('group must be an integer >= 1')
+            A.integer(group, 'group must be an integer >= 1', 1, integral_float=True)
             desc = (score, int(group))
         elif score == 'neighbor_max':
-            if threshold is None or isinstance(threshold, bool) or not math.isfinite(float(threshold)) or float(threshold) < 0:
-                raise ValueError('neighbor_max needs a finite threshold >= 0')
+            A.real(threshold, 'neighbor_max needs a finite threshold >= 0', lambda v: v >= 0, convert=threshold is not None)
             desc = (score, float(threshold))
         elif score == 'expected_distance':
-            if top_k is not None and (isinstance(top_k, bool) or int(top_k) != top_k or not 1 <= top_k <= self.V):
-                raise ValueError(f'top_k must be None or an integer in [1, {self.V}]')
+            if top_k is not None:
+                A.integer(top_k, f'top_k must be None or an integer in [1, {self.V}]', 1, self.V, integral_float=True)
             desc = (score, 0 if top_k is None else int(top_k))
         else:
             desc = (score,)
@@ -1648,24 +1482,13 @@ class VAR(nn.Module):
                 or x.shape[2] != 16 * P or x.shape[3] != 16 * P):
             raise ValueError(f'img must be an (N, 3, {16 * P}, {16 * P}) float32 tensor with N >= 1')
         N = x.shape[0]
-        lab = torch.as_tensor(label)
-        if lab.dim() == 1:
-            lab = lab.unsqueeze(0).expand(N, -1)
-        if lab.dim() != 2 or lab.shape[0] != N or lab.shape[1] < 1 or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
-            raise ValueError(f'label must be (K,) or (N, K) integer class ids with K >= 1, N = {N}')
-        lo, hi = torch.stack(torch.aminmax(lab)).tolist()
-        if lo < 0 or hi > self.num_classes:
-            raise ValueError(f'labels must lie in [0, {self.num_classes}]')
-        c = last_kept_scale
-        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= c <= S - 2:
-            raise ValueError(f'last_kept_scale must be an integer scale index in [0, {S - 2}], got {c!r}')
+        lab = A.labels_2d(label, N, f'label must be (K,) or (N, K) integer class ids with K >= 1, N = {N}')
+        A.in_range(lab, self.num_classes, f'labels must lie in [0, {self.num_classes}]')
+        c = A.integer(last_kept_scale, f'last_kept_scale must be an integer scale index in [0, {S - 2}], got {last_kept_scale!r}', 0, S - 2)
         if not callable(feature) and feature not in GENERATIVE_FEATURES:
             raise ValueError(f'feature must be one of {GENERATIVE_FEATURES} or a callable, got {feature!r}')
-        cfg = float(cfg)
-        if not math.isfinite(cfg) or cfg < 0:
-            raise ValueError('cfg must be finite and >= 0')
-        if isinstance(max_rows, bool) or int(max_rows) != max_rows or max_rows < 1 + (cfg > 0):
-            raise ValueError(f'max_rows must be an integer >= {1 + (cfg > 0)}')
+        cfg = A.cfg_arg(cfg)
+        A.integer(max_rows, f'max_rows must be an integer >= {1 + (cfg > 0)}', 1 + (cfg > 0), integral_float=True)
         if not isinstance(match_input_range, bool):
             raise ValueError('match_input_range must be a bool')
         vae = self.vae_proxy[0]
@@ -1730,14 +1553,9 @@ class VAR(nn.Module):
                 raise ValueError('gt_tokens: every scale must be on one device')
             toks = torch.cat(list(toks), dim=1)
         gt = self._token_shape(toks)
-        lab = torch.as_tensor(label_B)
-        if lab.dim() != 1 or lab.shape[0] != gt.shape[0] or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
-            raise ValueError(f'label_B must be (N,) integer class ids, N = {gt.shape[0]}')
-        if isinstance(label_smooth, bool) or not isinstance(label_smooth, (int, float, np.integer, np.floating)) or not math.isfinite(float(label_smooth)) \
-                or not 0.0 <= float(label_smooth) < 1.0:
-            raise ValueError('label_smooth must be a finite number in [0, 1)')
-        if isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 1:
-            raise ValueError('max_rows must be an integer >= 1')
+        lab = A.labels_1d(label_B, gt.shape[0], f'label_B must be (N,) integer class ids, N = {gt.shape[0]}')
+        A.real(label_smooth, 'label_smooth must be a finite number in [0, 1)', lambda v: 0.0 <= v < 1.0)
+        A.integer(max_rows, 'max_rows must be an integer >= 1', 1)
         self._token_label_range(gt, lab)
         return gt.to(dev, torch.int64), lab.to(dev, torch.int64), float(label_smooth)
 
@@ -1745,16 +1563,10 @@ class VAR(nn.Module):
         """validation of token_log_likelihood / token_scores: -> (gt (N, L) int64, labels (N, K) int64 on the model's device, cfg)"""
         dev = self.lvl_1L.device
         gt = self._token_shape(gt_tokens)
-        lab = torch.as_tensor(label)
-        if lab.dim() == 1:
-            lab = lab.unsqueeze(0).expand(gt.shape[0], -1)
-        if lab.dim() != 2 or lab.shape[0] != gt.shape[0] or lab.shape[1] < 1 or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
-            raise ValueError(f'label must be (K,) or (N, K) integer class ids with K >= 1, N = {gt.shape[0]}')
-        cfg = float(cfg)
-        if not math.isfinite(cfg) or cfg < 0:
-            raise ValueError('cfg must be finite and >= 0')
-        if int(max_rows) != max_rows or max_rows < 1 + (cfg > 0):
-            raise ValueError(f'max_rows must be an integer >= {1 + (cfg > 0)} (the class rows of a pass plus the unconditional row with cfg > 0)')
+        lab = A.labels_2d(label, gt.shape[0], f'label must be (K,) or (N, K) integer class ids with K >= 1, N = {gt.shape[0]}')
+        cfg = A.cfg_arg(cfg)
+        A.integer(max_rows, f'max_rows must be an integer >= {1 + (cfg > 0)} (the class rows of a pass plus the unconditional row with cfg > 0)', 1 + (cfg > 0),
+                  integral_float=True)
         self._token_label_range(gt, lab)
         return gt.to(dev, torch.int64), lab.to(dev, torch.int64), cfg
 
@@ -1769,19 +1581,12 @@ class VAR(nn.Module):
         frequency table (include/var_hip.h) and leaves the token's (C, F); the rANS coder runs on the host.  A blob does not depend on what it
         was batched with, nor on the calls made before.  f32 only (ValueError under a 16-bit precision); a CPU model: RuntimeError."""
         from .. import abi, hip
-        dev = self._scored_device('compress')
+        dev = self._hip_only('compress')
         gt = self._token_shape(torch.cat(list(gt_tokens), 1) if isinstance(gt_tokens, (list, tuple)) else gt_tokens)
         B, S = gt.shape[0], len(self.patch_nums)
-        lab = torch.full((B,), int(label_B)) if isinstance(label_B, int) else torch.as_tensor(label_B)
-        if lab.dim() != 1 or lab.shape[0] != B or lab.is_floating_point() or lab.is_complex() or lab.dtype == torch.bool:
-            raise ValueError(f'label_B must be an int or ({B},) integer class ids')
-        cfg = float(cfg)
-        if not math.isfinite(cfg) or cfg < 0:
-            raise ValueError('cfg must be finite and >= 0')
-        last = S - 1 if scales is None else scales
-        if int(last) != last or not 0 <= last < S:
-            raise ValueError(f'scales must be None or an integer in [0, {S - 1}]')
-        last = int(last)
+        lab = A.labels_1d(label_B, B, f'label_B must be an int or ({B},) integer class ids', scalar=True)
+        cfg = A.cfg_arg(cfg)
+        last = S - 1 if scales is None else A.integer(scales, f'scales must be None or an integer in [0, {S - 1}]', 0, S - 1, integral_float=True)
         self._token_label_range(gt, lab)
         pairs, flags = self.engine().code_tokens(gt.to(dev, torch.int64), lab.to(dev, torch.int64), cfg, last)
         n = self.begin_ends[last][1]
@@ -1809,7 +1614,7 @@ class VAR(nn.Module):
         synchronisation inside it.  A blob that fails the decoder's bounds check, the end check or the token hash raises VarCodecError naming
         the image and the check: also what decoding with other weights gives.  f32 only; a CPU model: RuntimeError."""
         from .. import abi
-        dev = self._scored_device('decompress')
+        dev = self._hip_only('decompress')
         if complete not in (None, 'greedy'):
             raise ValueError("complete must be None or 'greedy'")
         blobs = list(blobs)
@@ -1825,9 +1630,7 @@ class VAR(nn.Module):
             raise ValueError(f"decompress: the blobs were coded for V = {h0['V']}, patch_nums = {h0['patch_nums']}; this model has {self.V}, {tuple(self.patch_nums)}")
         if h0['pb'] != abi.CODEC_PB or not 1 <= h0['coded'] <= S or not math.isfinite(h0['cfg']) or h0['cfg'] < 0:
             raise ValueError('decompress: the header names a table precision, scale count or cfg this build does not code with')
-        fill_cfg = float(fill_cfg)
-        if not math.isfinite(fill_cfg) or fill_cfg < 0:
-            raise ValueError('fill_cfg must be finite and >= 0')
+        fill_cfg = A.cfg_arg(fill_cfg, 'fill_cfg')
         lab = torch.tensor([h['label'] for h in heads], dtype=torch.int64)
         if int(lab.min()) < 0 or int(lab.max()) > self.num_classes:
             raise ValueError(f'labels must lie in [0, {self.num_classes}]')
@@ -1853,19 +1656,11 @@ class VAR(nn.Module):
 
     def _token_shape(self, gt_tokens) -> torch.Tensor:
         """the token argument of the scoring calls and of evaluate -> an (N, L) integer tensor, shape and dtype checked"""
-        gt = torch.as_tensor(gt_tokens)
-        if gt.dim() != 2 or gt.shape[1] != self.L or gt.shape[0] < 1 or gt.dtype in (torch.bool,) or gt.is_floating_point() or gt.is_complex():
-            raise ValueError(f'gt_tokens must be an (N, {self.L}) integer tensor of token ids')
-        return gt
+        return A.token_rows(gt_tokens, self.L)
 
     def _token_label_range(self, gt: torch.Tensor, lab: torch.Tensor):
         """explicit range checks (one host sync each): a bad token would index past a logits row, a bad label past class_emb"""
-        lo, hi = torch.stack(torch.aminmax(gt)).tolist()
-        if lo < 0 or hi >= self.V:
-            raise ValueError(f'gt_tokens must lie in [0, {self.V})')
-        lo, hi = torch.stack(torch.aminmax(lab)).tolist()
-        if lo < 0 or hi > self.num_classes:
-            raise ValueError(f'labels must lie in [0, {self.num_classes}]')
+        A.token_label_range(gt, lab, self.V, self.num_classes)
 
     def _scoring_on_hip(self, gt: torch.Tensor) -> bool:
         return not self.training and self.prog_si < 0 and gt.device.type == 'cuda' and self.head.weight.dtype == torch.float32 and self.C == 64 * self.num_heads
@@ -1900,19 +1695,12 @@ class VAR(nn.Module):
         Runs the same HIP loop as autoregressive_infer_cfg with the token replacement fused in (SamplingEngine.sample)."""
         if mask.shape != gt_tokens.shape:
             raise ValueError('Mask shape must match the latent token shape obtained from vae.img_to_idxBl')
-        dev = self.lvl_1L.device
-        if dev.type != 'cuda':
-            raise RuntimeError('VAR.inpainting: this build runs the sampling loop on MI355X HIP kernels only (no CPU fallback by design)')
+        dev = self._hip_only('inpainting', how=' (no CPU fallback by design)')
         B = gt_tokens.shape[0]
-        if label is None:
-            label = torch.multinomial(self.uniform_prob, num_samples=B, replacement=True).reshape(B)     # unseeded, as in the reference
-        elif isinstance(label, int):
-            label = torch.full((B,), fill_value=label, device=dev)
-        if g_seed is None: rng = None
-        else: self.rng.manual_seed(g_seed); rng = self.rng
+        rng, lab = self._rng_and_labels(B, label, g_seed, negative_is_uncond=False, seeded_draw=False, name='label')
         # more_smooth (var.py:332-341): the embeddings then come from the gumbel softmax of the filtered logits alone — the kept tokens
         # only enter through the reference's `final_tokens`, which that branch never reads; defined only when no scale is fully kept
-        return self.engine().sample(B, label.to(dev).long(), rng, cfg, top_k, top_p, gt_tokens=gt_tokens, keep_mask=mask, more_smooth=bool(more_smooth))
+        return self.engine().sample(B, lab, rng, cfg, top_k, top_p, gt_tokens=gt_tokens, keep_mask=mask, more_smooth=bool(more_smooth))
 
     def smooth_sampling(self, gt_tokens: torch.Tensor, n: int, label: Optional[Union[int, torch.LongTensor]] = None,
                         g_seed: Optional[int] = None, cfg: float = 1.5, more_smooth: bool = False,
@@ -1924,18 +1712,11 @@ class VAR(nn.Module):
         reference's `sampled_tokens.new_tensor(max_vals)` does —, sum of log_softmax(-distance) at the chosen candidates).
         The neighbour table uses the direct-form L2 distance with ties broken by index (var_hip.h), where the reference's
         torch.cdist/argsort pair leaves both to the BLAS and an unstable sort."""
-        dev = self.lvl_1L.device
-        if dev.type != 'cuda':
-            raise RuntimeError('VAR.smooth_sampling: this build runs the sampling loop on MI355X HIP kernels only (no CPU fallback by design)')
+        dev = self._hip_only('smooth_sampling', how=' (no CPU fallback by design)')
         B = gt_tokens.shape[0]
-        if label is None:
-            label = torch.multinomial(self.uniform_prob, num_samples=B, replacement=True).reshape(B)
-        elif isinstance(label, int):
-            label = torch.full((B,), fill_value=label, device=dev)
-        if g_seed is None: rng = None
-        else: self.rng.manual_seed(g_seed); rng = self.rng
+        rng, lab = self._rng_and_labels(B, label, g_seed, negative_is_uncond=False, seeded_draw=False, name='label')
         eng = self.engine()
-        img = eng.sample(B, label.to(dev).long(), rng, cfg, 0, 0.0, more_smooth=more_smooth,
+        img = eng.sample(B, lab, rng, cfg, 0, 0.0, more_smooth=more_smooth,
                          smooth=dict(gt=gt_tokens, n=n, thr=None if neighbor_threshold is None else float(neighbor_threshold)))
         sum_ll, sum_dist_ll = eng.last_smooth
         return img, sum_ll, sum_dist_ll
