@@ -156,6 +156,22 @@ int varhip_sampler_force_walk(int on);
 int varhip_cfg_sample_rows_f32(const float* logits, const float* noise, int64_t* idx_out, float* masked_out, int B, int l, int V,
                                const double* t_cfg, const int32_t* top_k, const double* top_p, int top_k_cap, varhip_stream_t stream);
 
+/* The same sampler over G row groups with one coefficient row per image (VAR.sample_composed: weighted multi-class guidance; the reference
+ * has the two-row case only, var.py:172-173).  logits: [G][B][l][V], group-major as above, the unconditional group last; coef: DEVICE fp32
+ * [B][G].  With c_1 .. c_K the class rows of row r = (b, t) (K = G - 1), u its unconditional row and a = coef[b]:
+ *   acc = a_1*c_1;   acc = acc + a_k*c_k  for k = 2 .. K, in this order;   x = acc - a_u*u
+ * where every *, + and - is one fp32 operation rounded on its own (no fma contraction), as varhip_cfg_sample_f32's expression above: with
+ * G = 2 and coef[b] = ((float)(1.0 + t), (float)t) idx_out and masked_out are bit-identical to varhip_cfg_sample_rows_f32 with t_cfg[b] = t.
+ * Everything after x is that entry's: top_k [B] int32 and top_p [B] double DEVICE arrays, top_k_cap, the refused image (idx_out = -1 on
+ * its rows, masked_out and guided_out left alone), both settings of varhip_sampler_force_walk.  guided_out (optional, may be NULL):
+ * [B*l][V], receives x before any filtering; masked_out (optional) as above.  G < 2 or G > 9, a NULL logits / noise / idx_out / coef /
+ * top_k / top_p, logits or guided_out not 16-byte aligned, and the constraints of varhip_cfg_sample_rows_f32 on B, l, V, top_k_cap:
+ * VARHIP_EINVAL, nothing is written. */
+/* pinned against varhip_cfg_sample_rows_f32 and a numpy float32 restatement of the mix (tests/test_compose_kernels_gpu.py) */
+int varhip_mix_sample_rows_f32(const float* logits, const float* noise, int64_t* idx_out, float* masked_out, float* guided_out,
+                               int B, int l, int V, int G, const float* coef, const int32_t* top_k, const double* top_p, int top_k_cap,
+                               varhip_stream_t stream);
+
 /* ---- counter-based Exp(1) fill (per-image sampling) ----------------------------------------------------------------------------------------
  * out[(b*l + t)*V + v] = -vm_log(u),  u = (2n + 1) * 2^-24,  n = x >> 9,  x = word v % 4 of Philox4x32-10(counter, key) with
  *   key = (low 32 bits of seeds[b], high 32 bits of seeds[b]),  counter = (v / 4, t, scale, draw)

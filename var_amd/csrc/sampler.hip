@@ -48,13 +48,57 @@ __device__ __forceinline__ unsigned long long vs_scan256_u64(unsigned long long 
     return v + add;
 }
 
+// Stage (1) of the shared body below: what fills xs[V], the row's working logits.  Which thread computes an element is irrelevant — the sums
+// of the later stages read xs in their own canonical assignment — so every form reads its rows 16 bytes per lane.
+// VsCfgPair: (1+t)*cond - t*uncond (var.py:172-173), three roundings as in the reference's tensor expression.
+struct VsCfgPair {
+    const float* lc; const float* lu; float ca, cb;
+    __device__ __forceinline__ void operator()(float* __restrict__ xs, int V, int tid) const {
+        for (int i4 = tid; i4 < (V >> 2); i4 += 256) {
+            const f32x4 c4 = *(const f32x4*)(lc + 4 * i4), u4 = *(const f32x4*)(lu + 4 * i4);
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float a = ca * c4[e]; const float b = cb * u4[e]; o[e] = a - b; }
+            *(f32x4*)(xs + 4 * i4) = o;
+        }
+    }
+};
+// VsMix: G - 1 class rows and the unconditional row (the last), `gs` floats apart, with the image's G coefficients `a`:
+//   acc = a[0]*c_0;  acc = acc + a[k]*c_k (k = 1 .. G-2, in this order);  x = acc - a[G-1]*u
+// every product, sum and difference rounded to fp32 on its own (the file is compiled with -ffp-contract=off).  G = 2 is VsCfgPair's
+// expression operation for operation.  `guided` (nullable): the row's copy of x in global memory.
+struct VsMix {
+    const float* row0; int64_t gs; int G; const float* a; float* guided;
+    __device__ __forceinline__ void operator()(float* __restrict__ xs, int V, int tid) const {
+        const float a0 = a[0], au = a[G - 1];
+        const float* ru = row0 + (int64_t)(G - 1) * gs;
+        for (int i4 = tid; i4 < (V >> 2); i4 += 256) {
+            const f32x4 c4 = *(const f32x4*)(row0 + 4 * i4), u4 = *(const f32x4*)(ru + 4 * i4);
+            f32x4 acc;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = a0 * c4[e];
+            for (int k = 1; k < G - 1; ++k) {
+                const float ak = a[k];
+                const f32x4 k4 = *(const f32x4*)(row0 + (int64_t)k * gs + 4 * i4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { const float p = ak * k4[e]; acc[e] = acc[e] + p; }
+            }
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float b = au * u4[e]; o[e] = acc[e] - b; }
+            *(f32x4*)(xs + 4 * i4) = o;
+            if (guided) *(f32x4*)(guided + 4 * i4) = o;
+        }
+    }
+};
+
 // NV = V / 256 when the caller's V is the common 4096 (the exponentials of a thread's NV elements then stay in registers between the
 // phases: one evaluation instead of three), 0 = any V (evaluated where needed)
-// The body is shared by the two kernels below (forced inline into each): k_cfg_sample hands it the batch's scalars, k_cfg_sample_rows the
-// ones of the row's image.
-template <int NV>
-__device__ __forceinline__ void vs_cfg_sample_row(const float* __restrict__ logits, const float* __restrict__ noise, int64_t* __restrict__ idx_out,
-                                                  float* __restrict__ masked_out, int64_t rows, int V, float ca, float cb,
+// The body is shared by the three kernels below (forced inline into each): k_cfg_sample hands it the batch's scalars, k_cfg_sample_rows the
+// ones of the row's image, k_mix_sample_rows the image's coefficient row; `fill` is the kernel's stage (1).
+template <int NV, class Fill>
+__device__ __forceinline__ void vs_cfg_sample_row(const Fill& fill, const float* __restrict__ noise, int64_t* __restrict__ idx_out,
+                                                  float* __restrict__ masked_out, int V,
                                                   int top_k, int use_top_p, float thr, int cap, int force_walk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm_raw[];
     float* xs = reinterpret_cast<float*>(sm_raw);                                   // [V] working logits
@@ -71,18 +115,9 @@ __device__ __forceinline__ void vs_cfg_sample_row(const float* __restrict__ logi
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t row = blockIdx.x;
-    const float* lc = logits + row * V;
-    const float* lu = logits + (rows + row) * V;
 
-    // (1) CFG combine: (1+t)*cond - t*uncond, three roundings as in the reference's tensor expression
-    // (16 bytes per lane; which thread computes an element is irrelevant here — the sums below read xs in their own canonical assignment)
-    for (int i4 = tid; i4 < (V >> 2); i4 += 256) {
-        const f32x4 c4 = *(const f32x4*)(lc + 4 * i4), u4 = *(const f32x4*)(lu + 4 * i4);
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float a = ca * c4[e]; const float b = cb * u4[e]; o[e] = a - b; }
-        *(f32x4*)(xs + 4 * i4) = o;
-    }
+    // (1) the row's working logits (VsCfgPair: the CFG combine; VsMix: the weighted classes)
+    fill(xs, V, tid);
     // the row's Exp(1) noise is needed last: requested now (NV > 0: into registers), it arrives behind everything else
     float qv[NV > 0 ? NV : 1];
     if constexpr (NV > 0) {
@@ -391,7 +426,8 @@ template <int NV>
 __global__ void __launch_bounds__(256) k_cfg_sample(const float* __restrict__ logits, const float* __restrict__ noise, int64_t* __restrict__ idx_out,
                                                     float* __restrict__ masked_out, int64_t rows, int V, float ca, float cb,
                                                     int top_k, int use_top_p, float thr, int cap, int force_walk) {
-    vs_cfg_sample_row<NV>(logits, noise, idx_out, masked_out, rows, V, ca, cb, top_k, use_top_p, thr, cap, force_walk);
+    const int64_t row = blockIdx.x;
+    vs_cfg_sample_row<NV>(VsCfgPair{logits + row * V, logits + (rows + row) * V, ca, cb}, noise, idx_out, masked_out, V, top_k, use_top_p, thr, cap, force_walk);
 }
 
 // per-image parameters: the workgroup of row r reads those of image r / l and rounds them as varhip_cfg_sample_f32 rounds its scalars on the
@@ -408,7 +444,27 @@ __global__ void __launch_bounds__(256) k_cfg_sample_rows(const float* __restrict
         if (threadIdx.x == 0) idx_out[blockIdx.x] = -1;
         return;
     }
-    vs_cfg_sample_row<NV>(logits, noise, idx_out, masked_out, rows, V, (float)(1.0 + t), (float)t, k, p > 0.0 ? 1 : 0, (float)(1.0 - p), cap, force_walk);
+    const int64_t row = blockIdx.x;
+    vs_cfg_sample_row<NV>(VsCfgPair{logits + row * V, logits + (rows + row) * V, (float)(1.0 + t), (float)t}, noise, idx_out, masked_out, V,
+                          k, p > 0.0 ? 1 : 0, (float)(1.0 - p), cap, force_walk);
+}
+
+// G row groups with one coefficient row per image (VAR.sample_composed): stage (1) is VsMix, the rest the shared body with the image's top_k /
+// top_p, read and refused as k_cfg_sample_rows reads and refuses them (a refused image writes neither masked_out nor guided_out).
+template <int NV>
+__global__ void __launch_bounds__(256) k_mix_sample_rows(const float* __restrict__ logits, const float* __restrict__ noise, int64_t* __restrict__ idx_out,
+                                                         float* __restrict__ masked_out, float* __restrict__ guided_out, int64_t rows, int l, int V, int G,
+                                                         const float* __restrict__ coef, const int* __restrict__ top_k, const double* __restrict__ top_p,
+                                                         int cap, int force_walk) {
+    const int64_t row = blockIdx.x, b = row / l;
+    const double p = top_p[b];
+    const int k = top_k[b];
+    if (k < 0 || k > V || (k > 0 ? k : V) > cap) {
+        if (threadIdx.x == 0) idx_out[row] = -1;
+        return;
+    }
+    vs_cfg_sample_row<NV>(VsMix{logits + row * V, rows * V, G, coef + b * G, guided_out ? guided_out + row * V : nullptr}, noise, idx_out, masked_out, V,
+                          k, p > 0.0 ? 1 : 0, (float)(1.0 - p), cap, force_walk);
 }
 
 static int g_sampler_force_walk = 0;
@@ -452,6 +508,28 @@ extern "C" int varhip_cfg_sample_rows_f32(const float* logits, const float* nois
     else
         hipLaunchKernelGGL(k_cfg_sample_rows<0>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, logits, noise, idx_out, masked_out, rows, l, V,
                            t_cfg, top_k, top_p, cap, g_sampler_force_walk);
+    return vh_launch_status();
+}
+
+extern "C" int varhip_mix_sample_rows_f32(const float* logits, const float* noise, int64_t* idx_out, float* masked_out, float* guided_out,
+                                          int B, int l, int V, int G, const float* coef, const int32_t* top_k, const double* top_p, int top_k_cap,
+                                          varhip_stream_t stream) {
+    if (B <= 0 || l <= 0 || V <= 0 || (V & 255) || V > 8192 || G < 2 || G > 9 || top_k_cap < 1 || top_k_cap > V) return VARHIP_EINVAL;
+    if (!logits || !noise || !idx_out || !coef || !top_k || !top_p) return VARHIP_EINVAL;
+    if (((uintptr_t)logits & 15) || ((uintptr_t)guided_out & 15)) return VARHIP_EINVAL;       // (rows are read and guided_out is written 16 bytes per lane)
+    const int64_t rows = (int64_t)B * l;
+    int cap = 2; while (cap < top_k_cap) cap <<= 1;
+    const size_t lds = sizeof(float) * (size_t)V + sizeof(unsigned long long) * (size_t)cap;
+    static bool attr_done = false;
+    if (!attr_done) { (void)hipFuncSetAttribute((const void*)k_mix_sample_rows<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 12 * 8192);
+                      (void)hipFuncSetAttribute((const void*)k_mix_sample_rows<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 12 * 8192); attr_done = true; }
+    VhScope sc(VH_FAM_SAMPLER, (hipStream_t)stream, 0, 4.0 * rows * V * (G + 1.0 + (masked_out ? 1.0 : 0.0) + (guided_out ? 1.0 : 0.0)));
+    if (V == 4096)
+        hipLaunchKernelGGL(k_mix_sample_rows<16>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, logits, noise, idx_out, masked_out, guided_out, rows, l, V, G,
+                           coef, top_k, top_p, cap, g_sampler_force_walk);
+    else
+        hipLaunchKernelGGL(k_mix_sample_rows<0>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, logits, noise, idx_out, masked_out, guided_out, rows, l, V, G,
+                           coef, top_k, top_p, cap, g_sampler_force_walk);
     return vh_launch_status();
 }
 

@@ -56,6 +56,24 @@ def per_image_tables(cfg, top_k, top_p, S: int, V: int) -> dict:
     return dict(t=t, top_k=k, top_p=np.asarray([float(x) for x in top_p], dtype=np.float64), cap=int(V if (k == 0).any() else k.max()))
 
 
+def compose_tables(cfg, weights, S: int) -> np.ndarray:
+    """the coefficient table of a composed call (VAR.sample_composed): coef [S, B, K + 1] float32 from cfg (B values) and weights (S, B, K).
+    With t = per_image_tables' t[si][b] and W = sum_k w_k, added in float64 in index order:
+        a_k = fl32((1 + t) * w_k)  for the K class rows,    a_u = fl32(t + (1 + t) * (W - 1))  for the unconditional row, the last entry
+    — u + (1 + t) * sum_k w_k (c_k - u) with the u terms collected — every entry evaluated in float64 and rounded once.  K = 1, w = 1 gives
+    ((float)(1 + t), (float)t): the two scalars varhip_cfg_sample_rows_f32 derives from t."""
+    w = np.asarray(weights, dtype=np.float64)
+    Sw, B, K = w.shape
+    if Sw != S or B != len(cfg):
+        raise ValueError(f'weights must be ({S}, {len(cfg)}, K), got {tuple(w.shape)}')
+    t = per_image_tables(cfg, [0] * B, [0.0] * B, S, 1)['t']
+    W = np.zeros((S, B), dtype=np.float64)
+    for k in range(K):                                            # index order
+        W = W + w[:, :, k]
+    one_t = 1.0 + t
+    return np.concatenate((one_t[:, :, None] * w, (t + one_t * (W - 1.0))[:, :, None]), axis=2).astype(np.float32)
+
+
 # the per-token outputs of varhip_sample_stats_f32 in the order of its arguments (the keys of SamplingEngine.sample's `stats`)
 STATS_FIELDS = ('logp_cond', 'logp_guided', 'logp_drawn', 'kept', 'entropy')
 
@@ -919,7 +937,7 @@ class SamplingEngine(_Engine):
     def __init__(self, var):
         super().__init__()
         self.var = var
-        self._ws: Dict[tuple, dict] = {}            # (batch size, HIP stream, precision) -> buffers of a call
+        self._ws: Dict[tuple, dict] = {}            # (batch size, HIP stream, precision) -> buffers of a call; (..., G): of a pass of sample_composed
         self._ws_tf: Dict[tuple, dict] = {}         # the same for teacher_forced_logits
         self._ws_bop: Dict[tuple, dict] = {}        # (capacity, HIP stream, precision, stage) -> buffers of a stage of sample_best_of_pruned
         self._labels_ok = None                      # (the last label tensor whose range was checked, its version counter, address, length): one host sync saved per repeated call
@@ -1043,21 +1061,41 @@ class SamplingEngine(_Engine):
         ws = self._ws[(B, sid, self.precision)] = self._alloc_workspace(B, dev)
         return ws
 
-    def _alloc_workspace(self, B: int, dev) -> dict:
-        """a fresh buffer set of a sampling call of B images in the current precision (workspace() and _bop_workspace() cache them)"""
+    def _alloc_workspace(self, B: int, dev, G: int = 2) -> dict:
+        """a fresh buffer set of a sampling call of B images in the current precision (workspace() and _bop_workspace() cache them).  G: the row
+        groups per image (2: the CFG pair; _mix_workspace: a composed call's K + 1), R = G * B transformer rows"""
         var = self.var
         C, L, H, V, Cv, P = var.C, var.L, var.num_heads, var.V, var.Cvae, var.patch_nums[-1]
         lmax = max(p * p for p in var.patch_nums)
-        M = 2 * B * lmax
+        R = G * B
+        M = R * lmax
         hid = var.blocks[0].ffn.fc1.weight.shape[0]
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
         act = DT16.get(self.precision, torch.float32)                           # GEMM operands and KV cache; x / x2 / logits stay fp32
         return dict(dev=dev, x=e(M, C), x2=e(M, C), xn=e(M, C, dt=act), q=e(M, C, dt=act), att=e(M, C, dt=act), hid=e(M, hid, dt=act), logits=e(M, V),
-                    idx=e(B * lmax, dt=torch.int64), lvl_pos=e(L, C), cond=e(2 * B, C), cond_silu=e(2 * B, C), hn=e(2 * B, 2 * C),
-                    ada=e(var.depth, 2 * B, 6 * C) if var.shared_aln else e(2 * B, var.depth * 6 * C), shared=e(2 * B, 6 * C) if var.shared_aln else None,
-                    kc=[torch.zeros(2 * B, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
-                    vc=[torch.zeros(2 * B, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
+                    idx=e(B * lmax, dt=torch.int64), lvl_pos=e(L, C), cond=e(R, C), cond_silu=e(R, C), hn=e(R, 2 * C),
+                    ada=e(var.depth, R, 6 * C) if var.shared_aln else e(R, var.depth * 6 * C), shared=e(R, 6 * C) if var.shared_aln else None,
+                    kc=[torch.zeros(R, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
+                    vc=[torch.zeros(R, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
                     f_hat=e(B, P, P, Cv), up=e(B, P, P, Cv), pooled=e(B * lmax, Cv))
+
+    def _mix_workspace(self, B: int, G: int) -> dict:
+        """the buffer set of a pass of sample_composed: B images of G row groups.  It lives in the plain calls' cache under a key of its own,
+        (B, HIP stream, precision, G) — one B resident per (stream, precision, G), the same bound on the number of sets, the same poisoning in
+        the tests — and adds what the composed sampler writes: `masked` (the filtered rows) and `mixed` (the guided rows, followed by as many
+        zero rows: varhip_sample_stats_f32 reads it as a CFG pair with t = 0).  The prologue gets the G * B labels themselves, and
+        first_map_f32 writes an unconditional twin behind every label it is given (unused here): cond, cond_silu and x have room for it."""
+        sid = int(torch.cuda.current_stream().cuda_stream)
+        dev = self.var.pos_start.device
+        key = (B, sid, self.precision, G)
+        ws = self._ws.get(key)
+        if ws is None or ws['dev'] != dev:
+            self._ws = self._evict(self._ws, sid, (G,))
+            ws = self._ws[key] = self._alloc_workspace(B, dev, G)
+            C, V, lmax = self.var.C, self.var.V, max(p * p for p in self.var.patch_nums)
+            e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+            ws.update(cond=e(2 * G * B, C), cond_silu=e(2 * G * B, C), x=e(2 * G * B * lmax, C), masked=e(B * lmax, V), mixed=e(2 * B * lmax, V))
+        return ws
 
     def _bop_workspace(self, cap: int, stage: int) -> dict:
         """the buffer set of stage `stage` of sample_best_of_pruned, for up to `cap` candidates (a chunk of fewer uses a prefix of every buffer:
@@ -1177,12 +1215,15 @@ class SamplingEngine(_Engine):
                  ws['q'], ws['kc'][bi], ws['vc'][bi], rows, l, H, cur, self.var.L)
 
     # -- the sampling walk -------------------------------------------------------------------------------------------
-    def _scales(self, ws: dict, B: int, first: int, last: int, tr: Optional[dict] = None, ev: Optional[list] = None):
+    def _scales(self, ws: dict, B: int, first: int, last: int, tr: Optional[dict] = None, ev: Optional[list] = None, G: int = 2):
         """the sampling loop over scales first .. last for the B images whose state sits in the first rows of ws (its prologue run, ws['x'] holding
         scale `first`'s input, the caches the scales below it).  Per scale: the blocks; the scale is yielded (si, pn, l = pn * pn, cur = its first
         token, r = the stage ratio) and the caller's loop body sets .idx, the int64 [B * l] tokens it chose, and where they apply .soft and .ed;
         then the quantizer step (_quant_step) and, between the walk's own scales, next_map_f32.  Ends behind the quantizer step of `last`: what
-        follows is the caller's (a prune or resampling boundary, the decoder).  tr: sample()'s trace; ev: its profile_scales events."""
+        follows is the caller's (a prune or resampling boundary, the decoder).  tr: sample()'s trace; ev: its profile_scales events.
+        G: the row groups of ws (sample_composed: K + 1), group-major, each of B rows; every group gets the same next-scale input: next_map_f32
+        writes a pair of groups per launch, so it runs once per pair (an odd G: the last launch writes group G - 2 a second time, with the
+        same bits), and the groups hold identical bits because one kernel computed them from one f_hat."""
         var, w = self.var, self.w
         C, Cv, P = var.C, var.Cvae, var.patch_nums[-1]
         x, x2 = ws['x'], ws['x2']
@@ -1192,13 +1233,15 @@ class SamplingEngine(_Engine):
             sc = SimpleNamespace(si=si, pn=pn, l=pn * pn, cur=var.begin_ends[si][0], r=r, idx=None, soft=None, ed=None)
             if ev: ev[si].record()
             for bi, blk in enumerate(w['blocks']):                        # AdaLNSelfAttn.forward, basic_var.py:152-159
-                self.block(blk, ws, bi, x, x2, 2 * B, sc.l, sc.cur)
+                self.block(blk, ws, bi, x, x2, G * B, sc.l, sc.cur)
             yield sc
             self._quant_step(ws, B, sc)
             if tr is not None: tr['f_hat'].append(ws['f_hat'].permute(0, 3, 1, 2).clone())
             if si != last:
                 pq = var.patch_nums[si + 1]
-                hip.call('next_map_f32', ws['f_hat'], w['word_w'], w['word_b'], ws['lvl_pos'][sc.cur + sc.l:], x, ws['pooled'], B, P, pq, C, Cv)
+                for g0 in list(range(0, G - 1, 2)) + ([G - 2] if G % 2 else []):          # groups (g0, g0 + 1); G = 2: one launch on x itself
+                    hip.call('next_map_f32', ws['f_hat'], w['word_w'], w['word_b'], ws['lvl_pos'][sc.cur + sc.l:], x[g0 * B * pq * pq:] if g0 else x,
+                             ws['pooled'], B, P, pq, C, Cv)
                 if tr is not None: tr['pooled'].append(ws['pooled'][:B * pq * pq].view(B, pq, pq, Cv).permute(0, 3, 1, 2).clone())
 
     def _quant_step(self, ws: dict, B: int, sc):
@@ -1220,9 +1263,9 @@ class SamplingEngine(_Engine):
             hip.call('quant_accum_f32', sc.idx, w['codebook'], *tail)
 
     # -- the choosers: each leaves a scale's tokens, int64 [B * l] -------------------------------------------------------------------
-    def _logits(self, ws: dict, B: int, sc, tr: Optional[dict]):
-        """get_logits (var.py:118-124): AdaLNBeforeHead + head over the scale's 2B * l rows, into ws['logits']"""
-        self.head(ws['x'], ws['hn'], ws['xn'], ws['logits'], 2 * B * sc.l, sc.l)
+    def _logits(self, ws: dict, B: int, sc, tr: Optional[dict], G: int = 2):
+        """get_logits (var.py:118-124): AdaLNBeforeHead + head over the scale's G * B * l rows (G = 2: the CFG pair), into ws['logits']"""
+        self.head(ws['x'], ws['hn'], ws['xn'], ws['logits'], G * B * sc.l, sc.l)
         if tr is not None: tr['logits'].append(ws['logits'][:2 * B * sc.l].view(2 * B, sc.l, self.var.V).clone())
 
     def _sampled(self, ws: dict, B: int, sc, noise: '_Exp1', masked: Optional[torch.Tensor], t: float = 0.0, top_k: int = 0, top_p: float = 0.0,
@@ -1527,6 +1570,58 @@ class SamplingEngine(_Engine):
         for sc in self._scales(ws, R, first, last):
             sc.idx = self._sampled(ws, R, sc, noise, ws['masked'], per=per, stats=stats)
             tokens[:, sc.cur:sc.cur + sc.l].copy_(sc.idx.view(R, sc.l))
+
+    # -- weighted multi-class guidance (VAR.sample_composed) ------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample_composed(self, labels: torch.Tensor, coef: np.ndarray, seeds, cfg, top_k, top_p, max_rows: int, decode: bool) -> dict:
+        """sample_per_image with K classes per image mixed inside the sampler.  labels (B, K) int64, coef [S, B, K + 1] float32 (compose_tables),
+        seeds / cfg / top_k / top_p host sequences of length B, all validated by the caller (cfg is only there for the tables' sake: the
+        sampler reads coef).  G = K + 1 row groups run through the sampling walk, group-major with the unconditional group last: class k of
+        image b is transformer row k * B + b.  Per scale: the head over the G * B * l rows, the Philox fill of sample_per_image (draw 0),
+        varhip_mix_sample_rows_f32 (tokens, the filtered rows, the guided rows), varhip_sample_stats_f32 on (guided rows | zero rows) with
+        t = 0 — 1 * m - 0 * 0 is m exactly, so its `guided` outputs describe the mixed row — and varhip_token_loglik_f32 on the G * B rows
+        against the drawn tokens.  Passes of max_rows // G images; a pass is the per-image walk on its own images, so the split changes no bit
+        of the tokens, and the decoder runs once on all B maps.
+        -> dict(tokens (B, L) int64, logp_class (B, G, L), logp_guided, logp_drawn, entropy (B, L) fp32, kept (B, L) int32, images or None)"""
+        var = self.var
+        self.resolve_precision()
+        self.refresh()
+        self._wait_ready()
+        dev = var.pos_start.device
+        (B, K), G = labels.shape, labels.shape[1] + 1
+        S, L, V, P, Cv = len(var.patch_nums), var.L, var.V, var.patch_nums[-1], var.Cvae
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
+        out = dict(tokens=e(B, L, dt=torch.int64), logp_class=e(B, G, L), images=None)
+        out.update({key: e(B, L, dt=torch.int32 if key == 'kept' else torch.float32) for key in STATS_FIELDS[1:]})
+        f_all = e(B, P, P, Cv)
+        ipp = max(1, int(max_rows) // G)
+        for b0 in range(0, B, ipp):
+            n = min(ipp, B - b0)
+            ws = self._mix_workspace(n, G)
+            per, seeds_d = self._per_image_upload(cfg[b0:b0 + n], top_k[b0:b0 + n], top_p[b0:b0 + n], seeds[b0:b0 + n])
+            coef_d = torch.from_numpy(np.ascontiguousarray(coef[:, b0:b0 + n])).to(dev)
+            lab = torch.cat((labels[b0:b0 + n].t().reshape(-1), torch.full((n,), var.num_classes, dtype=torch.int64, device=dev))).contiguous()
+            lp_g, lp_own = e(G, n, L), e(n, L)                    # (lp_own: the stats kernel's `lp_cond` of the pair it is handed = logp_guided)
+            noise = _Exp1(self._philox(seeds_d, 0), None, V, dev)
+            ws['f_hat'].zero_()
+            self._prologue(ws, lab, G * n)
+            for sc in self._scales(ws, n, 0, S - 1, G=G):
+                l, cur = sc.l, sc.cur
+                self._logits(ws, n, sc, None, G)
+                idx, mixed = ws['idx'][:n * l], ws['mixed'][:2 * n * l]
+                mixed[n * l:].zero_()
+                hip.call('mix_sample_rows_f32', ws['logits'], noise.draw(n, sc.si, l), idx, ws['masked'], mixed, n, l, V, G, coef_d[sc.si],
+                         per['top_k'], per['top_p'], int(per['cap']))
+                hip.call('sample_stats_f32', mixed, ws['masked'], idx, n, l, V, 0.0, None, lp_own[:, cur:],
+                         *[out[key][b0:, cur:] for key in STATS_FIELDS[1:]], L)
+                hip.call('token_loglik_f32', ws['logits'], idx.repeat(G), l, G * n, 1, l, V, 0, 1.0, 0.0, lp_g[:, :, cur:], L, L)
+                out['tokens'][b0:b0 + n, cur:cur + l].copy_(idx.view(n, l))
+                sc.idx = idx
+            out['logp_class'][b0:b0 + n].copy_(lp_g.permute(1, 0, 2))
+            f_all[b0:b0 + n].copy_(ws['f_hat'])
+        if decode:
+            out['images'] = self.dec.decode_nhwc(f_all, precision=self.precision)
+        return out
 
     # -- best-of-n (VAR.sample_best_of) ---------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -141,6 +141,32 @@ def sample_args(V: int, label_B, g_seeds, cfg, top_k, top_p):
     return lab, seeds, cfgs, ks, ps
 
 
+COMPOSE_MAX_CLASSES = 8              # classes per image of VAR.sample_composed (varhip_mix_sample_rows_f32 takes up to 9 row groups)
+
+
+def compose_args(V: int, num_classes: int, S: int, labels, weights, g_seeds, cfg, top_k, top_p, max_rows):
+    """the argument handling of VAR.sample_composed -> (labels (B, K) int64 tensor, weights (S, B, K) float64 ndarray, and sample_args' seeds,
+    cfgs, top_ks, top_ps: lists of B values).  labels: (B, K) integer class ids in [0, num_classes], 1 <= K <= 8; weights: (B, K) (every
+    scale the same) or (S, B, K), finite, any sign; max_rows: an integer that holds one image's K + 1 rows"""
+    lab = torch.as_tensor(labels)
+    if lab.dim() != 2 or lab.shape[0] < 1 or not 1 <= lab.shape[1] <= COMPOSE_MAX_CLASSES or not _integer_tensor(lab):
+        raise ValueError(f'labels must be a (B, K) integer tensor of class ids, B >= 1, 1 <= K <= {COMPOSE_MAX_CLASSES}')
+    B, K = lab.shape
+    in_range(lab, num_classes, f'labels must lie in [0, {num_classes}]')
+    try:
+        w = np.array(as_list(weights), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'weights must be a ({B}, {K}) or ({S}, {B}, {K}) array of numbers') from None
+    if w.shape == (B, K):
+        w = np.broadcast_to(w, (S, B, K)).copy()
+    if w.shape != (S, B, K):
+        raise ValueError(f'weights must be ({B}, {K}) or ({S}, {B}, {K}), got {tuple(w.shape)}')
+    if not np.isfinite(w).all():
+        raise ValueError('weights must be finite')
+    integer(max_rows, f'max_rows must be an integer >= K + 1 = {K + 1}: the rows of one image', K + 1, integral_float=True)
+    return (lab.long(), w) + sample_args(V, lab[:, 0], g_seeds, cfg, top_k, top_p)[1:]
+
+
 def candidate_args(V: int, fields, label_B, g_seeds, n, by, cfg, top_k, top_p, max_images, noun=None):
     """the front end of sample_best_of, sample_best_of_pruned and sample_smc: n candidates (particles) per image, g_seeds (B, n), labels and
     parameters one per image -> (B, n, and sample_args' result on the B * n rows, the seeds as B rows).  noun: refuse n > max_images"""

@@ -655,6 +655,31 @@ class SampleRecord:
 BEST_OF_FIELDS = ('logp_cond', 'logp_guided', 'logp_drawn')
 
 
+class ComposedRecord:
+    """What VAR.sample_composed returns, on the model's device (coef on the host):
+      images       (B, 3, H, W) fp32 in [0, 1], or None (decode=False)
+      tokens       (B, L) int64, the drawn tokens
+      logp_class   (B, K + 1, L) fp32: log p(token) under each class row's own logits, the unconditional row last (VAR.token_log_likelihood's
+                   value at cfg 0 for the same row)
+      logp_guided  (B, L) fp32: the same under the mixed row x = sum_k a_k c_k - a_u u
+      logp_drawn   (B, L) fp32: the same under the distribution the token was drawn from (x after top-k / top-p)
+      entropy      (B, L) fp32: the entropy of softmax(x) in nats
+      kept         (B, L) int32: how many codes top-k / top-p left to draw from
+      coef         (S, B, K + 1) float32 ndarray: the coefficients (a_1 .. a_K, a_u) used at each scale (var_amd.engine.compose_tables)
+      labels       (B, K) int64, as given;  patch_nums: the scales the L tokens are laid out in
+    logp_guided, logp_drawn, entropy and kept are SampleRecord's, with the mixed row as the guided row (DESIGN.md sections 26 and 34)."""
+    __slots__ = ('images', 'tokens', 'logp_class', 'logp_guided', 'logp_drawn', 'entropy', 'kept', 'coef', 'labels', 'patch_nums')
+
+    def __init__(self, images, tokens, logp_class, logp_guided, logp_drawn, entropy, kept, coef, labels, patch_nums):
+        self.images, self.tokens, self.logp_class, self.logp_guided, self.logp_drawn = images, tokens, logp_class, logp_guided, logp_drawn
+        self.entropy, self.kept, self.coef, self.labels, self.patch_nums = entropy, kept, coef, labels, tuple(patch_nums)
+
+    def __repr__(self):
+        B, G, L = tuple(self.logp_class.shape)
+        img = None if self.images is None else tuple(self.images.shape)
+        return f'ComposedRecord(B={B}, K={G - 1}, L={L}, images={img}, mean kept={float(self.kept.float().mean()):.1f})'
+
+
 def rule_order(totals: np.ndarray) -> np.ndarray:
     """indices of a 1-D float64 array in VAR.classify's order: higher total first, NaN below everything, equal totals by lower index"""
     nan = np.isnan(totals)
@@ -893,6 +918,29 @@ class VAR(nn.Module):
         img = self.engine().sample_per_image(lab.to(dev).long(), seeds, cfgs, ks, ps, more_smooth=bool(more_smooth), tokens_out=tok,
                                              decode=bool(decode), stats=st)
         return self._record(img if decode else None, tok, st)
+
+    @torch.no_grad()
+    def sample_composed(self, labels, weights, g_seeds, cfg=1.5, top_k=0, top_p=0.0, max_rows: int = 128, decode=True) -> ComposedRecord:
+        """Sample with K classes per image guiding one token stream: hybrids (weights 0.5 / 0.5), a negative class (a weight below 0), and a
+        schedule over the scales (class A on the coarse scales, class B on the fine ones).
+          labels    (B, K) integer class ids in [0, num_classes], 1 <= K <= 8
+          weights   (B, K), the same on every scale, or (S, B, K), one set per scale; finite, any sign, zero allowed
+          g_seeds, cfg, top_k, top_p: per image as in autoregressive_infer_cfg_per_image (a scalar for all or B values; the same Philox stream)
+        The sampler of image b at scale s draws from the row (t = cfg_b * s / (S - 1), W = sum_k w_k)
+            x = (1 + t) * sum_k w_k c_k - (t + (1 + t)(W - 1)) u     =  u + (1 + t) * sum_k w_k (c_k - u)
+        with c_k the logits under class k and u the unconditional ones: K = 1, w = 1 is autoregressive_infer_cfg_per_image_scored bit for bit.
+        The K + 1 coefficients are formed on the host in float64 and rounded once to fp32 (ComposedRecord.coef), the kernel adds the products
+        in class order, each operation rounded to fp32 (varhip_mix_sample_rows_f32).  The images run in passes of at most max_rows transformer
+        rows, K + 1 per image; a request's tokens and record do not depend on the pass or the batch it is in.  decode=False skips the decoder.
+        HIP path only (a CUDA / ROCm model in eval mode); no more_smooth, no edit mask (SamplingEngine.sample_composed)."""
+        lab, w, seeds, cfgs, ks, ps = A.compose_args(self.V, self.num_classes, len(self.patch_nums), labels, weights, g_seeds, cfg, top_k, top_p, max_rows)
+        dev = self._hip_only('sample_composed')
+        if self.training or self.prog_si >= 0:
+            raise RuntimeError('VAR.sample_composed: this build runs the sampling loop on MI355X HIP kernels only; put the model in eval mode with prog_si < 0')
+        from ..engine import compose_tables
+        coef = compose_tables(cfgs, w, len(self.patch_nums))
+        r = self.engine().sample_composed(lab.to(dev), coef, seeds, cfgs, ks, ps, int(max_rows), bool(decode))
+        return ComposedRecord(r['images'], r['tokens'], r['logp_class'], r['logp_guided'], r['logp_drawn'], r['entropy'], r['kept'], coef, lab, self.patch_nums)
 
     @torch.no_grad()
     def sample_best_of(self, label_B, g_seeds, n: Optional[int] = None, by: str = 'logp_cond', cfg=1.5, top_k=0, top_p=0.0, max_images: int = 64):
