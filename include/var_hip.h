@@ -838,6 +838,10 @@ int varhip_gemm_qkv_f16(const void* A, int64_t lda, const void* W, int64_t ldw, 
 /* attention over the fp16 KV cache (basic_var.py:107-117 on the flash path): fp32 scores and softmax, p rounded to fp16 for p.v, fp16 out */
 int varhip_attn_cached_f16(const void* q, const void* kcache, const void* vcache, void* out,
                            int B2, int l, int H, int curL, int Lmax, varhip_stream_t stream);
+/* testing: the waves per workgroup (NW of k_attn16<NW>, 1 .. 4; a wave owns 32 queries, the grid is ceil(l / (32 NW)) x H x B2) of the latest
+ * varhip_attn_cached_f16 / _bf16 launch, written by the launcher from the value it switches on.  0 before the first launch; a refused call
+ * (VARHIP_EINVAL) leaves it unchanged.  Read-only: it changes no dispatch.  Host only: it launches nothing and reads no device memory. */
+int varhip_attn16_last_waves(void);
 /* varhip_ln_modulate_f32 with the result rounded to fp16 (the A operand of the next GEMM) */
 int varhip_ln_modulate_f16out(const float* x, const float* scale, int64_t ld_scale, const float* shift, int64_t ld_shift,
                               void* out, int M, int C, int rows_per_group, float eps, varhip_stream_t stream);

@@ -298,6 +298,7 @@ NO_DEVICE_POINTER = {                                        # everything else v
     'conv16_last_pick': 'test hook: reports the kernel instantiation of the latest 16-bit convolution',
     'gemm16_deep': 'test hook: kernel choice', 'gemm16_last_pick': 'test hook: reports the kernel instantiations of the latest 16-bit GEMM',
     'quant_last_route': 'test hook: reports the kernel route of the latest quantizer-step, word-embed or nearest-code call',
+    'attn16_last_waves': 'test hook: reports the waves per workgroup of the latest 16-bit attention launch',
     'vq_stats_blocks': 'size helper: host arithmetic (the workgroup partials of varhip_vq_scale_stats_f32 for n elements)',
 }
 FLAVOURS = ('f16', 'bf16')

@@ -14,6 +14,8 @@
 #include "common.h"
 #include "elem16.h"
 
+extern int vh_g_attn16_last_waves;       // the NW of the latest launch of either flavour (timing.hip; varhip_attn16_last_waves)
+
 namespace VH16_NS {
 
 typedef vh_e16 h8 __attribute__((ext_vector_type(8)));
@@ -214,6 +216,7 @@ extern "C" int VH16_FN(attn_cached)(const void* q, const void* kcache, const voi
     if (B2 > 65535 || H > 65535 || (((uintptr_t)q | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)out) & 15)) return VARHIP_EINVAL;
     VhScope sc(VH_FAM_ATTN16, (hipStream_t)stream, 4.0 * B2 * H * (double)l * curL * 64, 2.0 * B2 * H * (2.0 * curL * 64 + 2.0 * l * 64));
     const int nw = attn16_waves(l);
+    vh_g_attn16_last_waves = nw;                                    // varhip_attn16_last_waves (a refused call never gets here)
     dim3 grid((l + nw * 32 - 1) / (nw * 32), H, B2);
     hipStream_t s = (hipStream_t)stream;
     const vh_e16 *q_ = (const vh_e16*)q, *k_ = (const vh_e16*)kcache, *v_ = (const vh_e16*)vcache;

@@ -53,6 +53,7 @@ int vh_g_conv16_force_wm = 0;
 int vh_g_gemm16_last_pick[2] = {0, 0};      // the kernels of the latest 16-bit GEMM call's launches, written by launch16 / launch16p (varhip_gemm16_last_pick)
 int vh_g_gemm16_nlaunch = 0;                // launches that call has made so far
 int vh_g_conv16_last_pick = -1;      // the instantiation of the latest dispatch_conv16 of either flavour (varhip_conv16_last_pick)
+int vh_g_attn16_last_waves = 0;      // the waves per workgroup (NW of k_attn16<NW>) of the latest 16-bit attention launch of either flavour (varhip_attn16_last_waves)
 
 extern "C" {
 
@@ -68,6 +69,8 @@ int varhip_gemm16_last_pick(int i) { return (i == 0 || i == 1) ? vh_g_gemm16_las
 int varhip_conv16_force_tile(int wm) { vh_g_conv16_force_wm = (wm == 2 || wm == 4 || wm == 8) ? wm : 0; return 0; }
 // tests: the kernel instantiation the latest 16-bit convolution of either flavour was dispatched to (include/var_hip.h has the packing); -1 before the first
 int varhip_conv16_last_pick(void) { return vh_g_conv16_last_pick; }
+// tests: NW of the k_attn16<NW> that the latest 16-bit attention call of either flavour launched; 0 before the first
+int varhip_attn16_last_waves(void) { return vh_g_attn16_last_waves; }
 
 const char* varhip_version(void) { return "var_hip 0.1.0 gfx950"; }
 
