@@ -172,6 +172,30 @@ int varhip_mix_sample_rows_f32(const float* logits, const float* noise, int64_t*
                                int B, int l, int V, int G, const float* coef, const int32_t* top_k, const double* top_p, int top_k_cap,
                                varhip_stream_t stream);
 
+/* varhip_cfg_sample_rows_f32 with four more per-image controls (VAR.sample_controlled): a logit bias, a temperature and min-p join top-k and
+ * top-p.  tau [B] and min_p [B] are DEVICE fp32 arrays; bias is a DEVICE fp32 table [R][ld_bias] (ld_bias >= V, ld_bias % 4 == 0, 16-byte
+ * aligned: rows are read 16 bytes per lane), bias_row [B] a DEVICE int32 array that names each image's row of it, -1 (any negative) = none.
+ * bias and bias_row may be NULL (no image has a bias; R is then not read).  Row r = (b, j), in this order:
+ *   1. combine   x = ca*cond - cb*uncond from t_cfg[b], exactly as varhip_cfg_sample_rows_f32
+ *   2. bias      where bias_row[b] >= 0:  x_v = x_v + bias[bias_row[b] * ld_bias + v], one fp32 add; -inf bans code v.  Where bias_row[b] < 0
+ *                the stage does not run at all (a signed zero of x survives)
+ *   3. temper    where tau[b] != 1:  x_v = x_v / tau[b], one correctly rounded fp32 division (no reciprocal multiply)
+ *   4. top-k     as above, on the biased and tempered row
+ *   5. min-p     where min_p[b] > 0:  m = the row's maximum after top-k, e_v = vm_exp(x_v - m) (include/var_math.h), x_v = -inf where
+ *                e_v < min_p[b] (an fp32 compare).  The maximum has e = 1 and always survives
+ *   6. top-p and the draw as above, on what remains
+ * masked_out (optional) receives the row after stage 6, idx_out the drawn index.  Contracts, under both settings of
+ * varhip_sampler_force_walk: with tau = 1, min_p = 0 and bias_row = -1 (or NULL) for every image, idx_out and masked_out are bit-identical
+ * to varhip_cfg_sample_rows_f32 on the same operands; and for every image b, its l rows are bit-identical to the same call with B = 1 on
+ * those rows and that image's parameters alone.  Refused image (idx_out = -1 on its rows, masked_out left alone, no LDS touched): top_k as
+ * in varhip_cfg_sample_rows_f32; tau[b] not in (0, inf) or NaN; min_p[b] not in [0, 1] or NaN; bias_row[b] >= R.  VARHIP_EINVAL before any
+ * launch, nothing written: a NULL logits / noise / idx_out / t_cfg / top_k / top_p / tau / min_p, bias_row without bias, a bias that is not
+ * 16-byte aligned or whose ld_bias is below V or no multiple of 4, R < 0, and the constraints of varhip_cfg_sample_rows_f32. */
+/* pinned against varhip_cfg_sample_rows_f32 on rows prepared by a numpy float32 restatement of stages 2, 3 and 5 (tests/test_controlled_kernels_gpu.py) */
+int varhip_ctl_sample_rows_f32(const float* logits, const float* noise, int64_t* idx_out, float* masked_out, int B, int l, int V,
+                               const double* t_cfg, const int32_t* top_k, const double* top_p, const float* tau, const float* min_p,
+                               const float* bias, const int32_t* bias_row, int R, int ld_bias, int top_k_cap, varhip_stream_t stream);
+
 /* ---- counter-based Exp(1) fill (per-image sampling) ----------------------------------------------------------------------------------------
  * out[(b*l + t)*V + v] = -vm_log(u),  u = (2n + 1) * 2^-24,  n = x >> 9,  x = word v % 4 of Philox4x32-10(counter, key) with
  *   key = (low 32 bits of seeds[b], high 32 bits of seeds[b]),  counter = (v / 4, t, scale, draw)

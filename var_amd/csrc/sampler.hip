@@ -52,6 +52,7 @@ __device__ __forceinline__ unsigned long long vs_scan256_u64(unsigned long long 
 // of the later stages read xs in their own canonical assignment — so every form reads its rows 16 bytes per lane.
 // VsCfgPair: (1+t)*cond - t*uncond (var.py:172-173), three roundings as in the reference's tensor expression.
 struct VsCfgPair {
+    static constexpr bool kMinP = false;
     const float* lc; const float* lu; float ca, cb;
     __device__ __forceinline__ void operator()(float* __restrict__ xs, int V, int tid) const {
         for (int i4 = tid; i4 < (V >> 2); i4 += 256) {
@@ -68,6 +69,7 @@ struct VsCfgPair {
 // every product, sum and difference rounded to fp32 on its own (the file is compiled with -ffp-contract=off).  G = 2 is VsCfgPair's
 // expression operation for operation.  `guided` (nullable): the row's copy of x in global memory.
 struct VsMix {
+    static constexpr bool kMinP = false;
     const float* row0; int64_t gs; int G; const float* a; float* guided;
     __device__ __forceinline__ void operator()(float* __restrict__ xs, int V, int tid) const {
         const float a0 = a[0], au = a[G - 1];
@@ -91,11 +93,39 @@ struct VsMix {
         }
     }
 };
+// VsCtl (VAR.sample_controlled): VsCfgPair's expression, then per element  x = x + bias[v]  where the image has a bias row (`bias` != nullptr)
+// and  x = x / tau  where tau != 1 — one fp32 add, one correctly rounded fp32 division (never a reciprocal multiply), both skipped outright
+// where they do not apply, so a signed zero of the combine survives.  kMinP: the body below runs its min-p stage (between top-k and top-p)
+// with this fill's min_p; the trait is a compile-time constant, so the bodies of the other kernels contain no trace of that stage.
+struct VsCtl {
+    static constexpr bool kMinP = true;
+    const float* lc; const float* lu; float ca, cb; const float* bias; float tau, min_p;
+    __device__ __forceinline__ void operator()(float* __restrict__ xs, int V, int tid) const {
+        const bool temper = tau != 1.0f;
+        for (int i4 = tid; i4 < (V >> 2); i4 += 256) {
+            const f32x4 c4 = *(const f32x4*)(lc + 4 * i4), u4 = *(const f32x4*)(lu + 4 * i4);
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float a = ca * c4[e]; const float b = cb * u4[e]; o[e] = a - b; }
+            if (bias) {
+                const f32x4 b4 = *(const f32x4*)(bias + 4 * i4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = o[e] + b4[e];
+            }
+            if (temper) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = o[e] / tau;
+            }
+            *(f32x4*)(xs + 4 * i4) = o;
+        }
+    }
+};
 
 // NV = V / 256 when the caller's V is the common 4096 (the exponentials of a thread's NV elements then stay in registers between the
 // phases: one evaluation instead of three), 0 = any V (evaluated where needed)
-// The body is shared by the three kernels below (forced inline into each): k_cfg_sample hands it the batch's scalars, k_cfg_sample_rows the
-// ones of the row's image, k_mix_sample_rows the image's coefficient row; `fill` is the kernel's stage (1).
+// The body is shared by the four kernels below (forced inline into each): k_cfg_sample hands it the batch's scalars, k_cfg_sample_rows the
+// ones of the row's image, k_mix_sample_rows the image's coefficient row, k_ctl_sample_rows the image's controls; `fill` is the kernel's
+// stage (1), and Fill::kMinP says at compile time whether the min-p stage exists in this instantiation.
 template <int NV, class Fill>
 __device__ __forceinline__ void vs_cfg_sample_row(const Fill& fill, const float* __restrict__ noise, int64_t* __restrict__ idx_out,
                                                   float* __restrict__ masked_out, int V,
@@ -159,6 +189,16 @@ __device__ __forceinline__ void vs_cfg_sample_row(const Fill& fill, const float*
     for (int i = tid; i < V; i += 256) m = fmaxf(m, xs[i]);
     m = vh_block_max256(m, red);
     float ev[NV > 0 ? NV : 1];                                      // (NV > 0) exp(x - m) of this thread's elements
+
+    // (2b) min-p (Fill::kMinP only): an entry goes where its exponential relative to the mode's, e = vm_exp(x - m), is below min_p (an fp32
+    // compare).  The maximum has e = 1 >= min_p and stays, so m is still the row's maximum; everything below reads xs again, so the
+    // exponentials that top-p keeps in registers are those of the row after this stage (a removed entry: vm_exp(-inf - m) = 0).
+    if constexpr (Fill::kMinP) {
+        if (fill.min_p > 0.0f) {
+            for (int i = tid; i < V; i += 256) if (vm_exp(xs[i] - m) < fill.min_p) xs[i] = -INFINITY;
+            __syncthreads();
+        }
+    }
 
     // (3) top-p
     if (use_top_p) {
@@ -467,6 +507,29 @@ __global__ void __launch_bounds__(256) k_mix_sample_rows(const float* __restrict
                           k, p > 0.0 ? 1 : 0, (float)(1.0 - p), cap, force_walk);
 }
 
+// k_cfg_sample_rows with the image's controls (VAR.sample_controlled): bias row, temperature and min-p join the image's parameters; stage (1)
+// is VsCtl, the rest the shared body with its min-p stage compiled in.  An image with a control outside its domain is refused as one with a
+// bad top_k is: -1 on its rows, nothing else written, no LDS touched.
+template <int NV>
+__global__ void __launch_bounds__(256) k_ctl_sample_rows(const float* __restrict__ logits, const float* __restrict__ noise, int64_t* __restrict__ idx_out,
+                                                         float* __restrict__ masked_out, int64_t rows, int l, int V, const double* __restrict__ t_cfg,
+                                                         const int* __restrict__ top_k, const double* __restrict__ top_p, const float* __restrict__ tau,
+                                                         const float* __restrict__ min_p, const float* __restrict__ bias, const int* __restrict__ bias_row,
+                                                         int R, int ld_bias, int cap, int force_walk) {
+    const int64_t row = blockIdx.x, b = row / l;
+    const double t = t_cfg[b], p = top_p[b];
+    const int k = top_k[b];
+    const float ta = tau[b], mp = min_p[b];
+    const int br = bias_row ? bias_row[b] : -1;
+    if (k < 0 || k > V || (k > 0 ? k : V) > cap || !(ta > 0.0f && ta < INFINITY) || !(mp >= 0.0f && mp <= 1.0f) || br >= R) {
+        if (threadIdx.x == 0) idx_out[row] = -1;
+        return;
+    }
+    vs_cfg_sample_row<NV>(VsCtl{logits + row * V, logits + (rows + row) * V, (float)(1.0 + t), (float)t,
+                                br >= 0 ? bias + (int64_t)br * ld_bias : nullptr, ta, mp},
+                          noise, idx_out, masked_out, V, k, p > 0.0 ? 1 : 0, (float)(1.0 - p), cap, force_walk);
+}
+
 static int g_sampler_force_walk = 0;
 // testing: 1 = decide every top-p cut by the sequential walk (the definition), 0 = by the parallel prefix sum wherever that is provably the same
 extern "C" int varhip_sampler_force_walk(int on) { g_sampler_force_walk = on ? 1 : 0; return 0; }
@@ -530,6 +593,31 @@ extern "C" int varhip_mix_sample_rows_f32(const float* logits, const float* nois
     else
         hipLaunchKernelGGL(k_mix_sample_rows<0>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, logits, noise, idx_out, masked_out, guided_out, rows, l, V, G,
                            coef, top_k, top_p, cap, g_sampler_force_walk);
+    return vh_launch_status();
+}
+
+extern "C" int varhip_ctl_sample_rows_f32(const float* logits, const float* noise, int64_t* idx_out, float* masked_out, int B, int l, int V,
+                                          const double* t_cfg, const int32_t* top_k, const double* top_p, const float* tau, const float* min_p,
+                                          const float* bias, const int32_t* bias_row, int R, int ld_bias, int top_k_cap, varhip_stream_t stream) {
+    if (B <= 0 || l <= 0 || V <= 0 || (V & 255) || V > 8192 || top_k_cap < 1 || top_k_cap > V) return VARHIP_EINVAL;
+    if (!logits || !noise || !idx_out || !t_cfg || !top_k || !top_p || !tau || !min_p) return VARHIP_EINVAL;
+    if ((uintptr_t)logits & 15) return VARHIP_EINVAL;
+    if (R < 0 || (bias_row && !bias)) return VARHIP_EINVAL;
+    if (bias && (((uintptr_t)bias & 15) || ld_bias < V || (ld_bias & 3))) return VARHIP_EINVAL;     // (bias rows are read 16 bytes per lane)
+    const int64_t rows = (int64_t)B * l;
+    int cap = 2; while (cap < top_k_cap) cap <<= 1;
+    const size_t lds = sizeof(float) * (size_t)V + sizeof(unsigned long long) * (size_t)cap;
+    static bool attr_done = false;
+    if (!attr_done) { (void)hipFuncSetAttribute((const void*)k_ctl_sample_rows<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 12 * 8192);
+                      (void)hipFuncSetAttribute((const void*)k_ctl_sample_rows<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 12 * 8192); attr_done = true; }
+    VhScope sc(VH_FAM_SAMPLER, (hipStream_t)stream, 0, 4.0 * rows * V * (3.0 + (bias ? 1.0 : 0.0)));
+    const int Rk = bias ? R : 0;                                        // (no table: every bias_row >= 0 is out of range)
+    if (V == 4096)
+        hipLaunchKernelGGL(k_ctl_sample_rows<16>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, logits, noise, idx_out, masked_out, rows, l, V,
+                           t_cfg, top_k, top_p, tau, min_p, bias, bias_row, Rk, ld_bias, cap, g_sampler_force_walk);
+    else
+        hipLaunchKernelGGL(k_ctl_sample_rows<0>, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, logits, noise, idx_out, masked_out, rows, l, V,
+                           t_cfg, top_k, top_p, tau, min_p, bias, bias_row, Rk, ld_bias, cap, g_sampler_force_walk);
     return vh_launch_status();
 }
 

@@ -56,6 +56,32 @@ def per_image_tables(cfg, top_k, top_p, S: int, V: int) -> dict:
     return dict(t=t, top_k=k, top_p=np.asarray([float(x) for x in top_p], dtype=np.float64), cap=int(V if (k == 0).any() else k.max()))
 
 
+def control_tables(cfg, top_k, top_p, temperature, min_p, logit_bias, S: int, V: int, B: int, cfg_ramp: bool = True) -> dict:
+    """the host tables of a controlled call (VAR.sample_controlled).  Every knob is a scalar, (B,) or (S, B), a size-1 B axis broadcasting ((S, 1)
+    is a pure per-scale schedule); logit_bias is None, (V,), (B, V) or (S, B, V), again with a size-1 B (models/args.py: control_args checks
+    them) -> dict(t [S, B] float64, top_k [S, B] int32, top_p [S, B] float64, tau [S, B] float32, min_p [S, B] float32, cap [S] int: per scale
+    the largest top_k (V if any image has none), bias [R, V] float32: the distinct bias rows in order of first use (None without a bias),
+    bias_row [S, B] int32: each (scale, image)'s row of it, -1 = none).  cfg_ramp: t[s][b] = cfg[s][b] * (s / (S - 1)), formed exactly as
+    per_image_tables forms it (the reference's ramp); without it t[s][b] = cfg[s][b], the schedule is the caller's."""
+    from .models.args import control_args
+    a = control_args(V, S, B, cfg, top_k, top_p, temperature, min_p, logit_bias)
+    c = a['cfg']
+    t = np.stack([c[si] * (si / (S - 1)) if S > 1 else np.zeros(B) for si in range(S)]) if cfg_ramp else c.copy()
+    k = a['top_k'].astype(np.int32)
+    cap = [int(V if (k[si] == 0).any() else k[si].max()) for si in range(S)]
+    bias, bias_row = None, np.full((S, B), -1, dtype=np.int32)
+    if a['bias'] is not None:
+        src = a['bias'].reshape(-1, V)                                # the rows as given: a shared row is looked at once
+        seen, rows, which = {}, [], np.empty(len(src), dtype=np.int32)
+        for i, row in enumerate(src):
+            which[i] = seen.setdefault(row.tobytes(), len(rows))
+            if which[i] == len(rows):
+                rows.append(row)
+        bias = np.ascontiguousarray(np.stack(rows), dtype=np.float32)
+        bias_row = np.ascontiguousarray(np.broadcast_to(which.reshape(a['bias'].shape[:-1] or (1,)), (S, B)), dtype=np.int32)
+    return dict(t=t, top_k=k, top_p=a['top_p'], tau=a['tau'], min_p=a['min_p'], cap=cap, bias=bias, bias_row=bias_row)
+
+
 def compose_tables(cfg, weights, S: int) -> np.ndarray:
     """the coefficient table of a composed call (VAR.sample_composed): coef [S, B, K + 1] float32 from cfg (B values) and weights (S, B, K).
     With t = per_image_tables' t[si][b] and W = sum_k w_k, added in float64 in index order:
@@ -1272,14 +1298,20 @@ class SamplingEngine(_Engine):
                  per: Optional[dict] = None, stats: Optional[dict] = None, tr: Optional[dict] = None) -> torch.Tensor:
         """CFG + top-k/top-p + multinomial (var.py:172-175) with one fill of `noise`.  per = dict(t=[S, B] float64, top_k=[B] int32, top_p=[B] float64
         on the device, cap=int): every image samples with its own parameters (varhip_cfg_sample_rows_f32), and t, top_k and top_p are not read.
-        masked: None, or [>= B * l, V] fp32 that receives the filtered logits.  stats: the (B, L) tensors of STATS_FIELDS; varhip_sample_stats_f32
+        A per that holds 'tau' is _controlled_upload's: top_k, top_p, tau, min_p, bias_row [S, B] and cap [S] indexed by the scale, bias [R, V] or
+        None (varhip_ctl_sample_rows_f32).  masked: None, or [>= B * l, V] fp32 that receives the filtered logits.  stats: the (B, L) tensors of STATS_FIELDS; varhip_sample_stats_f32
         runs behind the sampler into this scale's slice of them (the drawn tokens' log-probabilities, kept counts and entropies)."""
         var = self.var
         l, cur, V = sc.l, sc.cur, var.V
         self._logits(ws, B, sc, tr)
         idx = ws['idx'][:B * l]
         fill = noise.draw(B, sc.si, l)
-        if per is not None:
+        if per is not None and 'tau' in per:                              # sample_controlled: every table is indexed by the scale
+            si, bias = sc.si, per['bias']
+            hip.call('ctl_sample_rows_f32', ws['logits'], fill, idx, masked, B, l, V, per['t'][si], per['top_k'][si], per['top_p'][si], per['tau'][si],
+                     per['min_p'][si], bias, per['bias_row'][si] if bias is not None else None, 0 if bias is None else bias.shape[0], V,
+                     int(per['cap'][si]))
+        elif per is not None:
             hip.call('cfg_sample_rows_f32', ws['logits'], fill, idx, masked, B, l, V, per['t'][sc.si], per['top_k'], per['top_p'], int(per['cap']))
         else:
             hip.call('cfg_sample_f32', ws['logits'], fill, idx, masked, B, l, V, float(t), int(top_k), float(top_p))
@@ -1536,6 +1568,37 @@ class SamplingEngine(_Engine):
         # one upload: [S*R t | R top_p] float64, then the two integer tables
         f64 = torch.from_numpy(np.concatenate((tab['t'].reshape(-1), tab['top_p']))).to(dev)
         per = dict(t=f64[:S * R].view(S, R), top_p=f64[S * R:], top_k=torch.from_numpy(tab['top_k']).to(dev), cap=tab['cap'])
+        return per, None if seeds is None else torch.from_numpy(np.asarray(seeds, dtype=np.int64)).to(dev)
+
+    # -- temperature, min-p, logit bias and per-scale schedules (VAR.sample_controlled) ----------------------------------------------
+    @torch.no_grad()
+    def sample_controlled(self, label_B: torch.Tensor, seeds, tab: dict, tokens_out: Optional[torch.Tensor] = None, decode: bool = True,
+                          stats: Optional[dict] = None, trace: bool = False) -> torch.Tensor:
+        """sample_per_image(stats=...) with the sampler's whole parameter set per image and scale: tab is control_tables' result (validated
+        there), seeds a host sequence of length B.  The walk, the Philox noise, the stats kernel, the quantizer step and the decode are those
+        of sample_per_image; the one difference is the sampler's entry (_sampled: varhip_ctl_sample_rows_f32 reads the scale's rows of the
+        tables).  logp_cond, logp_guided and entropy are the stats kernel's on the logits and t, so they describe the row before bias and
+        temperature; logp_drawn and kept come from the filtered row the sampler left, so they describe the controlled distribution."""
+        per, seeds_d = self._controlled_upload(tab, seeds)
+        return self.sample(len(seeds), label_B, None, 0.0, 0, 0.0, noises=self._philox(seeds_d, 0), tokens_out=tokens_out, per_image=per,
+                           decode=decode, stats=stats, trace=trace)
+
+    def _controlled_upload(self, tab: dict, seeds=None) -> tuple:
+        """the device side of control_tables' result, uploaded once, outside the scale loop -> (sample()'s `per_image` dict in its controlled form,
+        the int64 [B] seeds on the device or None).  Three transfers, one per element type: [t | top_p] float64, [bias | tau | min_p] float32
+        (the bias table first: its rows are read 16 bytes per lane and V % 256 == 0 keeps them aligned), [top_k | bias_row] int32."""
+        dev = self.var.pos_start.device
+        S, R = tab['t'].shape
+        bias = tab['bias']
+        nb = 0 if bias is None else bias.size
+        f64 = torch.from_numpy(np.concatenate((tab['t'].reshape(-1), tab['top_p'].reshape(-1)))).to(dev)
+        f32 = torch.from_numpy(np.concatenate(([] if bias is None else [bias.reshape(-1)]) + [tab['tau'].reshape(-1), tab['min_p'].reshape(-1)])
+                               .astype(np.float32)).to(dev)
+        i32 = torch.from_numpy(np.concatenate((tab['top_k'].reshape(-1), tab['bias_row'].reshape(-1))).astype(np.int32)).to(dev)
+        n = S * R
+        per = dict(t=f64[:n].view(S, R), top_p=f64[n:].view(S, R), tau=f32[nb:nb + n].view(S, R), min_p=f32[nb + n:].view(S, R),
+                   top_k=i32[:n].view(S, R), bias_row=i32[n:].view(S, R), bias=None if bias is None else f32[:nb].view(-1, self.var.V),
+                   cap=list(tab['cap']))
         return per, None if seeds is None else torch.from_numpy(np.asarray(seeds, dtype=np.int64)).to(dev)
 
     def _philox(self, seeds_d: torch.Tensor, draw: int):

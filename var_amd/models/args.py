@@ -141,6 +141,64 @@ def sample_args(V: int, label_B, g_seeds, cfg, top_k, top_p):
     return lab, seeds, cfgs, ks, ps
 
 
+def scheduled(x, name: str, S: int, B: int, integral: bool = False) -> np.ndarray:
+    """a knob of VAR.sample_controlled -> (S, B) float64 (integral: int64): a scalar, (B,) per image, or (S, B) per scale and image; a B axis
+    of size 1 broadcasts, so (S, 1) is a pure per-scale schedule"""
+    shapes = f'a scalar, ({B},), ({S}, {B}) or ({S}, 1)'
+    try:
+        a = np.array(as_list(x))
+        if a.dtype == bool or a.dtype == object or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+            raise TypeError
+        a = a.astype(np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'{name} must be {shapes} of numbers') from None
+    if not (a.ndim == 0 or (a.ndim == 1 and a.shape[0] in (1, B)) or (a.ndim == 2 and a.shape[0] == S and a.shape[1] in (1, B))):
+        raise ValueError(f'{name} must be {shapes}, got shape {tuple(a.shape)}')
+    a = np.broadcast_to(a, (S, B))
+    if integral:
+        if not np.isfinite(a).all() or (a != np.floor(a)).any():
+            raise ValueError(f'{name} must hold integers')
+        return a.astype(np.int64)
+    return a.copy()
+
+
+def control_args(V: int, S: int, B: int, cfg, top_k, top_p, temperature, min_p, logit_bias) -> dict:
+    """the knobs of VAR.sample_controlled, each a scalar, (B,) or (S, B) with a size-1 B axis broadcasting (`scheduled`); logit_bias None, (V,),
+    (B, V) or (S, B, V), again with a size-1 B -> dict(cfg, top_p (S, B) float64; top_k (S, B) int64; tau, min_p (S, B) float32, checked as the
+    float32 values the sampler reads; bias: None or a float32 array that broadcasts to (S, B, V))"""
+    out = dict(cfg=scheduled(cfg, 'cfg', S, B), top_k=scheduled(top_k, 'top_k', S, B, integral=True), top_p=scheduled(top_p, 'top_p', S, B))
+    if not np.isfinite(out['cfg']).all():
+        raise ValueError('cfg must be finite')
+    if (out['top_k'] < 0).any() or (out['top_k'] > V).any():
+        raise ValueError(f'top_k must lie in [0, {V}]')
+    if not ((out['top_p'] >= 0.0) & (out['top_p'] <= 1.0)).all():                 # (NaN fails the comparison)
+        raise ValueError('top_p must lie in [0, 1]')
+    with np.errstate(over='ignore'):
+        tau = scheduled(temperature, 'temperature', S, B).astype(np.float32)
+        mp = scheduled(min_p, 'min_p', S, B).astype(np.float32)
+    if (tau == 0).any():
+        raise ValueError('temperature must be finite and > 0 (as a float32); for the limit temperature -> 0, greedy selection, use top_k=1')
+    if not (np.isfinite(tau) & (tau > 0)).all():
+        raise ValueError('temperature must be finite and > 0')
+    if not ((mp >= 0) & (mp <= 1)).all():
+        raise ValueError('min_p must lie in [0, 1]')
+    out.update(tau=tau, min_p=mp, bias=None)
+    if logit_bias is not None:
+        shapes = f'({V},), ({B}, {V}), ({S}, {B}, {V}) or ({S}, 1, {V})'
+        try:
+            lb = np.array(as_list(logit_bias), dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError(f'logit_bias must be {shapes} of numbers') from None
+        if not (lb.ndim in (1, 2, 3) and lb.shape[-1] == V and (lb.ndim < 2 or lb.shape[-2] in (1, B)) and (lb.ndim < 3 or lb.shape[0] == S)):
+            raise ValueError(f'logit_bias must be {shapes}, got shape {tuple(lb.shape)}')
+        if np.isnan(lb).any() or (lb == np.inf).any():
+            raise ValueError('logit_bias must hold no NaN and no +inf (-inf bans a code)')
+        if not (lb > -np.inf).any(axis=-1).all():
+            raise ValueError('logit_bias bans every code of a row: each row needs at least one entry above -inf')
+        out['bias'] = lb
+    return out
+
+
 COMPOSE_MAX_CLASSES = 8              # classes per image of VAR.sample_composed (varhip_mix_sample_rows_f32 takes up to 9 row groups)
 
 

@@ -648,6 +648,8 @@ class SampleRecord:
         B, L = tuple(self.tokens.shape)
         tot = lambda f: '[' + ', '.join(f'{v:.2f}' for v in self.total(f).tolist()[:4]) + (', ...' if B > 4 else '') + ']'
         img = None if self.images is None else tuple(self.images.shape)
+        if self.kept is None:                    # (sample_controlled off the HIP path: tokens and images only)
+            return f'SampleRecord(B={B}, L={L}, images={img}, no per-token statistics)'
         return (f'SampleRecord(B={B}, L={L}, images={img}, logp_cond={tot("logp_cond")}, logp_guided={tot("logp_guided")}, '
                 f'logp_drawn={tot("logp_drawn")}, mean kept={float(self.kept.float().mean()):.1f})')
 
@@ -943,6 +945,44 @@ class VAR(nn.Module):
         return ComposedRecord(r['images'], r['tokens'], r['logp_class'], r['logp_guided'], r['logp_drawn'], r['entropy'], r['kept'], coef, lab, self.patch_nums)
 
     @torch.no_grad()
+    def sample_controlled(self, label_B, g_seeds, cfg=1.5, top_k=0, top_p=0.0, *, temperature=1.0, min_p=0.0, logit_bias=None, cfg_ramp=True,
+                          decode=True) -> SampleRecord:
+        """autoregressive_infer_cfg_per_image_scored with the sampler's full set of controls, each per image and per scale.
+          label_B, g_seeds   as in autoregressive_infer_cfg_per_image: (B,) class ids, (B,) seeds in [0, 2^63) (the same Philox stream)
+          cfg, top_k, top_p, temperature, min_p   each a scalar, (B,) values per image, or (S, B) per scale and image; a B axis of size 1
+                             broadcasts, so (S, 1) is a pure per-scale schedule.  temperature finite and > 0 (for the limit 0 use top_k=1),
+                             min_p in [0, 1], top_k in [0, V], top_p in [0, 1]
+          logit_bias         None, (V,) for every request, (B, V) or (S, B, V) (a size-1 B broadcasts): added to the guided logits; -inf bans a
+                             code; no NaN, no +inf, and not every code of a row banned
+          cfg_ramp           True: t = cfg * s / (S - 1), the reference's ramp, as every other call; False: t = cfg, the schedule is the caller's
+        Per token row, in this order: x = (1 + t) * cond - t * uncond;  x += bias;  x /= temperature;  top-k;  min-p: with p_max the largest
+        probability of what top-k left, codes with p_v < min_p * p_max go (exp(x_v - max x) < min_p, compared in fp32);  top-p;  the draw.  A
+        stage whose knob is neutral (no bias, temperature 1, top_k 0, min_p 0, top_p 0) does not run: with every control at its default
+        the record and the images are autoregressive_infer_cfg_per_image_scored's bit for bit.
+        The record (SampleRecord): logp_cond and logp_guided keep their meaning — they are computed before bias and temperature, so with
+        cfg_ramp=True and a cfg that is not scheduled logp_guided is bit-equal in f32 to token_log_likelihood of the drawn tokens at that
+        cfg; entropy is the guided row's.  logp_drawn and kept describe the biased, tempered and filtered row the token was drawn from.
+        A request's tokens and record depend on its own label, seed and controls only, not on what it is batched with — except that a
+        logit_bias given as (V,) is by definition part of every request of the call.  On the HIP path (a CUDA / ROCm model in eval mode,
+        prog_si < 0; f32, f16 and bf16) the sampler is varhip_ctl_sample_rows_f32 (SamplingEngine.sample_controlled).
+        Elsewhere (a CPU model, train mode, prog_si >= 0) the loop runs in PyTorch, request by request, with the stages in torch fp32 and the
+        host Philox fill; the per-image scored call has no statistics there, and this one has none either: images and tokens are
+        returned, the five per-token fields are None.  No more_smooth."""
+        lab, seeds = self._per_image_args(label_B, g_seeds, 0.0, 0, 0.0)[:2]
+        B, dev = lab.numel(), self.lvl_1L.device
+        from ..engine import control_tables
+        tab = control_tables(cfg, top_k, top_p, temperature, min_p, logit_bias, len(self.patch_nums), self.V, B, bool(cfg_ramp))
+        lab = lab.to(dev).long()
+        if dev.type == 'cuda' and not self.training and self.prog_si < 0:
+            tok = torch.empty(B, self.L, dtype=torch.int64, device=dev)
+            st = {}
+            img = self.engine().sample_controlled(lab, seeds, tab, tokens_out=tok, decode=bool(decode), stats=st)
+            return self._record(img if decode else None, tok, st)
+        self.engine()._check_labels(lab)
+        img, tok = self._per_image_torch(lab, seeds, None, None, None, False, ctl=tab)
+        return SampleRecord(img if decode else None, tok, None, None, None, None, None, self.patch_nums)
+
+    @torch.no_grad()
     def sample_best_of(self, label_B, g_seeds, n: Optional[int] = None, by: str = 'logp_cond', cfg=1.5, top_k=0, top_p=0.0, max_images: int = 64):
         """Best-of-n sampling: n candidates per image, ranked by their own likelihood, only the winners decoded.
           label_B   (B,) integer class ids;  g_seeds (B, n) integers in [0, 2^63), one seed per candidate;  n: optional, must equal g_seeds' width
@@ -1056,9 +1096,11 @@ class VAR(nn.Module):
         """the argument handling of the per-image calls -> (labels (B,) integer tensor, seeds, cfgs, top_ks, top_ps: lists of B values)"""
         return A.sample_args(self.V, label_B, g_seeds, cfg, top_k, top_p)
 
-    def _per_image_torch(self, lab, seeds, cfgs, ks, ps, more_smooth: bool):
+    def _per_image_torch(self, lab, seeds, cfgs, ks, ps, more_smooth: bool, ctl: Optional[dict] = None):
         """the PyTorch side of autoregressive_infer_cfg_per_image (reference var.py:126-190, one request at a time): the Exp(1) fills are
-        the host twin's (varhip_exp1_philox_host_f32), the sampler is helpers.py:6-19 with the multinomial written as argmax(p / noise)"""
+        the host twin's (varhip_exp1_philox_host_f32), the sampler is helpers.py:6-19 with the multinomial written as argmax(p / noise).
+        ctl: control_tables' result (sample_controlled; cfgs, ks and ps are then not read): t, top_k and top_p come from the tables' entry of
+        (scale, request), and bias, temperature and min-p run in torch fp32 where varhip_ctl_sample_rows_f32 runs them."""
         from .. import hip
         vae, quant = self.vae_proxy[0], self.vae_quant_proxy[0]
         dev, S, V = lab.device, len(self.patch_nums), self.V
@@ -1085,13 +1127,19 @@ class VAR(nn.Module):
                     for blk in self.blocks:
                         x = blk(x=x, cond_BD=cond_or_gss, attn_bias=None)
                     z = self.get_logits(x, cond_BD)
-                    t = cfgs[b] * ratio
+                    t, k, p = (cfgs[b] * ratio, ks[b], ps[b]) if ctl is None else (float(ctl['t'][si, b]), int(ctl['top_k'][si, b]), float(ctl['top_p'][si, b]))
                     z = (1 + t) * z[:1] - t * z[1:]
-                    if ks[b] > 0:
-                        z = z.masked_fill(z < z.topk(ks[b], largest=True, sorted=False, dim=-1)[0].amin(dim=-1, keepdim=True), -torch.inf)
-                    if ps[b] > 0:
+                    if ctl is not None and ctl['bias_row'][si, b] >= 0:
+                        z = z + torch.from_numpy(ctl['bias'][ctl['bias_row'][si, b]]).to(dev)
+                    if ctl is not None and ctl['tau'][si, b] != 1:
+                        z = z / torch.full_like(z, float(ctl['tau'][si, b]))          # (a tensor divisor: a true fp32 division on every backend)
+                    if k > 0:
+                        z = z.masked_fill(z < z.topk(k, largest=True, sorted=False, dim=-1)[0].amin(dim=-1, keepdim=True), -torch.inf)
+                    if ctl is not None and ctl['min_p'][si, b] > 0:
+                        z = z.masked_fill((z - z.amax(dim=-1, keepdim=True)).exp() < float(ctl['min_p'][si, b]), -torch.inf)
+                    if p > 0:
                         srt, order = z.sort(dim=-1, descending=False)
-                        drop = srt.softmax(dim=-1).cumsum_(dim=-1) <= (1 - ps[b])
+                        drop = srt.softmax(dim=-1).cumsum_(dim=-1) <= (1 - p)
                         drop[..., -1:] = False
                         z = z.masked_fill(drop.scatter(order.ndim - 1, order, drop), -torch.inf)
                     idx = (z.softmax(dim=-1)[0] / fill(seeds[b], l, si, 0)).argmax(dim=-1).view(1, l)
