@@ -27,7 +27,9 @@ The fixture stores, per case, one line per launch ("name digest-of-its-arguments
 first launch that differs.  `python tests/test_launch_trace_cpu.py --write PATH` writes it.  It only drives entry points that keep their
 signature (decode_nhwc, encode, the SamplingEngine and QuantizerEngine methods), so the same file records any revision of engine.py;
 every case of tests/golden/launch_trace.json is the record of the revision that first had it: the revision before the engines' fp32 /
-16-bit paths were folded into one walk each, and for the stats, best-of and particle cases the one before the samplers shared one scale walk."""
+16-bit paths were folded into one walk each, for the stats, best-of and particle cases the one before the samplers shared one scale walk, and for the token_scores, distance_profile,
+class_information, attention_profile, classify, code_tokens and decode_tokens cases the one before the teacher-forced calls shared one pass
+walk (2f8fb50)."""
 import contextlib
 import hashlib
 import json
@@ -46,13 +48,16 @@ if ROOT not in sys.path:
 from var_amd import engine, hip                                             # noqa: E402
 
 FIXTURE = os.path.join(ROOT, 'tests', 'golden', 'launch_trace.json')
-HOST_ARRAYS = {('edit_keep_u8', 4), ('eval_reduce_f32', 6)}                 # tensor arguments the launcher reads on the host: recorded by content
+HOST_ARRAYS = {('edit_keep_u8', 4), ('eval_reduce_f32', 6), ('attn_profile_f32', 7)}    # tensor arguments the launcher reads on the host: recorded by content
 POINTER_ARRAYS = {('kv_compact', 0), ('kv_compact', 1), ('kv_resample', 0)}    # host arrays of device addresses: recorded as the buffers they point to
 ADA_ATTR = 'ADA_PACKED_MAX_BYTES'                                           # SamplingEngine: above it the per-block AdaLN projections replace the packed one
 
 # every entry point named in a hip.call of _VaeOps, DecoderEngine, EncoderEngine, of SamplingEngine's prologue, block() and head(), and of
-# the per-image, stats, best-of and particle routes of its sampling walk: the cases below must reach all of them
+# the per-image, stats, best-of and particle routes of its sampling walk, of its teacher-forced calls and of the token coder: the cases
+# below must reach all of them
 MUST_REACH = {
+    'word_embed_f32', 'token_loglik_f32', 'token_score_f32', 'token_eval_f32', 'eval_reduce_f32', 'code_dist_f32', 'dist_profile_f32', 'class_mix_f32',
+    'class_mix_finish_f32', 'attn_profile_f32', 'code_table_f32', 'rans_decode_u32',
     'conv3x3_nhwc_f32', 'conv3x3_gn_nhwc_f32', 'conv3x3_wino_nhwc_f32', 'conv3x3_s2_nhwc_f32', 'gn_stats_f32', 'gn_stats_part_f32', 'gn_apply_f32',
     'gn_silu_conv_out_f32', 'gemm_nt_f32', 'softmax_rows_f32', 'upconv_phase_f32', 'upconv_phase_gn_f32', 'nchw_to_nhwc_pad_f32', 'gn_scale_shift_f32',
     'lvl_pos_f32', 'first_map_f32', 'silu_f32', 'add_bcast_f32', 'adaln_block_f32', 'ln_modulate_f32',
@@ -282,6 +287,28 @@ def sampling_cases():
     out['token_scores neighbor_max'] = record(lambda: eng.token_scores(gt, labels, 1.5, 4, ('neighbor_max', 0.5)))
     out['evaluate'] = record(lambda: eng.evaluate(gt, lab, 2))
     out['evaluate one row per pass'] = record(lambda: eng.evaluate(gt, lab, 1))
+    # the rest of the teacher-forced family, on both packings (whole images per pass | one image per pass, its classes in chunks)
+    S = len(pns)
+    out['token_scores group_smoothed'] = record(lambda: eng.token_scores(gt, labels, 0.0, 4, ('group_smoothed', 50)))
+    out['token_scores expected_distance chunked'] = record(lambda: eng.token_scores(gt, labels, 1.5, 2, ('expected_distance', 8)))
+    edges = torch.tensor([0.0, 0.5, 1.0, float('inf')])
+    out['distance_profile cfg chunked'] = record(lambda: eng.distance_profile(gt, labels, 1.5, 3, edges, 1e-4))
+    out['distance_profile no cfg'] = record(lambda: eng.distance_profile(gt, labels, 0.0, 8, edges, 1e-4))
+    prior = torch.full((2, 3), 1 / 3)
+    out['class_information'] = record(lambda: eng.class_information(gt, labels, 1.5, 8, prior))
+    out['class_information chunked'] = record(lambda: eng.class_information(gt, labels, 1.5, 3, prior))
+    out['class_information V above the LDS limit'] = record(
+        lambda: _switched(eng, 'CLASS_MIX_LDS_V', 1024, lambda: eng.class_information(gt, labels, 1.5, 8, prior)))
+    out['attention_profile tokens'] = record(lambda: eng.attention_profile(gt, lab, 1, (0, 1), 1, return_tokens=True))
+    out['attention_profile'] = record(lambda: eng.attention_profile(gt, lab, 0, (1,), 2))
+    out['classify pruned'] = record(lambda: (eng.classify(gt, labels, 1.5, 2, ('log_prob',), [(0, 2)]), eng.classify_work))
+    out['classify neighbor_max'] = record(lambda: eng.classify(gt, labels, 0.0, 4, ('neighbor_max', 0.5), []))
+    # the sampling walk's two newest users
+    out['code_tokens'] = record(lambda: eng.code_tokens(gt, lab, 1.5, S - 1))
+    out['code_tokens last=1'] = record(lambda: eng.code_tokens(gt, lab, 1.5, 1))
+    coded = (np.zeros(8, np.uint32), np.array([0, 4], np.int64), np.array([4, 4], np.int64))
+    out['decode_tokens'] = record(lambda: eng.decode_tokens(*coded, lab, 1.5, 1, None, False))
+    out['decode_tokens fill decode'] = record(lambda: eng.decode_tokens(*coded, lab, 1.5, 1, 1.5, True))
 
     # the per-block AdaLN projections: a fresh model whose engine packs nothing
     var = build()

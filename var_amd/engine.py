@@ -927,9 +927,8 @@ class EncoderEngine(_VaeOps):
 AUTOCAST_PRECISION = {torch.float16: 'f16', torch.bfloat16: 'bf16'}
 
 
-# score -> mode of varhip_token_score_f32 (0: varhip_token_loglik_f32; 4: varhip_dist_profile_f32, which fills histograms instead of token scores;
-# 5: varhip_class_mix_f32, which reduces across the classes of a token)
-_SCORE_MODES = {'log_prob': 0, 'group_smoothed': 1, 'neighbor_max': 2, 'expected_distance': 3, 'distance_profile': 4, 'class_information': 5}
+_SCORE_MODES = {'group_smoothed': 1, 'neighbor_max': 2, 'expected_distance': 3}     # score -> mode of varhip_token_score_f32 ('log_prob' has its own kernel)
+_DIST_SCORES = ('neighbor_max', 'expected_distance')                                # the scores that read the code distance table
 
 
 class _Exp1:
@@ -1998,21 +1997,38 @@ class SamplingEngine(_Engine):
         KV cache instead of one masked pass: the cache holds exactly the scales <= the current one, which is what the block-causal
         mask `attn_bias_for_masking` allows (SURVEY.md §4 identity (i): identical to 3e-8 in the reference itself).
         No CFG doubling: B rows.  label_B may contain num_classes (dropped condition)."""
+        tf = self._tf_begin(label_B)
+        R = int(label_B.numel())                               # rows: one per image, no CFG pair
+        V = self.var.V
+        self._check_labels(label_B)
+        xin = None if x_BLCv_wo_first_l is None else x_BLCv_wo_first_l.to(tf.dev, torch.float32).contiguous()
+
+        def head(p, si, cur, l):
+            out[:, cur:cur + l] = p.ws['lg'][:R * l].view(R, l, V)
+        for p in self._tf_rows(tf.lab.view(-1), xin, R):         # a single pass
+            # (behind the workspace: a call with another row count frees the resident set before the logits are allocated)
+            out = torch.empty(R, self.var.L, V, dtype=torch.float32, device=tf.dev)
+            self._tf_pass(p, head=head)
+        return out
+
+    def _tf_begin(self, labels: torch.Tensor, gt_tokens: Optional[torch.Tensor] = None, f32_only: Optional[str] = None, before_tokens=None):
+        """what every teacher-forced call does first: the call's precision (f32_only: the sentence, with {} for the precision, that refuses any
+        other), the weights and the stream handshake; the labels on the device as int64; before_tokens(tf), the caller's own refusals and
+        tables, which come before the tokens are touched; then the tokens (N, L) on the device as int64, and from them the teacher-forcing
+        input of every image (eval_prob.py:437), one encode-side call for all of them -> (dev, lab, gt, xin); without tokens gt and xin are None"""
         var = self.var
-        self.resolve_precision()
+        if self.resolve_precision() != 'f32' and f32_only:
+            raise ValueError(f32_only.format(self.precision) + ' (set_hip_precision(\'f32\'), no 16-bit autocast)')
         self.refresh()
         self._wait_ready()
-        R = int(label_B.numel())                               # rows: one per image, no CFG pair
-        dev = var.pos_start.device
-        L, V = var.L, var.V
-        self._check_labels(label_B)
-        ws = self._tf_workspace(R)
-        lab = label_B.to(dev).long().contiguous()
-        out = torch.empty(R, L, V, dtype=torch.float32, device=dev)
-        xin = None if x_BLCv_wo_first_l is None else x_BLCv_wo_first_l.to(dev, torch.float32).contiguous()
-        for si, cur, l in self._tf_scales(ws, lab, xin, R):
-            out[:, cur:cur + l] = ws['lg'][:R * l].view(R, l, V)
-        return out
+        tf = SimpleNamespace(dev=var.pos_start.device, dist=None, gt=None, xin=None)
+        tf.lab = labels.to(tf.dev, torch.int64).contiguous()
+        if before_tokens is not None:
+            before_tokens(tf)
+        if gt_tokens is not None:
+            tf.gt = gt_tokens.to(tf.dev, torch.int64).contiguous()
+            tf.xin = var.vae_proxy[0].quantize.idxBl_to_var_input([tf.gt[:, b:e] for b, e in var.begin_ends]).to(tf.dev, torch.float32)
+        return tf
 
     def _tf_workspace(self, R: int, last: Optional[int] = None) -> dict:
         """buffers of a teacher-forced pass of up to R rows through scale `last` (default: the last scale): KV caches of L_e = end of that scale
@@ -2040,30 +2056,40 @@ class SamplingEngine(_Engine):
             self._ws_tf[(R, sid, self.precision, Le)] = ws
         return ws
 
-    def _tf_scales(self, ws: dict, lab: torch.Tensor, xin: Optional[torch.Tensor], R: int, last: Optional[int] = None, head_from: int = 0,
-                   after_block=None):
-        """the teacher-forced loop over R rows (labels `lab`, next-scale inputs `xin` (R, >= L_e - first_l, Cvae)) through scale `last` (default:
-        the last; ws must reach it): yields (si, cur, l) after the head of each scale si >= head_from has left that scale's fp32 logits in
-        ws['lg'][:R * l] (row r, token t at r * l + t); scales below head_from only fill the KV caches.  after_block(bi, si, cur, l), if given,
-        runs right behind every block: ws['q'] then holds that block's queries [R * l][C], normalised and scaled, ws['kc'][bi] the keys 0 .. cur + l - 1"""
-        var, w = self.var, self.w
+    def _tf_rows(self, lab: torch.Tensor, xin: Optional[torch.Tensor], max_rows: int):
+        """the pass loop of the calls that run one row per image: the N images of lab (N,) and xin (N, L - first_l, Cvae), in order, as passes p
+        of at most max_rows rows over one workspace (sized once: a shorter last pass uses a prefix); p.i0: the pass's first image.  The loop
+        body runs the pass (_tf_pass) between whatever it keeps per pass"""
+        N = lab.shape[0]
+        rpp = min(int(max_rows), N)
+        ws = self._tf_workspace(rpp)
+        for i0 in range(0, N, rpp):
+            R = min(rpp, N - i0)
+            yield SimpleNamespace(ws=ws, i0=i0, R=R, lab=lab[i0:i0 + R].contiguous(), xin=None if xin is None else xin[i0:i0 + R].contiguous())
+
+    def _tf_pass(self, p, last: Optional[int] = None, done: int = -1, head=None, after_block=None):
+        """one teacher-forced pass: the p.R rows of labels p.lab and next-scale inputs p.xin (R, >= L_e - first_l, Cvae) through scale `last`
+        (default: the last; p.ws must reach it).  head(p, si, cur, l) runs after the head of each scale si > done has left that scale's fp32
+        logits in p.ws['lg'][:R * l] (row r, token t at r * l + t); the scales up to `done` only fill the KV caches, and without `head` no
+        scale runs a head.  after_block(p, bi, si, cur, l), if given, runs right behind every block: p.ws['q'] then holds that block's queries
+        [R * l][C], normalised and scaled, p.ws['kc'][bi] the keys 0 .. cur + l - 1"""
+        var, w, ws, R = self.var, self.w, p.ws, p.R
         C, Cv = var.C, var.Cvae
-        self._prologue(ws, lab, R)
+        self._prologue(ws, p.lab, R)
         x, x2 = ws['x'], ws['x2']
         cur = 0
         for si, pn in enumerate(var.patch_nums[:(len(var.patch_nums) if last is None else last + 1)]):
             l = pn * pn
-            M = R * l
             if si > 0:                                           # word_embed(teacher-forcing input) + lvl_pos  (var.py:206-207)
-                seg = xin[:, cur - var.first_l:cur - var.first_l + l].contiguous()
+                seg = p.xin[:, cur - var.first_l:cur - var.first_l + l].contiguous()
                 hip.call('word_embed_f32', seg, w['word_w'], w['word_b'], ws['lvl_pos'][cur:], x, R, l, C, Cv)
             for bi, blk in enumerate(w['blocks']):
                 self.block(blk, ws, bi, x, x2, R, l, cur, ws['Lmax'])
                 if after_block is not None:
-                    after_block(bi, si, cur, l)
-            if si >= head_from:
-                self.head(x, ws['hn'], ws['xn'], ws['lg'], M, l)
-                yield si, cur, l
+                    after_block(p, bi, si, cur, l)
+            if head is not None and si > done:
+                self.head(x, ws['hn'], ws['xn'], ws['lg'], R * l, l)
+                head(p, si, cur, l)
             cur += l
 
     # -- teacher-forced class scoring (VAR.token_log_likelihood, VAR.token_scores) --------------------------------------------------
@@ -2074,29 +2100,34 @@ class SamplingEngine(_Engine):
         The N x K rows are packed into passes of at most max_rows rows: images_in_pass x (classes_in_pass + [cfg > 0]), the unconditional
         row of every image of a pass (label num_classes) after its class rows.  Each scale's logits are reduced to one value per row by
         varhip_token_loglik_f32 right after the head: no (rows, L, V) tensor exists at any time."""
-        return self._score_passes(gt_tokens, labels, cfg, max_rows, ('log_prob',))
+        return self.token_scores(gt_tokens, labels, cfg, max_rows, ('log_prob',))
 
     @torch.no_grad()
     def token_scores(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, score: tuple) -> torch.Tensor:
         """(N, K, L) fp32 per-token scores of VAR.token_scores: as token_log_likelihood, with each scale's logits reduced by
         varhip_token_score_f32.  score: ('group_smoothed', group) | ('neighbor_max', threshold) | ('expected_distance', top_k or 0),
-        already validated by the caller."""
-        return self._score_passes(gt_tokens, labels, cfg, max_rows, score)
+        already validated by the caller; ('log_prob',) is token_log_likelihood.  One stage through the last scale over every candidate."""
+        sc = self._score_setup(gt_tokens, labels, cfg, dist=score[0] in _DIST_SCORES)
+        N, K = labels.shape
+        out = torch.empty(N, K, self.var.L, dtype=torch.float32, device=sc.dev)
+        self._score_stage(sc, sc.lab, len(self.var.patch_nums) - 1, -1, max_rows, self._token_reducer(sc, score, out))
+        return out
 
     @torch.no_grad()
     def distance_profile(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, edges: torch.Tensor, min_prob: float):
         """VAR.distance_profile on the HIP path -> (mass_q, count), two (N, K, S, B) int64 arrays: as token_scores, with each scale's logits
         reduced behind the head by varhip_dist_profile_f32 into that scale's histograms (zeroed here, once per call).  edges: (B + 1,) fp32,
         min_prob: an fp32 value, both already validated by the caller."""
-        sc = self._score_setup(gt_tokens, labels, cfg, ('distance_profile',))
-        dev = sc['gt'].device
-        sc['edges'] = edges.to(dev, torch.float32).contiguous()
-        sc['min_prob'] = float(min_prob)
+        sc = self._score_setup(gt_tokens, labels, cfg, dist=True)
+        edges = edges.to(sc.dev, torch.float32).contiguous()
         N, K = labels.shape
-        S, B = len(self.var.patch_nums), edges.numel() - 1
-        out = (torch.zeros(N, K, S, B, dtype=torch.int64, device=dev), torch.zeros(N, K, S, B, dtype=torch.int64, device=dev))
-        self._score_stage(sc, sc['lab'], S - 1, -1, max_rows, out)
-        return out
+        V, S, B = self.var.V, len(self.var.patch_nums), edges.numel() - 1
+        mass, count = torch.zeros(N, K, S, B, dtype=torch.int64, device=sc.dev), torch.zeros(N, K, S, B, dtype=torch.int64, device=sc.dev)
+
+        def reduce(p, si, cur, l):
+            hip.call('dist_profile_f32', *p.args, sc.dist, V, edges, B, float(min_prob), mass[p.i0:, p.k0:, si], count[p.i0:, p.k0:, si], K * S * B, S * B)
+        self._score_stage(sc, sc.lab, S - 1, -1, max_rows, reduce)
+        return mass, count
 
     CLASS_MIX_LDS_V = 4096             # varhip_class_mix_f32 holds a token's mixture on the chip up to this V
 
@@ -2106,117 +2137,97 @@ class SamplingEngine(_Engine):
         each scale's logits reduced behind the head by varhip_class_mix_f32.  A pass that holds all K classes of its images finalises in that
         kernel; otherwise the chunks of an image add into an (L, V) int64 accumulator of the teacher-forced workspace (zeroed once per image)
         and varhip_class_mix_finish_f32 runs per scale after the last chunk.  prior: (N, K) fp32, already validated by the caller."""
-        sc = self._score_setup(gt_tokens, labels, cfg, ('class_information',))
-        dev = sc['gt'].device
+        sc = self._score_setup(gt_tokens, labels, cfg)
+        dev = sc.dev
         N, K = labels.shape
-        L = self.var.L
-        sc['prior'] = prior.to(dev, torch.float32).contiguous()
+        L, V = self.var.L, self.var.V
+        prior = prior.to(dev, torch.float32).contiguous()
         out = dict(entropy=torch.empty(N, K, L, dtype=torch.float32, device=dev))
         for k in ('h_mix', 'h_cond', 'mi', 'logp_mix'):
             out[k] = torch.empty(N, L, dtype=torch.float32, device=dev)
-        self._score_stage(sc, sc['lab'], len(self.var.patch_nums) - 1, -1, max_rows, out)
+
+        def reduce(p, si, cur, l):
+            i0, k0 = p.i0, p.k0
+            mix = (*p.args, prior[i0:, k0:], K, out['entropy'][i0:, k0:, cur:], K * L, L)
+            res = [out[k][i0:, cur:] for k in ('h_mix', 'h_cond', 'mi', 'logp_mix')]
+            if p.nk == K and V <= self.CLASS_MIX_LDS_V:              # all classes of the pass's images: the mixture stays on the chip
+                hip.call('class_mix_f32', *mix, None, None, None, 0, *res, L)
+                return
+            if k0 == 0 and si == 0:                                  # the chunked route: the sums of a full pass's images, zeroed once per image
+                if 'class_mix' not in p.ws or p.ws['class_mix'][1].shape[0] < p.ipp:
+                    p.ws['class_mix'] = (torch.empty(p.ipp, L, V, dtype=torch.int64, device=dev), torch.empty(p.ipp, L, dtype=torch.int64, device=dev),
+                                         torch.empty(p.ipp, L, dtype=torch.int32, device=dev))
+                for a in p.ws['class_mix']:
+                    a[:p.ni].zero_()
+            acc = [a[:, cur:] for a in p.ws['class_mix']]
+            hip.call('class_mix_f32', *mix, *acc, L, None, None, None, None, 0)
+            if k0 + p.nk == K:                                       # an image's last chunk
+                hip.call('class_mix_finish_f32', *acc, L, sc.gt[i0:, cur:], L, p.ni, l, V, *res, L)
+        self._score_stage(sc, sc.lab, len(self.var.patch_nums) - 1, -1, max_rows, reduce)
         return out
 
-    def _score_passes(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, max_rows: int, score: tuple) -> torch.Tensor:
-        """the pass loop of token_log_likelihood / token_scores: one stage through the last scale over every candidate"""
-        sc = self._score_setup(gt_tokens, labels, cfg, score)
-        N, K = labels.shape
-        out = torch.empty(N, K, self.var.L, dtype=torch.float32, device=sc['gt'].device)
-        self._score_stage(sc, sc['lab'], len(self.var.patch_nums) - 1, -1, max_rows, out)
-        return out
+    def _token_reducer(self, sc, score: tuple, out: torch.Tensor):
+        """the reducer of token_log_likelihood, token_scores and classify: one value per row and token into out (N, K, >= L_e), by
+        varhip_token_loglik_f32 (score ('log_prob',)) or varhip_token_score_f32 in the mode score names, with its parameter"""
+        K, Lo = out.shape[1:]
+        if score[0] != 'log_prob':
+            mode = _SCORE_MODES[score[0]]
+            param, thr = (0, float(score[1])) if score[0] == 'neighbor_max' else (int(score[1]), 0.0)
 
-    def _score_setup(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, score: tuple) -> dict:
-        """what every stage of a scoring call shares: tokens, labels, teacher-forcing inputs, guidance factors, the kernel's mode"""
-        var = self.var
-        self.resolve_precision()
-        self.refresh()
-        self._wait_ready()
-        dev = var.pos_start.device
-        S = len(var.patch_nums)
-        sc = dict(mode=_SCORE_MODES[score[0]], param=0, thr=0.0, dist=None, u=1 if cfg > 0 else 0)
-        if score[0] == 'group_smoothed':
-            sc['param'] = int(score[1])
-        elif score[0] == 'neighbor_max':
-            sc['thr'] = float(score[1])
-        elif score[0] == 'expected_distance':
-            sc['param'] = int(score[1])
-        if score[0] in ('neighbor_max', 'expected_distance', 'distance_profile'):
-            sc['dist'] = self.code_distance_table()
+        def reduce(p, si, cur, l):
+            dst = out[p.i0:, p.k0:, cur:]
+            if score[0] == 'log_prob':
+                hip.call('token_loglik_f32', *p.args, dst, K * Lo, Lo)
+            else:
+                hip.call('token_score_f32', *p.args, mode, param, thr, sc.dist, self.var.V, dst, K * Lo, Lo)
+        return reduce
+
+    def _score_setup(self, gt_tokens: torch.Tensor, labels: torch.Tensor, cfg: float, dist: bool = False):
+        """what every stage of a scoring call shares: _tf_begin's tokens, labels and teacher-forcing inputs, the code distance table (dist) or
+        None, and the guidance factors"""
+        def table(tf):
+            tf.dist = self.code_distance_table()
             self._wait_ready()
-        sc['gt'] = gt = gt_tokens.to(dev, torch.int64).contiguous()
-        sc['lab'] = labels.to(dev, torch.int64).contiguous()
-        # teacher-forcing input of every image (eval_prob.py:437), one encode-side call for all of them
-        sc['xin'] = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in var.begin_ends]).to(dev, torch.float32)
+        sc = self._tf_begin(labels, gt_tokens, before_tokens=table if dist else None)
+        S = len(self.var.patch_nums)
+        sc.u = 1 if cfg > 0 else 0
         # guidance factors per scale, rounded where var_analysis.py:333-344 rounds them (a float32 ratio tensor times the Python cfg)
-        sc['t32'] = [np.float32(np.float32(cfg) * np.float32(si / (S - 1) if S > 1 else 0.0)) for si in range(S)]
+        sc.t32 = [np.float32(np.float32(cfg) * np.float32(si / (S - 1) if S > 1 else 0.0)) for si in range(S)]
         return sc
 
-    def _score_stage(self, sc: dict, lab_all: torch.Tensor, last: int, done: int, max_rows: int, out: torch.Tensor):
+    def _score_stage(self, sc, lab_all: torch.Tensor, last: int, done: int, max_rows: int, reduce):
         """one stage: the rows of labels lab_all (N, K) through scale `last`, packed into passes of at most max_rows rows:
         images_in_pass x (classes_in_pass + [cfg > 0]), the unconditional row of every image of a pass (label num_classes) after its class rows.
-        Scales <= `done` only rebuild the KV caches; each later scale's logits are reduced by the scoring kernel into out (N, K, >= L_e), in
-        the distance_profile mode added by varhip_dist_profile_f32 into scale si of out = (mass_q, count), two (N, K, S, B) int64 arrays; in
-        the class_information mode reduced across the classes by varhip_class_mix_f32 into out = dict(entropy, h_mix, h_cond, mi, logp_mix)."""
+        Scales <= `done` only rebuild the KV caches; behind the head of each later scale runs reduce(p, si, cur, l), the caller's scoring
+        kernel over the pass p: images p.i0 .. + p.ni, classes p.k0 .. + p.nk of lab_all (p.ipp: the images of a full pass), p.args the ten
+        arguments every scoring kernel begins with (logits, the scale's tokens of the pass's images, the row geometry, the guidance factors)"""
         var = self.var
         dev = lab_all.device
         N, K = lab_all.shape
-        L, V = var.L, var.V
-        u, mode, t32, gt = sc['u'], sc['mode'], sc['t32'], sc['gt']
-        if mode == 4:
-            mass, count = out
-            SB, B = mass.shape[2] * mass.shape[3], mass.shape[3]
-        elif mode == 5:
-            ci = [out[k] for k in ('h_mix', 'h_cond', 'mi', 'logp_mix')]
-        else:
-            Lo = out.shape[2]
+        L, V, u = var.L, var.V, sc.u
         if K + u <= max_rows:
             ipp, kpp = max(1, max_rows // (K + u)), K            # whole images per pass
         else:
             ipp, kpp = 1, max_rows - u                           # one image per pass, its classes in chunks (each pass with its own uncond row)
         passes = [(i0, min(ipp, N - i0), k0, min(kpp, K - k0)) for i0 in range(0, N, ipp) for k0 in range(0, K, kpp)]
         ws = self._tf_workspace(max(ni * (nk + u) for _, ni, _, nk in passes), last)   # sized once: a shorter pass uses a prefix
-        xin_img = sc['xin'][:, :var.begin_ends[last][1] - var.first_l]
-        if mode == 5 and (kpp < K or V > self.CLASS_MIX_LDS_V):       # the chunked route: the sums of ipp images leave the chip
-            acc = ws.get('class_mix')
-            if acc is None or acc[1].shape[0] < ipp:
-                acc = ws['class_mix'] = (torch.empty(ipp, L, V, dtype=torch.int64, device=dev), torch.empty(ipp, L, dtype=torch.int64, device=dev),
-                                         torch.empty(ipp, L, dtype=torch.int32, device=dev))
-        else:
-            acc = None
+        xin_img = sc.xin[:, :var.begin_ends[last][1] - var.first_l]
+
+        def head(p, si, cur, l):
+            t = sc.t32[si]
+            p.args = (ws['lg'], sc.gt[p.i0:, cur:], L, p.ni, p.nk, l, V, u, float(np.float32(1) + t), float(t))
+            reduce(p, si, cur, l)
         for i0, ni, k0, nk in passes:
-            R = ni * (nk + u)
             rows_img = torch.arange(i0, i0 + ni, device=dev)
             lab = lab_all[i0:i0 + ni, k0:k0 + nk].reshape(-1)
             src = rows_img.repeat_interleave(nk)
             if u:
                 lab = torch.cat((lab, torch.full((ni,), var.num_classes, dtype=torch.int64, device=dev)))
                 src = torch.cat((src, rows_img))
-            xin = xin_img.index_select(0, src).contiguous()     # each image's input broadcast to its rows
-            for si, cur, l in self._tf_scales(ws, lab.contiguous(), xin, R, last, done + 1):
-                t = t32[si]
-                if mode == 0:
-                    hip.call('token_loglik_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
-                             out[i0:, k0:, cur:], K * Lo, Lo)
-                elif mode == 4:
-                    hip.call('dist_profile_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t), sc['dist'], V,
-                             sc['edges'], B, sc['min_prob'], mass[i0:, k0:, si], count[i0:, k0:, si], K * SB, SB)
-                elif mode == 5:
-                    ca, cb = float(np.float32(1) + t), float(t)
-                    if acc is None:
-                        hip.call('class_mix_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, ca, cb, sc['prior'][i0:], K, out['entropy'][i0:, :, cur:],
-                                 K * L, L, None, None, None, 0, *[o[i0:, cur:] for o in ci], L)
-                        continue
-                    if k0 == 0 and si == 0:
-                        for a in acc:
-                            a[:ni].zero_()
-                    hip.call('class_mix_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, ca, cb, sc['prior'][i0:, k0:], K,
-                             out['entropy'][i0:, k0:, cur:], K * L, L, acc[0][:, cur:], acc[1][:, cur:], acc[2][:, cur:], L, None, None, None, None, 0)
-                    if k0 + nk == K:
-                        hip.call('class_mix_finish_f32', acc[0][:, cur:], acc[1][:, cur:], acc[2][:, cur:], L, gt[i0:, cur:], L, ni, l, V,
-                                 *[o[i0:, cur:] for o in ci], L)
-                else:
-                    hip.call('token_score_f32', ws['lg'], gt[i0:, cur:], L, ni, nk, l, V, u, float(np.float32(1) + t), float(t),
-                             mode, sc['param'], sc['thr'], sc['dist'], V, out[i0:, k0:, cur:], K * Lo, Lo)
+            # the pass and the inputs gathered for it end with _tf_pass: a call holds one pass's copy however many passes it runs
+            self._tf_pass(SimpleNamespace(ws=ws, R=ni * (nk + u), lab=lab.contiguous(), i0=i0, ni=ni, k0=k0, nk=nk, ipp=ipp, args=None,
+                                          xin=xin_img.index_select(0, src).contiguous()),     # each image's input broadcast to its rows
+                          last, done, head)
 
     # -- validation metrics (VAR.evaluate) -------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -2227,26 +2238,19 @@ class SamplingEngine(_Engine):
         image; varhip_token_eval_f32 reduces each scale's logits right behind the head, varhip_eval_reduce_f32 the per-token arrays at the
         end: no (rows, L, V) tensor exists at any time."""
         var = self.var
-        self.resolve_precision()
-        self.refresh()
-        self._wait_ready()
-        dev = var.pos_start.device
+        tf = self._tf_begin(label_B, gt_tokens)
+        dev, gt = tf.dev, tf.gt
         L, V, S = var.L, var.V, len(var.patch_nums)
-        gt = gt_tokens.to(dev, torch.int64).contiguous()
-        lab = label_B.to(dev, torch.int64).contiguous()
         N = gt.shape[0]
-        xin = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in var.begin_ends]).to(dev, torch.float32)
         out = dict(nll_BL=torch.empty(N, L, dtype=torch.float32, device=dev), smooth_BL=torch.empty(N, L, dtype=torch.float32, device=dev),
                    pred_BL=torch.empty(N, L, dtype=torch.int64, device=dev), rank_BL=torch.empty(N, L, dtype=torch.int32, device=dev),
                    nll_S=torch.empty(S, dtype=torch.float64, device=dev), smooth_S=torch.empty(S, dtype=torch.float64, device=dev),
                    correct_S=torch.empty(S, dtype=torch.int64, device=dev), pred_hist_V=torch.zeros(V, dtype=torch.int64, device=dev))
-        rpp = min(int(max_rows), N)
-        ws = self._tf_workspace(rpp)                                  # sized once: a shorter last pass uses a prefix
-        for i0 in range(0, N, rpp):
-            R = min(rpp, N - i0)
-            for si, cur, l in self._tf_scales(ws, lab[i0:i0 + R].contiguous(), xin[i0:i0 + R].contiguous(), R):
-                hip.call('token_eval_f32', ws['lg'], gt[i0:, cur:], L, R, l, V, out['nll_BL'][i0:, cur:], out['smooth_BL'][i0:, cur:],
-                         out['pred_BL'][i0:, cur:], out['rank_BL'][i0:, cur:], L)
+
+        def head(p, si, cur, l):
+            hip.call('token_eval_f32', p.ws['lg'], gt[p.i0:, cur:], L, p.R, l, V, *[out[k][p.i0:, cur:] for k in ('nll_BL', 'smooth_BL', 'pred_BL', 'rank_BL')], L)
+        for p in self._tf_rows(tf.lab, tf.xin, max_rows):
+            self._tf_pass(p, head=head)
         begins = torch.tensor([0] + [e for _, e in var.begin_ends], dtype=torch.int32)      # a host array: the launcher copies it into the kernel's arguments
         hip.call('eval_reduce_f32', out['nll_BL'], out['smooth_BL'], out['pred_BL'], out['rank_BL'], L, N, begins, S, V,
                  out['nll_S'], out['smooth_S'], out['correct_S'], out['pred_hist_V'])
@@ -2266,52 +2270,43 @@ class SamplingEngine(_Engine):
         last key bin (index si + 1); it is moved to index S at the end.  _tap (tests): called after a stream sync with clones of the queries
         and of the keys 0 .. cur + l - 1 and (bi, si, cur, l) for every launch."""
         var = self.var
-        if self.resolve_precision() != 'f32':
-            raise ValueError(f'attention_profile runs in f32: the {self.precision} workspaces hold 16-bit queries and keys (set_hip_precision(\'f32\'), '
-                             f'no 16-bit autocast)')
-        self.refresh()
-        self._wait_ready()
-        dev = var.pos_start.device
         L, S, H = var.L, len(var.patch_nums), var.num_heads
-        if L > self.ATTN_PROFILE_MAX_L or S > self.ATTN_PROFILE_MAX_S:
-            raise ValueError(f'attention_profile takes at most {self.ATTN_PROFILE_MAX_L} tokens and {self.ATTN_PROFILE_MAX_S} scales, got {L} and {S}')
-        gt = gt_tokens.to(dev, torch.int64).contiguous()
-        lab = label_N.to(dev, torch.int64).contiguous()
-        self._check_labels(lab)
-        N, Dn = gt.shape[0], len(layers)
+
+        def refusals(tf):
+            if L > self.ATTN_PROFILE_MAX_L or S > self.ATTN_PROFILE_MAX_S:
+                raise ValueError(f'attention_profile takes at most {self.ATTN_PROFILE_MAX_L} tokens and {self.ATTN_PROFILE_MAX_S} scales, got {L} and {S}')
+            self._check_labels(tf.lab)
+        tf = self._tf_begin(label_N, gt_tokens, 'attention_profile runs in f32: the {} workspaces hold 16-bit queries and keys', refusals)
+        dev = tf.dev
+        N, Dn = tf.gt.shape[0], len(layers)
         slot = {bi: d for d, bi in enumerate(layers)}
-        xin = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in var.begin_ends]).to(dev, torch.float32)
         share = torch.zeros(N, Dn, H, S, S + 1, dtype=torch.int64, device=dev)
         nanq = torch.zeros(N, Dn, H, S, dtype=torch.int32, device=dev)
         tokens = torch.zeros(N, Dn, H, L, S + 1, dtype=torch.int32, device=dev) if return_tokens else None
         ends = [torch.tensor([e for _, e in var.begin_ends[:si + 1]], dtype=torch.int32) for si in range(S)]      # host arrays: the launcher copies them
-        rpp = min(int(max_rows), N)
-        ws = self._tf_workspace(rpp)                                  # sized once: a shorter last pass uses a prefix
-        for i0 in range(0, N, rpp):
-            R = min(rpp, N - i0)
-            nan_pass = torch.zeros(Dn, S, R, H, dtype=torch.int32, device=dev)      # the kernel's nan_count is dense [row][head]
 
-            def tap(bi, si, cur, l):
-                d = slot.get(bi)
-                if d is None:
-                    return
-                S1, pn = si + 1, var.patch_nums[si]
-                tok = torch.empty(R, H, l, S1 + 1, dtype=torch.int32, device=dev) if return_tokens else None
-                hip.call('attn_profile_f32', ws['q'], ws['kc'][bi], R, l, H, cur + l, ws['Lmax'], ends[si], S1, pn, int(radius),
-                         share[i0:, d, :, si], Dn * H * S * (S + 1), S * (S + 1), nan_pass[d, si], tok, H * l * (S1 + 1), l * (S1 + 1))
-                if return_tokens:
-                    dst = tokens[i0:i0 + R, d, :, cur:cur + l]
-                    dst[..., :S1] = tok[..., :S1]
-                    dst[..., S] = tok[..., S1]
-                    if S1 < S:
-                        dst[..., S1:S] = -(tok[..., :1] < 0).to(torch.int32)           # a NaN query: -1 in every entry
-                if _tap is not None:
-                    torch.cuda.current_stream().synchronize()
-                    _tap(ws['q'][:R * l].clone(), ws['kc'][bi][:R, :, :cur + l].clone(), (bi, si, cur, l))
-
-            for _ in self._tf_scales(ws, lab[i0:i0 + R].contiguous(), xin[i0:i0 + R].contiguous(), R, head_from=S, after_block=tap):
-                pass
-            nanq[i0:i0 + R] = nan_pass.permute(2, 0, 3, 1)
+        def tap(p, bi, si, cur, l):
+            d = slot.get(bi)
+            if d is None:
+                return
+            ws, i0, R = p.ws, p.i0, p.R
+            S1, pn = si + 1, var.patch_nums[si]
+            tok = torch.empty(R, H, l, S1 + 1, dtype=torch.int32, device=dev) if return_tokens else None
+            hip.call('attn_profile_f32', ws['q'], ws['kc'][bi], R, l, H, cur + l, ws['Lmax'], ends[si], S1, pn, int(radius),
+                     share[i0:, d, :, si], Dn * H * S * (S + 1), S * (S + 1), p.nan[d, si], tok, H * l * (S1 + 1), l * (S1 + 1))
+            if return_tokens:
+                dst = tokens[i0:i0 + R, d, :, cur:cur + l]
+                dst[..., :S1] = tok[..., :S1]
+                dst[..., S] = tok[..., S1]
+                if S1 < S:
+                    dst[..., S1:S] = -(tok[..., :1] < 0).to(torch.int32)           # a NaN query: -1 in every entry
+            if _tap is not None:
+                torch.cuda.current_stream().synchronize()
+                _tap(ws['q'][:R * l].clone(), ws['kc'][bi][:R, :, :cur + l].clone(), (bi, si, cur, l))
+        for p in self._tf_rows(tf.lab, tf.xin, max_rows):
+            p.nan = torch.zeros(Dn, S, p.R, H, dtype=torch.int32, device=dev)      # the kernel's nan_count is dense [row][head]
+            self._tf_pass(p, after_block=tap)                             # no head: no logits are needed
+            nanq[p.i0:p.i0 + p.R] = p.nan.permute(2, 0, 3, 1)
         for si in range(S - 1):                                       # near bin: from behind the scale's last key bin to index S
             share[..., si, S] = share[..., si, si + 1]
             share[..., si, si + 1] = 0
@@ -2334,8 +2329,8 @@ class SamplingEngine(_Engine):
         N, K = labels.shape
         if K > self.CLASSIFY_MAX_CAND:
             raise ValueError(f'classify takes at most {self.CLASSIFY_MAX_CAND} candidates per image on the HIP path, got {K}')
-        sc = self._score_setup(gt_tokens, labels, cfg, score)
-        dev = sc['gt'].device
+        sc = self._score_setup(gt_tokens, labels, cfg, dist=score[0] in _DIST_SCORES)
+        dev = sc.dev
         L, S = var.L, len(var.patch_nums)
         lmax = max(p * p for p in var.patch_nums)
         ends = [e for _, e in var.begin_ends]
@@ -2350,7 +2345,7 @@ class SamplingEngine(_Engine):
             Le, t0 = ends[last], ends[done] if done >= 0 else 0
             rows = max_rows * min(L // Le, lmax // var.patch_nums[last] ** 2)
             buf = torch.empty(N, m, Le, dtype=torch.float32, device=dev)
-            self._score_stage(sc, sc['lab'].gather(1, pos), last, done, rows, buf)
+            self._score_stage(sc, sc.lab.gather(1, pos), last, done, rows, self._token_reducer(sc, score, buf))
             tokens[img, pos, t0:Le] = buf[:, :, t0:]
             nk = min(keep, m)
             kept = torch.empty(N, nk, dtype=torch.int32, device=dev)
