@@ -825,6 +825,33 @@ int varhip_eval_reduce_f32(const float* nll, const float* smooth, const int64_t*
                            const int32_t* begin_S1, int S, int V, double* nll_S, double* smooth_S, int64_t* correct_S,
                            int64_t* pred_hist_V, varhip_stream_t stream);
 
+/* ---- the logit lens (VAR.logit_lens): a block's prediction against the final one ----------------------------------------------------------
+ * One scale of one pass.  logits: the head applied to the residual stream behind a block, final_logits: the head's output behind the last
+ * block, both [R * l][V] fp32 with row r, token t at r * l + t; gt[r * ld_gt + t] the ground-truth token; the five outputs share one
+ * addressing, out[r * ld_out + t].  With z the layer's row, zf the final row, m = max z, mf = max zf (exact, order-free):
+ *   nll, pred, rank: varhip_token_eval_f32's on the layer row, bit for bit (one piece of device code, rowlse.h, on the same path: both rows in
+ *            registers where V % 4 == 0, V <= 4096 and BOTH operands are 16-byte aligned; two passes over memory otherwise).  A token outside
+ *            [0, V) is never dereferenced: nll = NaN, rank = -1.  Ties and NaN rows as there.
+ *   With d_v = z_v - m, df_v = zf_v - mf (fp32, one rounding each), e_v = vm_exp(d_v), ef_v = vm_exp(df_v) (include/var_math.h),
+ *            S = sum_v e_v,  A = sum_{e_v > 0} e_v * d_v,  Sf = sum_v ef_v,  B = sum_{ef_v > 0} ef_v * (df_v - d_v)
+ *        every product, difference and addition of the four sums in float64, in ONE order that depends on V alone (varhip_token_eval_f32's
+ *        `smooth` order: lane i of 64 adds the elements j * 256 + 4 * i + c in ascending (j, c) order, the lanes by the xor butterfly 32 .. 1),
+ *        and ls = vm_log((float)S), lsf = vm_log((float)Sf):
+ *   entropy = (float)((double)ls - A / S)                     -sum_v p_v log p_v of the layer row in nats, in [0, log V]
+ *   kl      = (float)((B / Sf - (double)lsf) + (double)ls)    KL(pf || p) = sum_v pf_v (log pf_v - log p_v)
+ *        Neither depends on which path ran (they do not use the row pass's fp32 sum).  ef_v == 0 adds nothing whatever z_v is; ef_v > 0
+ *        against z_v = -inf gives +inf; a NaN difference (a NaN element, a +inf maximum, a row of -inf) in the layer row makes entropy and kl
+ *        NaN, in the final row kl.  Equal rows, one pointer or equal contents: B = +0, lsf == ls, kl = +0.0 exactly.
+ * V < 2^24.  VARHIP_EINVAL before any launch, nothing written: a NULL operand, R, l, V < 1, ld_gt < l, ld_out < l. */
+/* pinned bit for bit against its host twin and against varhip_token_eval_f32 (tests/test_logit_lens_kernels_gpu.py) */
+int varhip_token_lens_f32(const float* logits, const float* final_logits, const int64_t* gt, int64_t ld_gt, int R, int l, int V,
+                          float* nll, float* entropy, float* kl, int64_t* pred, int32_t* rank, int64_t ld_out, varhip_stream_t stream);
+/* the host twin: plain host code (no GPU), host pointers, the contract above row by row: the kernel's bits on 16-byte aligned device operands
+ * (host addresses carry no alignment constraint: the register path's row pass is taken wherever V % 4 == 0 and V <= 4096) */
+/* pinned against float64 (tests/test_logit_lens_cpu.py) */
+int varhip_token_lens_host_f32(const float* logits, const float* final_logits, const int64_t* gt, int64_t ld_gt, int R, int l, int V,
+                               float* nll, float* entropy, float* kl, int64_t* pred, int32_t* rank, int64_t ld_out);
+
 /* ==== 16-bit-input throughput mode ("f16") ===================================================================
  * The reference's harness runs the path under torch.autocast('cuda', dtype=torch.float16) (demo_sample.py:66-68): every F.linear of
  * basic_var.py then computes in fp16 and attention takes the flash path with fp16 q/k/v (basic_var.py:97,113).  These entry points are

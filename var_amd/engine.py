@@ -2312,6 +2312,53 @@ class SamplingEngine(_Engine):
             share[..., si, si + 1] = 0
         return dict(share_q=share, nan_queries=nanq, tokens=tokens)
 
+    # -- every block's prediction against the final one (VAR.logit_lens) ----------------------------------------------------------------
+    @torch.no_grad()
+    def logit_lens(self, gt_tokens: torch.Tensor, label_N: torch.Tensor, layers: tuple, max_rows: int, _tap=None) -> dict:
+        """VAR.logit_lens on the HIP path -> dict(nll, entropy, kl (N, D', L) fp32, pred int64, rank int32).  gt_tokens (N, L) int64, label_N
+        (N,) int64, layers: the selected block indices, ascending; all validated by the caller.  The images run teacher-forced in passes of at
+        most max_rows rows, one row per image, as in evaluate.  Per scale, the residual stream behind every selected block but the model's last
+        (ws['x'][:R * l]) is copied into its stash slot; behind the head, which has left the final logits in ws['lg'], the head runs once more
+        per stashed layer into a second logits buffer lg2 and varhip_token_lens_f32 reduces (lg2, ws['lg']) into the (layer, scale) slice of
+        the outputs.  The model's last block is reduced with logits = final_logits = ws['lg'] (no second GEMM).  No per-layer (rows, L, V)
+        tensor exists at any time; the stash (D' x R lmax x C fp32) and lg2 (R lmax x V) live for the call only.  _tap (tests): called after a
+        stream sync with clones of the layer's logits, of ws['lg'] and (bi, si, cur, l) for every launch."""
+        var = self.var
+        tf = self._tf_begin(label_N, gt_tokens)
+        dev, gt = tf.dev, tf.gt
+        L, V, C = var.L, var.V, var.C
+        N, Dn = gt.shape[0], len(layers)
+        final = var.depth - 1
+        slot = {bi: d for d, bi in enumerate(layers)}
+        e = lambda dt: torch.empty(N, Dn, L, dtype=dt, device=dev)
+        out = dict(nll=e(torch.float32), entropy=e(torch.float32), kl=e(torch.float32), pred=e(torch.int64), rank=e(torch.int32))
+        keys = ('nll', 'entropy', 'kl', 'pred', 'rank')
+        stash = lg2 = None
+
+        def keep(p, bi, si, cur, l):
+            if bi in slot and bi != final:
+                stash[slot[bi], :p.R * l].copy_(p.ws['x'][:p.R * l])
+
+        def head(p, si, cur, l):
+            ws, R = p.ws, p.R
+            for bi in layers:
+                d = slot[bi]
+                lg = ws['lg']
+                if bi != final:
+                    lg = lg2
+                    self.head(stash[d], ws['hn'], ws['xn'], lg2, R * l, l)
+                hip.call('token_lens_f32', lg, ws['lg'], gt[p.i0:, cur:], L, R, l, V, *[out[k][p.i0:, d, cur:] for k in keys], Dn * L)
+                if _tap is not None:
+                    torch.cuda.current_stream().synchronize()
+                    _tap(lg[:R * l].clone(), ws['lg'][:R * l].clone(), (bi, si, cur, l))
+        for p in self._tf_rows(tf.lab, tf.xin, max_rows):
+            if stash is None:                                         # (behind the workspace, sized by the passes' row count)
+                M = p.R * var.patch_nums[-1] ** 2
+                stash = torch.empty(max(Dn - (final in slot), 1), M, C, dtype=torch.float32, device=dev)
+                lg2 = torch.empty(M, V, dtype=torch.float32, device=dev)
+            self._tf_pass(p, head=head, after_block=keep)
+        return out
+
     # -- zero-shot classification with per-scale pruning (VAR.classify) -------------------------------------------------------------
     CLASSIFY_MAX_CAND = 16384          # varhip_class_select_f32 stages a stage's totals in LDS
 

@@ -117,6 +117,20 @@ def token_label_range(gt: torch.Tensor, lab: torch.Tensor, V: int, num_classes: 
     in_range(lab, num_classes, f'labels must lie in [0, {num_classes}]')
 
 
+def block_layers(layers, depth: int) -> tuple:
+    """the `layers` of attention_profile and logit_lens -> the selected block indices, ascending: None means every block"""
+    if layers is None:
+        return tuple(range(depth))
+    try:
+        layers = tuple(layers)
+    except TypeError:
+        raise ValueError('layers must be None or a strictly increasing sequence of block indices') from None
+    if not layers or not all(is_int(b) for b in layers) \
+            or any(b < 0 or b >= depth for b in layers) or any(b1 <= b0 for b0, b1 in zip(layers, layers[1:])):
+        raise ValueError(f'layers must be None or a strictly increasing sequence of block indices in [0, {depth})')
+    return tuple(int(b) for b in layers)
+
+
 def cfg_arg(cfg, name: str = 'cfg') -> float:
     """cfg / fill_cfg: whatever float() takes, a bool included (1.0 / 0.0), as in the per-image samplers"""
     return real(float(cfg) if isinstance(cfg, bool) else cfg, f'{name} must be finite and >= 0', lambda v: v >= 0, convert=True)

@@ -463,6 +463,88 @@ def attention_profile_torch(var, gt: torch.Tensor, label: torch.Tensor, radius: 
     return share, nanq, tokens
 
 
+class LogitLens:
+    """VAR.logit_lens's result: the prediction the trained head makes from the residual stream behind every selected block, per token, on the
+    model's device.  With z the head's fp32 logits behind block layers[d], p their softmax, and pf the softmax of the final logits:
+      nll      (N, D', L) fp32   -log p[gt]                       (behind the model's last block: VAR.evaluate's nll_BL)
+      entropy  (N, D', L) fp32   -sum_v p_v log p_v, in nats
+      kl       (N, D', L) fp32   KL(pf || p) = sum_v pf_v (log pf_v - log p_v); exactly 0 behind the model's last block
+      pred     (N, D', L) int64  argmax z;  rank (N, D', L) int32: |{v : z_v > z_gt or (z_v == z_gt and v < gt)}|
+      layers (the D' block indices), patch_nums: the scales the result covers
+    The methods run in PyTorch with float64 sums."""
+    __slots__ = ('layers', 'nll', 'entropy', 'kl', 'pred', 'rank', 'patch_nums')
+
+    def __init__(self, layers, nll, entropy, kl, pred, rank, patch_nums):
+        self.layers, self.patch_nums = tuple(layers), tuple(patch_nums)
+        self.nll, self.entropy, self.kl, self.pred, self.rank = nll, entropy, kl, pred, rank
+
+    def _scale_mean(self, x: torch.Tensor) -> torch.Tensor:
+        """x (N, D', L) -> (D', S) float64: the mean over the images and the tokens of each scale"""
+        out, b = [], 0
+        for pn in self.patch_nums:
+            out.append(x[..., b:b + pn * pn].double().mean(dim=(0, 2)))
+            b += pn * pn
+        return torch.stack(out, -1)
+
+    def per_scale(self) -> dict:
+        """{'nll', 'entropy', 'kl', 'agree', 'acc'}: (D', S) float64 means per layer and scale"""
+        return dict(nll=self._scale_mean(self.nll), entropy=self._scale_mean(self.entropy), kl=self._scale_mean(self.kl),
+                    agree=self._scale_mean(self.agree()), acc=self.acc())
+
+    def agree(self) -> torch.Tensor:
+        """(N, D', L) bool: the layer predicts what the last selected layer predicts"""
+        return self.pred == self.pred[:, -1:]
+
+    def settle_depth(self) -> torch.Tensor:
+        """(N, L) int64: the first selected layer (a block index) from which pred stays equal to the last selected layer's"""
+        a = self.agree().to(torch.int64)
+        stays = torch.flip(torch.cumprod(torch.flip(a, (1,)), 1), (1,))                   # agrees here and at every later selected layer
+        first = a.shape[1] - stays.sum(1)
+        return torch.tensor(self.layers, dtype=torch.int64, device=a.device)[first]
+
+    def acc(self) -> torch.Tensor:
+        """(D', S) float64: the share of tokens with rank == 0, per layer and scale"""
+        return self._scale_mean(self.rank == 0)
+
+    def __repr__(self):
+        N, D, L = self.nll.shape
+        return f'LogitLens(images={N}, layers={self.layers}, tokens={L})'
+
+
+def logit_lens_torch(var, gt: torch.Tensor, label: torch.Tensor, layers: tuple, max_rows: int):
+    """VAR.logit_lens's definitions in PyTorch (CPU models, train mode, prog_si >= 0): _forward_torch's pass with a forward hook on every
+    selected block, get_logits on each hooked output, and the per-token values from float64 log-softmaxes.  gt (N, L) tokens, label (N,)
+    labels -> (nll, entropy, kl fp32, pred int64, rank int32), each (N, D', ed) with ed the tokens _forward_torch covers"""
+    ed = var.begin_ends[var.prog_si][1] if var.prog_si >= 0 else var.L
+    x_all = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in var.begin_ends])[:, :ed - var.first_l]
+    final = var.depth - 1
+    parts = []
+    for i0 in range(0, gt.shape[0], int(max_rows)):
+        lab, g = label[i0:i0 + max_rows], gt[i0:i0 + max_rows, :ed]
+        caught = {}
+        hooks = [var.blocks[bi].register_forward_hook(lambda mod, inp, out, bi=bi: caught.__setitem__(bi, out)) for bi in layers if bi != final]
+        try:
+            zf = var._forward_torch(lab, x_all[i0:i0 + max_rows]).float()
+        finally:
+            for h in hooks:
+                h.remove()
+        cond = var.class_emb(lab)
+        lpf = torch.log_softmax(zf.double(), dim=-1)
+        pf = lpf.exp()
+        per = []
+        for bi in layers:
+            z = zf if bi == final else var.get_logits(caught[bi].float(), cond).float()
+            _, _, pred, rank = token_eval_torch(z, g)
+            lp = lpf if bi == final else torch.log_softmax(z.double(), dim=-1)
+            p = lp.exp()
+            zero = torch.zeros((), dtype=torch.float64, device=z.device)
+            ent = -torch.where(p > 0, p * lp, zero).sum(-1)
+            kl = torch.where(pf > 0, pf * (lpf - lp), zero).sum(-1)
+            per.append(((-lp.gather(-1, g.unsqueeze(-1)).squeeze(-1)).float(), ent.float(), kl.float(), pred, rank))
+        parts.append(tuple(torch.stack(f, 1) for f in zip(*per)))
+    return tuple(torch.cat(f) for f in zip(*parts))
+
+
 class EvidenceMaps:
     """VAR.evidence_maps' result: where in the image the evidence for each class sits.  With m[n, k, y, x] the map of class k (the selected
     scales' per-token scores, each resampled bilinearly to size x size and weighted by its share of the selected tokens):
@@ -1411,17 +1493,7 @@ class VAR(nn.Module):
         lab = A.labels_1d(label, N, f'label must be an int or (N,) integer class ids, N = {N}', scalar=True)
         A.integer(radius, 'radius must be an integer >= 0', 0)
         A.integer(max_rows, 'max_rows must be an integer >= 1', 1)
-        if layers is None:
-            layers = tuple(range(self.depth))
-        else:
-            try:
-                layers = tuple(layers)
-            except TypeError:
-                raise ValueError('layers must be None or a strictly increasing sequence of block indices') from None
-            if not layers or not all(A.is_int(b) for b in layers) \
-                    or any(b < 0 or b >= self.depth for b in layers) or any(b1 <= b0 for b0, b1 in zip(layers, layers[1:])):
-                raise ValueError(f'layers must be None or a strictly increasing sequence of block indices in [0, {self.depth})')
-            layers = tuple(int(b) for b in layers)
+        layers = A.block_layers(layers, self.depth)
         self._token_label_range(gt, lab)
         gt, lab = gt.to(dev, torch.int64), lab.to(dev, torch.int64)
         radius = int(radius)
@@ -1433,6 +1505,34 @@ class VAR(nn.Module):
             raise ValueError('attention_profile covers every scale: prog_si must be < 0')
         share, nanq, tokens = attention_profile_torch(self, gt, lab, r_eff, layers, bool(return_tokens))
         return AttentionProfile(share, nanq, tokens, self.patch_nums, radius, layers)
+
+    @torch.no_grad()
+    def logit_lens(self, gt_tokens, label, *, layers=None, max_rows: int = 64) -> LogitLens:
+        """At which depth the next-scale prediction forms -> LogitLens (per-token values; see there).
+
+        The "logit lens": the trained head (head_nm + head, get_logits of reference var.py:118-124) applied to the residual stream behind every
+        selected block, compared with the final prediction: per token and layer the loss, the entropy, KL(final || layer), the argmax and the
+        rank of the ground-truth token.  Taking them from forward hooks needs depth x (N, L, V) logits and as many softmaxes.  gt_tokens: (N, L)
+        integer tokens, teacher-forced as in evaluate; label: an int or (N,) class ids in [0, num_classes], used as given; layers: None (all
+        blocks) or strictly increasing block indices; max_rows bounds the images of one transformer pass, and no value depends on it.
+        On the HIP path (the conditions of token_log_likelihood; the precision follows set_hip_precision / torch.autocast, the residual stream
+        and the logits are fp32 in all of them) each selected block's output is kept per scale, the head runs on it behind the final head, and
+        varhip_token_lens_f32 reduces the two logits rows of a token to the five values: no per-layer logits tensor is made, and the last
+        block's nll / pred / rank are evaluate's bit for bit.  Elsewhere logit_lens_torch runs the same definitions on hooked block outputs
+        (with prog_si >= 0 over the scales 0 .. prog_si)."""
+        dev = self.lvl_1L.device
+        gt = self._token_shape(gt_tokens)
+        N = gt.shape[0]
+        lab = A.labels_1d(label, N, f'label must be an int or (N,) integer class ids, N = {N}', scalar=True)
+        A.integer(max_rows, 'max_rows must be an integer >= 1', 1)
+        layers = A.block_layers(layers, self.depth)
+        self._token_label_range(gt, lab)
+        gt, lab = gt.to(dev, torch.int64), lab.to(dev, torch.int64)
+        if self._scoring_on_hip(gt):
+            r = self.engine().logit_lens(gt, lab, layers, int(max_rows))
+            return LogitLens(layers, r['nll'], r['entropy'], r['kl'], r['pred'], r['rank'], self.patch_nums)
+        nsc = self.prog_si + 1 if self.prog_si >= 0 else len(self.patch_nums)
+        return LogitLens(layers, *logit_lens_torch(self, gt, lab, layers, int(max_rows)), self.patch_nums[:nsc])
 
     @staticmethod
     def _prior_arg(prior, N: int, K: int) -> torch.Tensor:
