@@ -111,6 +111,14 @@ int varhip_gemm_qkv_f32(const float* A, int64_t lda, const float* W, int64_t ldw
  *   - out = O * (1 / l). */
 int varhip_attn_cached_f32(const float* q, const float* kcache, const float* vcache, float* out,
                            int B2, int l, int H, int curL, int Lmax, varhip_stream_t stream);
+/* testing / experiments (host global, no launch): the waves per workgroup (NW of k_attn_cached<NW>; a wave owns 32 queries, the grid is
+ * ceil(l / (32 NW)) x H x B2) of the following varhip_attn_cached_f32 launches, varhip_adaln_block_f32's included: 1 .. 4 forces that NW,
+ * 0 (and anything else) leaves the choice to the dispatch, which never launches a wave without queries; starts from the environment
+ * variable VARHIP_ATTN_WAVES.  A query's arithmetic depends on its own wave's 32 queries and on the tile walk only: every NW computes the same bits. */
+int varhip_attn_force_waves(int nw);
+/* testing: the NW of the latest varhip_attn_cached_f32 launch, written by the launcher from the value it switches on.  0 before the first
+ * launch; a refused call (VARHIP_EINVAL) leaves it unchanged.  Host only: it launches nothing and reads no device memory. */
+int varhip_attn_last_waves(void);
 
 /* ---- one AdaLNSelfAttn block (basic_var.py:152-159) in one call ---------------------------------------------
  * x <- x + gamma1 * proj(attn(LN(x)(1+scale1)+shift1));  x <- x + gamma2 * fc2(gelu(fc1(LN(x)(1+scale2)+shift2)))

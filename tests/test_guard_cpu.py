@@ -299,6 +299,8 @@ NO_DEVICE_POINTER = {                                        # everything else v
     'gemm16_deep': 'test hook: kernel choice', 'gemm16_last_pick': 'test hook: reports the kernel instantiations of the latest 16-bit GEMM',
     'quant_last_route': 'test hook: reports the kernel route of the latest quantizer-step, word-embed or nearest-code call',
     'attn16_last_waves': 'test hook: reports the waves per workgroup of the latest 16-bit attention launch',
+    'attn_force_waves': 'test hook: waves per workgroup of the fp32 attention launches',
+    'attn_last_waves': 'test hook: reports the waves per workgroup of the latest fp32 attention launch',
     'vq_stats_blocks': 'size helper: host arithmetic (the workgroup partials of varhip_vq_scale_stats_f32 for n elements)',
 }
 FLAVOURS = ('f16', 'bf16')

@@ -268,14 +268,22 @@ static int attn_waves(int l) {
     return best;
 }
 
+// tests and experiments only (include/var_hip.h): 0 = attn_waves(l), 1..4 = that NW for every following launch; starts from VARHIP_ATTN_WAVES
+static int vh_g_attn_force_waves = [] { const char* e = getenv("VARHIP_ATTN_WAVES"); const int n = e ? atoi(e) : 0; return (n >= 1 && n <= 4) ? n : 0; }();
+static int vh_g_attn_last_waves = 0;      // the NW of the latest launch (varhip_attn_last_waves)
+
+extern "C" int varhip_attn_force_waves(int nw) { vh_g_attn_force_waves = (nw >= 1 && nw <= 4) ? nw : 0; return 0; }
+extern "C" int varhip_attn_last_waves(void) { return vh_g_attn_last_waves; }
+
 extern "C" int varhip_attn_cached_f32(const float* q, const float* kcache, const float* vcache, float* out,
                                       int B2, int l, int H, int curL, int Lmax, varhip_stream_t stream) {
     if (B2 <= 0 || l <= 0 || H <= 0 || curL <= 0 || curL > Lmax) return VARHIP_EINVAL;
     if (B2 > 65535 || H > 65535) return VARHIP_EINVAL;
     VhScope sc(VH_FAM_ATTN, (hipStream_t)stream, 4.0 * B2 * H * (double)l * curL * 64,
                4.0 * B2 * H * (2.0 * curL * 64 + 2.0 * l * 64));
-    static const int forced = [] { const char* e = getenv("VARHIP_ATTN_WAVES"); return e ? atoi(e) : 0; }();   // experiments only
-    const int nw = (forced >= 1 && forced <= 4) ? forced : attn_waves(l);
+    const int forced = vh_g_attn_force_waves;
+    const int nw = forced ? forced : attn_waves(l);
+    vh_g_attn_last_waves = nw;                                      // varhip_attn_last_waves (a refused call never gets here)
     dim3 grid((l + nw * 32 - 1) / (nw * 32), H, B2);
     hipStream_t s = (hipStream_t)stream;
     switch (nw) {
