@@ -209,7 +209,8 @@ int varhip_ctl_sample_rows_f32(const float* logits, const float* noise, int64_t*
  *   key = (low 32 bits of seeds[b], high 32 bits of seeds[b]),  counter = (v / 4, t, scale, draw)
  * (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85: Random123's philox4x32_10).  The value is a function of
  * (seed, scale, t, v, draw) alone: not of B, of the image's position in the batch, or of what was drawn before.  draw: 0 = the multinomial
- * fill (the noise of varhip_cfg_sample*_f32), 1 = the gumbel fill of more_smooth (the noise of varhip_gumbel_softmax_f32).  u is exact in
+ * fill (the noise of varhip_cfg_sample*_f32), 1 = the gumbel fill of more_smooth (the noise of varhip_gumbel_softmax_f32), 2 and 3 = the fresh
+ * values of varhip_exp1_posterior_f32 below (the losers' E_v, and at v = 0 the minimum T).  u is exact in
  * fp32 and lies in [2^-24, 1 - 2^-24]; vm_log (include/var_math.h) consists of correctly rounded operations only, so the kernel and the
  * host twin give the same bits.  This is the project's own stream, not torch's.  seeds: DEVICE int64 [B] (the host twin: host pointers);
  * out 16-byte aligned (the kernel stores 16 bytes per lane).  V % 4 != 0, B or l < 1, scale or draw < 0, a misaligned out: VARHIP_EINVAL. */
@@ -223,6 +224,31 @@ int varhip_exp1_philox_host_f32(const int64_t* seeds, int B, int l, int V, int s
 int varhip_philox4x32_host(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 /* the fill's transform alone on the host: out[i] = -vm_log((2 (bits[i] >> 9) + 1) * 2^-24)  (exhaustive tests over the 2^23 values of n) */
 int varhip_exp1_from_bits_host_f32(const uint32_t* bits, int64_t n, float* out);
+
+/* ---- posterior Exp(1) noise given the drawn token (VAR.abduct_noise / VAR.counterfactual) ----------------------------------------------------
+ * The noise under which varhip_cfg_sample_rows_f32, without top-k / top-p, draws the GIVEN token g from the given logits, sampled from the
+ * law of the Exp(1) noise conditioned on that outcome (the Gumbel-max posterior in its exponential-race form).
+ * logits: [2B][l][V] as the sampler reads them (conditional rows first); t_cfg: DEVICE double [B]; gt: int64, the token of row (b, t) at
+ * gt[b * ld_gt + t]; seeds: DEVICE int64 [B]; every output of row (b, t) is addressed at row b * ld_out + t (ld_gt, ld_out >= l: a scale
+ * reads and writes its slice of (B, L) tensors).  Row (b, t), one 256-thread workgroup:
+ *   x_v = ca*cond_v - cb*uncond_v, ca = (float)(1.0 + t_cfg[b]), cb = (float)t_cfg[b]      the sampler's combine, one piece of code
+ *   m = max x,  ev_v = vm_exp(x_v - m),  S = the sampler's canonical W256 sum of ev,  p_v = ev_v / S      the sampler's stage (4) values
+ *   E_v = the Exp(1) stream's value at (seeds[b], scale, t, v, draw 2),  T = its value at (seeds[b], scale, t, 0, draw 3)
+ *   noise_g = max(fl(T * p_g), FLT_MIN);   r_g = p_g / noise_g
+ *   noise_v (v != g) = the smallest float n >= fl(fl(T * p_v) + E_v) with (ev_v / S) / n < r_g strictly in fp32 — the sampler's own score
+ *             expression; reached from max(that candidate, pred(fl(p_v / r_g))) by five conditional one-ulp steps, no data-dependent loop
+ *   logp = (x_g - m) - vm_log(S),  flag = 0
+ * A row whose g lies outside [0, V), that holds a NaN, whose p_g == 0 or whose r_g is not finite and positive is flagged and not repaired:
+ * flag = 1, logp = -inf, noise_v = E_v for every v (the prior).  On every unflagged row varhip_cfg_sample_rows_f32 with top_k = 0,
+ * top_p = 0 and this noise returns g, under both settings of varhip_sampler_force_walk.  V % 4 != 0, V > 8192, B or l < 1, scale < 0,
+ * ld_gt or ld_out < l, a NULL operand, logits or noise_out not 16-byte aligned: VARHIP_EINVAL, nothing is written. */
+/* pinned against its host twin below and the sampler's replay (tests/test_abduct_kernels_gpu.py) */
+int varhip_exp1_posterior_f32(const float* logits, const double* t_cfg, const int64_t* gt, int64_t ld_gt, const int64_t* seeds, int B, int l,
+                              int V, int scale, float* noise_out, float* logp_out, int32_t* flag_out, int64_t ld_out, varhip_stream_t stream);
+/* the host twin: plain host code (usable without a GPU), same arguments with host pointers, no alignment constraint; the kernel's bits */
+/* pinned against a numpy restatement, the oracle's sampler and the Exp(1) law (tests/test_abduct_cpu.py) */
+int varhip_exp1_posterior_host_f32(const float* logits, const double* t_cfg, const int64_t* gt, int64_t ld_gt, const int64_t* seeds, int B, int l,
+                                   int V, int scale, float* noise_out, float* logp_out, int32_t* flag_out, int64_t ld_out);
 
 /* ---- scored sampling (VAR.autoregressive_infer_cfg_scored, VAR.sample_best_of) -----------------------------------------------------------
  * What the sampler's operands say about the token it drew, one wave per token row r = b * l + j, launched right behind varhip_cfg_sample*_f32

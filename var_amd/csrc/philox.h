@@ -1,7 +1,9 @@
 // philox.h — Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), shared by the Exp(1) fill (rng.hip) and the resampling uniform
-// (smcresample.hip).  Integer arithmetic only: the kernel and the host code produce the same words.
+// (smcresample.hip).  Integer arithmetic only: the kernel and the host code produce the same words.  vr_exp1, the fill's transform of a
+// word to Exp(1), follows it: built from include/var_math.h's vm_log, so the same bits on both sides too.
 #pragma once
 #include <stdint.h>
+#include "../../include/var_math.h"
 
 struct VrPhilox { uint32_t w[4]; };
 
@@ -16,4 +18,11 @@ __host__ __device__ static inline VrPhilox vr_philox4x32_10(uint32_t c0, uint32_
     VrPhilox o;
     o.w[0] = c0; o.w[1] = c1; o.w[2] = c2; o.w[3] = c3;
     return o;
+}
+
+// 32 random bits -> Exp(1): the top 23 bits n give u = (2n + 1) * 2^-24 in [2^-24, 1 - 2^-24] (2n + 1 < 2^24: the conversion and the scaling
+// are exact), e = -ln u in (0, 16.7]
+__host__ __device__ static inline float vr_exp1(uint32_t x) {
+    const float u = (float)(int32_t)(2u * (x >> 9) + 1u) * 5.9604644775390625e-08f;
+    return -vm_log(u);
 }

@@ -7,12 +7,7 @@
 #include "common.h"
 #include "philox.h"
 
-// 32 random bits -> Exp(1): the top 23 bits n give u = (2n + 1) * 2^-24 in [2^-24, 1 - 2^-24] (2n + 1 < 2^24: the conversion and the scaling
-// are exact), e = -ln u in (0, 16.7]
-__host__ __device__ static inline float vr_exp1(uint32_t x) {
-    const float u = (float)(int32_t)(2u * (x >> 9) + 1u) * 5.9604644775390625e-08f;
-    return -vm_log(u);
-}
+// (vr_exp1, 32 random bits -> Exp(1), lives in philox.h: abduct.hip draws single values of this stream with it)
 
 // one lane = one Philox block = four consecutive columns of one row = one 16-byte store
 __global__ void __launch_bounds__(256) k_exp1_philox(const int64_t* __restrict__ seeds, int l, int V4, int scale, int draw, int64_t nblk,

@@ -7,6 +7,7 @@
 // top-k) with the fp64 running sum ATen's cumsum uses would make — decided by a parallel prefix sum wherever that is provably the
 // same decision, by the walk itself otherwise — and the two softmax denominators use the canonical W256 sum.
 #include "common.h"
+#include "samplerow.h"
 
 __device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int src) {
     return ((unsigned long long)__shfl((unsigned)(v >> 32), src, 64) << 32) | (unsigned)__shfl((unsigned)v, src, 64);
@@ -48,22 +49,8 @@ __device__ __forceinline__ unsigned long long vs_scan256_u64(unsigned long long 
     return v + add;
 }
 
-// Stage (1) of the shared body below: what fills xs[V], the row's working logits.  Which thread computes an element is irrelevant — the sums
-// of the later stages read xs in their own canonical assignment — so every form reads its rows 16 bytes per lane.
-// VsCfgPair: (1+t)*cond - t*uncond (var.py:172-173), three roundings as in the reference's tensor expression.
-struct VsCfgPair {
-    static constexpr bool kMinP = false;
-    const float* lc; const float* lu; float ca, cb;
-    __device__ __forceinline__ void operator()(float* __restrict__ xs, int V, int tid) const {
-        for (int i4 = tid; i4 < (V >> 2); i4 += 256) {
-            const f32x4 c4 = *(const f32x4*)(lc + 4 * i4), u4 = *(const f32x4*)(lu + 4 * i4);
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float a = ca * c4[e]; const float b = cb * u4[e]; o[e] = a - b; }
-            *(f32x4*)(xs + 4 * i4) = o;
-        }
-    }
-};
+// Stage (1) of the shared body below: what fills xs[V], the row's working logits.  VsCfgPair, the CFG combine (var.py:172-173), lives in
+// samplerow.h, shared with abduct.hip.
 // VsMix: G - 1 class rows and the unconditional row (the last), `gs` floats apart, with the image's G coefficients `a`:
 //   acc = a[0]*c_0;  acc = acc + a[k]*c_k (k = 1 .. G-2, in this order);  x = acc - a[G-1]*u
 // every product, sum and difference rounded to fp32 on its own (the file is compiled with -ffp-contract=off).  G = 2 is VsCfgPair's
@@ -436,9 +423,9 @@ __device__ __forceinline__ void vs_cfg_sample_row(const Fill& fill, const float*
     };
     if constexpr (NV > 0) {
 #pragma unroll
-        for (int k = 0; k < NV; ++k) consider((ev[k] / S) / qv[k], tid + 256 * k);
+        for (int k = 0; k < NV; ++k) consider(vs_score(ev[k], S, qv[k]), tid + 256 * k);
     } else
-    for (int i = tid; i < V; i += 256) consider((vm_exp(xs[i] - m) / S) / qn[i], i);
+    for (int i = tid; i < V; i += 256) consider(vs_score(vm_exp(xs[i] - m), S, qn[i]), i);
     // combine across threads: NaN beats number; larger beats smaller; ties -> smaller index
     auto better = [](float av, int ai, int an, float cv, int ci, int cn) -> bool {      // is (c) better than (a)?
         if (ci < 0) return false;

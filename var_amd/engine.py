@@ -1461,7 +1461,7 @@ class SamplingEngine(_Engine):
                decode: bool = True, gt_tokens: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
                more_smooth: bool = False, gumbel_noises=None, smooth: Optional[dict] = None, greedy: bool = False,
                tokens_out: Optional[torch.Tensor] = None, edit: Optional[dict] = None, per_image: Optional[dict] = None,
-               stats: Optional[dict] = None) -> torch.Tensor:
+               stats: Optional[dict] = None, kept_scales: Optional[tuple] = None) -> torch.Tensor:
         """label_B: int64 [B] on the device.  noises: optional per-scale Exp(1) tensors [B*l, V] — a list, or a callable
         (si, l) -> tensor (tests inject the CPU generator's stream; var_amd.multi hands each rank its rows); by default they
         are drawn with `exponential_(generator=rng)` exactly as torch.multinomial (helpers.py:19) would (_Exp1).  gumbel_noises: the same for
@@ -1477,6 +1477,10 @@ class SamplingEngine(_Engine):
         'entropy'] (fp32) and stats['kept'] (int32).  One launch per scale and nothing else (_sampled): the RNG draws, the other kernels and
         their order are those of the call without it.  Combines with more_smooth and per_image; not with smooth, greedy, gt_tokens /
         keep_mask or edit, whose kept positions have no drawn distribution.
+        kept_scales = (tokens int64 [B, L] on the device, first): every scale below `first` takes the given tokens by the route of a fully kept
+        scale of inpainting — no head, no sampler, no draw (a callable noise source is not called for it), the plain quantizer step — and the
+        scales from `first` on sample as without it (counterfactual).  With stats the kept scales' slices are left as the caller filled them.
+        Not with gt_tokens / keep_mask, edit, smooth sampling, greedy selection or more_smooth.
         force_idx/trace are test hooks (teacher forcing; keep per-scale logits/tokens/f_hat, with stats also the filtered logits 'masked')."""
         var = self.var
         self.resolve_precision()
@@ -1496,6 +1500,8 @@ class SamplingEngine(_Engine):
             raise ValueError('per-image parameters belong to the sampler: they do not combine with greedy selection or smooth sampling')
         if stats is not None and (smooth is not None or greedy or gt_tokens is not None or keep_mask is not None or edit is not None):
             raise ValueError('stats describe sampled tokens: they do not combine with smooth sampling, greedy selection, gt_tokens / keep_mask or edit')
+        if kept_scales is not None and (gt_tokens is not None or keep_mask is not None or edit is not None or smooth is not None or greedy or more_smooth):
+            raise ValueError('kept_scales does not combine with gt_tokens / keep_mask, edit, smooth sampling, greedy selection or more_smooth')
         if tokens_out is not None and (tokens_out.dtype != torch.int64 or tuple(tokens_out.shape) != (B, var.L) or not tokens_out.is_contiguous()):
             raise ValueError(f'tokens_out must be a contiguous int64 ({B}, {var.L}) tensor')
         tr = dict(logits=[], idx=[], f_hat=[], pooled=[]) if trace else None
@@ -1509,6 +1515,12 @@ class SamplingEngine(_Engine):
             raise ValueError('smooth sampling and inpainting are separate entry points')
         sm = self._smooth_setup(B, smooth, dev) if smooth is not None else None
         skip = (inp or ed or (None, None, None))[2]
+        forced = None
+        if kept_scales is not None:
+            forced, first = kept_scales
+            if forced.dtype != torch.int64 or tuple(forced.shape) != (B, var.L) or forced.device != dev:
+                raise ValueError(f'kept_scales tokens must be an int64 ({B}, {var.L}) tensor on the model\'s device')
+            skip = [si < first for si in range(S)]
         noise = _Exp1(noises, rng, var.V, dev)
         gumbel = _Exp1(gumbel_noises, rng, var.V, dev) if more_smooth else None
 
@@ -1521,7 +1533,7 @@ class SamplingEngine(_Engine):
             if kept and ed is not None:
                 idx = self._edit_kept(B, sc, ed[0], noise, gumbel)
             elif kept:        # inpainting, every token of this scale is kept: no head, no sampling, no RNG draw (var.py:312-313, fork)
-                idx = inp[0][:, sc.cur:sc.cur + sc.l].contiguous().view(-1)
+                idx = (forced if inp is None else inp[0])[:, sc.cur:sc.cur + sc.l].contiguous().view(-1)
             elif sm is not None:
                 idx = self._smooth_select(ws, B, sc, sm, t, masked, tr)
             elif greedy:
@@ -1610,6 +1622,68 @@ class SamplingEngine(_Engine):
             hip.call('exp1_philox_f32', seeds_d, R, l, V, si, draw, out)
             return out
         return fill
+
+    # -- the noise behind given tokens, and its replay (VAR.abduct_noise / VAR.counterfactual) ---------------------------------------------
+    @torch.no_grad()
+    def abduct(self, gt_tokens: torch.Tensor, label_B: torch.Tensor, seeds, cfg, first: int) -> dict:
+        """code_tokens' walk — the tokens are given, sc.idx = gt — with varhip_exp1_posterior_f32 behind the head of every scale >= first: the
+        Exp(1) noise under which the unfiltered guided sampler of image b (guidance t[si][b] = cfg[b] * si / (S - 1), per_image_tables' roundings:
+        those of varhip_cfg_sample_rows_f32's table) draws exactly these tokens, sampled from its law given that outcome with fresh values of
+        the Philox stream keyed by seeds[b] (draws 2 and 3).  gt_tokens (B, L) int64 in [0, V) on the device, label_B (B,) int64, seeds and
+        cfg host sequences of B values.  The logits are fp32 in every precision, so the call runs in f32, f16 and bf16 alike.
+        -> dict(noise (B, L, V) fp32 — below `first` the stream's draw-2 fill, which nothing reads —, logp (B, L) fp32: log p(gt token) under
+        the guided row, NaN below `first`; flags (B, L) int32: 1 where no noise explains the token (probability 0 or a NaN row: the row
+        holds the prior fill, logp -inf); precision, sig: the arithmetic and the weights the logits came from).  Nothing is kept by the engine."""
+        var = self.var
+        B = gt_tokens.shape[0]
+        self.resolve_precision()
+        self.refresh()
+        self._wait_ready()
+        ws = self.workspace(B)
+        dev, S, V, L = ws['dev'], len(var.patch_nums), var.V, var.L
+        if label_B.dtype != torch.int64 or label_B.numel() != B:
+            raise ValueError('label_B must be an int64 tensor of B labels')
+        self._check_labels(label_B)
+        label_B = label_B.to(dev).contiguous()
+        gt = gt_tokens.to(dev, torch.int64).contiguous()
+        per, seeds_d = self._per_image_upload(cfg, [0] * B, [0.0] * B, seeds)
+        noise = torch.empty(B, L, V, dtype=torch.float32, device=dev)
+        logp = torch.full((B, L), float('nan'), dtype=torch.float32, device=dev)
+        flags = torch.zeros(B, L, dtype=torch.int32, device=dev)
+        prior = self._philox(seeds_d, 2)
+        for si in range(min(first, S)):
+            b0, e0 = var.begin_ends[si]
+            noise[:, b0:e0].copy_(prior(si, e0 - b0).view(B, e0 - b0, V))
+        if first < S:
+            ws['f_hat'].zero_()
+            self._prologue(ws, label_B, 2 * B)
+            for sc in self._scales(ws, B, 0, S - 1):
+                if sc.si >= first:
+                    self._logits(ws, B, sc, None)
+                    hip.call('exp1_posterior_f32', ws['logits'], per['t'][sc.si], gt[:, sc.cur:], L, seeds_d, B, sc.l, V, sc.si,
+                             noise[:, sc.cur:], logp[:, sc.cur:], flags[:, sc.cur:], L)
+                sc.idx = gt[:, sc.cur:sc.cur + sc.l].contiguous().view(-1)
+        return dict(noise=noise, logp=logp, flags=flags, precision=self.precision, sig=self._sig)
+
+    @torch.no_grad()
+    def counterfactual(self, noise: torch.Tensor, rows: torch.Tensor, gt_tokens: torch.Tensor, label_R: torch.Tensor, cfg, top_k, top_p, first: int,
+                       tokens_out: torch.Tensor, stats: dict, decode: bool) -> Optional[torch.Tensor]:
+        """sample() for R requests whose noise is stored: request r reads noise[rows[r]] ((B, L, V) fp32 of abduct, rows int64 [R] on the
+        device), scale si its slice [cur, cur + l) — gathered per scale, (R, l, V), never the whole record — and samples under label_R[r]
+        with its own cfg / top_k / top_p (host sequences of R values: sample_per_image's tables).  Scales below `first` are forced to
+        gt_tokens ((R, L) int64 on the device) through sample()'s kept-scale route.  stats: the (R, L) tensors of STATS_FIELDS, filled by the
+        caller; the kept scales' slices stay as they are.  No new sampler: varhip_cfg_sample_rows_f32 reads the stored noise.
+        -> the images, or None (decode=False)"""
+        var = self.var
+        R = rows.numel()
+        per, _ = self._per_image_upload(cfg, top_k, top_p)
+
+        def stored(si, l):
+            cur = var.begin_ends[si][0]
+            return noise[:, cur:cur + l].index_select(0, rows).view(R * l, var.V)
+        img = self.sample(R, label_R, None, 0.0, 0, 0.0, noises=stored, tokens_out=tokens_out, per_image=per, decode=decode, stats=stats,
+                          kept_scales=(gt_tokens, first) if first > 0 else None)
+        return img if decode else None
 
     def _begin_rows(self, who: str, what: str, label_N: torch.Tensor, N: int, n: int, most: int, max_images: int):
         """how a call over N = B * n rows, n `what` per image, opens: its limits, the call's precision and weights, the labels' check -> the device"""

@@ -4,7 +4,7 @@ from typing import Tuple
 import torch.nn as nn
 
 from .quant import VectorQuantizer2
-from .var import VAR, ComposedRecord, CompressResult, DecompressResult, SampleRecord, VarCodecError
+from .var import VAR, ComposedRecord, CompressResult, CounterfactualResult, DecompressResult, NoiseRecord, SampleRecord, VarCodecError
 from .vqvae import VQVAE
 
 # layers whose default initialisers the reference's factory switches off process-wide (checkpoints, or init_weights, fill them)

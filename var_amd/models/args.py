@@ -299,3 +299,34 @@ def normalize_keep(keep, S: int, alive: int) -> list:
             schedule.append((si, m))
             alive = m
     return schedule
+
+
+def counterfactual_args(V: int, L: int, S: int, num_classes: int, gt_tokens, label_src, label_dst, g_seeds, cfg, cfg_dst, top_k, top_p, first_scale,
+                        max_images):
+    """the argument handling of VAR.abduct_noise (label_dst None) and VAR.counterfactual -> dict(gt (B, L) integer tensor, lab_src (B,),
+    lab_dst (B, K) or None, seeds, cfg: lists of B values; cfg_dst, top_k, top_p: lists of B * K values, request (b, k) at b * K + k; first,
+    max_images).  label_dst: (B,) — K = 1 — or (B, K); cfg_dst None: the source's cfg; cfg_dst, top_k and top_p per image, shared by its K
+    replays.  first_scale: an integer in [0, S] (S: nothing is abducted, nothing can change)."""
+    gt = token_rows(gt_tokens, L)
+    B = gt.shape[0]
+    lab_src, seeds, cfgs = sample_args(V, label_src, g_seeds, cfg, 0, 0.0)[:3]
+    if lab_src.numel() != B:
+        raise ValueError(f'label_src must hold one class id per image ({B}), got {lab_src.numel()}')
+    token_label_range(gt, lab_src, V, num_classes)
+    first = integer(first_scale, f'first_scale must be an integer in [0, {S}], got {first_scale!r}', 0, S)
+    most = integer(max_images, 'max_images must be an integer >= 1', 1, integral_float=True)
+    out = dict(gt=gt, lab_src=lab_src, lab_dst=None, seeds=seeds, cfg=cfgs, first=first, max_images=most)
+    if label_dst is None:
+        return out
+    lab = torch.as_tensor(label_dst)
+    if lab.dim() == 1:
+        lab = lab.unsqueeze(1)
+    if lab.dim() != 2 or lab.shape[0] != B or lab.shape[1] < 1 or not _integer_tensor(lab):
+        raise ValueError(f'label_dst must be ({B},) or ({B}, K) integer class ids, K >= 1')
+    in_range(lab, num_classes, f'labels must lie in [0, {num_classes}]')
+    K = lab.shape[1]
+    spread = lambda x, name: per_image(x, name, B, None, K)
+    _, _, cd, ks, ps = sample_args(V, lab.reshape(-1), [0] * (B * K), spread(cfgs if cfg_dst is None else cfg_dst, 'cfg_dst'), spread(top_k, 'top_k'),
+                                   spread(top_p, 'top_p'))
+    out.update(lab_dst=lab, cfg_dst=cd, top_k=ks, top_p=ps)
+    return out

@@ -739,6 +739,56 @@ class SampleRecord:
 BEST_OF_FIELDS = ('logp_cond', 'logp_guided', 'logp_drawn')
 
 
+class NoiseRecord:
+    """What VAR.abduct_noise returns: the sampler's noise behind given tokens, on the model's device.
+      noise        (B, L, V) fp32: under it the unfiltered guided sampler of (label_src, cfg) draws the tokens; L * V * 4 bytes per image
+      logp_src     (B, L) fp32: log p(token) under the guided source distribution, NaN on scales below first_scale, -inf where unreachable
+      unreachable  (B, L) bool: no noise explains the token (probability 0 under the source distribution, or a NaN row): the row holds
+                   prior noise and a replay is free to draw another token there
+      cfg          the B source cfg values;  first_scale: the first abducted scale;  precision: the arithmetic the logits were computed in
+    A record belongs to the weights and the precision it was made with (VAR.counterfactual checks both)."""
+    __slots__ = ('noise', 'logp_src', 'unreachable', 'cfg', 'first_scale', 'precision', '_sig')
+
+    def __init__(self, noise, logp_src, unreachable, cfg, first_scale, precision, sig):
+        self.noise, self.logp_src, self.unreachable, self.cfg = noise, logp_src, unreachable, tuple(cfg)
+        self.first_scale, self.precision, self._sig = int(first_scale), precision, sig
+
+    def __repr__(self):
+        B, L, V = tuple(self.noise.shape)
+        return (f'NoiseRecord(B={B}, L={L}, V={V}, first_scale={self.first_scale}, precision={self.precision!r}, '
+                f'unreachable={int(self.unreachable.sum())}, {self.noise.numel() * 4 / 1e6:.1f} MB)')
+
+
+class CounterfactualResult:
+    """What VAR.counterfactual returns, on the model's device; request (b, k) is image b replayed under label_dst[b, k]:
+      images       (B, K, 3, H, W) fp32 in [0, 1], or None (decode=False)
+      tokens       (B, K, L) int64;  changed (B, K, L) bool: tokens != the given ones
+      first_changed_scale  (B, K) int64: the first scale holding a changed token, S where nothing changed
+      logp_src, unreachable  (B, L): the NoiseRecord's
+      record       the replay's SampleRecord over the B * K requests (row b * K + k); scales below first_scale were not sampled:
+                   their log-probabilities and entropy are NaN, kept is 0
+      noise        the NoiseRecord the replay read (pass it as noise= to replay again without a second abduction)"""
+    __slots__ = ('images', 'tokens', 'changed', 'first_changed_scale', 'logp_src', 'unreachable', 'record', 'noise', 'patch_nums')
+
+    def __init__(self, images, tokens, changed, first_changed_scale, logp_src, unreachable, record, noise, patch_nums):
+        self.images, self.tokens, self.changed, self.first_changed_scale = images, tokens, changed, first_changed_scale
+        self.logp_src, self.unreachable, self.record, self.noise, self.patch_nums = logp_src, unreachable, record, noise, tuple(patch_nums)
+
+    def change_rate(self) -> torch.Tensor:
+        """(B, K, S) float64 (a CPU tensor): per request and scale the share of its tokens that changed"""
+        c = self.changed.detach().cpu().numpy()
+        cols, b = [], 0
+        for pn in self.patch_nums:
+            cols.append(c[:, :, b:b + pn * pn].mean(axis=2, dtype=np.float64))
+            b += pn * pn
+        return torch.from_numpy(np.stack(cols, axis=2))
+
+    def __repr__(self):
+        B, K, L = tuple(self.tokens.shape)
+        return (f'CounterfactualResult(B={B}, K={K}, L={L}, images={None if self.images is None else tuple(self.images.shape)}, '
+                f'changed={float(self.changed.float().mean()):.3f}, unreachable={int(self.unreachable.sum())})')
+
+
 class ComposedRecord:
     """What VAR.sample_composed returns, on the model's device (coef on the host):
       images       (B, 3, H, W) fp32 in [0, 1], or None (decode=False)
@@ -1063,6 +1113,85 @@ class VAR(nn.Module):
         self.engine()._check_labels(lab)
         img, tok = self._per_image_torch(lab, seeds, None, None, None, False, ctl=tab)
         return SampleRecord(img if decode else None, tok, None, None, None, None, None, self.patch_nums)
+
+    def _counterfactual_begin(self, name: str):
+        dev = self._hip_only(name)
+        if self.training or self.prog_si >= 0:
+            raise RuntimeError(f'VAR.{name}: this build runs the sampling loop on MI355X HIP kernels only; put the model in eval mode with prog_si < 0')
+        return dev
+
+    @torch.no_grad()
+    def abduct_noise(self, gt_tokens, label_B, g_seeds, cfg=1.5, first_scale=0, max_images=8) -> NoiseRecord:
+        """The noise under which the model would have produced these tokens: for every token of scales >= first_scale, a draw from the law
+        of the sampler's Exp(1) noise given that the unfiltered guided sampler (label_B, cfg, no top-k / top-p) returned it — the Gumbel-max
+        posterior in the exponential-race form the sampler uses.  Replayed under the same label and cfg it gives
+        the tokens back bit for bit; replayed under another label it gives the coupled sample (VAR.counterfactual).
+          gt_tokens  (B, L) integer token ids in [0, V), e.g. vae.img_to_idxBl's, concatenated
+          label_B    (B,) class ids;  g_seeds (B,) integers in [0, 2^63): the fresh values come from the per-image Philox stream of seed b
+                     (draws 2 and 3: the record of a request does not depend on what it is batched with, self.rng is not touched)
+          cfg        a scalar or B values;  first_scale in [0, S];  max_images: images per pass
+        One teacher-forced walk (no decode) with varhip_exp1_posterior_f32 behind each head; f32, f16 and bf16.  The record costs
+        L * V * 4 bytes per image (11.1 MB at 256 px, 36.7 MB at 512 px).  HIP path only."""
+        a = A.counterfactual_args(self.V, self.L, len(self.patch_nums), self.num_classes, gt_tokens, label_B, None, g_seeds, cfg, None, 0, 0.0,
+                                  first_scale, max_images)
+        dev = self._counterfactual_begin('abduct_noise')
+        gt, lab, B, m = a['gt'].to(dev).long(), a['lab_src'].to(dev).long(), a['gt'].shape[0], a['max_images']
+        eng = self.engine()
+        parts = [eng.abduct(gt[b0:b0 + m], lab[b0:b0 + m].contiguous(), a['seeds'][b0:b0 + m], a['cfg'][b0:b0 + m], a['first']) for b0 in range(0, B, m)]
+        cat = lambda key: parts[0][key] if len(parts) == 1 else torch.cat([p[key] for p in parts])
+        return NoiseRecord(cat('noise'), cat('logp'), cat('flags').ne(0), a['cfg'], a['first'], parts[0]['precision'], parts[0]['sig'])
+
+    @torch.no_grad()
+    def counterfactual(self, gt_tokens, label_src, label_dst, g_seeds, cfg=1.5, cfg_dst=None, top_k=0, top_p=0.0, first_scale=0, noise=None,
+                       decode=True, max_images=8) -> CounterfactualResult:
+        """Re-sample given images under another class with their own noise: abduct_noise(gt_tokens, label_src, g_seeds, cfg, first_scale), then
+        the per-image sampler replays that noise under label_dst — what the model would have drawn, had the class been another, everything
+        else being equal.  Tokens the target distribution still prefers under that noise stay; the others move.
+          label_dst  (B,) or (B, K): K replays of one abduction;  cfg_dst (default: cfg), top_k, top_p: the TARGET side's, per image
+          first_scale  scales below it are kept as given (forced through the kept-scale route), the rest is replayed
+          noise      a NoiseRecord of an earlier call on the same tokens, label_src, seeds and cfg: no second abduction.  A record made in
+                     another precision, under other weights or with a larger first_scale raises ValueError
+        With label_dst == label_src, cfg_dst == cfg and no filter the result is gt_tokens bit for bit wherever `unreachable` is false.
+        Source-side filters are not offered (a token outside a filter has no noise that explains it); no more_smooth.  A request's result
+        does not depend on its batch, on K or on max_images (which chunks both phases); self.rng is neither read nor advanced.  HIP path only
+        (SamplingEngine.abduct / .counterfactual)."""
+        S = len(self.patch_nums)
+        a = A.counterfactual_args(self.V, self.L, S, self.num_classes, gt_tokens, label_src, label_dst, g_seeds, cfg, cfg_dst, top_k, top_p,
+                                  first_scale, max_images)
+        dev = self._counterfactual_begin('counterfactual')
+        eng = self.engine()
+        gt, B, K, m, first = a['gt'].to(dev).long().contiguous(), a['gt'].shape[0], a['lab_dst'].shape[1], a['max_images'], a['first']
+        if noise is None:
+            noise = self.abduct_noise(gt, a['lab_src'], a['seeds'], a['cfg'], first, m)
+        else:
+            if not isinstance(noise, NoiseRecord) or tuple(noise.noise.shape) != (B, self.L, self.V) or noise.noise.device != gt.device:
+                raise ValueError(f'noise must be a NoiseRecord of these {B} images on the model\'s device')
+            prec = eng.resolve_precision()
+            eng.refresh()
+            if noise.precision != prec:
+                raise ValueError(f'the NoiseRecord was made in {noise.precision}, this call runs in {prec}: the logits differ, the noise explains nothing')
+            if noise._sig != eng._sig:
+                raise ValueError('the NoiseRecord was made under other weights')
+            if noise.first_scale > first:
+                raise ValueError(f'the NoiseRecord starts at scale {noise.first_scale}: it holds no noise for first_scale = {first}')
+        R = B * K
+        rows = torch.arange(B, device=dev).repeat_interleave(K)
+        lab = a['lab_dst'].to(dev).long().reshape(-1).contiguous()
+        gt_rows = gt.index_select(0, rows)
+        tok = torch.empty(R, self.L, dtype=torch.int64, device=dev)
+        st = {key: torch.zeros(R, self.L, dtype=torch.int32, device=dev) if key == 'kept' else torch.full((R, self.L), float('nan'), device=dev)
+              for key in SampleRecord.FIELDS}
+        imgs = []
+        for c0 in range(0, R, m):
+            c1 = min(c0 + m, R)
+            imgs.append(eng.counterfactual(noise.noise, rows[c0:c1], gt_rows[c0:c1], lab[c0:c1], a['cfg_dst'][c0:c1], a['top_k'][c0:c1], a['top_p'][c0:c1],
+                                           first, tok[c0:c1], {key: v[c0:c1] for key, v in st.items()}, bool(decode)))
+        img = torch.cat(imgs) if decode else None
+        changed = tok.ne(gt_rows)
+        per_scale = torch.stack([changed[:, b0:e0].any(1) for b0, e0 in self.begin_ends], dim=1)                # (R, S)
+        fcs = torch.where(per_scale.any(1), per_scale.to(torch.int64).argmax(1), torch.full((R,), S, dtype=torch.int64, device=dev))
+        return CounterfactualResult(None if img is None else img.view(B, K, *img.shape[1:]), tok.view(B, K, self.L), changed.view(B, K, self.L),
+                                    fcs.view(B, K), noise.logp_src, noise.unreachable, self._record(img, tok, st), noise, self.patch_nums)
 
     @torch.no_grad()
     def sample_best_of(self, label_B, g_seeds, n: Optional[int] = None, by: str = 'logp_cond', cfg=1.5, top_k=0, top_p=0.0, max_images: int = 64):
