@@ -886,6 +886,40 @@ int varhip_token_lens_f32(const float* logits, const float* final_logits, const 
 int varhip_token_lens_host_f32(const float* logits, const float* final_logits, const int64_t* gt, int64_t ld_gt, int R, int l, int V,
                                float* nll, float* entropy, float* kl, int64_t* pred, int32_t* rank, int64_t ld_out);
 
+/* ---- activation patching (VAR.patch_effects): ablate or replace column ranges of an activation matrix, in place ---------------------------------
+ * act: [rows * l][ld] fp32, row r, token t at (r * l + t) * ld; only columns below `width` are ever touched (ld > width: the padding stays).
+ * It is the attention output in front of proj (width C, head h at columns 64 h .. 64 h + 63) or the MLP hidden activation behind the GELU
+ * (width hidden).  dir: a DEVICE array (the host twin: a host array) of n_dir directives of four int32 (row, c0, c1, src); a directive
+ * rewrites act[row][t][c0 .. c1 - 1] for every token t of the row:
+ *   src == -1   +0.0f
+ *   src == -2   the column's mean over the row's l tokens, m_c = s / (float)l: s is the fp32 sum of act[row][t][c] in ascending t, one
+ *               rounding per add, starting from the t = 0 element; the division is one correctly rounded fp32 division.  l == 1: the bits stay.
+ *   src >= 0    act[src][t][c], token by token; no directive of the same launch may write those columns of row src (the caller's duty).
+ * A directive is skipped whole, and writes nothing, where row is outside [0, rows), src is outside [-2, rows), c0 < 0, c1 > width, c0 >= c1,
+ * or c0 or c1 is no multiple of 4.  Directives of one launch that name the same row have disjoint column ranges (the caller's duty).
+ * n_dir == 0: success without a launch (dir may be NULL).  VARHIP_EINVAL before any launch, nothing written: n_dir < 0, a NULL operand with
+ * n_dir > 0, rows, l or width < 1, ld < width, ld % 4 != 0, act not 16-byte aligned, width above 2^22.
+ * A bandwidth kernel: 16-byte loads and stores, the lanes of a wave on consecutive column groups, no LDS; the one lane that owns a column
+ * group of a mean directive walks t, so the sum has one order. */
+/* pinned bit for bit against its host twin (tests/test_patch_kernels_gpu.py) */
+int varhip_act_patch_f32(float* act, int64_t ld, int rows, int l, int width, const int32_t* dir, int n_dir, varhip_stream_t stream);
+/* the host twin: plain host code (no GPU), host pointers, the directives one after the other: the kernel's bits (a NaN's payload aside) */
+/* pinned against the numpy restatement tests/patchref.py (tests/test_patch_cpu.py) */
+int varhip_act_patch_host_f32(float* act, int64_t ld, int rows, int l, int width, const int32_t* dir, int n_dir);
+/* varhip_adaln_block_f32 with interventions: the same seven launches, varhip_act_patch_f32(att, C, B2, l, C, dir_att, n_att) between attention
+ * and proj, varhip_act_patch_f32(hid, hidden, B2, l, hidden, dir_hid, n_hid) between fc1 and fc2.  An empty table launches nothing:
+ * n_att == n_hid == 0 issues exactly the seven launches and leaves varhip_adaln_block_f32's bits.  VARHIP_EINVAL before any launch: what
+ * varhip_adaln_block_f32 refuses, a negative count, a non-empty table that is NULL or whose matrix is NULL or not 16-byte aligned,
+ * n_hid > 0 with hidden % 4 != 0.  f32 only. */
+/* pinned bit for bit against varhip_adaln_block_f32 (tests/test_patch_kernels_gpu.py) and against weight surgery (tests/test_patch_effects_gpu.py) */
+int varhip_adaln_block_patched_f32(float* x, float* x2, float* xn, float* q, float* att, float* hid,
+                                   const float* ada, int64_t ld_ada,
+                                   const float* qkv_w, const float* qkv_b, const float* scale_mul, float plain_scale, int l2norm,
+                                   const float* proj_w, const float* proj_b, const float* fc1_w, const float* fc1_b,
+                                   const float* fc2_w, const float* fc2_b, float* kcache, float* vcache,
+                                   int B2, int l, int C, int H, int hidden, int pos0, int Lmax, float eps,
+                                   const int32_t* dir_att, int n_att, const int32_t* dir_hid, int n_hid, varhip_stream_t stream);
+
 /* ==== 16-bit-input throughput mode ("f16") ===================================================================
  * The reference's harness runs the path under torch.autocast('cuda', dtype=torch.float16) (demo_sample.py:66-68): every F.linear of
  * basic_var.py then computes in fp16 and attention takes the flash path with fp16 q/k/v (basic_var.py:97,113).  These entry points are

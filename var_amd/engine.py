@@ -1198,6 +1198,15 @@ class SamplingEngine(_Engine):
                  gw['fc1_w'], blk['fc1_b'], gw['fc2_w'], blk['fc2_b'], ws['kc'][bi], ws['vc'][bi],
                  rows, l, C, var.num_heads, blk['fc1_w'].shape[0], cur, Lmax, var.norm_eps)
 
+    def block_patched(self, blk, ws, bi, x, x2, rows, l, cur, Lmax: int, dir_att, n_att: int, dir_hid, n_hid: int):
+        """block() in f32 with interventions (varhip_adaln_block_patched_f32): dir_att / dir_hid, device tables of n_att / n_hid directives
+        (row, c0, c1, src) on the attention output in front of proj and on the MLP hidden activation behind the GELU"""
+        var = self.var
+        hip.call('adaln_block_patched_f32', x, x2, ws['xn'], ws['q'], ws['att'], ws['hid'], ws['ada_view'][bi][0], ws['ada_view'][bi][1],
+                 blk['qkv_w'], blk['qkv_b'], blk['smul'], blk['plain_scale'], int(blk['l2']), blk['proj_w'], blk['proj_b'],
+                 blk['fc1_w'], blk['fc1_b'], blk['fc2_w'], blk['fc2_b'], ws['kc'][bi], ws['vc'][bi],
+                 rows, l, var.C, var.num_heads, blk['fc1_w'].shape[0], cur, Lmax, var.norm_eps, dir_att, n_att, dir_hid, n_hid)
+
     def head(self, x, hn, xn, logits, M, l):
         """get_logits (var.py:118-124): AdaLNBeforeHead (LayerNorm + scale/shift) then the vocabulary projection -> fp32 logits"""
         var, w = self.var, self.w
@@ -2141,12 +2150,13 @@ class SamplingEngine(_Engine):
             R = min(rpp, N - i0)
             yield SimpleNamespace(ws=ws, i0=i0, R=R, lab=lab[i0:i0 + R].contiguous(), xin=None if xin is None else xin[i0:i0 + R].contiguous())
 
-    def _tf_pass(self, p, last: Optional[int] = None, done: int = -1, head=None, after_block=None):
+    def _tf_pass(self, p, last: Optional[int] = None, done: int = -1, head=None, after_block=None, block=None):
         """one teacher-forced pass: the p.R rows of labels p.lab and next-scale inputs p.xin (R, >= L_e - first_l, Cvae) through scale `last`
         (default: the last; p.ws must reach it).  head(p, si, cur, l) runs after the head of each scale si > done has left that scale's fp32
         logits in p.ws['lg'][:R * l] (row r, token t at r * l + t); the scales up to `done` only fill the KV caches, and without `head` no
         scale runs a head.  after_block(p, bi, si, cur, l), if given, runs right behind every block: p.ws['q'] then holds that block's queries
-        [R * l][C], normalised and scaled, p.ws['kc'][bi] the keys 0 .. cur + l - 1"""
+        [R * l][C], normalised and scaled, p.ws['kc'][bi] the keys 0 .. cur + l - 1.  block(p, blk, bi, si, cur, l), if given, runs every block in
+        place of self.block (patch_effects: the block with its interventions)"""
         var, w, ws, R = self.var, self.w, p.ws, p.R
         C, Cv = var.C, var.Cvae
         self._prologue(ws, p.lab, R)
@@ -2158,7 +2168,10 @@ class SamplingEngine(_Engine):
                 seg = p.xin[:, cur - var.first_l:cur - var.first_l + l].contiguous()
                 hip.call('word_embed_f32', seg, w['word_w'], w['word_b'], ws['lvl_pos'][cur:], x, R, l, C, Cv)
             for bi, blk in enumerate(w['blocks']):
-                self.block(blk, ws, bi, x, x2, R, l, cur, ws['Lmax'])
+                if block is None:
+                    self.block(blk, ws, bi, x, x2, R, l, cur, ws['Lmax'])
+                else:
+                    block(p, blk, bi, si, cur, l)
                 if after_block is not None:
                     after_block(p, bi, si, cur, l)
             if head is not None and si > done:
@@ -2431,6 +2444,93 @@ class SamplingEngine(_Engine):
                 stash = torch.empty(max(Dn - (final in slot), 1), M, C, dtype=torch.float32, device=dev)
                 lg2 = torch.empty(M, V, dtype=torch.float32, device=dev)
             self._tf_pass(p, head=head, after_block=keep)
+        return out
+
+    # -- head / MLP ablation and activation patching (VAR.patch_effects) ----------------------------------------------------------------
+    PATCH_SRC = dict(zero=-1, mean=-2)                 # the `src` of varhip_act_patch_f32's directives; 'donor': the donor row's index
+
+    @torch.no_grad()
+    def patch_effects(self, gt_tokens: torch.Tensor, label_N: torch.Tensor, sites: tuple, mode: str, donor_N: Optional[torch.Tensor], scales: tuple,
+                      max_rows: int, _tap=None) -> dict:
+        """VAR.patch_effects on the HIP path -> dict(nll, entropy, kl (N, P + 1, L) fp32, pred int64, rank int32), index 0 the clean row.
+        gt_tokens (N, L) int64, label_N (N,) int64; sites: P entries, each a tuple of elementary sites ('att' | 'hid', block, c0, c1); mode
+        'zero' | 'mean' | 'donor' with donor_N (N,) int64 labels; scales: the scale indices at which the interventions apply, ascending; all
+        validated by the caller.  The rows of a pass are image-major: per image the donor row (mode 'donor': the image's tokens under its
+        donor label), the clean row, then one row per site.  Images whose rows fit max_rows share passes; otherwise an image's sites are chunked
+        over passes, each with its own clean (and donor) row, as token_scores chunks classes.  The directives of every block are built on the
+        host and uploaded once per pass layout (image count, site chunk); a block with directives at an active scale runs
+        varhip_adaln_block_patched_f32, every other block self.block.  Behind each scale's head the clean row of every row's image is
+        gathered into a second logits buffer and varhip_token_lens_f32 reduces (row, its clean row): no (rows, L, V) tensor exists at any
+        time, and the tables, the second buffer and the per-pass outputs live for the call only.  _tap (tests): called after a stream sync
+        with clones of the scale's logits, of the gathered clean rows, the pass's (image, slot) per row (slot -1: the donor row, 0: the clean
+        row, j + 1: site j) and (si, cur, l)."""
+        var = self.var
+        tf = self._tf_begin(torch.stack((label_N, label_N if donor_N is None else donor_N), 1), gt_tokens,
+                            'patch_effects runs in f32: the {} workspaces hold 16-bit activations', lambda tf: self._check_labels(tf.lab))
+        dev, gt = tf.dev, tf.gt
+        L, V, C, S = var.L, var.V, var.C, len(var.patch_nums)
+        N, P = gt.shape[0], len(sites)
+        d = 1 if mode == 'donor' else 0
+        keys = ('nll', 'entropy', 'kl', 'pred', 'rank')
+        dts = (torch.float32, torch.float32, torch.float32, torch.int64, torch.int32)
+        out = {k: torch.empty(N, P + 1, L, dtype=dt, device=dev) for k, dt in zip(keys, dts)}
+        if d + 1 + P <= max_rows:
+            ipp, spp = max(1, max_rows // (d + 1 + P)), P                # whole images per pass
+        else:
+            ipp, spp = 1, max_rows - d - 1                               # one image per pass, its sites in chunks
+        passes = [(i0, min(ipp, N - i0), j0, min(spp, P - j0)) for i0 in range(0, N, ipp) for j0 in range(0, P, spp)]
+        Rmax = max(ni * (d + 1 + nj) for _, ni, _, nj in passes)
+        ws = self._tf_workspace(Rmax)                                    # sized once: a shorter pass uses a prefix
+        lg2 = torch.empty(Rmax * var.patch_nums[-1] ** 2, V, dtype=torch.float32, device=dev)
+        res = [torch.empty(Rmax, L, dtype=dt, device=dev) for dt in dts]
+        active = set(scales)
+        layouts = {}
+
+        def layout(ni, j0, nj):
+            """the rows of a pass of ni images with the sites j0 .. j0 + nj: (image, slot) per row, each row's clean row, and per block the
+            device tables of the attention and the hidden directives; built once, one upload"""
+            if (ni, j0, nj) not in layouts:
+                per = d + 1 + nj
+                rows = [(i, s) for i in range(ni) for s in ([-1] * d + [0] + list(range(j0 + 1, j0 + nj + 1)))]
+                tabs = {}
+                for i in range(ni):
+                    src = i * per if d else self.PATCH_SRC[mode]
+                    for j in range(nj):
+                        for kind, bi, c0, c1 in sites[j0 + j]:
+                            tabs.setdefault((bi, kind), []).extend((i * per + d + 1 + j, c0, c1, src))
+                flat, where = [], {}
+                for key, t in tabs.items():
+                    where[key] = (len(flat), len(t) // 4)
+                    flat.extend(t)
+                table = torch.tensor(flat or [0], dtype=torch.int32).to(dev)
+                views = {key: (table[o:], n) for key, (o, n) in where.items()}
+                layouts[(ni, j0, nj)] = SimpleNamespace(rows=rows, views=views, blocks={bi for bi, _ in tabs},
+                                                        clean=torch.tensor([i * per + d for i, _ in rows], dtype=torch.int64).to(dev))
+            return layouts[(ni, j0, nj)]
+
+        def block(p, blk, bi, si, cur, l):
+            if si not in active or bi not in p.lay.blocks:
+                return self.block(blk, p.ws, bi, p.ws['x'], p.ws['x2'], p.R, l, cur, p.ws['Lmax'])
+            a, h = p.lay.views.get((bi, 'att'), (None, 0)), p.lay.views.get((bi, 'hid'), (None, 0))
+            self.block_patched(blk, p.ws, bi, p.ws['x'], p.ws['x2'], p.R, l, cur, p.ws['Lmax'], a[0], a[1], h[0], h[1])
+
+        def head(p, si, cur, l):
+            R = p.R
+            torch.index_select(ws['lg'][:R * l].view(R, l * V), 0, p.lay.clean, out=lg2[:R * l].view(R, l * V))
+            hip.call('token_lens_f32', ws['lg'], lg2, p.gt[:, cur:], L, R, l, V, *[r[:, cur:] for r in res], L)
+            if _tap is not None:
+                torch.cuda.current_stream().synchronize()
+                _tap(ws['lg'][:R * l].clone(), lg2[:R * l].clone(), [(p.i0 + i, s) for i, s in p.lay.rows], (si, cur, l))
+        for i0, ni, j0, nj in passes:
+            lay = layout(ni, j0, nj)
+            img = torch.tensor([i0 + i for i, _ in lay.rows], dtype=torch.int64).to(dev)
+            slot = torch.tensor([s for _, s in lay.rows], dtype=torch.int64).to(dev)
+            lab = tf.lab[img, (slot < 0).to(torch.int64)].contiguous()            # the donor rows under the donor labels
+            self._tf_pass(SimpleNamespace(ws=ws, R=len(lay.rows), lab=lab, i0=i0, lay=lay, gt=gt.index_select(0, img),
+                                          xin=tf.xin.index_select(0, img).contiguous()), head=head, block=block)
+            keep = slot >= 0
+            for k, r in zip(keys, res):
+                out[k][img[keep], slot[keep]] = r[:len(lay.rows)][keep]
         return out
 
     # -- zero-shot classification with per-scale pruning (VAR.classify) -------------------------------------------------------------

@@ -131,6 +131,79 @@ def block_layers(layers, depth: int) -> tuple:
     return tuple(int(b) for b in layers)
 
 
+PATCH_MODES = ('zero', 'mean', 'donor')
+
+
+def _patch_site(site, depth: int, H: int) -> tuple:
+    """one elementary site of VAR.patch_effects, checked: ('head', layer, head) | ('attn', layer) | ('mlp', layer)"""
+    forms = "('head', layer, head), ('attn', layer) or ('mlp', layer)"
+    if not isinstance(site, (tuple, list)) or not site or site[0] not in ('head', 'attn', 'mlp') or len(site) != (3 if site[0] == 'head' else 2):
+        raise ValueError(f'sites: {site!r} is not {forms}')
+    if not is_int(site[1]) or not 0 <= site[1] < depth:
+        raise ValueError(f'sites: {tuple(site)!r}: the layer must be an integer in [0, {depth})')
+    if site[0] == 'head' and (not is_int(site[2]) or not 0 <= site[2] < H):
+        raise ValueError(f'sites: {tuple(site)!r}: the head must be an integer in [0, {H})')
+    return (site[0],) + tuple(int(v) for v in site[1:])
+
+
+def patch_sites(sites, depth: int, H: int) -> tuple:
+    """the `sites` of VAR.patch_effects -> a tuple of entries, each a tuple of elementary sites applied together in one row.  None: every
+    head, every 'attn' and every 'mlp' of the model, in that order; an entry is an elementary site or a non-empty sequence of them, which
+    may not name a column twice (a site twice, or a head beside the 'attn' of its layer)"""
+    if sites is None:
+        return tuple((('head', b, h),) for b in range(depth) for h in range(H)) + tuple((('attn', b),) for b in range(depth)) \
+            + tuple((('mlp', b),) for b in range(depth))
+    if isinstance(sites, (str, bytes, dict)) or not hasattr(sites, '__iter__'):
+        raise ValueError('sites must be None or a sequence of sites')
+    out = []
+    for entry in sites:
+        if isinstance(entry, (tuple, list)) and entry and isinstance(entry[0], str):
+            entry = (entry,)
+        if not isinstance(entry, (tuple, list)) or not entry:
+            raise ValueError(f'sites: {entry!r} is neither a site nor a non-empty tuple of sites')
+        group = tuple(_patch_site(e, depth, H) for e in entry)
+        for i, e in enumerate(group):
+            for f in group[:i]:
+                if e == f or (e[1] == f[1] and {e[0], f[0]} == {'head', 'attn'}):
+                    raise ValueError(f'sites: {e!r} and {f!r} of one entry name the same columns')
+        out.append(group)
+    if not out:
+        raise ValueError('sites must be None or hold at least one site')
+    return tuple(out)
+
+
+def patch_columns(sites: tuple, C: int, hidden: int) -> tuple:
+    """normalised sites -> per entry the column ranges (matrix 'att' | 'hid', layer, c0, c1) of varhip_act_patch_f32's directives: a head's 64
+    columns of the attention output in front of proj, all C of them, or the whole MLP hidden activation"""
+    col = lambda e: ('att', e[1], 64 * e[2], 64 * e[2] + 64) if e[0] == 'head' else ('att', e[1], 0, C) if e[0] == 'attn' else ('hid', e[1], 0, hidden)
+    return tuple(tuple(col(e) for e in group) for group in sites)
+
+
+def patch_scales(scales, S: int) -> tuple:
+    """the `scales` of VAR.patch_effects -> the scale indices at which the interventions apply, ascending: None means every scale"""
+    if scales is None:
+        return tuple(range(S))
+    try:
+        scales = tuple(scales)
+    except TypeError:
+        raise ValueError('scales must be None or a sequence of scale indices') from None
+    if not scales or not all(is_int(s) and 0 <= s < S for s in scales) or len(set(scales)) != len(scales):
+        raise ValueError(f'scales must be None or distinct scale indices in [0, {S}), got {scales!r}')
+    return tuple(sorted(int(s) for s in scales))
+
+
+def patch_mode(mode, donor_label, N: int, max_rows) -> tuple:
+    """mode, donor_label and max_rows of VAR.patch_effects -> (mode, donor labels (N,) integer tensor or None, max_rows)"""
+    if mode not in PATCH_MODES:
+        raise ValueError(f'mode must be one of {PATCH_MODES}, got {mode!r}')
+    if (mode == 'donor') != (donor_label is not None):
+        raise ValueError("donor_label goes with mode='donor', and only with it")
+    donor = None if donor_label is None else labels_1d(donor_label, N, f'donor_label must be an int or (N,) integer class ids, N = {N}', scalar=True)
+    least = 2 + (mode == 'donor')
+    what = 'the donor row, the clean row and one site row' if mode == 'donor' else 'the clean row and one site row'
+    return mode, donor, integer(max_rows, f'max_rows must be an integer >= {least}: {what}', least)
+
+
 def cfg_arg(cfg, name: str = 'cfg') -> float:
     """cfg / fill_cfg: whatever float() takes, a bool included (1.0 / 0.0), as in the per-image samplers"""
     return real(float(cfg) if isinstance(cfg, bool) else cfg, f'{name} must be finite and >= 0', lambda v: v >= 0, convert=True)

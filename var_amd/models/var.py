@@ -545,6 +545,127 @@ def logit_lens_torch(var, gt: torch.Tensor, label: torch.Tensor, layers: tuple, 
     return tuple(torch.cat(f) for f in zip(*parts))
 
 
+class PatchEffects:
+    """VAR.patch_effects' result: what an image's prediction loses when a head, an attention layer or an MLP is ablated or patched, per token,
+    on the model's device.  Index 0 of the second axis is the clean row, index j + 1 the row with the intervention sites[j]; with z the row's
+    fp32 logits, p their softmax and pc the clean row's softmax:
+      nll      (N, P + 1, L) fp32   -log p[gt]                       (index 0: VAR.evaluate's nll_BL)
+      entropy  (N, P + 1, L) fp32   -sum_v p_v log p_v, in nats
+      kl       (N, P + 1, L) fp32   KL(pc || p) = sum_v pc_v (log pc_v - log p_v); exactly 0 at index 0
+      pred     (N, P + 1, L) int64  argmax z;  rank (N, P + 1, L) int32: |{v : z_v > z_gt or (z_v == z_gt and v < gt)}|
+      sites: the P entries, each a tuple of elementary sites ('head', layer, head) | ('attn', layer) | ('mlp', layer); mode, scales (the
+      scale indices at which the interventions applied), patch_nums (the scales the result covers), depth and num_heads of the model
+    The methods run in PyTorch with float64 sums."""
+    __slots__ = ('sites', 'mode', 'scales', 'nll', 'entropy', 'kl', 'pred', 'rank', 'patch_nums', 'depth', 'num_heads')
+
+    def __init__(self, sites, mode, scales, nll, entropy, kl, pred, rank, patch_nums, depth, num_heads):
+        self.sites, self.mode, self.scales, self.patch_nums = tuple(sites), mode, tuple(scales), tuple(patch_nums)
+        self.nll, self.entropy, self.kl, self.pred, self.rank = nll, entropy, kl, pred, rank
+        self.depth, self.num_heads = int(depth), int(num_heads)
+
+    def effect(self) -> torch.Tensor:
+        """(N, P, L) fp32: the loss a site's intervention adds, nll[:, 1:] - nll[:, :1]"""
+        return self.nll[:, 1:] - self.nll[:, :1]
+
+    def _scale_mean(self, x: torch.Tensor) -> torch.Tensor:
+        """x (N, P, L) -> (P, S) float64: the mean over the images and the tokens of each scale"""
+        out, b = [], 0
+        for pn in self.patch_nums:
+            out.append(x[..., b:b + pn * pn].double().mean(dim=(0, 2)))
+            b += pn * pn
+        return torch.stack(out, -1)
+
+    def per_scale(self) -> dict:
+        """{'effect', 'kl'}: (P, S) float64 means per site and scale"""
+        return dict(effect=self._scale_mean(self.effect()), kl=self._scale_mean(self.kl[:, 1:]))
+
+    def head_matrix(self) -> torch.Tensor:
+        """(depth, H) float64: the mean effect of every site that is one single head, NaN where a head was not asked for (a head asked for
+        more than once: its last entry)"""
+        m = torch.full((self.depth, self.num_heads), float('nan'), dtype=torch.float64, device=self.nll.device)
+        mean = self.effect().double().mean(dim=(0, 2))
+        for j, group in enumerate(self.sites):
+            if len(group) == 1 and group[0][0] == 'head':
+                m[group[0][1], group[0][2]] = mean[j]
+        return m
+
+    def __repr__(self):
+        N, P1, L = self.nll.shape
+        return f'PatchEffects(images={N}, sites={P1 - 1}, mode={self.mode!r}, tokens={L})'
+
+
+def patch_effects_torch(var, gt: torch.Tensor, label: torch.Tensor, columns: tuple, mode: str, donor: Optional[torch.Tensor], scales: tuple, _tap=None):
+    """VAR.patch_effects' definitions in PyTorch on the module stack (CPU models, train mode, prog_si >= 0; the arithmetic follows the parameters'
+    dtype): one masked teacher-forced pass per row, a manual block loop that rewrites the attention output in front of proj and the MLP hidden
+    activation behind the GELU.  gt (N, L) tokens, label (N,) labels, columns: per site the (matrix 'att' | 'hid', block, c0, c1) ranges
+    (args.patch_columns), donor (N,) labels or None, scales: the scale indices at which the interventions apply -> (nll, entropy, kl float64,
+    pred int64, rank int32), each (N, P + 1, ed) with ed the tokens the pass covers.  'zero' writes 0, 'mean' the mean over the tokens of the
+    scale (per scale, row and column), 'donor' the activation of a pass on the same tokens under the donor label.  Every row is a pass of its
+    own with batch size 1, so a row's values do not depend on its neighbours; dropout and drop path are not applied (the deterministic pass).
+    _tap (tests): called with (image, row index, the row's logits (ed, V)) for every row."""
+    F = torch.nn.functional
+    ed = var.begin_ends[var.prog_si][1] if var.prog_si >= 0 else var.L
+    dt = var.pos_start.dtype
+    mask = var.attn_bias_for_masking[:, :, :ed, :ed].to(dt)
+    spans = [var.begin_ends[si] for si in scales if var.begin_ends[si][1] <= ed]
+    x_in = lambda n: var.vae_proxy[0].quantize.idxBl_to_var_input([gt[n:n + 1, b:e] for b, e in var.begin_ends])[:, :ed - var.first_l].to(dt)
+
+    def run(n, lab, group, acts, record):
+        """the logits (ed, V) of image n under label lab with the column ranges of `group` rewritten; record: keep every activation in acts"""
+        todo = {}
+        for kind, bi, c0, c1 in group:
+            todo.setdefault((bi, kind), []).append((c0, c1))
+
+        def rewrite(a, key):
+            if record:
+                acts[key] = a
+            if key not in todo:
+                return a
+            a = a.clone()
+            for c0, c1 in todo[key]:
+                for b, e in spans:
+                    a[:, b:e, c0:c1] = 0 if mode == 'zero' else a[:, b:e, c0:c1].mean(1, keepdim=True) if mode == 'mean' else acts[key][:, b:e, c0:c1]
+            return a
+        cond = var.class_emb(lab.view(1))
+        sos = cond.unsqueeze(1).expand(1, var.first_l, -1) + var.pos_start.expand(1, var.first_l, -1)
+        x = torch.cat((sos, var.word_embed(xs[n])), dim=1) if ed > var.first_l else sos
+        x = x + var.lvl_embed(var.lvl_1L[:, :ed].expand(1, -1)) + var.pos_1LC[:, :ed]
+        cond_or_gss = var.shared_ada_lin(cond)
+        for bi, blk in enumerate(var.blocks):
+            at = blk.attn
+            gamma1, gamma2, scale1, scale2, shift1, shift2 = blk._six(cond_or_gss)
+            q, k, v = at._heads(blk.ln_wo_grad(x) * (scale1 + 1) + shift1)
+            if at.attn_l2_norm:
+                q, k = F.normalize(q, dim=-1) * at.scale_mul_1H11.clamp_max(at.max_scale_mul).exp(), F.normalize(k, dim=-1)
+            ctx = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, scale=at.scale).transpose(1, 2).reshape(1, ed, var.C)
+            x = x + at.proj(rewrite(ctx, (bi, 'att'))) * gamma1
+            hid = blk.ffn.act(blk.ffn.fc1(blk.ln_wo_grad(x) * (scale2 + 1) + shift2))
+            x = x + blk.ffn.fc2(rewrite(hid, (bi, 'hid'))) * gamma2
+        return var.head(var.head_nm(x, cond))[0]
+
+    zero = torch.zeros((), dtype=torch.float64, device=gt.device)
+    rows, xs = [], {}
+    for n in range(gt.shape[0]):
+        acts = {}
+        xs = {n: x_in(n)}                                       # (an image's input on its own: the interpolation is not batch-invariant either)
+        if mode == 'donor':
+            run(n, donor[n], (), acts, True)
+        g = gt[n, :ed]
+        per, lpc = [], None
+        for group in ((),) + tuple(columns):
+            z = run(n, label[n], group, acts, False)
+            if _tap is not None:
+                _tap(n, len(per), z)
+            lp = torch.log_softmax(z.double(), dim=-1)
+            lpc = lp if lpc is None else lpc
+            p, pc = lp.exp(), lpc.exp()
+            _, _, pred, rank = token_eval_torch(z.float().unsqueeze(0), g.unsqueeze(0))
+            per.append((-lp.gather(-1, g.unsqueeze(-1)).squeeze(-1), -torch.where(p > 0, p * lp, zero).sum(-1),
+                        torch.where(pc > 0, pc * (lpc - lp), zero).sum(-1), pred[0], rank[0]))
+        rows.append(tuple(torch.stack(f) for f in zip(*per)))
+    return tuple(torch.stack(f) for f in zip(*rows))
+
+
 class EvidenceMaps:
     """VAR.evidence_maps' result: where in the image the evidence for each class sits.  With m[n, k, y, x] the map of class k (the selected
     scales' per-token scores, each resampled bilinearly to size x size and weighted by its share of the selected tokens):
@@ -1662,6 +1783,46 @@ class VAR(nn.Module):
             return LogitLens(layers, r['nll'], r['entropy'], r['kl'], r['pred'], r['rank'], self.patch_nums)
         nsc = self.prog_si + 1 if self.prog_si >= 0 else len(self.patch_nums)
         return LogitLens(layers, *logit_lens_torch(self, gt, lab, layers, int(max_rows)), self.patch_nums[:nsc])
+
+    @torch.no_grad()
+    def patch_effects(self, gt_tokens, label, sites=None, *, mode: str = 'mean', donor_label=None, scales=None, max_rows: int = 64) -> PatchEffects:
+        """Which heads and MLPs an image's prediction depends on -> PatchEffects (per-token values; see there).
+
+        Ablation and activation patching: per site one teacher-forced row in which the site's activation is replaced, compared with the clean
+        row of the same image.  An elementary site is ('head', layer, head): that head's 64 columns of the attention output in front of proj
+        (reference basic_var.py:117-119); ('attn', layer): all heads of the layer; ('mlp', layer): the MLP hidden activation behind the GELU,
+        what fc2 reads.  An entry of `sites` is an elementary site or a tuple of them applied together in one row (a group of heads, a head
+        and an MLP); None: every head, every 'attn' and every 'mlp' of the model, in that order.  mode 'zero' writes 0; 'mean' the mean over
+        the tokens of the scale, per row and column; 'donor' the activation of the same tokens under donor_label (an int or (N,) class ids in
+        [0, num_classes]; num_classes: the unconditional row), which shows through which sites the class reaches the tokens.  scales: None
+        (the interventions apply at every scale) or the scale indices at which they apply while that scale is the query scale; later scales
+        then see their effect through the keys and values.  gt_tokens: (N, L) integer tokens, teacher-forced as in evaluate; label: an int or
+        (N,) class ids in [0, num_classes], used as given; max_rows bounds the rows of one transformer pass (an image's clean row, its donor
+        row and at least one site row must fit), and no value depends on it.
+        On the HIP path (the conditions of token_log_likelihood; f32 only: under a 16-bit precision ValueError) the rows of a sweep are ordinary
+        rows of ordinary passes: varhip_act_patch_f32 rewrites the activation between two launches of the block, varhip_token_lens_f32 reduces
+        every row against its image's clean row behind each scale's head, and no logits tensor is made; the clean row's nll / pred / rank are
+        evaluate's bit for bit.  Elsewhere patch_effects_torch runs the same definitions on the module stack, one pass per row (with prog_si
+        >= 0 over the scales 0 .. prog_si)."""
+        dev = self.lvl_1L.device
+        gt = self._token_shape(gt_tokens)
+        N = gt.shape[0]
+        lab = A.labels_1d(label, N, f'label must be an int or (N,) integer class ids, N = {N}', scalar=True)
+        sites = A.patch_sites(sites, self.depth, self.num_heads)
+        mode, donor, max_rows = A.patch_mode(mode, donor_label, N, max_rows)
+        scales = A.patch_scales(scales, len(self.patch_nums))
+        self._token_label_range(gt, lab)
+        if donor is not None:
+            A.in_range(donor, self.num_classes, f'donor_label must lie in [0, {self.num_classes}]')
+            donor = donor.to(dev, torch.int64)
+        gt, lab = gt.to(dev, torch.int64), lab.to(dev, torch.int64)
+        columns = A.patch_columns(sites, self.C, self.blocks[0].ffn.fc1.weight.shape[0])
+        if self._scoring_on_hip(gt):
+            r = self.engine().patch_effects(gt, lab, columns, mode, donor, scales, max_rows)
+            return PatchEffects(sites, mode, scales, r['nll'], r['entropy'], r['kl'], r['pred'], r['rank'], self.patch_nums, self.depth, self.num_heads)
+        nsc = self.prog_si + 1 if self.prog_si >= 0 else len(self.patch_nums)
+        nll, ent, kl, pred, rank = patch_effects_torch(self, gt, lab, columns, mode, donor, scales)
+        return PatchEffects(sites, mode, scales, nll.float(), ent.float(), kl.float(), pred, rank, self.patch_nums[:nsc], self.depth, self.num_heads)
 
     @staticmethod
     def _prior_arg(prior, N: int, K: int) -> torch.Tensor:
