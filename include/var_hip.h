@@ -409,7 +409,8 @@ int varhip_upconv_phase_gn_f32(const float* in, const float* w_phase, const floa
                                int B, int H, int W, int Cin, int Cout, varhip_stream_t stream);
 
 /* GroupNorm statistics: stats[b][g] = {mean, rstd} over (HW, C/G) with biased variance (basic_vae.py:18-19, eps 1e-6).
- * scratch: caller-provided, at least varhip_gn_scratch_elems(B,HW,C,G) doubles. */
+ * scratch: caller-provided, at least varhip_gn_scratch_elems(B,HW,C,G) doubles.  C % 4 == 0, C <= 1024 (fp32; the 16-bit forms: C % 8 == 0,
+ * C <= 2048), G divides C, any HW.  A null x, stats, scratch (gamma, beta, out for the apply) is VARHIP_EINVAL. */
 int64_t varhip_gn_scratch_elems(int B, int HW, int C, int G);
 int varhip_gn_stats_f32(const float* x, float* stats, double* scratch, int B, int HW, int C, int G, float eps, varhip_stream_t stream);
 /* out = ((x - mean) * rstd) * gamma[c] + beta[c], then SiLU if silu != 0   (basic_vae.py:58,59,74,225) */

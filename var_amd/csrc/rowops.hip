@@ -265,7 +265,7 @@ extern "C" int64_t varhip_gn_scratch_elems(int B, int HW, int C, int G) {
     return (int64_t)B * ((HW + GN_PIX - 1) / GN_PIX) * G * 2;
 }
 extern "C" int varhip_gn_stats_f32(const float* x, float* stats, double* scratch, int B, int HW, int C, int G, float eps, varhip_stream_t stream) {
-    if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || !scratch || (C & 3) || C > 1024 || ((uintptr_t)x & 15)) return VARHIP_EINVAL;
+    if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || !x || !stats || !scratch || (C & 3) || C > 1024 || ((uintptr_t)x & 15)) return VARHIP_EINVAL;
     const int nchunk = (HW + GN_PIX - 1) / GN_PIX;
     VhScope sc(VH_FAM_GN, (hipStream_t)stream, 0, 4.0 * B * (double)HW * C);
     const size_t lds = (size_t)(256 / (C / 4)) * C * 2 * sizeof(double);
@@ -296,7 +296,7 @@ __global__ void __launch_bounds__(64) k_gn_final_part(const double* __restrict__
     }
 }
 extern "C" int varhip_gn_stats_part_f32(const double* part, float* stats, int B, int nblk, int HW, int C, int G, float eps, varhip_stream_t stream) {
-    if (B <= 0 || nblk <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || !part) return VARHIP_EINVAL;
+    if (B <= 0 || nblk <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || !part || !stats) return VARHIP_EINVAL;
     VhScope sc(VH_FAM_GN, (hipStream_t)stream, 0, 16.0 * B * (double)nblk * C);
     hipLaunchKernelGGL(k_gn_final_part, dim3(B * G), dim3(64), 0, (hipStream_t)stream, part, stats, G, nblk, C, (double)HW * (C / G), eps);
     return vh_launch_status();
@@ -369,6 +369,7 @@ __global__ void __launch_bounds__(256) k_gn_apply(const float* __restrict__ x, c
 extern "C" int varhip_gn_apply_f32(const float* x, const float* stats, const float* gamma, const float* beta, float* out,
                                    int B, int HW, int C, int G, int silu, varhip_stream_t stream) {
     if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || (C & 3) || C > 1024) return VARHIP_EINVAL;
+    if (!x || !stats || !gamma || !beta || !out) return VARHIP_EINVAL;
     if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15) return VARHIP_EINVAL;
     VhScope sc(VH_FAM_GN, (hipStream_t)stream, 0, 8.0 * B * (double)HW * C);
     hipLaunchKernelGGL(k_gn_apply, dim3((HW + GN_PIX - 1) / GN_PIX, B), dim3(256), 0, (hipStream_t)stream, x, stats, gamma, beta, out, HW, C, G, silu);

@@ -80,7 +80,7 @@ __global__ void k_gn16_final(const double* __restrict__ scratch, float* __restri
 }
 // stats[b][g] = (mean, 1/sqrt(var + eps)); scratch: varhip_gn_scratch_elems(B, HW, C, G) doubles
 extern "C" int VH16_FN(gn_stats)(const void* x, float* stats, double* scratch, int B, int HW, int C, int G, float eps, varhip_stream_t stream) {
-    if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || !scratch || (C & 7) || C > 2048 || ((uintptr_t)x & 15)) return VARHIP_EINVAL;
+    if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || !x || !stats || !scratch || (C & 7) || C > 2048 || ((uintptr_t)x & 15)) return VARHIP_EINVAL;
     const int nchunk = (HW + GN16_PIX - 1) / GN16_PIX;
     VhScope sc(VH_FAM_GN, (hipStream_t)stream, 0, 2.0 * B * (double)HW * C);
     const size_t lds = (size_t)(256 / (C / 8)) * C * 2 * sizeof(double);
@@ -117,6 +117,7 @@ __global__ void __launch_bounds__(256) k_gn16_apply(const vh_e16* __restrict__ x
 extern "C" int VH16_FN(gn_apply)(const void* x, const float* stats, const float* gamma, const float* beta, void* out,
                                    int B, int HW, int C, int G, int silu, varhip_stream_t stream) {
     if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || (C % G) || (C & 7) || C > 2048) return VARHIP_EINVAL;
+    if (!x || !stats || !gamma || !beta || !out) return VARHIP_EINVAL;
     if (((uintptr_t)x | (uintptr_t)out) & 15) return VARHIP_EINVAL;
     VhScope sc(VH_FAM_GN, (hipStream_t)stream, 0, 4.0 * B * (double)HW * C);
     hipLaunchKernelGGL(k_gn16_apply, dim3((HW + GN16_PIX - 1) / GN16_PIX, B), dim3(256), 0, (hipStream_t)stream,
