@@ -24,6 +24,7 @@ import torch
 
 from . import hip
 from .abi import EPI_GELU, EPI_NONE, EPI_RESID
+from .workspace import Dims, allocate, cached, keep_precision, sampler_rows, workspace_spec
 
 
 def bicubic_taps(pn: int, P: int):
@@ -104,6 +105,22 @@ def compose_tables(cfg, weights, S: int) -> np.ndarray:
 STATS_FIELDS = ('logp_cond', 'logp_guided', 'logp_drawn', 'kept', 'entropy')
 
 
+def _stats_dtype(key: str) -> torch.dtype:
+    return torch.int32 if key == 'kept' else torch.float32
+
+
+def stats_record(shape: tuple, dev, fill: Optional[tuple] = None, fields: tuple = STATS_FIELDS) -> dict:
+    """{field: tensor of `shape`} for the sampler's statistics; fill: (the value of `kept`, the value of the others), default uninitialised"""
+    if fill is None:
+        return {key: torch.empty(shape, dtype=_stats_dtype(key), device=dev) for key in fields}
+    return {key: torch.full(shape, fill[0] if key == 'kept' else fill[1], dtype=_stats_dtype(key), device=dev) for key in fields}
+
+
+def pointer_table(tensors) -> torch.Tensor:
+    """the addresses of a list of device tensors as a host int64 array (the launcher that takes it copies it)"""
+    return torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64)
+
+
 def phi_index(si: int, S: int, K: int) -> int:
     """which shared Phi conv serves scale si (reference quant.py:218-226)"""
     ticks = np.linspace(1 / 3 / K, 1 - 1 / 3 / K, K) if K == 4 else np.linspace(1 / 2 / K, 1 - 1 / 2 / K, K)
@@ -112,6 +129,20 @@ def phi_index(si: int, S: int, K: int) -> int:
 
 PRECISIONS = ('f32', 'f16', 'bf16')
 DT16 = {'f16': torch.float16, 'bf16': torch.bfloat16}      # storage type of the two 16-bit flavours (include/var_hip.h "f16" / "bf16")
+
+
+def gemm_nt(prec: str, A, W, bias, out, M: int, N: int, K: int, *, lda: int, ldw: int, ldo: int, epi: int = EPI_NONE, resid=None, ldr: int = 0,
+            gamma=None, ldg: int = 0, rpg: int = 1, bias_per_row: int = 0, batch: int = 1, sA: int = 0, sW: int = 0, sO: int = 0):
+    """out[M, N] = epi(A[M, K] . W[N, K]^T + bias), `batch` of them at element strides sA / sW / sO, on varhip_gemm_nt_<prec>: the one place that
+    knows the two argument orders.  The 16-bit entry points take A and W in `prec`, are told whether out and resid are 16-bit or fp32 (read
+    off the tensors here) and have no per-row bias"""
+    if prec == 'f32':
+        hip.call('gemm_nt_f32', A, lda, W, ldw, bias, out, ldo, M, N, K, epi, resid, ldr, gamma, ldg, rpg, bias_per_row, batch, sA, sW, sO)
+        return
+    if bias_per_row:
+        raise ValueError(f'varhip_gemm_nt_{prec} has no per-row bias')
+    hip.call('gemm_nt_' + prec, A, lda, W, ldw, bias, out, ldo, int(out.dtype != torch.float32), M, N, K, epi, resid, ldr,
+             int(resid is not None and resid.dtype != torch.float32), gamma, ldg, rpg, batch, sA, sW, sO)
 
 
 def _ver(p: torch.Tensor) -> int:
@@ -468,8 +499,7 @@ class _VaeOps(_Engine):
         N, K = wt.shape
         M = x2d.shape[0]
         out = torch.empty((M, N), dtype=torch.float32, device=x2d.device)
-        hip.call('gemm_nt_f32', x2d, K, wt, K, self.w[key + '.bias'], out, N, M, N, K, EPI_RESID if resid is not None else EPI_NONE,
-                 resid, N, None, 0, 1, 0, 1, 0, 0, 0)
+        gemm_nt('f32', x2d, wt, self.w[key + '.bias'], out, M, N, K, lda=K, ldw=K, ldo=N, epi=EPI_RESID if resid is not None else EPI_NONE, resid=resid, ldr=N)
         return out
 
     def resblock(self, x, pre, B, Hh, Ww):
@@ -485,17 +515,15 @@ class _VaeOps(_Engine):
         xn = self.gn(x, pre + '.norm', B, HW, False).view(B * HW, Cc)
         wqkv, bqkv = self.w[pre + '.qkv.weight'], self.w[pre + '.qkv.bias']
         qk = torch.empty((B * HW, 2 * Cc), dtype=torch.float32, device=dev)
-        hip.call('gemm_nt_f32', xn, Cc, wqkv, Cc, bqkv, qk, 2 * Cc, B * HW, 2 * Cc, Cc, EPI_NONE, None, 0, None, 0, 1, 0, 1, 0, 0, 0)
+        gemm_nt('f32', xn, wqkv, bqkv, qk, B * HW, 2 * Cc, Cc, lda=Cc, ldw=Cc, ldo=2 * Cc)
         vt = torch.empty((B, Cc, HW), dtype=torch.float32, device=dev)                   # V^T[b][c][j], bias per row (c)
-        hip.call('gemm_nt_f32', wqkv[2 * Cc:], Cc, xn, Cc, bqkv[2 * Cc:], vt, HW, Cc, HW, Cc, EPI_NONE, None, 0, None, 0, 1, 1,
-                 B, 0, HW * Cc, Cc * HW)
+        gemm_nt('f32', wqkv[2 * Cc:], xn, bqkv[2 * Cc:], vt, Cc, HW, Cc, lda=Cc, ldw=Cc, ldo=HW, bias_per_row=1, batch=B, sA=0, sW=HW * Cc, sO=Cc * HW)
         s = torch.empty((B, HW, HW), dtype=torch.float32, device=dev)
-        hip.call('gemm_nt_f32', qk, 2 * Cc, qk[:, Cc:], 2 * Cc, None, s, HW, HW, HW, Cc, EPI_NONE, None, 0, None, 0, 1, 0,
-                 B, HW * 2 * Cc, HW * 2 * Cc, HW * HW)
+        gemm_nt('f32', qk, qk[:, Cc:], None, s, HW, HW, Cc, lda=2 * Cc, ldw=2 * Cc, ldo=HW, batch=B, sA=HW * 2 * Cc, sW=HW * 2 * Cc, sO=HW * HW)
         p = torch.empty_like(s)
         hip.call('softmax_rows_f32', s, p, B * HW, HW, float(np.float32(int(Cc) ** (-0.5))))
         o = torch.empty((B * HW, Cc), dtype=torch.float32, device=dev)
-        hip.call('gemm_nt_f32', p, HW, vt, HW, None, o, Cc, HW, Cc, HW, EPI_NONE, None, 0, None, 0, 1, 0, B, HW * HW, Cc * HW, HW * Cc)
+        gemm_nt('f32', p, vt, None, o, HW, Cc, HW, lda=HW, ldw=HW, ldo=Cc, batch=B, sA=HW * HW, sW=Cc * HW, sO=HW * Cc)
         return self.lin(o, pre + '.proj_out', resid=x.view(B * HW, Cc)).view(B, Hh, Ww, Cc)
 
 
@@ -569,7 +597,7 @@ class _Ops16:
             wt = self.w16[pre + '.nin_shortcut.weight']
             N, K = wt.shape
             sc = torch.empty((B, Hh, Ww, N), dtype=self.dt, device=x.device)
-            hip.call('gemm_nt_' + self.fl, x, K, wt, K, self.w[pre + '.nin_shortcut.bias'], sc, N, 1, B * HW, N, K, EPI_NONE, None, 0, 0, None, 0, 1, 1, 0, 0, 0)
+            gemm_nt(self.fl, x, wt, self.w[pre + '.nin_shortcut.bias'], sc, B * HW, N, K, lda=K, ldw=K, ldo=N)
         return self.norm_conv(h, pre + '.norm2', pre + '.conv2', B, Hh, Ww, resid=sc)
 
     def attnblock(self, x, pre, B, Hh, Ww):
@@ -584,23 +612,22 @@ class _Ops16:
             return self._to16(self.eng.attnblock(x32, pre, B, Hh, Ww))
         xn = self.gn(x, pre + '.norm', B, HW, False).view(B * HW, Cc)
         wqkv, bqkv = self.w16[pre + '.qkv.weight'], self.w[pre + '.qkv.bias']
-        g16 = lambda A, lda, W, ldw, bias, out, ldo, o16, M, N, K, epi=EPI_NONE, resid=None, ldr=0, r16=0, batch=1, sA=0, sW=0, sO=0: \
-            hip.call('gemm_nt_' + self.fl, A, lda, W, ldw, bias, out, ldo, o16, M, N, K, epi, resid, ldr, r16, None, 0, 1, batch, sA, sW, sO)
         qk = torch.empty((B * HW, 2 * Cc), dtype=f16, device=dev)
-        g16(xn, Cc, wqkv, Cc, bqkv, qk, 2 * Cc, 1, B * HW, 2 * Cc, Cc)
+        gemm_nt(self.fl, xn, wqkv, bqkv, qk, B * HW, 2 * Cc, Cc, lda=Cc, ldw=Cc, ldo=2 * Cc)
         # V^T[b][c][j] WITHOUT its bias: the GEMM's bias is per column and here c is the row.  The rows of p sum to one, so the bias is added
         # to p.v instead (column c of that product) — equal up to the fp16 rounding of p (|sum p - 1| <= 1e-3, bias ~1e-2: 1e-5)
         vt = torch.empty((B, Cc, HW), dtype=f16, device=dev)
-        g16(wqkv[2 * Cc:], Cc, xn, Cc, None, vt, HW, 1, Cc, HW, Cc, batch=B, sA=0, sW=HW * Cc, sO=Cc * HW)
+        gemm_nt(self.fl, wqkv[2 * Cc:], xn, None, vt, Cc, HW, Cc, lda=Cc, ldw=Cc, ldo=HW, batch=B, sA=0, sW=HW * Cc, sO=Cc * HW)
         s = torch.empty((B, HW, HW), dtype=torch.float32, device=dev)
-        g16(qk, 2 * Cc, qk[:, Cc:], 2 * Cc, None, s, HW, 0, HW, HW, Cc, batch=B, sA=HW * 2 * Cc, sW=HW * 2 * Cc, sO=HW * HW)
+        gemm_nt(self.fl, qk, qk[:, Cc:], None, s, HW, HW, Cc, lda=2 * Cc, ldw=2 * Cc, ldo=HW, batch=B, sA=HW * 2 * Cc, sW=HW * 2 * Cc, sO=HW * HW)
         p32 = torch.empty_like(s)
         hip.call('softmax_rows_f32', s, p32, B * HW, HW, float(np.float32(int(Cc) ** (-0.5))))
         p = self._to16(p32)
         o = torch.empty((B * HW, Cc), dtype=f16, device=dev)
-        g16(p, HW, vt, HW, bqkv[2 * Cc:], o, Cc, 1, HW, Cc, HW, batch=B, sA=HW * HW, sW=Cc * HW, sO=HW * Cc)
+        gemm_nt(self.fl, p, vt, bqkv[2 * Cc:], o, HW, Cc, HW, lda=HW, ldw=HW, ldo=Cc, batch=B, sA=HW * HW, sW=Cc * HW, sO=HW * Cc)
         y = torch.empty((B, Hh, Ww, Cc), dtype=f16, device=dev)
-        g16(o, Cc, self.w16[pre + '.proj_out.weight'], Cc, self.w[pre + '.proj_out.bias'], y, Cc, 1, B * HW, Cc, Cc, epi=EPI_RESID, resid=x, ldr=Cc, r16=1)
+        gemm_nt(self.fl, o, self.w16[pre + '.proj_out.weight'], self.w[pre + '.proj_out.bias'], y, B * HW, Cc, Cc, lda=Cc, ldw=Cc, ldo=Cc,
+                epi=EPI_RESID, resid=x, ldr=Cc)
         return y
 
     def upsample(self, h, key, B, Hh, Ww):
@@ -1065,7 +1092,7 @@ class SamplingEngine(_Engine):
         if precision != 'auto' and precision != self.precision:
             self.precision = precision
             for cache in ('_ws', '_ws_tf', '_ws_bop'):                                   # an explicit switch releases the other modes' buffers (6-11 GB each at d16 / B=64)
-                setattr(self, cache, {k: v for k, v in getattr(self, cache, {}).items() if k[2] == precision})
+                keep_precision(getattr(self, cache, {}), precision)
 
     def invalidate(self):
         """forget the packed weight copies of the sampling loop and of the decoder (call after editing parameters through `.data`)"""
@@ -1073,78 +1100,38 @@ class SamplingEngine(_Engine):
         self.dec.invalidate()
 
     # -- workspaces --------------------------------------------------------------------------------------------------
-    def workspace(self, B: int):
-        """buffers of one call (residual stream, GEMM operands, KV caches ...), cached per (batch size, HIP stream): calls issued on
-        DIFFERENT streams may be in flight together — each owns its buffers, everything else a call allocates comes from torch's
-        stream-ordered allocator — and a call's latency-bound small scales then run beside another call's decoder"""
-        sid = int(torch.cuda.current_stream().cuda_stream)
-        ws = self._ws.get((B, sid, self.precision))
-        dev = self.var.pos_start.device
-        if ws is not None and ws['dev'] == dev:
-            return ws
-        self._ws = self._evict(self._ws, sid)
-        ws = self._ws[(B, sid, self.precision)] = self._alloc_workspace(B, dev)
-        return ws
-
-    def _alloc_workspace(self, B: int, dev, G: int = 2) -> dict:
-        """a fresh buffer set of a sampling call of B images in the current precision (workspace() and _bop_workspace() cache them).  G: the row
-        groups per image (2: the CFG pair; _mix_workspace: a composed call's K + 1), R = G * B transformer rows"""
+    def _dims(self) -> Dims:
         var = self.var
-        C, L, H, V, Cv, P = var.C, var.L, var.num_heads, var.V, var.Cvae, var.patch_nums[-1]
-        lmax = max(p * p for p in var.patch_nums)
-        R = G * B
-        M = R * lmax
-        hid = var.blocks[0].ffn.fc1.weight.shape[0]
-        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
-        act = DT16.get(self.precision, torch.float32)                           # GEMM operands and KV cache; x / x2 / logits stay fp32
-        return dict(dev=dev, x=e(M, C), x2=e(M, C), xn=e(M, C, dt=act), q=e(M, C, dt=act), att=e(M, C, dt=act), hid=e(M, hid, dt=act), logits=e(M, V),
-                    idx=e(B * lmax, dt=torch.int64), lvl_pos=e(L, C), cond=e(R, C), cond_silu=e(R, C), hn=e(R, 2 * C),
-                    ada=e(var.depth, R, 6 * C) if var.shared_aln else e(R, var.depth * 6 * C), shared=e(R, 6 * C) if var.shared_aln else None,
-                    kc=[torch.zeros(R, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
-                    vc=[torch.zeros(R, H, L, 64, dtype=act, device=dev) for _ in range(var.depth)],
-                    f_hat=e(B, P, P, Cv), up=e(B, P, P, Cv), pooled=e(B * lmax, Cv))
+        return Dims(C=var.C, H=var.num_heads, V=var.V, Cvae=var.Cvae, P=var.patch_nums[-1], depth=var.depth, hidden=var.blocks[0].ffn.fc1.weight.shape[0],
+                    shared_aln=bool(var.shared_aln), L=var.L)
+
+    def _workspace(self, cache: dict, bound: int, size: int, slot: tuple, R: int, lmax: Optional[int] = None, Lkv: Optional[int] = None, **on_top) -> dict:
+        """the buffer set cache[(size, HIP stream, precision, *slot)] in the call's precision: R transformer rows of up to lmax tokens a scale
+        (default: the widest scale) over caches of Lkv tokens (default: all L), plus what `on_top` names (workspace.workspace_spec), held by
+        the one cache rule (workspace.cached)"""
+        var = self.var
+        dev = var.pos_start.device
+        lmax = max(p * p for p in var.patch_nums) if lmax is None else lmax
+        spec = lambda: workspace_spec(self._dims(), DT16.get(self.precision, torch.float32), R, lmax, var.L if Lkv is None else Lkv, **on_top)
+        return cached(cache, size, (int(torch.cuda.current_stream().cuda_stream), self.precision) + slot, bound, dev, lambda: allocate(spec(), dev))
+
+    def workspace(self, B: int) -> dict:
+        """buffers of one call of B images, the 2B rows of its CFG pairs (residual stream, GEMM operands, KV caches ...), cached per (batch size,
+        HIP stream, precision): calls issued on DIFFERENT streams may be in flight together — each owns its buffers, everything else a call
+        allocates comes from torch's stream-ordered allocator — and a call's latency-bound small scales then run beside another call's decoder"""
+        return self._workspace(self._ws, self.MAX_WORKSPACES, B, (), 2 * B, B=B)
 
     def _mix_workspace(self, B: int, G: int) -> dict:
         """the buffer set of a pass of sample_composed: B images of G row groups.  It lives in the plain calls' cache under a key of its own,
         (B, HIP stream, precision, G) — one B resident per (stream, precision, G), the same bound on the number of sets, the same poisoning in
-        the tests — and adds what the composed sampler writes: `masked` (the filtered rows) and `mixed` (the guided rows, followed by as many
-        zero rows: varhip_sample_stats_f32 reads it as a CFG pair with t = 0).  The prologue gets the G * B labels themselves, and
-        first_map_f32 writes an unconditional twin behind every label it is given (unused here): cond, cond_silu and x have room for it."""
-        sid = int(torch.cuda.current_stream().cuda_stream)
-        dev = self.var.pos_start.device
-        key = (B, sid, self.precision, G)
-        ws = self._ws.get(key)
-        if ws is None or ws['dev'] != dev:
-            self._ws = self._evict(self._ws, sid, (G,))
-            ws = self._ws[key] = self._alloc_workspace(B, dev, G)
-            C, V, lmax = self.var.C, self.var.V, max(p * p for p in self.var.patch_nums)
-            e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-            ws.update(cond=e(2 * G * B, C), cond_silu=e(2 * G * B, C), x=e(2 * G * B * lmax, C), masked=e(B * lmax, V), mixed=e(2 * B * lmax, V))
-        return ws
+        the tests — and adds what the composed sampler writes, `masked` and `mixed`.  The prologue gets the G * B labels themselves (twin)"""
+        return self._workspace(self._ws, self.MAX_WORKSPACES, B, (G,), G * B, B=B, twin=True, masked=True, mixed=True)
 
     def _bop_workspace(self, cap: int, stage: int) -> dict:
         """the buffer set of stage `stage` of sample_best_of_pruned, for up to `cap` candidates (a chunk of fewer uses a prefix of every buffer:
         all of them are row-major in the candidate).  A cache of its own, keyed (capacity, HIP stream, precision, stage): one capacity resident per
         (stream, precision, stage), so the stages evict neither one another nor the plain calls' workspace, and a repeated call allocates nothing."""
-        sid = int(torch.cuda.current_stream().cuda_stream)
-        dev = self.var.pos_start.device
-        key = (cap, sid, self.precision, stage)
-        ws = self._ws_bop.get(key)
-        if ws is None or ws['dev'] != dev:
-            self._ws_bop = {k: v for k, v in self._ws_bop.items() if k[1:] != key[1:]}          # (before allocating: the replaced set is freed first)
-            while len(self._ws_bop) >= 4 * len(self.var.patch_nums):                            # other streams' and precisions' sets, oldest first
-                self._ws_bop.pop(next(iter(self._ws_bop)))
-            ws = self._ws_bop[key] = self._alloc_workspace(cap, dev)
-            ws['masked'] = torch.empty(cap * max(p * p for p in self.var.patch_nums), self.var.V, dtype=torch.float32, device=dev)
-        return ws
-
-    def _evict(self, cache: dict, sid: int, slot: tuple = ()) -> dict:
-        """make room for a new buffer set: one batch size resident at a time per (stream, precision[, slot]), and a bounded number of sets (oldest
-        first: a d16 / B=64 set is 6-11 GB; its memory returns to the stream it was allocated on, so work still queued there is safe)"""
-        cache = {k: v for k, v in cache.items() if k[1:] != (sid, self.precision) + slot}
-        while len(cache) >= self.MAX_WORKSPACES:
-            cache.pop(next(iter(cache)))
-        return cache
+        return self._workspace(self._ws_bop, 4 * len(self.var.patch_nums), cap, (stage,), 2 * cap, B=cap, masked=True)
 
     def _check_labels(self, label_B: torch.Tensor):
         """labels index class_emb: out-of-range ones must not reach the kernel.  One device-side reduction and ONE host sync (a sync drains the
@@ -1167,7 +1154,7 @@ class SamplingEngine(_Engine):
 
     def gemm(self, A, W, bias, out, M, epi=EPI_NONE, resid=None, gamma=None, ldg=0, rpg=1):
         N, K = W.shape
-        hip.call('gemm_nt_f32', A, K, W, K, bias, out, N, M, N, K, epi, resid, N, gamma, ldg, rpg, 0, 1, 0, 0, 0)
+        gemm_nt('f32', A, W, bias, out, M, N, K, lda=K, ldw=K, ldo=N, epi=epi, resid=resid, ldr=N, gamma=gamma, ldg=ldg, rpg=rpg)
 
     def neighbor_table(self, n: int):
         """(idx int32 [V, n], dist float32 [V, n]) nearest codes of every code (var.py:459-462); cached until the codebook changes."""
@@ -1215,8 +1202,8 @@ class SamplingEngine(_Engine):
         hip.call('ln_modulate_f32' if prec == 'f32' else f'ln_modulate_{prec}out', x, hn, 2 * C, hn[:, C:], 2 * C, xn, M, C, l, var.norm_eps)
         if prec == 'f32':
             self.gemm(xn, w['head_w'], w['head_b'], logits, M)
-        else:                                                            # (the 16-bit GEMM's own argument list: fp32 output, no residual)
-            hip.call('gemm_nt_' + prec, xn, C, w['head_w16'][prec], C, w['head_b'], logits, V, 0, M, V, C, EPI_NONE, None, 0, 0, None, 0, 1, 1, 0, 0, 0)
+        else:
+            gemm_nt(prec, xn, w['head_w16'][prec], w['head_b'], logits, M, V, C, lda=C, ldw=C, ldo=V)
 
     def _prologue(self, ws, labels, rows):
         """what a pass computes once, before its scales (var.py:151-157): the level + position embedding, the first map and the condition of
@@ -1239,7 +1226,7 @@ class SamplingEngine(_Engine):
                 self.gemm(ws['cond_silu'], w['ada_w_all'], w['ada_b_all'], ws['ada'], rows)
             else:
                 for (view, _), blk in zip(ws['ada_view'], w['blocks']):
-                    hip.call('gemm_nt_f32', ws['cond_silu'], C, blk['ada_w'], C, blk['ada_b'], view, D6, rows, 6 * C, C, EPI_NONE, None, 0, None, 0, 1, 0, 1, 0, 0, 0)
+                    gemm_nt('f32', ws['cond_silu'], blk['ada_w'], blk['ada_b'], view, rows, 6 * C, C, lda=C, ldw=C, ldo=D6)
         self.gemm(ws['cond_silu'], w['hn_w'], w['hn_b'], ws['hn'], rows)
 
     def qkv(self, xn, blk, ws, bi, rows, l, cur):
@@ -1391,17 +1378,18 @@ class SamplingEngine(_Engine):
     def _masked(self, ws: dict, B: int, soft: bool) -> torch.Tensor:
         """the workspace's buffer for the sampler's filtered logits (B * l_max * V * 4 bytes: more_smooth and stats share it), made on first use;
         soft: with it the gumbel-softmax probabilities and their embedding of more_smooth"""
-        var = self.var
-        for key, cols in (('masked', var.V), ('probs', var.V), ('h', var.Cvae))[:3 if soft else 1]:
+        rows = sampler_rows(self._dims(), B, max(p * p for p in self.var.patch_nums))
+        for key in ('masked', 'probs', 'h') if soft else ('masked',):
+            shape, dt, _ = rows[key]
             if key not in ws:
-                ws[key] = torch.empty(B * max(p * p for p in var.patch_nums), cols, dtype=torch.float32, device=ws['dev'])
+                ws[key] = torch.empty(shape, dtype=dt, device=ws['dev'])
         return ws['masked']
 
     def _stats_setup(self, B: int, stats: dict, dev):
         """stats: the (B, L) tensors of STATS_FIELDS, allocated here unless the caller put contiguous ones there"""
         var = self.var
         for key in STATS_FIELDS:
-            dt = torch.int32 if key == 'kept' else torch.float32
+            dt = _stats_dtype(key)
             if key not in stats:
                 stats[key] = torch.empty(B, var.L, dtype=dt, device=dev)
             sv = stats[key]
@@ -1737,7 +1725,7 @@ class SamplingEngine(_Engine):
         S, L, V, P, Cv = len(var.patch_nums), var.L, var.V, var.patch_nums[-1], var.Cvae
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
         out = dict(tokens=e(B, L, dt=torch.int64), logp_class=e(B, G, L), images=None)
-        out.update({key: e(B, L, dt=torch.int32 if key == 'kept' else torch.float32) for key in STATS_FIELDS[1:]})
+        out.update(stats_record((B, L), dev, fields=STATS_FIELDS[1:]))
         f_all = e(B, P, P, Cv)
         ipp = max(1, int(max_rows) // G)
         for b0 in range(0, B, ipp):
@@ -1782,7 +1770,7 @@ class SamplingEngine(_Engine):
         B = N // n
         if n > self.CLASSIFY_MAX_CAND:
             raise ValueError(f'sample_best_of takes at most {self.CLASSIFY_MAX_CAND} candidates per image, got {n}')
-        rec = {key: torch.empty(N, L, dtype=torch.int32 if key == 'kept' else torch.float32, device=dev) for key in STATS_FIELDS}
+        rec = stats_record((N, L), dev)
         rec['tokens'] = torch.empty(N, L, dtype=torch.int64, device=dev)
         f_all = torch.empty(N, Cv, P, P, dtype=torch.float32, device=dev)
         for c0 in range(0, N, max_images):
@@ -1823,8 +1811,7 @@ class SamplingEngine(_Engine):
             first, m = s + 1, k
         per_chunk = min(B, max_images // n)
         esz = 4 if self.precision == 'f32' else 2
-        rec = {key: torch.full((B, n, L), -1 if key == 'kept' else float('nan'), dtype=torch.int32 if key == 'kept' else torch.float32, device=dev)
-               for key in STATS_FIELDS}
+        rec = stats_record((B, n, L), dev, fill=(-1, float('nan')))
         rec['tokens'] = torch.full((B, n, L), -1, dtype=torch.int64, device=dev)
         totals = torch.empty(B, n, dtype=torch.float64, device=dev)
         depth = torch.empty(B, n, dtype=torch.int64, device=dev)
@@ -1854,12 +1841,11 @@ class SamplingEngine(_Engine):
                     seeds_d = seeds_d.index_select(0, rows)
                     ws['f_hat'][:R].copy_(prev['f_hat'][:R0].index_select(0, rows))
                     rows2 = torch.cat((rows, rows + R0)).to(torch.int32)
-                    ptr = lambda bufs: torch.tensor([t.data_ptr() for t in bufs], dtype=torch.int64)      # host arrays: the launcher copies them
-                    hip.call('kv_compact', ptr(prev['kc'] + prev['vc']), ptr(ws['kc'] + ws['vc']), 2 * var.depth, rows2, 2 * R0, ws['kc'][0].shape[0],
+                    hip.call('kv_compact', pointer_table(prev['kc'] + prev['vc']), pointer_table(ws['kc'] + ws['vc']), 2 * var.depth, rows2, 2 * R0, ws['kc'][0].shape[0],
                              2 * R, H, L, var.begin_ends[first][0], esz)
                     hip.call('next_map_f32', ws['f_hat'], self.w['word_w'], self.w['word_b'], ws['lvl_pos'][var.begin_ends[first][0]:], ws['x'], ws['pooled'],
                              R, var.patch_nums[-1], var.patch_nums[first], var.C, var.Cvae)
-                st = {key: torch.empty(R, L, dtype=torch.int32 if key == 'kept' else torch.float32, device=dev) for key in STATS_FIELDS}
+                st = stats_record((R, L), dev)
                 tok = torch.empty(R, L, dtype=torch.int64, device=dev)
                 self._scored_scales(ws, R, first, last, pers[j], seeds_d, st, tok)
                 t0, t1 = var.begin_ends[first][0], var.begin_ends[last][1]
@@ -1914,7 +1900,7 @@ class SamplingEngine(_Engine):
         per_chunk = min(B, max_images // n)
         esz = 4 if self.precision == 'f32' else 2
         ref = bool(self.smc_reference)
-        rec = {key: torch.empty(N, L, dtype=torch.int32 if key == 'kept' else torch.float32, device=dev) for key in STATS_FIELDS}
+        rec = stats_record((N, L), dev)
         rec['tokens'] = torch.empty(N, L, dtype=torch.int64, device=dev)
         f_all = torch.empty(N, P, P, Cv, dtype=torch.float32, device=dev)
         logw = torch.zeros(B, n, dtype=torch.float64, device=dev)
@@ -1935,7 +1921,7 @@ class SamplingEngine(_Engine):
             per, seeds_d = self._per_image_upload(*[x[b0 * n:b1 * n] for x in (cfg, top_k, top_p, seeds)])
             ws = self._bop_workspace(per_chunk * n, 0)
             caches = ws['kc'] + ws['vc']
-            ptrs = torch.tensor([t.data_ptr() for t in caches], dtype=torch.int64)          # a host array: the launcher copies it
+            ptrs = pointer_table(caches)
             off = (torch.arange(nb, device=dev, dtype=torch.int32) * n).view(nb, 1)
             self._prologue(ws, lab[b0 * n:b1 * n], 2 * R)
             ws['f_hat'][:R].zero_()
@@ -2118,26 +2104,9 @@ class SamplingEngine(_Engine):
         tokens, activations of its l_e = pn^2 rows per row; cached per (rows, HIP stream, precision, L_e), one R resident per L_e; a pass of fewer
         rows uses a prefix"""
         var = self.var
-        dev = var.pos_start.device
-        C, H, V, L = var.C, var.num_heads, var.V, var.L
         last = len(var.patch_nums) - 1 if last is None else last
-        Le, lmax = var.begin_ends[last][1], var.patch_nums[last] ** 2
-        hid = var.blocks[0].ffn.fc1.weight.shape[0]
-        sid = int(torch.cuda.current_stream().cuda_stream)
-        ws = self._ws_tf.get((R, sid, self.precision, Le))
-        if ws is None or ws['dev'] != dev:
-            self._ws_tf = self._evict(self._ws_tf, sid, (Le,))          # (before allocating: the replaced set is freed first)
-            e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
-            act = DT16.get(self.precision, torch.float32)
-            M = R * lmax
-            # x is written by first_map_f32 / word_embed_f32, which also emit the CFG copy of every row (unused here): room for 2x
-            ws = dict(dev=dev, x=e(2 * M, C), x2=e(M, C), xn=e(M, C, dt=act), q=e(M, C, dt=act), att=e(M, C, dt=act), hid=e(M, hid, dt=act), lg=e(R * lmax, V),
-                      lvl_pos=e(L, C), cond=e(2 * R, C), cond_silu=e(2 * R, C), hn=e(R, 2 * C), ada=e(var.depth, R, 6 * C) if var.shared_aln else e(R, var.depth * 6 * C),
-                      shared=e(R, 6 * C) if var.shared_aln else None,
-                      kc=[torch.zeros(R, H, Le, 64, dtype=act, device=dev) for _ in range(var.depth)],
-                      vc=[torch.zeros(R, H, Le, 64, dtype=act, device=dev) for _ in range(var.depth)], Lmax=Le)
-            self._ws_tf[(R, sid, self.precision, Le)] = ws
-        return ws
+        Le = var.begin_ends[last][1]
+        return self._workspace(self._ws_tf, self.MAX_WORKSPACES, R, (Le,), R, var.patch_nums[last] ** 2, Le, twin=True, logits='lg', Lmax=True)
 
     def _tf_rows(self, lab: torch.Tensor, xin: Optional[torch.Tensor], max_rows: int):
         """the pass loop of the calls that run one row per image: the N images of lab (N,) and xin (N, L - first_l, Cvae), in order, as passes p
