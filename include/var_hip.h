@@ -119,6 +119,22 @@ int varhip_attn_force_waves(int nw);
 /* testing: the NW of the latest varhip_attn_cached_f32 launch, written by the launcher from the value it switches on.  0 before the first
  * launch; a refused call (VARHIP_EINVAL) leaves it unchanged.  Host only: it launches nothing and reads no device memory. */
 int varhip_attn_last_waves(void);
+/* ---- attention over a per-(row, head) subset of the key scales (VAR.attention_knockout) ----------------------------------
+ * The operands of varhip_attn_cached_f32, with the cache cut into S1 key scales by ends (a HOST array with the rules of
+ * varhip_attn_profile_f32: strictly increasing, ends[0] >= 1, ends[S1-1] == curL, S1 in [1, 16]; scale i holds the keys ends[i-1] <= j < ends[i])
+ * and keymask, a DEVICE array of B2 * H words: bit i of keymask[b * H + h] set = row b, head h sees key scale i; bits at or above S1 are ignored.
+ * Contract: the visible keys of (b, h), in ascending cache order, form a logical sequence of n = sum over visible i of (ends[i] - ends[i-1])
+ * keys, and out[b][:][h] is what varhip_attn_cached_f32 computes on a cache that holds exactly those keys and values at positions 0 .. n - 1
+ * with curL = n, bit for bit: the same 32-key tiles over the logical sequence, the same running-maximum recurrence, 4-interleaved fma order
+ * and four partial row sums.  So a full mask leaves varhip_attn_cached_f32's bits; n == 0 writes +0 to the l x 64 outputs of (b, h); the
+ * keys and values of hidden scales, and the cache beyond curL, are not read (a NaN there has no effect).
+ * varhip_attn_force_waves and varhip_attn_last_waves act on this launcher as on the plain one.
+ * VARHIP_EINVAL before any launch, nothing written: a NULL pointer, a size <= 0, curL > Lmax, l > curL, S1 outside [1, 16], ends not as above,
+ * q, kcache or vcache not 16-byte aligned, B2 or H above 65535.  f32 only. */
+/* pinned bit for bit against varhip_attn_cached_f32 on the gathered cache (tests/test_knockout_kernels_gpu.py) */
+int varhip_attn_keysel_f32(const float* q, const float* kcache, const float* vcache, float* out,
+                           int B2, int l, int H, int curL, int Lmax, const int32_t* ends, int S1, const int32_t* keymask,
+                           varhip_stream_t stream);
 
 /* ---- one AdaLNSelfAttn block (basic_var.py:152-159) in one call ---------------------------------------------
  * x <- x + gamma1 * proj(attn(LN(x)(1+scale1)+shift1));  x <- x + gamma2 * fc2(gelu(fc1(LN(x)(1+scale2)+shift2)))
@@ -920,6 +936,18 @@ int varhip_adaln_block_patched_f32(float* x, float* x2, float* xn, float* q, flo
                                    const float* fc2_w, const float* fc2_b, float* kcache, float* vcache,
                                    int B2, int l, int C, int H, int hidden, int pos0, int Lmax, float eps,
                                    const int32_t* dir_att, int n_att, const int32_t* dir_hid, int n_hid, varhip_stream_t stream);
+/* varhip_adaln_block_f32 with varhip_attn_keysel_f32(q, kcache, vcache, att, B2, l, H, pos0 + l, Lmax, ends, S1, keymask) in the place of
+ * varhip_attn_cached_f32: the same seven launches, and with full masks varhip_adaln_block_f32's bits.  The new keys and values are appended
+ * to the caches whatever the masks say (a mask hides keys from this block's queries only).  VARHIP_EINVAL before any launch: what either
+ * refuses.  f32 only. */
+/* pinned bit for bit against varhip_adaln_block_f32 (tests/test_knockout_kernels_gpu.py) */
+int varhip_adaln_block_keysel_f32(float* x, float* x2, float* xn, float* q, float* att, float* hid,
+                                  const float* ada, int64_t ld_ada,
+                                  const float* qkv_w, const float* qkv_b, const float* scale_mul, float plain_scale, int l2norm,
+                                  const float* proj_w, const float* proj_b, const float* fc1_w, const float* fc1_b,
+                                  const float* fc2_w, const float* fc2_b, float* kcache, float* vcache,
+                                  int B2, int l, int C, int H, int hidden, int pos0, int Lmax, float eps,
+                                  const int32_t* ends, int S1, const int32_t* keymask, varhip_stream_t stream);
 
 /* ==== 16-bit-input throughput mode ("f16") ===================================================================
  * The reference's harness runs the path under torch.autocast('cuda', dtype=torch.float16) (demo_sample.py:66-68): every F.linear of

@@ -73,10 +73,31 @@ __device__ __forceinline__ float vh_exp_le0_s(float x) {
     return __uint_as_float(__float_as_uint(y) + (__float_as_uint(t) << 23));
 }
 
-// NW waves per workgroup; the register allocation is capped for 4 workgroups per CU (NW waves per SIMD: 128 registers at NW = 4)
-template <int NW>
+// The key scales of varhip_attn_keysel_f32, by value in the kernel's arguments: ends[i] = one past the last key of scale i, padded with curL
+// from S1 on (a padded scale is empty: its mask bit selects nothing)
+#define VH_KEYSEL_MAX_S 16
+struct VhKeyScales { int32_t ends[VH_KEYSEL_MAX_S]; };
+
+// k_attn_cached below, with SEL (the selecting instantiation): the workgroup's (row, head) sees the key scales whose bit is set in its mask word.  The visible keys in ascending cache order form a LOGICAL sequence of n keys, and everything that is arithmetic
+// (the tile walk, the ragged tile, the repeated last key) runs on logical indices with n in the place of curL; only where an address is formed
+// (dma_k, load_v) is a logical index mapped to its physical row.  The map is a table of at most 16 segments (logical begin, physical begin -
+// logical begin), derived once per workgroup from the mask word and the scales' ends in scalar registers (it is wave-uniform); a lane maps ONE key per
+// tile, lane & 31 -> logical key kt * 32 + (lane & 31) clamped to n - 1, by 16 compare / select pairs against those scalars, and the lanes that
+// form the addresses fetch the row they need from that lane (ds_bpermute: no memory).  Without SEL none of this is compiled.
+// the lane number, computed where it stands (volatile: not hoisted out of a loop)
+__device__ __forceinline__ int vh_lane_fresh() { int x; asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(x)); return x; }
+__device__ __forceinline__ uint32_t vh_keysel_mask(int) { return 0u; }
+__device__ __forceinline__ uint32_t vh_keysel_mask(int i, const int32_t* keymask, const VhKeyScales&) { return (uint32_t)keymask[i]; }
+__device__ __forceinline__ int vh_keysel_end(int) { return 0; }
+__device__ __forceinline__ int vh_keysel_end(int i, const int32_t*, const VhKeyScales& ks) { return ks.ends[i]; }
+
+// NW waves per workgroup; the register allocation is capped for 4 workgroups per CU (NW waves per SIMD: 128 registers at NW = 4).
+// k_attn_cached<NW> is the plain kernel; k_attn_cached<NW, const int32_t*, VhKeyScales> takes (keymask, ks) behind Lmax and is the selecting one
+// (one template, so that the plain instantiations keep their argument list and their code).
+template <int NW, typename... Sel>
 __global__ void __launch_bounds__(NW * 64, NW) k_attn_cached(const float* __restrict__ q, const float* __restrict__ kcache, const float* __restrict__ vcache,
-                                                              float* __restrict__ out, int l, int H, int curL, int Lmax) {
+                                                              float* __restrict__ out, int l, int H, int curL, int Lmax, const Sel... sel) {
+    constexpr bool SEL = sizeof...(Sel) != 0;
     constexpr int NT = NW * 64, NIT = (256 + NT - 1) / NT;       // V staging items (key row, 8-float chunk) per thread and tile
     constexpr int KST = 8 * KPIECE;                               // floats per K stage
     // one LDS array: K stages | V stages; the O transpose at the end aliases it
@@ -93,7 +114,42 @@ __global__ void __launch_bounds__(NW * 64, NW) k_attn_cached(const float* __rest
     const int t0 = (blockIdx.x * NW + wave) * 32;                  // this wave's first query
     const float* Kc = kcache + ((int64_t)b * H + hd) * Lmax * 64;
     const float* Vc = vcache + ((int64_t)b * H + hd) * Lmax * 64;
-    const int ntile = (curL + 31) / 32;
+    // SEL: segment i of the map is key scale i; a hidden one begins at INT_MAX and is never chosen.  n = the visible keys (uniform in the workgroup)
+    int n = curL;
+    int seg_lb[VH_KEYSEL_MAX_S], seg_d[VH_KEYSEL_MAX_S];
+    if constexpr (SEL) {
+        const uint32_t mask = vh_keysel_mask(b * H + hd, sel...);
+        int lb = 0, prev = 0;
+#pragma unroll
+        for (int i = 0; i < VH_KEYSEL_MAX_S; ++i) {
+            const int e = vh_keysel_end(i, sel...);
+            const bool vis = (mask >> i) & 1u;
+            seg_lb[i] = vis ? lb : 0x7fffffff;
+            seg_d[i] = prev - lb;
+            lb += vis ? e - prev : 0;
+            prev = e;
+        }
+        n = lb;
+        if (n == 0) {                                             // nothing visible: +0, before the first barrier (the whole workgroup leaves)
+            for (int qi = 0; qi < 32; ++qi) {
+                const int t = t0 + qi;
+                if (t < l) out[((int64_t)b * l + t) * C + hd * 64 + lane] = 0.f;
+            }
+            return;
+        }
+    }
+    // the physical row of logical key kt * 32 + (lane & 31), clamped to the last visible key (SEL only).  ln: the lane number from
+    // vh_lane_fresh() at the place of use: the lane-derived addresses of the SEL paths are rebuilt per tile (a few instructions) and not
+    // kept in registers through the tile's arithmetic, where every register is taken (128 at NW = 4)
+    auto phys = [&](int kt, int ln) {
+        int key = kt * 32 + (ln & 31);
+        key = key < n ? key : n - 1;
+        int d = 0;
+#pragma unroll
+        for (int i = 0; i < VH_KEYSEL_MAX_S; ++i) d = key >= seg_lb[i] ? seg_d[i] : d;
+        return key + d;
+    };
+    const int ntile = (n + 31) / 32;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
     // ---- Q fragments straight from global memory: lane (query r, half h) keeps q[8c + 4h + u], c = 0..7, u = 0..3
@@ -111,25 +167,33 @@ __global__ void __launch_bounds__(NW * 64, NW) k_attn_cached(const float* __rest
     // K tile: 8 pieces of 4 key rows (1 KiB each) by LDS-DMA, piece n of stage st at sK + st*KST + n*KPIECE; wave w issues pieces
     // w, w + NW, ...  Rows past curL repeat the last key (inside the cache; their scores are masked).  The requests are counted by
     // hand: the explicit s_waitcnt vmcnt(0) in front of the barrier that publishes the tile.
-    auto dma_k = [&](int kt, int st) {
+    // (SEL: pk = phys(kt) of this lane; the row of tile position i is lane i's)
+    auto dma_k = [&](int kt, int st, int pk, int ln) {
 #pragma unroll
-        for (int n = wave; n < 8; n += NW) {
-            int key = kt * 32 + n * 4 + (lane >> 4);
-            key = key < curL ? key : curL - 1;
-            vh_attn_dma16(Kc, (uint32_t)key * 256u + (uint32_t)(lane & 15) * 16u,
-                          (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(sK + st * KST + n * KPIECE));
+        for (int pc = wave; pc < 8; pc += NW) {
+            int key;
+            if constexpr (SEL) {
+                key = __builtin_amdgcn_ds_bpermute((pc * 4 + (ln >> 4)) * 4, pk);
+            } else {
+                key = kt * 32 + pc * 4 + (lane >> 4);
+                key = key < curL ? key : curL - 1;
+            }
+            vh_attn_dma16(Kc, (uint32_t)key * 256u + (uint32_t)((SEL ? ln : lane) & 15) * 16u,
+                          (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(sK + st * KST + pc * KPIECE));
         }
     };
     // V tile staging through registers, split so the global loads of tile kt+1 are in flight during the math of tile kt and only
     // meet their LDS stores at the end of the tile
     f32x4 gv0[NIT], gv1[NIT];
-    auto load_v = [&](int kt) {
+    auto load_v = [&](int kt, int pk, int ln) {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            const int item = tid + it * NT, sr = item >> 3, sc = item & 7, key = kt * 32 + sr;
+            const int item = (SEL ? wave * 64 + ln : tid) + it * NT, sr = item >> 3, sc = item & 7, key = kt * 32 + sr;
             gv0[it] = zero4; gv1[it] = zero4;
-            if ((NIT * NT == 256 || item < 256) && key < curL) {
-                const float* sv = Vc + (int64_t)key * 64 + sc * 8; gv0[it] = *(const f32x4*)sv; gv1[it] = *(const f32x4*)(sv + 4);
+            int row = key;
+            if constexpr (SEL) row = __builtin_amdgcn_ds_bpermute((sr & 31) * 4, pk);
+            if ((NIT * NT == 256 || item < 256) && key < n) {
+                const float* sv = Vc + (int64_t)row * 64 + sc * 8; gv0[it] = *(const f32x4*)sv; gv1[it] = *(const f32x4*)(sv + 4);
             }
         }
     };
@@ -154,12 +218,12 @@ __global__ void __launch_bounds__(NW * 64, NW) k_attn_cached(const float* __rest
     for (int e = 0; e < 16; ++e) { o0[e] = 0.f; o1[e] = 0.f; }
     f32x2 lsum = {0.f, 0.f};
     float mx = -INFINITY;
-    dma_k(0, 0); load_v(0); store_v(0);
+    { const int ln = SEL ? vh_lane_fresh() : 0, pk = SEL ? phys(0, ln) : 0; dma_k(0, 0, pk, ln); load_v(0, pk, ln); store_v(0); }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int kt = 0; kt < ntile; ++kt) {
         const int buf = kt & 1;
-        if (kt + 1 < ntile) { dma_k(kt + 1, buf ^ 1); load_v(kt + 1); }       // stage buf^1 was last read before the previous barrier
+        if (kt + 1 < ntile) { const int ln = SEL ? vh_lane_fresh() : 0, pk = SEL ? phys(kt + 1, ln) : 0; dma_k(kt + 1, buf ^ 1, pk, ln); load_v(kt + 1, pk, ln); }   // stage buf^1 was last read before the previous barrier
         if (t0 < l) {                                               // (ragged last workgroup: a wave without queries only stages and syncs)
             // S^T tile: rows = keys, col (lane) = query
             f32x16 p;
@@ -177,12 +241,12 @@ __global__ void __launch_bounds__(NW * 64, NW) k_attn_cached(const float* __rest
                     for (int u = 0; u < 4; ++u) p = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[u], qf[c * 4 + u], p, 0, 0, 0);
                 }
             }
-            const bool ragged = kt * 32 + 32 > curL;                // only the last tile can hold keys past curL (wave-uniform)
+            const bool ragged = kt * 32 + 32 > n;                   // only the last tile can hold keys past n (= curL without SEL; wave-uniform)
             if (ragged) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int key = kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h2;
-                    if (key >= curL) p[e] = -INFINITY;
+                    if (key >= n) p[e] = -INFINITY;
                 }
             }
             // The FIRST read of the score accumulators is compiler-generated code: hipcc pads the MFMA -> VALU read hazard for its own
@@ -212,7 +276,7 @@ __global__ void __launch_bounds__(NW * 64, NW) k_attn_cached(const float* __rest
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int key = kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h2;
-                    if (key >= curL) p[e] = 0.f;
+                    if (key >= n) p[e] = 0.f;
                 }
             }
             // PV: register 4g + j of lane half h is key 8g + 4h + j — the B operand of the step that contracts keys 8g + j and 8g + 4 + j
@@ -288,6 +352,46 @@ extern "C" int varhip_attn_cached_f32(const float* q, const float* kcache, const
     hipStream_t s = (hipStream_t)stream;
     switch (nw) {
 #define VH_ATTN_LAUNCH(NW_) hipLaunchKernelGGL((k_attn_cached<NW_>), grid, dim3(NW_ * 64), 0, s, q, kcache, vcache, out, l, H, curL, Lmax)
+        case 1: VH_ATTN_LAUNCH(1); break;
+        case 2: VH_ATTN_LAUNCH(2); break;
+        case 3: VH_ATTN_LAUNCH(3); break;
+        default: VH_ATTN_LAUNCH(4); break;
+#undef VH_ATTN_LAUNCH
+    }
+    return vh_launch_status();
+}
+
+// The same launch over a per-(row, head) subset of the key scales (include/var_hip.h).  ends is read here, on the host, and travels in the
+// kernel's arguments; the masks stay on the device, so the visible key count n is known to the workgroup only (the timing table's FLOPs and
+// bytes are those of the full cache, an upper bound).
+int vh_attn_keysel_refused(const void* q, const void* kcache, const void* vcache, const void* out, int B2, int l, int H, int curL, int Lmax,
+                           const int32_t* ends, int S1, const int32_t* keymask, int32_t* ends16) {
+    if (!q || !kcache || !vcache || !out || !ends || !keymask) return 1;
+    if (B2 <= 0 || l <= 0 || H <= 0 || curL <= 0 || Lmax <= 0 || curL > Lmax || l > curL) return 1;
+    if (B2 > 65535 || H > 65535 || S1 < 1 || S1 > VH_KEYSEL_MAX_S) return 1;
+    if ((((uintptr_t)q | (uintptr_t)kcache | (uintptr_t)vcache) & 15) != 0 || ((uintptr_t)keymask & 3) != 0) return 1;
+    for (int i = 0, prev = 0; i < VH_KEYSEL_MAX_S; ++i) {
+        if (i < S1 && ends[i] <= prev) return 1;                    // strictly increasing from ends[0] >= 1
+        prev = i < S1 ? ends[i] : curL;
+        if (ends16) ends16[i] = prev;
+    }
+    return ends[S1 - 1] != curL;
+}
+
+extern "C" int varhip_attn_keysel_f32(const float* q, const float* kcache, const float* vcache, float* out,
+                                      int B2, int l, int H, int curL, int Lmax, const int32_t* ends, int S1, const int32_t* keymask,
+                                      varhip_stream_t stream) {
+    VhKeyScales ks;
+    if (vh_attn_keysel_refused(q, kcache, vcache, out, B2, l, H, curL, Lmax, ends, S1, keymask, ks.ends)) return VARHIP_EINVAL;
+    VhScope sc(VH_FAM_ATTN, (hipStream_t)stream, 4.0 * B2 * H * (double)l * curL * 64,
+               4.0 * B2 * H * (2.0 * curL * 64 + 2.0 * l * 64));
+    const int forced = vh_g_attn_force_waves;
+    const int nw = forced ? forced : attn_waves(l);
+    vh_g_attn_last_waves = nw;
+    dim3 grid((l + nw * 32 - 1) / (nw * 32), H, B2);
+    hipStream_t s = (hipStream_t)stream;
+    switch (nw) {
+#define VH_ATTN_LAUNCH(NW_) hipLaunchKernelGGL((k_attn_cached<NW_, const int32_t*, VhKeyScales>), grid, dim3(NW_ * 64), 0, s, q, kcache, vcache, out, l, H, curL, Lmax, keymask, ks)
         case 1: VH_ATTN_LAUNCH(1); break;
         case 2: VH_ATTN_LAUNCH(2); break;
         case 3: VH_ATTN_LAUNCH(3); break;

@@ -53,6 +53,30 @@ extern "C" int varhip_adaln_block_patched_f32(float* x, float* x2, float* xn, fl
     return varhip_gemm_nt_f32(hid, hidden, fc2_w, hidden, fc2_b, x, C, M, C, hidden, VARHIP_EPI_RESID, x2, C, g2, ld_ada, l, 0, 1, 0, 0, 0, stream);
 }
 
+// The fp32 block with edges of the block-causal graph cut (VAR.attention_knockout): the same seven launches with varhip_attn_keysel_f32 (attn.hip)
+// in the place of varhip_attn_cached_f32.  The q/k/v GEMM appends this scale's keys and values as ever: a mask hides keys from this block's
+// queries only.  What the attention launcher would refuse is asked before the first launch.
+extern "C" int varhip_adaln_block_keysel_f32(float* x, float* x2, float* xn, float* q, float* att, float* hid,
+                                             const float* ada, int64_t ld_ada,
+                                             const float* qkv_w, const float* qkv_b, const float* scale_mul, float plain_scale, int l2norm,
+                                             const float* proj_w, const float* proj_b, const float* fc1_w, const float* fc1_b,
+                                             const float* fc2_w, const float* fc2_b, float* kcache, float* vcache,
+                                             int B2, int l, int C, int H, int hidden, int pos0, int Lmax, float eps,
+                                             const int32_t* ends, int S1, const int32_t* keymask, varhip_stream_t stream) {
+    if (B2 <= 0 || l <= 0 || C <= 0 || H <= 0 || C != H * 64 || hidden <= 0 || !ada || pos0 < 0) return VARHIP_EINVAL;
+    if (vh_attn_keysel_refused(q, kcache, vcache, att, B2, l, H, pos0 + l, Lmax, ends, S1, keymask, nullptr)) return VARHIP_EINVAL;
+    const int M = B2 * l;
+    const float *g1 = ada, *g2 = ada + C, *s1 = ada + 2 * C, *s2 = ada + 3 * C, *h1 = ada + 4 * C, *h2 = ada + 5 * C;
+    int rc;
+    if ((rc = varhip_ln_modulate_f32(x, s1, ld_ada, h1, ld_ada, xn, M, C, l, eps, stream))) return rc;
+    if ((rc = varhip_gemm_qkv_f32(xn, C, qkv_w, C, qkv_b, M, C, C, scale_mul, plain_scale, l2norm, q, kcache, vcache, B2, l, H, pos0, Lmax, stream))) return rc;
+    if ((rc = varhip_attn_keysel_f32(q, kcache, vcache, att, B2, l, H, pos0 + l, Lmax, ends, S1, keymask, stream))) return rc;
+    if ((rc = varhip_gemm_nt_f32(att, C, proj_w, C, proj_b, x2, C, M, C, C, VARHIP_EPI_RESID, x, C, g1, ld_ada, l, 0, 1, 0, 0, 0, stream))) return rc;
+    if ((rc = varhip_ln_modulate_f32(x2, s2, ld_ada, h2, ld_ada, xn, M, C, l, eps, stream))) return rc;
+    if ((rc = varhip_gemm_nt_f32(xn, C, fc1_w, C, fc1_b, hid, hidden, M, hidden, C, VARHIP_EPI_GELU, nullptr, 0, nullptr, 0, 1, 0, 1, 0, 0, 0, stream))) return rc;
+    return varhip_gemm_nt_f32(hid, hidden, fc2_w, hidden, fc2_b, x, C, M, C, hidden, VARHIP_EPI_RESID, x2, C, g2, ld_ada, l, 0, 1, 0, 0, 0, stream);
+}
+
 // The same block in the 16-bit throughput mode (gemm16.hip, attn16.hip): the residual stream x / x2 and the AdaLN parameters stay fp32,
 // the GEMM operands (LayerNorm output, q, attention output, MLP hidden), the weights and the KV cache are fp16.
 extern "C" int varhip_adaln_block_f16(float* x, float* x2, void* xn16, void* q16, void* att16, void* hid16,

@@ -88,6 +88,11 @@ __device__ __forceinline__ void vh_dma16_buf(__amdgpu_buffer_rsrc_t rsrc, uint32
 // quant.hip: Phi (3x3 residual mix) + f_hat accumulation of one quantizer step on a gathered `up` map (also behind edit.hip's fused steps)
 void vh_quant_phi_accum(const float* up, const float* phi_w, const float* phi_b, float ratio, float* f_hat, int B, int P, int Cv, hipStream_t s);
 
+// attn.hip: everything varhip_attn_keysel_f32 refuses, checked on the host (block.hip asks before its first launch); ends16 (may be NULL)
+// receives ends padded with curL to 16 entries
+int vh_attn_keysel_refused(const void* q, const void* kcache, const void* vcache, const void* out, int B2, int l, int H, int curL, int Lmax,
+                           const int32_t* ends, int S1, const int32_t* keymask, int32_t* ends16);
+
 static inline int vh_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : -(1000 + (int)e);

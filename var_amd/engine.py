@@ -1194,6 +1194,15 @@ class SamplingEngine(_Engine):
                  blk['fc1_w'], blk['fc1_b'], blk['fc2_w'], blk['fc2_b'], ws['kc'][bi], ws['vc'][bi],
                  rows, l, var.C, var.num_heads, blk['fc1_w'].shape[0], cur, Lmax, var.norm_eps, dir_att, n_att, dir_hid, n_hid)
 
+    def block_keysel(self, blk, ws, bi, x, x2, rows, l, cur, Lmax: int, ends, S1: int, keymask):
+        """block() in f32 with edges of the block-causal graph cut (varhip_adaln_block_keysel_f32): ends, a host int32 array of the S1 key
+        scales' ends (the last one cur + l), keymask, a device int32 table [rows * H] whose bit i says that the row's head sees key scale i"""
+        var = self.var
+        hip.call('adaln_block_keysel_f32', x, x2, ws['xn'], ws['q'], ws['att'], ws['hid'], ws['ada_view'][bi][0], ws['ada_view'][bi][1],
+                 blk['qkv_w'], blk['qkv_b'], blk['smul'], blk['plain_scale'], int(blk['l2']), blk['proj_w'], blk['proj_b'],
+                 blk['fc1_w'], blk['fc1_b'], blk['fc2_w'], blk['fc2_b'], ws['kc'][bi], ws['vc'][bi],
+                 rows, l, var.C, var.num_heads, blk['fc1_w'].shape[0], cur, Lmax, var.norm_eps, ends, S1, keymask)
+
     def head(self, x, hn, xn, logits, M, l):
         """get_logits (var.py:118-124): AdaLNBeforeHead (LayerNorm + scale/shift) then the vocabulary projection -> fp32 logits"""
         var, w = self.var, self.w
@@ -2500,6 +2509,93 @@ class SamplingEngine(_Engine):
             keep = slot >= 0
             for k, r in zip(keys, res):
                 out[k][img[keep], slot[keep]] = r[:len(lay.rows)][keep]
+        return out
+
+    # -- cutting scale-to-scale attention (VAR.attention_knockout) -------------------------------------------------------------------------
+    ATTN_KEYSEL_MAX_S = 16             # varhip_attn_keysel_f32 takes at most 16 key scales (include/var_hip.h)
+
+    @torch.no_grad()
+    def attention_knockout(self, gt_tokens: torch.Tensor, label_N: torch.Tensor, cuts: tuple, max_rows: int, _tap=None) -> dict:
+        """VAR.attention_knockout on the HIP path -> dict(nll, entropy, kl (N, P + 1, L) fp32, pred int64, rank int32), index 0 the clean row.
+        gt_tokens (N, L) int64, label_N (N,) int64; cuts: P entries, each {(query scale, block): the H key-scale masks of that block's heads
+        while that scale is the query scale} (args.knockout_masks; bit i set = key scale i is visible); all validated by the caller.  The rows
+        of a pass are image-major: per image the clean row, then one row per entry.  Images whose rows fit max_rows share passes; otherwise
+        an image's entries are chunked over passes, each with its own clean row, as in patch_effects.  Per pass layout (image count, entry
+        chunk) one int32 table is built on the host and uploaded: per (scale, block) some row of the layout touches, the [R * H] masks (the
+        full mask for the rows that do not).  Those (scale, block) pairs run varhip_adaln_block_keysel_f32, every other one self.block.
+        Behind each scale's head the clean row of every row's image is gathered into a second logits buffer and varhip_token_lens_f32
+        reduces (row, its clean row): no (rows, L, V) tensor exists at any time, and the tables, the second buffer and the per-pass outputs
+        live for the call only.  _tap (tests): called after a stream sync with clones of the scale's logits, of the gathered clean rows, the
+        pass's (image, slot) per row (slot 0: the clean row, j + 1: entry j) and (si, cur, l)."""
+        var = self.var
+        S, H = len(var.patch_nums), var.num_heads
+
+        def refusals(tf):
+            if S > self.ATTN_KEYSEL_MAX_S:
+                raise ValueError(f'attention_knockout takes at most {self.ATTN_KEYSEL_MAX_S} scales, got {S}')
+            self._check_labels(tf.lab)
+        tf = self._tf_begin(label_N, gt_tokens, 'attention_knockout runs in f32: the {} workspaces hold 16-bit queries and keys', refusals)
+        dev, gt = tf.dev, tf.gt
+        L, V = var.L, var.V
+        N, P = gt.shape[0], len(cuts)
+        keys = ('nll', 'entropy', 'kl', 'pred', 'rank')
+        dts = (torch.float32, torch.float32, torch.float32, torch.int64, torch.int32)
+        out = {k: torch.empty(N, P + 1, L, dtype=dt, device=dev) for k, dt in zip(keys, dts)}
+        if 1 + P <= max_rows:
+            ipp, spp = max(1, max_rows // (1 + P)), P                    # whole images per pass
+        else:
+            ipp, spp = 1, max_rows - 1                                   # one image per pass, its entries in chunks
+        passes = [(i0, min(ipp, N - i0), j0, min(spp, P - j0)) for i0 in range(0, N, ipp) for j0 in range(0, P, spp)]
+        Rmax = max(ni * (1 + nj) for _, ni, _, nj in passes)
+        ws = self._tf_workspace(Rmax)                                    # sized once: a shorter pass uses a prefix
+        lg2 = torch.empty(Rmax * var.patch_nums[-1] ** 2, V, dtype=torch.float32, device=dev)
+        res = [torch.empty(Rmax, L, dtype=dt, device=dev) for dt in dts]
+        ends = [torch.tensor([e for _, e in var.begin_ends[:si + 1]], dtype=torch.int32) for si in range(S)]      # host arrays: the launcher copies them
+        layouts = {}
+
+        def layout(ni, j0, nj):
+            """the rows of a pass of ni images with the entries j0 .. j0 + nj: (image, slot) per row, each row's clean row, and per touched
+            (scale, block) the device view of its [R * H] mask table; built once, one upload"""
+            if (ni, j0, nj) not in layouts:
+                per = 1 + nj
+                rows = [(i, s) for i in range(ni) for s in [0] + list(range(j0 + 1, j0 + nj + 1))]
+                tabs = {}
+                for j in range(nj):
+                    for (si, bi), masks in cuts[j0 + j].items():
+                        t = tabs.setdefault((si, bi), [(2 << si) - 1] * (len(rows) * H))
+                        for i in range(ni):
+                            r = i * per + 1 + j
+                            t[r * H:(r + 1) * H] = masks
+                flat, where = [], {}
+                for key, t in tabs.items():
+                    where[key] = len(flat)
+                    flat.extend(t)
+                table = torch.tensor(flat or [0], dtype=torch.int32).to(dev)
+                layouts[(ni, j0, nj)] = SimpleNamespace(rows=rows, views={key: table[o:] for key, o in where.items()},
+                                                        clean=torch.tensor([i * per for i, _ in rows], dtype=torch.int64).to(dev))
+            return layouts[(ni, j0, nj)]
+
+        def block(p, blk, bi, si, cur, l):
+            mask = p.lay.views.get((si, bi))
+            if mask is None:
+                return self.block(blk, p.ws, bi, p.ws['x'], p.ws['x2'], p.R, l, cur, p.ws['Lmax'])
+            self.block_keysel(blk, p.ws, bi, p.ws['x'], p.ws['x2'], p.R, l, cur, p.ws['Lmax'], ends[si], si + 1, mask)
+
+        def head(p, si, cur, l):
+            R = p.R
+            torch.index_select(ws['lg'][:R * l].view(R, l * V), 0, p.lay.clean, out=lg2[:R * l].view(R, l * V))
+            hip.call('token_lens_f32', ws['lg'], lg2, p.gt[:, cur:], L, R, l, V, *[r[:, cur:] for r in res], L)
+            if _tap is not None:
+                torch.cuda.current_stream().synchronize()
+                _tap(ws['lg'][:R * l].clone(), lg2[:R * l].clone(), [(p.i0 + i, s) for i, s in p.lay.rows], (si, cur, l))
+        for i0, ni, j0, nj in passes:
+            lay = layout(ni, j0, nj)
+            img = torch.tensor([i0 + i for i, _ in lay.rows], dtype=torch.int64).to(dev)
+            slot = torch.tensor([s for _, s in lay.rows], dtype=torch.int64).to(dev)
+            self._tf_pass(SimpleNamespace(ws=ws, R=len(lay.rows), lab=tf.lab[img].contiguous(), i0=i0, lay=lay, gt=gt.index_select(0, img),
+                                          xin=tf.xin.index_select(0, img).contiguous()), head=head, block=block)
+            for k, r in zip(keys, res):
+                out[k][img, slot] = r[:len(lay.rows)]
         return out
 
     # -- zero-shot classification with per-scale pruning (VAR.classify) -------------------------------------------------------------

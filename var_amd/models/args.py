@@ -204,6 +204,85 @@ def patch_mode(mode, donor_label, N: int, max_rows) -> tuple:
     return mode, donor, integer(max_rows, f'max_rows must be an integer >= {least}: {what}', least)
 
 
+def block_heads(heads, H: int) -> tuple:
+    """the `heads` of VAR.attention_knockout -> the selected head indices, ascending: None means every head"""
+    if heads is None:
+        return tuple(range(H))
+    try:
+        heads = tuple(heads)
+    except TypeError:
+        raise ValueError('heads must be None or a strictly increasing sequence of head indices') from None
+    if not heads or not all(is_int(h) and 0 <= h < H for h in heads) or any(h1 <= h0 for h0, h1 in zip(heads, heads[1:])):
+        raise ValueError(f'heads must be None or a strictly increasing sequence of head indices in [0, {H})')
+    return tuple(int(h) for h in heads)
+
+
+def _knockout_edge(edge, S: int, layers: tuple, heads: tuple, depth: int, H: int) -> tuple:
+    """one elementary edge of VAR.attention_knockout, checked -> (q, k, blocks, heads): (q, k) in the call's layers and heads, (q, k, layer) in
+    one block, (q, k, layer, head) in one head of one block (a None in either place: the call's)"""
+    forms = '(q, k), (q, k, layer) or (q, k, layer, head)'
+    if not isinstance(edge, (tuple, list)) or not 2 <= len(edge) <= 4:
+        raise ValueError(f'edges: {edge!r} is not {forms}')
+    q, k = edge[0], edge[1]
+    if not is_int(q) or not is_int(k) or not 0 <= k <= q < S:
+        raise ValueError(f'edges: {tuple(edge)!r}: the scales must be integers with 0 <= k <= q < {S}')
+    bi = edge[2] if len(edge) > 2 else None
+    h = edge[3] if len(edge) > 3 else None
+    if bi is not None and (not is_int(bi) or not 0 <= bi < depth):
+        raise ValueError(f'edges: {tuple(edge)!r}: the layer must be None or an integer in [0, {depth})')
+    if h is not None and (not is_int(h) or not 0 <= h < H):
+        raise ValueError(f'edges: {tuple(edge)!r}: the head must be None or an integer in [0, {H})')
+    return int(q), int(k), layers if bi is None else (int(bi),), heads if h is None else (int(h),)
+
+
+def knockout_edges(edges, S: int, layers: tuple, heads: tuple, depth: int, H: int) -> tuple:
+    """the `edges` of VAR.attention_knockout -> a tuple of entries, each a tuple of elementary edges (q, k, blocks, heads) applied together in one
+    row.  None: every (q, k) with k < q, then (q, q) for q >= 1, in the call's layers and heads.  An entry is an elementary edge or a non-empty
+    sequence of them; it may not cut the same (q, k, block, head) twice, and it must leave every (query scale, block, head) a visible key (scale 0
+    sees only itself; cutting (q, 0) .. (q, q) together hides everything)"""
+    if edges is None:
+        edges = [(q, k) for q in range(S) for k in range(q)] + [(q, q) for q in range(1, S)]
+    if isinstance(edges, (str, bytes, dict)) or not hasattr(edges, '__iter__'):
+        raise ValueError('edges must be None or a sequence of edges')
+    out = []
+    for entry in edges:
+        if isinstance(entry, (tuple, list)) and entry and not isinstance(entry[0], (tuple, list)):
+            entry = (entry,)
+        if not isinstance(entry, (tuple, list)) or not entry:
+            raise ValueError(f'edges: {entry!r} is neither an edge nor a non-empty tuple of edges')
+        group = tuple(_knockout_edge(e, S, layers, heads, depth, H) for e in entry)
+        cut = {}
+        for q, k, bs, hs in group:
+            for bi in bs:
+                for h in hs:
+                    seen = cut.setdefault((q, bi, h), set())
+                    if k in seen:
+                        raise ValueError(f'edges: {entry!r} cuts ({q}, {k}) twice in block {bi}, head {h}: duplicate edges')
+                    seen.add(k)
+        for (q, bi, h), ks in cut.items():
+            if len(ks) == q + 1:
+                raise ValueError(f'edges: {entry!r} leaves the queries of scale {q} without a visible key in block {bi}, head {h}')
+        out.append(group)
+    if not out:
+        raise ValueError('edges must be None or hold at least one edge')
+    return tuple(out)
+
+
+def knockout_masks(entries: tuple, H: int) -> tuple:
+    """normalised edges -> per entry {(query scale, block): [H key-scale masks]}: bit i of a mask set = key scale i is visible; only the
+    (scale, block) pairs an entry touches appear, each with the full mask (bits 0 .. q) for the heads it leaves alone"""
+    out = []
+    for group in entries:
+        m = {}
+        for q, k, bs, hs in group:
+            for bi in bs:
+                row = m.setdefault((q, bi), [(2 << q) - 1] * H)
+                for h in hs:
+                    row[h] &= ~(1 << k)
+        out.append({key: tuple(v) for key, v in m.items()})
+    return tuple(out)
+
+
 def cfg_arg(cfg, name: str = 'cfg') -> float:
     """cfg / fill_cfg: whatever float() takes, a bool included (1.0 / 0.0), as in the per-image samplers"""
     return real(float(cfg) if isinstance(cfg, bool) else cfg, f'{name} must be finite and >= 0', lambda v: v >= 0, convert=True)

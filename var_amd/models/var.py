@@ -666,6 +666,125 @@ def patch_effects_torch(var, gt: torch.Tensor, label: torch.Tensor, columns: tup
     return tuple(torch.stack(f) for f in zip(*rows))
 
 
+class AttentionKnockout:
+    """VAR.attention_knockout's result: what an image's prediction loses when queries of one scale may not read the keys of another, per token, on
+    the model's device.  Index 0 of the second axis is the clean row, index j + 1 the row with the cut edges[j]; with z the row's fp32 logits,
+    p their softmax and pc the clean row's softmax:
+      nll      (N, P + 1, L) fp32   -log p[gt]                       (index 0: VAR.evaluate's nll_BL)
+      entropy  (N, P + 1, L) fp32   -sum_v p_v log p_v, in nats
+      kl       (N, P + 1, L) fp32   KL(pc || p) = sum_v pc_v (log pc_v - log p_v); exactly 0 at index 0
+      pred     (N, P + 1, L) int64  argmax z;  rank (N, P + 1, L) int32: |{v : z_v > z_gt or (z_v == z_gt and v < gt)}|
+      edges: the P entries, each a tuple of elementary edges (q, k, blocks, heads): queries of scale q do not see the keys of scale k in those
+      blocks and heads; layers, heads (the call's), patch_nums (the scales the result covers)
+    The methods run in PyTorch with float64 sums."""
+    __slots__ = ('edges', 'layers', 'heads', 'nll', 'entropy', 'kl', 'pred', 'rank', 'patch_nums')
+
+    def __init__(self, edges, layers, heads, nll, entropy, kl, pred, rank, patch_nums):
+        self.edges, self.layers, self.heads, self.patch_nums = tuple(edges), tuple(layers), tuple(heads), tuple(patch_nums)
+        self.nll, self.entropy, self.kl, self.pred, self.rank = nll, entropy, kl, pred, rank
+
+    def effect(self) -> torch.Tensor:
+        """(N, P, L) fp32: the loss an entry's cut adds, nll[:, 1:] - nll[:, :1]"""
+        return self.nll[:, 1:] - self.nll[:, :1]
+
+    def _begins(self) -> list:
+        b = [0]
+        for pn in self.patch_nums:
+            b.append(b[-1] + pn * pn)
+        return b
+
+    def per_scale(self) -> dict:
+        """{'effect', 'kl'}: (P, S) float64 means per entry and token scale, over the images and the scale's tokens"""
+        b = self._begins()
+        mean = lambda x: torch.stack([x[..., b[s]:b[s + 1]].double().mean(dim=(0, 2)) for s in range(len(self.patch_nums))], -1)
+        return dict(effect=mean(self.effect()), kl=mean(self.kl[:, 1:]))
+
+    def edge_matrix(self, at: str = 'query') -> torch.Tensor:
+        """(S, S) float64, [q, k]: the mean added loss of every entry that is one single edge (q, k), over the images and the tokens of scale q
+        (at='query') or the tokens of scale q and every later scale (at='all'); NaN where no entry exists (an edge asked for more than once:
+        its last entry)"""
+        if at not in ('query', 'all'):
+            raise ValueError(f"at must be 'query' or 'all', got {at!r}")
+        S, b = len(self.patch_nums), self._begins()
+        m = torch.full((S, S), float('nan'), dtype=torch.float64, device=self.nll.device)
+        eff = self.effect().double()
+        for j, group in enumerate(self.edges):
+            if len(group) == 1 and group[0][0] < S:
+                q, k = group[0][:2]
+                m[q, k] = eff[:, j, b[q]:(b[q + 1] if at == 'query' else b[S])].mean()
+        return m
+
+    def __repr__(self):
+        N, P1, L = self.nll.shape
+        return f'AttentionKnockout(images={N}, edges={P1 - 1}, tokens={L})'
+
+
+def attention_knockout_torch(var, gt: torch.Tensor, label: torch.Tensor, cuts: tuple, _tap=None):
+    """VAR.attention_knockout's definitions in PyTorch on the module stack (CPU models, train mode, prog_si >= 0; the arithmetic follows the
+    parameters' dtype): one masked teacher-forced pass per row with batch size 1, a manual block loop whose attention takes, on top of the
+    block-causal mask, an additive bias per head that is -inf where the row's cut hides a key scale from a query scale.  gt (N, L) tokens,
+    label (N,) labels, cuts: per entry {(query scale, block): the H key-scale masks} (args.knockout_masks) -> (nll, entropy, kl float64, pred
+    int64, rank int32), each (N, P + 1, ed) with ed the tokens the pass covers.  A row's values do not depend on its neighbours; dropout and
+    drop path are not applied (the deterministic pass).  _tap (tests): called with (image, row index, the row's logits (ed, V)) for every row."""
+    F = torch.nn.functional
+    ed = var.begin_ends[var.prog_si][1] if var.prog_si >= 0 else var.L
+    dt = var.pos_start.dtype
+    H = var.num_heads
+    mask = var.attn_bias_for_masking[:, :, :ed, :ed].to(dt)
+
+    def bias_of(cut, bi):
+        """(1, H, ed, ed): the block-causal mask with the block's hidden (query scale, key scale) rectangles at -inf, or the mask itself"""
+        todo = [(si, masks) for (si, b), masks in cut.items() if b == bi and var.begin_ends[si][1] <= ed]
+        if not todo:
+            return mask
+        bias = mask.expand(1, H, ed, ed).clone()
+        for si, masks in todo:
+            bq, eq = var.begin_ends[si]
+            for h, m in enumerate(masks):
+                for k in range(si + 1):
+                    if not (m >> k) & 1:
+                        bk, ek = var.begin_ends[k]
+                        bias[0, h, bq:eq, bk:ek] = float('-inf')
+        return bias
+
+    def run(lab, x_in, cut):
+        cond = var.class_emb(lab.view(1))
+        sos = cond.unsqueeze(1).expand(1, var.first_l, -1) + var.pos_start.expand(1, var.first_l, -1)
+        x = torch.cat((sos, var.word_embed(x_in)), dim=1) if ed > var.first_l else sos
+        x = x + var.lvl_embed(var.lvl_1L[:, :ed].expand(1, -1)) + var.pos_1LC[:, :ed]
+        cond_or_gss = var.shared_ada_lin(cond)
+        for bi, blk in enumerate(var.blocks):
+            at = blk.attn
+            gamma1, gamma2, scale1, scale2, shift1, shift2 = blk._six(cond_or_gss)
+            q, k, v = at._heads(blk.ln_wo_grad(x) * (scale1 + 1) + shift1)
+            if at.attn_l2_norm:
+                q, k = F.normalize(q, dim=-1) * at.scale_mul_1H11.clamp_max(at.max_scale_mul).exp(), F.normalize(k, dim=-1)
+            ctx = F.scaled_dot_product_attention(q, k, v, attn_mask=bias_of(cut, bi), scale=at.scale).transpose(1, 2).reshape(1, ed, var.C)
+            x = x + at.proj(ctx) * gamma1
+            x = x + blk.ffn.fc2(blk.ffn.act(blk.ffn.fc1(blk.ln_wo_grad(x) * (scale2 + 1) + shift2))) * gamma2
+        return var.head(var.head_nm(x, cond))[0]
+
+    zero = torch.zeros((), dtype=torch.float64, device=gt.device)
+    rows = []
+    for n in range(gt.shape[0]):
+        # (an image's input on its own: the quantizer's interpolation is not batch-invariant)
+        x_in = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[n:n + 1, b:e] for b, e in var.begin_ends])[:, :ed - var.first_l].to(dt)
+        g = gt[n, :ed]
+        per, lpc = [], None
+        for cut in ({},) + tuple(cuts):
+            z = run(label[n], x_in, cut)
+            if _tap is not None:
+                _tap(n, len(per), z)
+            lp = torch.log_softmax(z.double(), dim=-1)
+            lpc = lp if lpc is None else lpc
+            p, pc = lp.exp(), lpc.exp()
+            _, _, pred, rank = token_eval_torch(z.float().unsqueeze(0), g.unsqueeze(0))
+            per.append((-lp.gather(-1, g.unsqueeze(-1)).squeeze(-1), -torch.where(p > 0, p * lp, zero).sum(-1),
+                        torch.where(pc > 0, pc * (lpc - lp), zero).sum(-1), pred[0], rank[0]))
+        rows.append(tuple(torch.stack(f) for f in zip(*per)))
+    return tuple(torch.stack(f) for f in zip(*rows))
+
+
 class EvidenceMaps:
     """VAR.evidence_maps' result: where in the image the evidence for each class sits.  With m[n, k, y, x] the map of class k (the selected
     scales' per-token scores, each resampled bilinearly to size x size and weighted by its share of the selected tokens):
@@ -1823,6 +1942,42 @@ class VAR(nn.Module):
         nsc = self.prog_si + 1 if self.prog_si >= 0 else len(self.patch_nums)
         nll, ent, kl, pred, rank = patch_effects_torch(self, gt, lab, columns, mode, donor, scales)
         return PatchEffects(sites, mode, scales, nll.float(), ent.float(), kl.float(), pred, rank, self.patch_nums[:nsc], self.depth, self.num_heads)
+
+    @torch.no_grad()
+    def attention_knockout(self, gt_tokens, label, edges=None, *, layers=None, heads=None, max_rows: int = 64) -> AttentionKnockout:
+        """Which coarser scales a scale needs -> AttentionKnockout (per-token values; see there).
+
+        attention_profile reports where the attention mass goes; mass is not dependence.  Here an edge of the block-causal graph is removed:
+        per entry one teacher-forced row in which the queries of scale q may not read the keys (and values) of scale k, compared with the clean
+        row of the same image.  An elementary edge is (q, k) with 0 <= k <= q < S, cut in the blocks of `layers` and the heads of `heads`
+        (None: all; strictly increasing indices otherwise); (q, k, layer) and (q, k, layer, head) name one block, or one head of one block,
+        instead.  The keys of scale k stay in the cache: later scales read them unless their own edge is cut too.  An entry of `edges` is an
+        elementary edge or a tuple of them applied together in one row; None: every (q, k) with k < q, then (q, q) for q >= 1 (54 rows at 10
+        scales).  ValueError before the tokens are touched for an entry that leaves some (query scale, block, head) without a visible key
+        ((0, 0), or all of (q, 0) .. (q, q) together), that names an edge out of range, or that cuts the same edge twice.  gt_tokens: (N, L)
+        integer tokens, teacher-forced as in evaluate; label: an int or (N,) class ids in [0, num_classes], used as given; max_rows (>= 2: the
+        clean row and one entry's row) bounds the rows of one transformer pass, and no value depends on it.
+        On the HIP path (the conditions of token_log_likelihood; f32 only: under a 16-bit precision ValueError) the rows of a sweep are
+        ordinary rows of ordinary passes: where a row's mask is not full, varhip_attn_keysel_f32 runs the attention over the visible key scales
+        only (hidden keys are not read), varhip_token_lens_f32 reduces every row against its image's clean row behind each scale's head, and
+        no logits tensor is made; the clean row's nll / pred / rank are evaluate's bit for bit.  Elsewhere attention_knockout_torch runs the
+        same definitions on the module stack, one pass per row (with prog_si >= 0 over the scales 0 .. prog_si)."""
+        dev = self.lvl_1L.device
+        gt = self._token_shape(gt_tokens)
+        N = gt.shape[0]
+        lab = A.labels_1d(label, N, f'label must be an int or (N,) integer class ids, N = {N}', scalar=True)
+        layers, heads = A.block_layers(layers, self.depth), A.block_heads(heads, self.num_heads)
+        edges = A.knockout_edges(edges, len(self.patch_nums), layers, heads, self.depth, self.num_heads)
+        max_rows = A.integer(max_rows, 'max_rows must be an integer >= 2: the clean row and one row with a cut', 2)
+        self._token_label_range(gt, lab)
+        gt, lab = gt.to(dev, torch.int64), lab.to(dev, torch.int64)
+        cuts = A.knockout_masks(edges, self.num_heads)
+        if self._scoring_on_hip(gt):
+            r = self.engine().attention_knockout(gt, lab, cuts, max_rows)
+            return AttentionKnockout(edges, layers, heads, r['nll'], r['entropy'], r['kl'], r['pred'], r['rank'], self.patch_nums)
+        nsc = self.prog_si + 1 if self.prog_si >= 0 else len(self.patch_nums)
+        nll, ent, kl, pred, rank = attention_knockout_torch(self, gt, lab, cuts)
+        return AttentionKnockout(edges, layers, heads, nll.float(), ent.float(), kl.float(), pred, rank, self.patch_nums[:nsc])
 
     @staticmethod
     def _prior_arg(prior, N: int, K: int) -> torch.Tensor:
