@@ -949,6 +949,67 @@ int varhip_adaln_block_keysel_f32(float* x, float* x2, float* xn, float* q, floa
                                   int B2, int l, int C, int H, int hidden, int pos0, int Lmax, float eps,
                                   const int32_t* ends, int S1, const int32_t* keymask, varhip_stream_t stream);
 
+/* ---- direct logit attribution (VAR.logit_attribution): the final logit of a token as a sum over what was written into the residual stream ----
+ * The head is W (LN(x) (1 + s) + sh) + b with an affine-free LayerNorm (var.py:118-124), the stream a plain sum (basic_var.py:157-158).  With
+ * r = W[a] - W[b'] (no rival: r = W[a]), g = r (1 + s), mu and sigma the LayerNorm statistics of the final x (biased variance, eps inside the
+ * root) and ghat = (g - mean(g)) / sigma:   r . (LN(x) (1 + s) + sh) + b_a - b_b' = ghat . x + konst,  konst = r . sh + b_a - b_b'.
+ *
+ * The target of every token of one scale of one pass.  logits: [R * l][V] fp32, row r, token t at r * l + t; gt[r * ld_gt + t] the target
+ * token a, against[r * ld_gt + t] (mode 2 only; NULL otherwise) the rival; rival and value share one addressing, out[r * ld_out + t].
+ *   mode 0   no rival:  rival = -1, value = z_a
+ *   mode 1   rival = the exact arg-max of z over v != a, the lowest index on ties;  value = z_a - z_rival (one fp32 subtraction)
+ *   mode 2   rival = against;  value = z_a - z_rival
+ * One pass over the row.  Nothing here depends on an order of summation (a maximum, an index, one subtraction), so the row is read with 16-byte
+ * loads where V % 4 == 0 and logits is 16-byte aligned and with scalar loads otherwise, to the same bits; rowlse.h's row pass (max and exp-sum)
+ * has nothing to add.  A token (or, in mode 2, a rival) outside [0, V) is never dereferenced: rival = -1, value = NaN.  A row that holds a NaN
+ * anywhere: rival = -1, value = NaN, in every mode.  V == 1 in mode 1 (no rival exists): rival = -1, value = NaN.
+ * V < 2^24.  VARHIP_EINVAL before any launch, nothing written: a NULL operand (against: in mode 2), a mode outside 0 .. 2, R, l, V < 1,
+ * ld_gt < l, ld_out < l. */
+/* pinned bit for bit against its host twin (tests/test_dla_kernels_gpu.py) */
+int varhip_dla_target_f32(const float* logits, const int64_t* gt, const int64_t* against, int64_t ld_gt, int mode, int R, int l, int V,
+                          int64_t* rival, float* value, int64_t ld_out, varhip_stream_t stream);
+/* the host twin: plain host code (no GPU), host pointers, the contract above row by row */
+/* pinned against the numpy restatement tests/dlaref.py (tests/test_dla_cpu.py) */
+int varhip_dla_target_host_f32(const float* logits, const int64_t* gt, const int64_t* against, int64_t ld_gt, int mode, int R, int l, int V,
+                               int64_t* rival, float* value, int64_t ld_out);
+/* The direction of every token of one scale of one pass.  x: the final residual stream [R * l][C] fp32 (dense); hn_scale[r * ld_hn + c] and
+ * hn_shift[r * ld_hn + c] the head's modulation s and sh of row r; head_w [V][C] and head_b [V] the head; tok_a[r * ld_tok + t] the target
+ * token, tok_b[r * ld_tok + t] the rival (tok_b == NULL: no rival for any token).  Outputs: ghat [R * l][C] fp32 (dense), konst and gx (double)
+ * at out[r * ld_out + t].  Per token, every operation below in float64 on the widened fp32 inputs (a product of two fp32 values is exact):
+ *   r_c = W[a][c] - W[b'][c]  (no rival: W[a][c]),   g_c = r_c * (1.0 + s_c)
+ *   S1 = sum_c x_c,  S2 = sum_c x_c * x_c,  G = sum_c g_c,  K = sum_c r_c * sh_c
+ *   mu = S1 / C,  var = max(S2 / C - mu * mu, 0),  sigma = sqrt(var + (double)eps),  mg = G / C          (correctly rounded division and root)
+ *   ghat_c = (float)((g_c - mg) / sigma)                                                  rounded to fp32 once
+ *   gx = sum_c (double)ghat_c * x_c  (with the rounded ghat),   konst = K + (b_a - b_b')   (no rival: K + b_a)
+ * The five sums have ONE order that depends on C alone, varhip_token_lens_f32's: lane i of 64 adds its elements j * 256 + 4 * i + c in
+ * ascending (j, c) order from +0.0, the 64 lanes by the xor butterfly 32 .. 1.  One wave per token, 16-byte loads and stores, no atomics.
+ * A target or a rival outside [0, V) is never dereferenced: that token's ghat, konst and gx are NaN.
+ * VARHIP_EINVAL before any launch, nothing written: a NULL operand (tok_b aside), R, l, C, V < 1, C % 4 != 0, ld_hn < C or ld_hn % 4 != 0,
+ * ld_tok < l, ld_out < l, a negative or NaN eps, x, hn_scale, hn_shift, head_w or ghat not 16-byte aligned, konst or gx not 8-byte aligned. */
+/* pinned bit for bit against its host twin (tests/test_dla_kernels_gpu.py) */
+int varhip_dla_direction_f32(const float* x, const float* hn_scale, const float* hn_shift, int64_t ld_hn, const float* head_w,
+                             const float* head_b, const int64_t* tok_a, const int64_t* tok_b, int64_t ld_tok, int R, int l, int C, int V,
+                             float eps, float* ghat, double* konst, double* gx, int64_t ld_out, varhip_stream_t stream);
+/* the host twin: plain host code (no GPU), host pointers, the operations above in the stated order: the kernel's bits (a NaN's payload aside) */
+/* pinned against the numpy restatement tests/dlaref.py (tests/test_dla_cpu.py) */
+int varhip_dla_direction_host_f32(const float* x, const float* hn_scale, const float* hn_shift, int64_t ld_hn, const float* head_w,
+                                  const float* head_b, const int64_t* tok_a, const int64_t* tok_b, int64_t ld_tok, int R, int l, int C,
+                                  int V, float eps, float* ghat, double* konst, double* gx, int64_t ld_out);
+/* Segmented row dots in float64: out[m * nseg + s] = sum over the columns j of segment s (width C / nseg) of (double)a[m * lda + j] *
+ * (double)b[m * ldb + j], m < M.  ldb == 0 reads one vector b for every row (a bias).  nseg == 1: ghat against a kept stream; nseg == H: u
+ * against the attention output, head by head.  The products are exact; the sum has ONE order that depends on (C, nseg) alone: with q = C /
+ * nseg / 4 the segment's groups of four columns and P the largest power of two <= min(64, q), lane i of P adds the groups i, i + P, ... in
+ * ascending order, the four columns of a group in order, from +0.0; the P lanes by the xor butterfly P / 2 .. 1.  A wave works on 64 / P
+ * consecutive (row, segment) pairs.  A bandwidth kernel: 16-byte loads, consecutive lanes on consecutive groups, 8 flops per 32 bytes; it is
+ * bounded by the 4 M C (ldb == 0) or 8 M C bytes it reads.
+ * VARHIP_EINVAL before any launch, nothing written: a NULL operand, M, C or nseg < 1, C % nseg != 0, a segment width that is no multiple
+ * of 4, lda < C, ldb neither 0 nor >= C, lda or ldb no multiple of 4, a or b not 16-byte aligned, out not 8-byte aligned. */
+/* pinned bit for bit against its host twin (tests/test_dla_kernels_gpu.py) */
+int varhip_rowdot_seg_f64(const float* a, int64_t lda, const float* b, int64_t ldb, int M, int C, int nseg, double* out, varhip_stream_t stream);
+/* the host twin: plain host code (no GPU), host pointers, the stated order */
+/* pinned against the numpy restatement tests/dlaref.py (tests/test_dla_cpu.py) */
+int varhip_rowdot_seg_host_f64(const float* a, int64_t lda, const float* b, int64_t ldb, int M, int C, int nseg, double* out);
+
 /* ==== 16-bit-input throughput mode ("f16") ===================================================================
  * The reference's harness runs the path under torch.autocast('cuda', dtype=torch.float16) (demo_sample.py:66-68): every F.linear of
  * basic_var.py then computes in fp16 and attention takes the flash path with fp16 q/k/v (basic_var.py:97,113).  These entry points are

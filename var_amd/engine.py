@@ -2424,6 +2424,107 @@ class SamplingEngine(_Engine):
             self._tf_pass(p, head=head, after_block=keep)
         return out
 
+    # -- the final logit as a sum over heads and MLPs (VAR.logit_attribution) ------------------------------------------------------------
+    DLA_MODE = dict(gt=0, margin=1, against=2)         # the `mode` of varhip_dla_target_f32
+
+    @torch.no_grad()
+    def logit_attribution(self, gt_tokens: torch.Tensor, label_N: torch.Tensor, mode: str, against: Optional[torch.Tensor], layers: tuple,
+                          max_rows: int, _tap=None) -> dict:
+        """VAR.logit_attribution on the HIP path -> dict(value, konst, embed, rest, residual (N, L) fp32, attn, mlp, attn_bias (N, D', L) fp32,
+        head (N, D', H, L) fp32, rival (N, L) int64).  gt_tokens (N, L) int64, label_N (N,) int64; mode 'gt' | 'margin' | 'against' with
+        against (N, L) int64; layers: the selected block indices, ascending; all validated by the caller (against is NOT range-checked: the
+        kernels answer an out-of-range rival with NaN).  The images run teacher-forced in passes of at most max_rows rows, one row per image, as
+        in evaluate.  Per scale the residual stream in front of every selected block and behind it (shared where two selected blocks follow one
+        another), the stream behind its attention residual (ws['x2'] when the block returns) and its proj input (ws['att']) are copied into the
+        call's stash.  Behind the scale's head varhip_dla_target_f32 reads the target off ws['lg'], varhip_dla_direction_f32 makes ghat, konst and
+        ghat . x from the final stream, and per selected block the product ghat * gamma1 (one torch multiply: one fp32 rounding per element),
+        u = (ghat * gamma1) proj.weight (varhip_gemm_nt_f32 on a transposed copy of proj.weight, made at the start of the call) and
+        varhip_rowdot_seg_f64 on (ghat, every kept stream), (u, att) per head and (ghat * gamma1, proj.bias) give float64 dots.  The terms are
+        their differences in float64 (torch, element-wise), rounded to fp32 once.  The stash (at most 3 D' + 1 buffers of R lmax x C fp32), the
+        transposed weights and the dots live for the call only.  _tap (tests): called after a stream sync with a dict of clones of everything
+        the reductions of a scale read, and of u, and (si, cur, l)."""
+        var = self.var
+        tf = self._tf_begin(label_N, gt_tokens, 'logit_attribution runs in f32: the {} workspaces hold 16-bit activations',
+                            lambda tf: self._check_labels(tf.lab))
+        w = self.w                                                    # (behind _tf_begin: it refreshes the weight table)
+        dev, gt = tf.dev, tf.gt
+        L, V, C, H, depth = var.L, var.V, var.C, var.num_heads, var.depth
+        N, Dn = gt.shape[0], len(layers)
+        kmode = self.DLA_MODE[mode]
+        against = None if against is None else against.to(dev, torch.int64).contiguous()
+        slot = {bi: d for d, bi in enumerate(layers)}
+        # stream point k: the stream in front of block k (= behind block k - 1); point `depth` is ws['x'] at the head and needs no copy
+        pt = {k: i for i, k in enumerate(sorted(({0} | set(layers) | {bi + 1 for bi in layers}) - {depth}))}
+        f = lambda *s: torch.empty(N, *s, dtype=torch.float32, device=dev)
+        out = dict(value=f(L), konst=f(L), embed=f(L), rest=f(L), residual=f(L), attn=f(Dn, L), mlp=f(Dn, L), attn_bias=f(Dn, L), head=f(Dn, H, L),
+                   rival=torch.empty(N, L, dtype=torch.int64, device=dev))
+        projT = {bi: w['blocks'][bi]['proj_w'].t().contiguous() for bi in layers}          # u = gg projT^T on the NT GEMM; freed with the call
+        st = None
+
+        def block(p, blk, bi, si, cur, l):
+            n = p.R * l
+            if bi in pt:
+                st.pts[pt[bi], :n].copy_(p.ws['x'][:n])
+            self.block(blk, p.ws, bi, p.ws['x'], p.ws['x2'], p.R, l, cur, p.ws['Lmax'])
+            if bi in slot:
+                st.mid[slot[bi], :n].copy_(p.ws['x2'][:n])
+                st.att[slot[bi], :n].copy_(p.ws['att'][:n])
+
+        def head(p, si, cur, l):
+            ws, R, i0 = p.ws, p.R, p.i0
+            n = R * l
+            hn = ws['hn']
+            g_, riv = gt[i0:, cur:], out['rival'][i0:, cur:]
+            hip.call('dla_target_f32', ws['lg'], g_, None if against is None else against[i0:, cur:], L, kmode, R, l, V, riv, out['value'][i0:, cur:], L)
+            hip.call('dla_direction_f32', ws['x'], hn, hn[:, C:], 2 * C, w['head_w'], w['head_b'], g_, None if kmode == 0 else riv, L, R, l, C, V,
+                     var.norm_eps, st.ghat, st.konst, st.dpt[-1], l)
+            for k, i in pt.items():
+                hip.call('rowdot_seg_f64', st.ghat, C, st.pts[i], C, n, C, 1, st.dpt[i])
+            g1 = {}
+            for bi in layers:
+                d, blk = slot[bi], w['blocks'][bi]
+                hip.call('rowdot_seg_f64', st.ghat, C, st.mid[d], C, n, C, 1, st.dmid[d])
+                ada, ld = ws['ada_view'][bi]
+                g1[bi] = torch.as_strided(ada, (R, 1, C), (ld, 0, 1), ada.storage_offset())          # gamma1 of every row
+                torch.mul(st.ghat[:n].view(R, l, C), g1[bi], out=st.gg[:n].view(R, l, C))
+                self.gemm(st.gg, projT[bi], None, st.u, n)
+                hip.call('rowdot_seg_f64', st.u, C, st.att[d], C, n, C, H, st.dhead[d])
+                hip.call('rowdot_seg_f64', st.gg, C, blk['proj_b'], 0, n, C, 1, st.dbias[d])
+                if _tap is not None:
+                    torch.cuda.current_stream().synchronize()
+                    _tap(dict(block=bi, u=st.u[:n].clone(), gg=st.gg[:n].clone(), g1=g1[bi].reshape(R, C).clone(), mid=st.mid[d, :n].clone(),
+                              att=st.att[d, :n].clone()), (si, cur, l))
+            xf = st.dpt[-1][:n]
+            at = lambda k: xf if k == depth else st.dpt[pt[k]][:n]
+            embed = at(0)
+            rest = xf - embed
+            img = lambda t: t.view(R, l).to(torch.float32)
+            for bi in layers:
+                d = slot[bi]
+                attn, mlp = st.dmid[d][:n] - at(bi), at(bi + 1) - st.dmid[d][:n]
+                rest = rest - (attn + mlp)
+                out['attn'][i0:i0 + R, d, cur:cur + l] = img(attn)
+                out['mlp'][i0:i0 + R, d, cur:cur + l] = img(mlp)
+                out['attn_bias'][i0:i0 + R, d, cur:cur + l] = img(st.dbias[d][:n])
+                out['head'][i0:i0 + R, d, :, cur:cur + l] = st.dhead[d][:n * H].view(R, l, H).permute(0, 2, 1).to(torch.float32)
+            out['embed'][i0:i0 + R, cur:cur + l] = img(embed)
+            out['rest'][i0:i0 + R, cur:cur + l] = img(rest)
+            out['konst'][i0:i0 + R, cur:cur + l] = img(st.konst[:n])
+            out['residual'][i0:i0 + R, cur:cur + l] = img(out['value'][i0:i0 + R, cur:cur + l].double().reshape(-1) - (st.konst[:n] + xf))
+            if _tap is not None:
+                torch.cuda.current_stream().synchronize()
+                _tap(dict(block=None, lg=ws['lg'][:n].clone(), x=ws['x'][:n].clone(), hn=hn[:R].clone(), ghat=st.ghat[:n].clone(),
+                          pts={k: st.pts[i, :n].clone() for k, i in pt.items()}, i0=i0, R=R), (si, cur, l))
+        for p in self._tf_rows(tf.lab, tf.xin, max_rows):
+            if st is None:                                            # (behind the workspace, sized by the passes' row count)
+                M = p.R * var.patch_nums[-1] ** 2
+                e32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+                e64 = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)
+                st = SimpleNamespace(pts=e32(len(pt), M, C), mid=e32(Dn, M, C), att=e32(Dn, M, C), ghat=e32(M, C), gg=e32(M, C), u=e32(M, C),
+                                     dpt=e64(len(pt) + 1, M), dmid=e64(Dn, M), dbias=e64(Dn, M), dhead=e64(Dn, M * H), konst=e64(M))
+            self._tf_pass(p, head=head, block=block)
+        return out
+
     # -- head / MLP ablation and activation patching (VAR.patch_effects) ----------------------------------------------------------------
     PATCH_SRC = dict(zero=-1, mean=-2)                 # the `src` of varhip_act_patch_f32's directives; 'donor': the donor row's index
 

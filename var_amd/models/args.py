@@ -131,6 +131,22 @@ def block_layers(layers, depth: int) -> tuple:
     return tuple(int(b) for b in layers)
 
 
+ATTRIBUTION_TARGETS = ('gt', 'margin')
+
+
+def attribution_target(target, against, N: int, L: int) -> tuple:
+    """the `target` and `against` of VAR.logit_attribution -> (target, against as an (N, L) integer tensor or None).  The rival's range is
+    not checked: an out-of-range rival is answered per token (NaN, rival -1), never dereferenced"""
+    if target not in ATTRIBUTION_TARGETS:
+        raise ValueError(f"target must be one of {ATTRIBUTION_TARGETS}, got {target!r}")
+    if against is None:
+        return target, None
+    riv = torch.as_tensor(against)
+    if riv.dim() != 2 or tuple(riv.shape) != (N, L) or not _integer_tensor(riv):
+        raise ValueError(f'against must be None or an ({N}, {L}) integer tensor of rival token ids')
+    return target, riv
+
+
 PATCH_MODES = ('zero', 'mean', 'donor')
 
 

@@ -545,6 +545,143 @@ def logit_lens_torch(var, gt: torch.Tensor, label: torch.Tensor, layers: tuple, 
     return tuple(torch.cat(f) for f in zip(*parts))
 
 
+class LogitAttribution:
+    """VAR.logit_attribution's result: the final logit of every token as a sum over what each head and each MLP wrote into the residual stream
+    (direct logit attribution), on the model's device.  With a the target token, b' the rival (none: r = W[a]), r = W[a] - W[b'], s and sh the
+    head's modulation, sigma the LayerNorm deviation of the final stream x and ghat = (r (1 + s) - mean(r (1 + s))) / sigma:
+      value      (N, L) fp32        z_a, or z_a - z_b', read from the real logits row
+      konst      (N, L) fp32        r . sh + b_a - b_b'
+      embed      (N, L) fp32        ghat . (the stream in front of block 0: first map or word embedding, plus level and position)
+      attn, mlp  (N, D', L) fp32    ghat . (what block layers[d]'s attention / MLP branch added to the stream)
+      head       (N, D', H, L) fp32 the part of attn that head h wrote;  attn_bias (N, D', L): the part proj's bias wrote
+      rest       (N, L) fp32        ghat . x - embed - sum over the selected blocks of (attn + mlp): the blocks `layers` leaves out
+      residual   (N, L) fp32        value - (konst + ghat . x): what the fp32 head GEMM and the frozen sigma leave unexplained
+      rival      (N, L) int64       b', -1 where there is none (target 'gt', or a token whose target or rival is out of range: its values are NaN)
+      layers (the D' block indices), patch_nums: the scales the result covers
+    Each fp32 value is rounded once from a float64 quantity.  The methods run in PyTorch with float64 sums."""
+    TERMS = ('value', 'konst', 'embed', 'rest', 'residual', 'attn', 'mlp', 'attn_bias', 'head')
+    __slots__ = TERMS + ('rival', 'layers', 'patch_nums')
+
+    def __init__(self, layers, patch_nums, rival, **terms):
+        self.layers, self.patch_nums, self.rival = tuple(layers), tuple(patch_nums), rival
+        for k in self.TERMS:
+            setattr(self, k, terms[k])
+
+    def _spans(self) -> list:
+        ends = np.cumsum([pn * pn for pn in self.patch_nums]).tolist()
+        return list(zip([0] + ends[:-1], ends))
+
+    def head_matrix(self) -> torch.Tensor:
+        """(D', H) float64: every head's term, the mean over the images and the tokens"""
+        return self.head.double().mean(dim=(0, 3))
+
+    def per_scale(self) -> dict:
+        """{term: float64 means over the images and the tokens of each scale, the scale last: (S,), (D', S) or (D', H, S)}"""
+        return {k: torch.stack([getattr(self, k)[..., b:e].double().mean(dim=(0, -1)) for b, e in self._spans()], -1) for k in self.TERMS}
+
+    def centered(self) -> 'LogitAttribution':
+        """every term minus its mean over the tokens of its scale and image (float64, rounded to fp32 once): the terms relative to the mean
+        token of the scale"""
+        out = {}
+        for k in self.TERMS:
+            x = getattr(self, k).double()
+            out[k] = torch.cat([x[..., b:e] - x[..., b:e].mean(-1, keepdim=True) for b, e in self._spans()], -1).to(torch.float32)
+        return LogitAttribution(self.layers, self.patch_nums, self.rival, **out)
+
+    def completeness(self) -> dict:
+        """{'residual': max |residual|, 'heads': max |sum_h head + attn_bias - attn|} as floats, over the tokens whose values are not NaN"""
+        gap = self.head.double().sum(2) + self.attn_bias.double() - self.attn.double()
+        fin = lambda t: t[~torch.isnan(t)]
+        mx = lambda t: float(fin(t).abs().max()) if fin(t).numel() else 0.0
+        return dict(residual=mx(self.residual.double()), heads=mx(gap))
+
+    def __repr__(self):
+        N, D, H, L = self.head.shape
+        return f'LogitAttribution(images={N}, layers={self.layers}, heads={H}, tokens={L})'
+
+
+def logit_attribution_torch(var, gt: torch.Tensor, label: torch.Tensor, target: str = 'gt', against: Optional[torch.Tensor] = None, layers=None,
+                            max_rows: int = 64) -> dict:
+    """VAR.logit_attribution's definitions in PyTorch on the module stack (any device; the arithmetic follows the parameters' dtype, float64
+    included; prog_si >= 0: the scales 0 .. prog_si): the masked teacher-forced pass with forward hooks on every selected block's attention
+    (its branch), on its proj (the input, head by head) and on its MLP.  Unlike the HIP route it takes a branch's term from the hooked branch
+    times its gate, not from a difference of streams.  gt (N, L) tokens, label (N,) labels, against None or (N, L) rivals -> the dict of
+    LogitAttribution's terms in the parameters' dtype, each over the ed tokens the pass covers, and rival int64.  Dropout and drop path must
+    be off (eval mode, or zero rates): the stream is then the plain sum the decomposition needs."""
+    ed = var.begin_ends[var.prog_si][1] if var.prog_si >= 0 else var.L
+    dt, dev = var.pos_start.dtype, gt.device
+    C, H, V = var.C, var.num_heads, var.V
+    layers = tuple(range(var.depth)) if layers is None else tuple(layers)
+    x_all = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[:, b:e] for b, e in var.begin_ends])[:, :ed - var.first_l].to(dt)
+    mask = var.attn_bias_for_masking[:, :, :ed, :ed].to(dt)
+    W, bias = var.head.weight, var.head.bias
+    eps = var.head_nm.ln_wo_grad.eps
+    parts = []
+    for i0 in range(0, gt.shape[0], int(max_rows)):
+        lab, g = label[i0:i0 + max_rows], gt[i0:i0 + max_rows, :ed]
+        B = lab.shape[0]
+        caught, hooks = {}, []
+        for bi in layers:
+            blk = var.blocks[bi]
+            hooks += [blk.attn.register_forward_hook(lambda m, i, o, bi=bi: caught.__setitem__(('attn', bi), o)),
+                      blk.attn.proj.register_forward_pre_hook(lambda m, i, bi=bi: caught.__setitem__(('att', bi), i[0])),
+                      blk.ffn.register_forward_hook(lambda m, i, o, bi=bi: caught.__setitem__(('mlp', bi), o))]
+        try:
+            cond = var.class_emb(lab)
+            sos = cond.unsqueeze(1).expand(B, var.first_l, -1) + var.pos_start.expand(B, var.first_l, -1)
+            x = torch.cat((sos, var.word_embed(x_all[i0:i0 + max_rows])), dim=1) if ed > var.first_l else sos
+            e = x = x + var.lvl_embed(var.lvl_1L[:, :ed].expand(B, -1)) + var.pos_1LC[:, :ed]
+            cgs = var.shared_ada_lin(cond)
+            for blk in var.blocks:
+                x = blk(x=x, cond_BD=cgs, attn_bias=mask)
+        finally:
+            for h in hooks:
+                h.remove()
+        s, sh = var.head_nm.ada_lin(cond).view(-1, 1, 2, C).unbind(2)
+        z = var.head(var.head_nm(x, cond))
+        za = z.gather(-1, g.unsqueeze(-1)).squeeze(-1)
+        ok = ~torch.isnan(z).any(-1)
+        if against is not None:
+            rival = against[i0:i0 + max_rows, :ed].to(dev, torch.int64)
+            ok = ok & (rival >= 0) & (rival < V)
+        elif target == 'margin':
+            zm = z.masked_fill(torch.nn.functional.one_hot(g, V).bool(), float('-inf'))
+            idx = torch.arange(V, device=dev).expand_as(zm)
+            rival = torch.where(zm == zm.amax(-1, keepdim=True), idx, torch.full_like(idx, V)).amin(-1)      # the lowest index on ties
+            ok = ok & (rival < V)
+        else:
+            rival = None
+        r, kb, value = W[g], bias[g], za
+        if rival is not None:
+            rb = rival.clamp(0, V - 1)
+            r, kb, value = r - W[rb], kb - bias[rb], za - z.gather(-1, rb.unsqueeze(-1)).squeeze(-1)
+        gv = r * (1 + s)
+        sigma = (x.var(-1, unbiased=False, keepdim=True) + eps).sqrt()
+        ghat = (gv - gv.mean(-1, keepdim=True)) / sigma
+        dot = lambda a: (ghat * a).sum(-1)
+        gx = dot(x)
+        o = dict(value=value, konst=(r * sh).sum(-1) + kb, embed=dot(e), attn=[], mlp=[], attn_bias=[], head=[])
+        o['residual'] = value - (o['konst'] + gx)
+        rest = gx - o['embed']
+        for bi in layers:
+            blk = var.blocks[bi]
+            g1, g2 = blk._six(cgs)[:2]
+            o['attn'].append(dot(caught[('attn', bi)] * g1))
+            o['mlp'].append(dot(caught[('mlp', bi)] * g2))
+            o['attn_bias'].append(dot(blk.attn.proj.bias * g1))
+            u = (ghat * g1) @ blk.attn.proj.weight
+            o['head'].append((u * caught[('att', bi)]).view(B, ed, H, C // H).sum(-1).transpose(1, 2))
+            rest = rest - (o['attn'][-1] + o['mlp'][-1])
+        o['rest'] = rest
+        for k in ('attn', 'mlp', 'attn_bias', 'head'):
+            o[k] = torch.stack(o[k], 1)
+        for k in o:
+            o[k] = torch.where(ok.view(B, *([1] * (o[k].dim() - 2)), ed), o[k], torch.full_like(o[k], float('nan')))
+        o['rival'] = torch.full_like(g, -1) if rival is None else torch.where(ok, rival, torch.full_like(rival, -1))
+        parts.append(o)
+    return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+
 class PatchEffects:
     """VAR.patch_effects' result: what an image's prediction loses when a head, an attention layer or an MLP is ablated or patched, per token,
     on the model's device.  Index 0 of the second axis is the clean row, index j + 1 the row with the intervention sites[j]; with z the row's
@@ -1902,6 +2039,43 @@ class VAR(nn.Module):
             return LogitLens(layers, r['nll'], r['entropy'], r['kl'], r['pred'], r['rank'], self.patch_nums)
         nsc = self.prog_si + 1 if self.prog_si >= 0 else len(self.patch_nums)
         return LogitLens(layers, *logit_lens_torch(self, gt, lab, layers, int(max_rows)), self.patch_nums[:nsc])
+
+    @torch.no_grad()
+    def logit_attribution(self, gt_tokens, label, *, target: str = 'gt', against=None, layers=None, max_rows: int = 64) -> LogitAttribution:
+        """What every head and every MLP wrote into a token's final logit -> LogitAttribution (per-token terms; see there).
+
+        Direct logit attribution: VAR's residual stream is a plain sum (reference basic_var.py:157-158) and its head an affine-free LayerNorm,
+        a modulation and a linear map (var.py:118-124), so with the final token's deviation frozen the logit is linear in every summand of
+        the stream and splits into one term per head, per proj bias, per MLP and for the embedding, in ONE teacher-forced pass per image.
+        patch_effects answers another question (the total effect of removing a site, everything downstream included) with one row per site.
+        gt_tokens: (N, L) integer tokens, teacher-forced as in evaluate; label: an int or (N,) class ids in [0, num_classes], used as given;
+        target 'gt': the logit of the ground-truth token; 'margin': that logit minus the greatest other logit (the lowest index on ties);
+        against: None or (N, L) integer rival tokens, which give the rival explicitly and imply the difference (a rival outside [0, V) is
+        never dereferenced: that token's values are NaN and its rival -1); layers: None (all blocks) or strictly increasing block indices,
+        the blocks whose terms are reported (`rest` collects the others); max_rows bounds the images of one transformer pass, and no value
+        depends on it.
+        On the HIP path (the conditions of token_log_likelihood; f32 only: under a 16-bit precision ValueError) every selected block's streams
+        and proj input are kept per scale, and behind the scale's head varhip_dla_target_f32, varhip_dla_direction_f32, one C x C GEMM per
+        selected block and varhip_rowdot_seg_f64 reduce them in float64: no tensor grows with the tokens, the blocks and the width at once.
+        Elsewhere logit_attribution_torch runs the same definitions on hooked modules in the parameters' dtype (with prog_si >= 0 over the
+        scales 0 .. prog_si)."""
+        dev = self.lvl_1L.device
+        gt = self._token_shape(gt_tokens)
+        N = gt.shape[0]
+        lab = A.labels_1d(label, N, f'label must be an int or (N,) integer class ids, N = {N}', scalar=True)
+        max_rows = A.integer(max_rows, 'max_rows must be an integer >= 1', 1)
+        layers = A.block_layers(layers, self.depth)
+        target, against = A.attribution_target(target, against, N, self.L)
+        self._token_label_range(gt, lab)
+        gt, lab = gt.to(dev, torch.int64), lab.to(dev, torch.int64)
+        against = None if against is None else against.to(dev, torch.int64)
+        if self._scoring_on_hip(gt):
+            r = self.engine().logit_attribution(gt, lab, target if against is None else 'against', against, layers, max_rows)
+            return LogitAttribution(layers, self.patch_nums, **r)
+        nsc = self.prog_si + 1 if self.prog_si >= 0 else len(self.patch_nums)
+        r = logit_attribution_torch(self, gt, lab, target, against, layers, max_rows)
+        rival = r.pop('rival')
+        return LogitAttribution(layers, self.patch_nums[:nsc], rival, **{k: v.to(torch.float32) for k, v in r.items()})
 
     @torch.no_grad()
     def patch_effects(self, gt_tokens, label, sites=None, *, mode: str = 'mean', donor_label=None, scales=None, max_rows: int = 64) -> PatchEffects:
