@@ -652,6 +652,56 @@ int varhip_attn_profile_host_f32(const float* q, const float* kcache, int B2, in
                                  int pn, int radius, int64_t* share_sum, int64_t ld_row, int64_t ld_head, int32_t* nan_count,
                                  int32_t* tokens, int64_t ld_tok_row, int64_t ld_tok_head);
 
+/* ---- where a token looks: rows of softmax(QK^T) and row vectors pushed through it (VAR.attention_maps, VAR.attention_rollout) ----------------
+ * For a handful of target tokens neither the (L, L) matrix P = softmax(QK^T) of reference basic_var.py:107-117 nor a product of `depth` of
+ * them is needed: a target's raw map is one row of P, its rollout (Abnar & Zuidema) a row vector pushed through the layers,
+ * r <- (1 - alpha) r + alpha r Pbar_l with Pbar_l the head mean, and r P is formed tile by tile from q . k.  Two launches per layer.
+ * Operands: q [B][Lq][H*64], the queries of ALL positions 0 .. Lq-1 of one block as varhip_gemm_qkv_f32 leaves them (normalised and scaled;
+ * the caller stashes them scale by scale); kcache [B][H][Lmax][64], varhip_attn_cached_f32's layout, keys 0 .. Lq-1 valid.  ends: a HOST array of
+ * S1 entries with the rules of varhip_attn_profile_f32 (strictly increasing, ends[0] >= 1, S1 in [1, 16]) and ends[S1-1] == Lq: query t belongs
+ * to the scale i with ends[i-1] <= t < ends[i] and sees the keys j < ends[i].  No key at or beyond Lq is read.
+ *
+ * varhip_attn_rowstats_f32: m[(b*H + h)*Lq + t] and rinv[(b*H + h)*Lq + t], per (row, head, query):
+ *   1. s_j = q_t . k_j for the visible j: one fp32 fma chain over the 64 channels in the 4-interleaved order 0,4,1,5,2,6,3,7, 8,12,... of
+ *      varhip_attn_cached_f32: the bits that kernel sees.
+ *   2. m = max_j s_j over the visible keys (exact, order-free; a NaN score is left out of it).
+ *   3. two partial sums of vm_exp_le0(s_j - m) (include/var_math.h): A over the visible keys with (j & 4) == 0, B over those with (j & 4) != 0,
+ *      each from +0 in ascending j with one rounding per add; rinv = 1.0f / (A + B), one rounding each.  The sum is >= 1 (the maximal key adds 1).
+ *   4. A query with a NaN score, or with a maximum that is not finite, gets rinv = NaN (m as in 2.), and 1 is added to nan_count[b*H + h] (an
+ *      integer atomic; the caller zeroes nan_count, a second call adds again).
+ *
+ * varhip_attn_flow_f32: r [B][T][Lq] fp32, 1 <= T <= 32; out must not overlap r.  With p_h[t][j] = vm_exp_le0(s_tj - m_t) * rinv_t (one rounding
+ * for the subtraction, one for the product, s_tj as in 1.) where query t sees key j, and exactly +0 where it does not:
+ *   per_head = 1: out[((b*H + h)*T + s)*Lq + j] = acc_h[s][j];  alpha is ignored
+ *   per_head = 0: out[(b*T + s)*Lq + j] = fma(alpha, hsum[s][j] * (1.0f / (float)H), (1.0f - alpha) * r[b][s][j])
+ * Arithmetic contract (what makes the kernel and the host twin bit-equal, per (b, s, j)):
+ *   5. acc_h[s][j] is ONE fp32 fma chain acc = fma(r[b][s][t], p_h[t][j], acc) from +0 over the queries in tiles of 32, tiles ascending, inside a
+ *      tile in the 4-interleaved order t = 0,4,1,5,2,6,3,7, 8,12,... (the channel order of 1.: what an MFMA 32x32x2 consumes when p comes straight
+ *      out of the score registers).  The chain starts at tile floor(b0 / 32), b0 the first query of the scale that holds key 32 floor(j / 32), the
+ *      first key of j's tile: the tiles before it hold no query that sees any key of j's tile and are skipped, their terms are NOT part of the
+ *      chain (this matters for a non-finite r only).  From there every term is part of it, those with p = +0 and the padding of the last tile
+ *      (r = p = +0) included: a term with a finite r and p = +0 leaves the bits.
+ *   6. hsum[s][j] = ((+0 + acc_0) + acc_1) + ... in ascending h, one rounding per add; then one rounding each for hsum * (1/H), 1 - alpha,
+ *      (1 - alpha) * r, and the final fma.  alpha = 0 returns r bit for bit where hsum is finite (and r is not -0).
+ *   7. rinv_t = NaN makes p_h[t][j] NaN at every key query t sees, and 0 * NaN = NaN: such a query poisons out[b][(h)][s][j] for every s and every
+ *      j it sees, in its own row b (per_head = 1: and head h) only; the keys it does not see keep their values.
+ *   8. No floating-point atomics: a workgroup owns (b, 32 keys), a wave a head at a time, the heads are added by one wave in the order of 6.  The
+ *      result does not depend on the launch geometry or on arrival order; a target's output does not depend on T or on the other targets.
+ * A one-hot r with per_head = 1 gives rows of P: out[b][h][s][:] = p_h[t_s][:] exactly (1 * p + 0).
+ * VARHIP_EINVAL before any launch, nothing written: a NULL pointer, a size <= 0, Lq > Lmax, Lq > 4096, T > 32, S1 outside [1, 16], ends not as
+ * above, q or kcache not 16-byte aligned, B or H above 65535.  Both launches are timed under "other". */
+/* pinned bit for bit against their host twins and within derived bars of float64 (tests/test_attn_flow_kernels_gpu.py) */
+int varhip_attn_rowstats_f32(const float* q, const float* kcache, int B, int Lq, int H, int Lmax, const int32_t* ends, int S1,
+                             float* m, float* rinv, int32_t* nan_count, varhip_stream_t stream);
+int varhip_attn_flow_f32(const float* q, const float* kcache, const float* m, const float* rinv, const float* r, float* out, int B, int Lq, int H,
+                         int Lmax, const int32_t* ends, int S1, int T, int per_head, float alpha, varhip_stream_t stream);
+/* the host twins: plain host code (no GPU), host pointers, the contract above entry by entry: the kernels' bits */
+/* pinned against float64 (tests/test_attn_flow_cpu.py) */
+int varhip_attn_rowstats_host_f32(const float* q, const float* kcache, int B, int Lq, int H, int Lmax, const int32_t* ends, int S1,
+                                  float* m, float* rinv, int32_t* nan_count);
+int varhip_attn_flow_host_f32(const float* q, const float* kcache, const float* m, const float* rinv, const float* r, float* out, int B, int Lq,
+                              int H, int Lmax, const int32_t* ends, int S1, int T, int per_head, float alpha);
+
 /* ---- per-pixel class evidence (VAR.evidence_maps; fork create_heatmaps_for_classes of eval_prob.py / var_analysis.py / inpainting.py /
  * smoothing.py / var_size_analysis.py: per class and scale one bilinear F.interpolate, K full-size maps, matplotlib on the CPU) -----------
  * scores: per-token class scores, class c of image i at scores[i * ld_img + c * ld_cls + token].  The nscales selected scales are HOST arrays

@@ -2377,6 +2377,67 @@ class SamplingEngine(_Engine):
             share[..., si, si + 1] = 0
         return dict(share_q=share, nan_queries=nanq, tokens=tokens)
 
+    # -- where a token looks (VAR.attention_maps, VAR.attention_rollout) ----------------------------------------------------------------
+    @torch.no_grad()
+    def attention_flow(self, gt_tokens: torch.Tensor, label_N: torch.Tensor, targets: tuple, layers: tuple, max_rows: int,
+                       alpha: Optional[float] = None) -> dict:
+        """VAR.attention_maps (alpha None) and VAR.attention_rollout (alpha in [0, 1]) on the HIP path -> dict(rows (N, D', H, T, L) fp32 or flow
+        (N, T, L) fp32, nan_queries (N, D', H) int32).  gt_tokens (N, L) int64, label_N (N,) int64, targets: at most 32 flat token indices,
+        layers: the selected block indices, ascending; all validated by the caller.  The images run teacher-forced in passes of at most
+        max_rows rows, one row per image (no CFG rows, no head).  Behind every selected block of every scale its queries (ws['q']) go into a
+        stash (D', R, L, C) that lives for this call only; after the pass ws['kc'][bi] holds every block's keys, and per selected layer
+        varhip_attn_rowstats_f32 and varhip_attn_flow_f32 run once over all L queries: for the maps with a one-hot r and per_head = 1, for the
+        rollout from the last selected layer to the first with per_head = 0, each layer's output the next one's r."""
+        var = self.var
+        L, S, H, C = var.L, len(var.patch_nums), var.num_heads, var.C
+
+        def refusals(tf):
+            if L > self.ATTN_PROFILE_MAX_L or S > self.ATTN_PROFILE_MAX_S:
+                raise ValueError(f'attention maps and rollout take at most {self.ATTN_PROFILE_MAX_L} tokens and {self.ATTN_PROFILE_MAX_S} scales, '
+                                 f'got {L} and {S}')
+            self._check_labels(tf.lab)
+        tf = self._tf_begin(label_N, gt_tokens, 'attention maps and rollout run in f32: the {} workspaces hold 16-bit queries and keys', refusals)
+        dev = tf.dev
+        N, Dn, T = tf.gt.shape[0], len(layers), len(targets)
+        slot = {bi: d for d, bi in enumerate(layers)}
+        ends = torch.tensor([e for _, e in var.begin_ends], dtype=torch.int32)            # a host array: the launcher copies it
+        rpp = min(int(max_rows), N)
+        onehot = torch.zeros(rpp, T, L, dtype=torch.float32, device=dev)
+        onehot[:, torch.arange(T, device=dev), torch.tensor(targets, dtype=torch.int64, device=dev)] = 1.0
+        stash = torch.empty(Dn, rpp, L, C, dtype=torch.float32, device=dev)
+        m, rinv = (torch.empty(rpp, H, L, dtype=torch.float32, device=dev) for _ in range(2))
+        nanq = torch.zeros(N, Dn, H, dtype=torch.int32, device=dev)
+        if alpha is None:
+            out = torch.empty(N, Dn, H, T, L, dtype=torch.float32, device=dev)
+            rows = torch.empty(rpp, H, T, L, dtype=torch.float32, device=dev)
+        else:
+            out = torch.empty(N, T, L, dtype=torch.float32, device=dev)
+            ping = [torch.empty(rpp, T, L, dtype=torch.float32, device=dev) for _ in range(2)]
+
+        def tap(p, bi, si, cur, l):
+            d = slot.get(bi)
+            if d is not None:
+                stash[d, :p.R, cur:cur + l] = p.ws['q'][:p.R * l].view(p.R, l, C)
+        for p in self._tf_rows(tf.lab, tf.xin, max_rows):
+            ws, i0, R = p.ws, p.i0, p.R
+            self._tf_pass(p, after_block=tap)                             # no head: no logits are needed
+            r = onehot
+            for d in (range(Dn) if alpha is None else reversed(range(Dn))):
+                bi = layers[d]
+                cnt = torch.zeros(R, H, dtype=torch.int32, device=dev)
+                hip.call('attn_rowstats_f32', stash[d], ws['kc'][bi], R, L, H, ws['Lmax'], ends, S, m, rinv, cnt)
+                nanq[i0:i0 + R, d] = cnt
+                if alpha is None:
+                    hip.call('attn_flow_f32', stash[d], ws['kc'][bi], m, rinv, onehot, rows, R, L, H, ws['Lmax'], ends, S, T, 1, 0.0)
+                    out[i0:i0 + R, d] = rows[:R]
+                else:
+                    dst = ping[0] if r is not ping[0] else ping[1]
+                    hip.call('attn_flow_f32', stash[d], ws['kc'][bi], m, rinv, r, dst, R, L, H, ws['Lmax'], ends, S, T, 0, float(alpha))
+                    r = dst
+            if alpha is not None:
+                out[i0:i0 + R] = r[:R]
+        return {'rows' if alpha is None else 'flow': out, 'nan_queries': nanq}
+
     # -- every block's prediction against the final one (VAR.logit_lens) ----------------------------------------------------------------
     @torch.no_grad()
     def logit_lens(self, gt_tokens: torch.Tensor, label_N: torch.Tensor, layers: tuple, max_rows: int, _tap=None) -> dict:

@@ -131,6 +131,43 @@ def block_layers(layers, depth: int) -> tuple:
     return tuple(int(b) for b in layers)
 
 
+FLOW_MAX_TARGETS = 32
+
+
+def flow_targets(targets, patch_nums) -> tuple:
+    """the `targets` of attention_maps and attention_rollout -> 1 .. 32 flat token indices: an entry is a flat index in [0, L) or a
+    (scale, row, col) triple of a scale's grid"""
+    pns = tuple(patch_nums)
+    L = sum(pn * pn for pn in pns)
+    msg = (f'targets must be 1 to {FLOW_MAX_TARGETS} entries, each a flat token index in [0, {L}) or (scale, row, col) with scale in '
+           f'[0, {len(pns)}) and row, col inside that scale\'s grid')
+    targets = as_list(targets)
+    if is_int(targets):
+        targets = [targets]
+    if not isinstance(targets, (list, tuple)) or not 1 <= len(targets) <= FLOW_MAX_TARGETS:
+        raise ValueError(msg)
+    out = []
+    for t in targets:
+        t = as_list(t)
+        if is_int(t):
+            if not 0 <= t < L:
+                raise ValueError(msg)
+            out.append(int(t))
+        elif isinstance(t, (list, tuple)) and len(t) == 3 and all(is_int(v) for v in t):
+            si, y, x = (int(v) for v in t)
+            if not 0 <= si < len(pns) or not 0 <= y < pns[si] or not 0 <= x < pns[si]:
+                raise ValueError(msg)
+            out.append(sum(pn * pn for pn in pns[:si]) + y * pns[si] + x)
+        else:
+            raise ValueError(msg)
+    return tuple(out)
+
+
+def rollout_alpha(alpha) -> float:
+    """attention_rollout's alpha: the weight of the attention against the residual path, in [0, 1]"""
+    return real(alpha, 'alpha must be a number in [0, 1]', lambda v: 0.0 <= v <= 1.0)
+
+
 ATTRIBUTION_TARGETS = ('gt', 'margin')
 
 

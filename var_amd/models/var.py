@@ -463,6 +463,138 @@ def attention_profile_torch(var, gt: torch.Tensor, label: torch.Tensor, radius: 
     return share, nanq, tokens
 
 
+class _TokenMaps:
+    """what AttentionMaps and AttentionRollout share: a field (..., T, L) of per-target weights over the L key positions"""
+    __slots__ = ()
+    _FIELD = ''
+
+    def _begins(self) -> list:
+        b = [0]
+        for pn in self.patch_nums:
+            b.append(b[-1] + pn * pn)
+        return b
+
+    def scale_mass(self) -> torch.Tensor:
+        """(..., T, S) float64: every target's weight on the keys of each scale (0 above the target's own scale: block-causal)"""
+        x, b = getattr(self, self._FIELD).double(), self._begins()
+        return torch.stack([x[..., b0:b1].sum(-1) for b0, b1 in zip(b, b[1:])], -1)
+
+    def scale_maps(self, si: int) -> torch.Tensor:
+        """(..., T, pn, pn): every target's weights on the grid of scale si, a view of the field"""
+        si = A.integer(si, f'si must be a scale index in [0, {len(self.patch_nums)})', 0, len(self.patch_nums) - 1)
+        x, b, pn = getattr(self, self._FIELD), self._begins(), self.patch_nums[si]
+        return x[..., b[si]:b[si + 1]].unflatten(-1, (pn, pn))
+
+
+class AttentionMaps(_TokenMaps):
+    """VAR.attention_maps' result: which positions the target tokens read, per selected block and head, on the model's device.
+      rows         (N, D', H, T, L) fp32 [n, d, h, s, j]: softmax_j(q_t . k_j) of target s = token t over the keys it sees (those of its own and
+                   of the coarser scales), exactly +0 at the others: a row sums to 1
+      nan_queries  (N, D', H) int32: queries (of all L, targets or not) with a NaN score or no finite maximum; a target among them has a NaN row
+      targets (the T flat token indices), layers (the D' block indices), patch_nums
+    A row depends on its own image, block, head and target only: the same bits whatever max_rows, the batch neighbours, the other targets,
+    the other selected layers or the call history."""
+    __slots__ = ('rows', 'nan_queries', 'targets', 'layers', 'patch_nums')
+    _FIELD = 'rows'
+
+    def __init__(self, rows, nan_queries, targets, layers, patch_nums):
+        self.rows, self.nan_queries = rows, nan_queries
+        self.targets, self.layers, self.patch_nums = tuple(targets), tuple(layers), tuple(patch_nums)
+
+    def __repr__(self):
+        N, D, H, T, L = self.rows.shape
+        return f'AttentionMaps(images={N}, layers={D}, heads={H}, targets={T}, tokens={L})'
+
+
+class AttentionRollout(_TokenMaps):
+    """VAR.attention_rollout's result: where the target tokens' information comes from through all selected blocks (Abnar & Zuidema).
+      flow         (N, T, L) fp32 [n, s, j]: target s's one-hot row pushed through the selected layers from last to first,
+                   r <- (1 - alpha) r + alpha r Pbar_l, Pbar_l the head mean of softmax(QK^T) under the block-causal mask: non-negative, sums to 1
+      nan_queries  (N, D', H) int32 as in AttentionMaps; a NaN query that a target reaches makes that target's flow NaN at the keys it sees
+      targets, layers, alpha, patch_nums
+    flow is in evidence_maps' (N, K, L) score layout: evidence(**kw) draws it."""
+    __slots__ = ('flow', 'nan_queries', 'targets', 'layers', 'alpha', 'patch_nums')
+    _FIELD = 'flow'
+
+    def __init__(self, flow, nan_queries, targets, layers, alpha, patch_nums):
+        self.flow, self.nan_queries, self.alpha = flow, nan_queries, float(alpha)
+        self.targets, self.layers, self.patch_nums = tuple(targets), tuple(layers), tuple(patch_nums)
+
+    def evidence(self, **kw) -> 'EvidenceMaps':
+        """evidence_maps(flow, patch_nums, **kw): the rollout of every target over the image (one 'class' per target)"""
+        return evidence_maps(self.flow.contiguous(), self.patch_nums, **kw)
+
+    def __repr__(self):
+        N, T, L = self.flow.shape
+        return f'AttentionRollout(images={N}, layers={len(self.layers)}, targets={T}, tokens={L}, alpha={self.alpha:g})'
+
+
+def _attention_probs_torch(var, gt: torch.Tensor, label: torch.Tensor, layers: tuple):
+    """yields (n, d, P (H, L, L) float64, bad (H, L) bool) per image n and selected block layers[d], ascending: the dense block-causal
+    softmax(QK^T) of the module stack (q and k as in attention_profile_torch, in the parameters' dtype; from the scores on float64)"""
+    L = var.L
+    dt = var.pos_start.dtype
+    mask = var.attn_bias_for_masking[:, :, :L, :L].to(dt)
+    slot = {bi: d for d, bi in enumerate(layers)}
+    for n in range(gt.shape[0]):
+        cond = var.class_emb(label[n:n + 1])
+        sos = cond.unsqueeze(1).expand(1, var.first_l, -1) + var.pos_start.expand(1, var.first_l, -1)
+        x_in = var.vae_proxy[0].quantize.idxBl_to_var_input([gt[n:n + 1, b:e] for b, e in var.begin_ends])
+        x = torch.cat((sos, var.word_embed(x_in.to(dt))), dim=1) if L > var.first_l else sos
+        x = x + var.lvl_embed(var.lvl_1L[:, :L].expand(1, -1)) + var.pos_1LC[:, :L]
+        cond_or_gss = var.shared_ada_lin(cond)
+        for bi, blk in enumerate(var.blocks):
+            d = slot.get(bi)
+            if d is not None:
+                at = blk.attn
+                _, _, scale1, _, shift1, _ = blk._six(cond_or_gss)
+                q, k, _ = at._heads(blk.ln_wo_grad(x) * (scale1 + 1) + shift1)
+                if at.attn_l2_norm:
+                    q = torch.nn.functional.normalize(q, dim=-1) * at.scale_mul_1H11.clamp_max(at.max_scale_mul).exp()
+                    k = torch.nn.functional.normalize(k, dim=-1)
+                sc = ((q @ k.transpose(-1, -2)) * at.scale + mask)[0].double()                   # (H, L, L)
+                bad = torch.isnan(sc).any(-1) | ~torch.isfinite(sc.max(-1).values)
+                e = torch.exp(sc - sc.max(-1, keepdim=True).values)
+                yield n, d, e / e.sum(-1, keepdim=True), bad
+            x = blk(x=x, cond_BD=cond_or_gss, attn_bias=mask)
+
+
+def attention_maps_torch(var, gt: torch.Tensor, label: torch.Tensor, targets: tuple, layers: tuple):
+    """VAR.attention_maps' definition in PyTorch on the module stack (CPU models, non-HIP tensors): per image the dense masked softmax in float64,
+    its target rows -> (rows (N, D', H, T, L) fp32, nan_queries (N, D', H) int32)"""
+    dev = gt.device
+    N, H = gt.shape[0], var.num_heads
+    tg = torch.tensor(targets, dtype=torch.int64, device=dev)
+    rows = torch.zeros(N, len(layers), H, len(targets), var.L, dtype=torch.float32, device=dev)
+    nanq = torch.zeros(N, len(layers), H, dtype=torch.int32, device=dev)
+    for n, d, P, bad in _attention_probs_torch(var, gt, label, layers):
+        rows[n, d] = P[:, tg].float()
+        nanq[n, d] = bad.sum(-1).to(torch.int32)
+    return rows, nanq
+
+
+def attention_rollout_torch(var, gt: torch.Tensor, label: torch.Tensor, targets: tuple, layers: tuple, alpha: float):
+    """VAR.attention_rollout's definition in PyTorch on the module stack: per image the head mean of the dense masked softmax of every selected
+    block in float64, and the recurrence r <- (1 - alpha) r + alpha r Pbar from the last selected block to the first, from one-hot rows
+    -> (flow (N, T, L) fp32, nan_queries (N, D', H) int32)"""
+    dev = gt.device
+    N, H, L = gt.shape[0], var.num_heads, var.L
+    tg = torch.tensor(targets, dtype=torch.int64, device=dev)
+    flow = torch.zeros(N, len(targets), L, dtype=torch.float32, device=dev)
+    nanq = torch.zeros(N, len(layers), H, dtype=torch.int32, device=dev)
+    pbar = {}
+    for n, d, P, bad in _attention_probs_torch(var, gt, label, layers):
+        pbar[d] = P.mean(0)
+        nanq[n, d] = bad.sum(-1).to(torch.int32)
+        if d == len(layers) - 1:
+            r = torch.nn.functional.one_hot(tg, L).double()
+            for dd in reversed(range(len(layers))):
+                r = (1.0 - alpha) * r + alpha * (r @ pbar[dd])
+            flow[n] = r.float()
+            pbar = {}
+    return flow, nanq
+
+
 class LogitLens:
     """VAR.logit_lens's result: the prediction the trained head makes from the residual stream behind every selected block, per token, on the
     model's device.  With z the head's fp32 logits behind block layers[d], p their softmax, and pf the softmax of the final logits:
@@ -2011,6 +2143,56 @@ class VAR(nn.Module):
             raise ValueError('attention_profile covers every scale: prog_si must be < 0')
         share, nanq, tokens = attention_profile_torch(self, gt, lab, r_eff, layers, bool(return_tokens))
         return AttentionProfile(share, nanq, tokens, self.patch_nums, radius, layers)
+
+    def _flow_args(self, gt_tokens, label, targets, layers, max_rows):
+        """what attention_maps and attention_rollout check first -> (gt, lab on the device as int64, targets as flat indices, layers)"""
+        dev = self.lvl_1L.device
+        gt = self._token_shape(gt_tokens)
+        N = gt.shape[0]
+        lab = A.labels_1d(label, N, f'label must be an int or (N,) integer class ids, N = {N}', scalar=True)
+        targets = A.flow_targets(targets, self.patch_nums)
+        A.integer(max_rows, 'max_rows must be an integer >= 1', 1)
+        layers = A.block_layers(layers, self.depth)
+        self._token_label_range(gt, lab)
+        return gt.to(dev, torch.int64), lab.to(dev, torch.int64), targets, layers
+
+    @torch.no_grad()
+    def attention_maps(self, gt_tokens, label, targets, *, layers=None, max_rows: int = 8) -> AttentionMaps:
+        """Which positions of its own and of the coarser maps a token reads -> AttentionMaps (see there): for every target token, selected block
+        and head the row softmax_j(q_t . k_j) of reference basic_var.py:107-117, without the depth x H x L^2 floats per image of the matrix.
+
+        gt_tokens: (N, L) integer tokens, teacher-forced as in token_log_likelihood; label: an int or (N,) class ids in [0, num_classes];
+        targets: 1 to 32 entries, each a flat token index in [0, L) or (scale, row, col), the same for every image; layers: None (all blocks)
+        or strictly increasing block indices; max_rows bounds the images of one transformer pass (a pass keeps D' x L x C floats of queries per
+        image).  On the HIP path (the conditions of token_log_likelihood; f32 only: under a 16-bit precision ValueError) the blocks run on the
+        KV cache, every selected block's queries are kept for the call, and varhip_attn_rowstats_f32 / varhip_attn_flow_f32 form the rows with
+        the scores of the sampler's attention kernel bit for bit.  Elsewhere attention_maps_torch forms the dense masked softmax per image in
+        float64."""
+        gt, lab, targets, layers = self._flow_args(gt_tokens, label, targets, layers, max_rows)
+        if self._scoring_on_hip(gt):
+            r = self.engine().attention_flow(gt, lab, targets, layers, int(max_rows))
+            return AttentionMaps(r['rows'], r['nan_queries'], targets, layers, self.patch_nums)
+        if self.prog_si >= 0:
+            raise ValueError('attention_maps covers every scale: prog_si must be < 0')
+        rows, nanq = attention_maps_torch(self, gt, lab, targets, layers)
+        return AttentionMaps(rows, nanq, targets, layers, self.patch_nums)
+
+    @torch.no_grad()
+    def attention_rollout(self, gt_tokens, label, targets, *, layers=None, alpha: float = 0.5, max_rows: int = 8) -> AttentionRollout:
+        """Where a token's information comes from through all selected blocks -> AttentionRollout (see there): attention rollout (Abnar &
+        Zuidema 2020) of every target token, r <- (1 - alpha) r + alpha r Pbar_l from the last selected block to the first, r one-hot at the
+        target, Pbar_l the head mean of block l's softmax(QK^T).  alpha in [0, 1] weighs the attention against the residual path (0.5: the
+        paper's); the other arguments, the routes and the refusals are attention_maps'.  On the HIP path no (L, L) matrix is made: the row
+        vectors are pushed through P tile by tile (varhip_attn_flow_f32), two launches per layer."""
+        gt, lab, targets, layers = self._flow_args(gt_tokens, label, targets, layers, max_rows)
+        alpha = A.rollout_alpha(alpha)
+        if self._scoring_on_hip(gt):
+            r = self.engine().attention_flow(gt, lab, targets, layers, int(max_rows), alpha)
+            return AttentionRollout(r['flow'], r['nan_queries'], targets, layers, alpha, self.patch_nums)
+        if self.prog_si >= 0:
+            raise ValueError('attention_rollout covers every scale: prog_si must be < 0')
+        flow, nanq = attention_rollout_torch(self, gt, lab, targets, layers, alpha)
+        return AttentionRollout(flow, nanq, targets, layers, alpha, self.patch_nums)
 
     @torch.no_grad()
     def logit_lens(self, gt_tokens, label, *, layers=None, max_rows: int = 64) -> LogitLens:
