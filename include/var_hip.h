@@ -471,6 +471,18 @@ int varhip_gn_stats_part_f32(const double* gn_part, float* stats, int B, int nbl
 /* pinned against float64 and the direct conv (tests/test_winograd_gpu.py) */
 int varhip_conv3x3_wino_nhwc_f32(const float* in, const float* u, const float* bias, const float* resid, float* out, double* gn_part,
                                  int B, int H, int W, int Cin, int Cout, varhip_stream_t stream);
+/* Upsample2x (nearest 2x, then conv3x3, padding 1) as position-sparse Winograd F(2x2,3x3) on the LOW-resolution map: in [B][H/2][W/2][Cin],
+ * w_phase the pre-summed phase kernels of varhip_upconv_pack_f32 (no table of its own), out [B][H][W][Cout] = conv + bias.
+ * Every 2x2 output tile at even coordinates sees a window whose rows and columns repeat (a, b, b, c), so row 2 and column 2 of B^T d B
+ * vanish: 9 multiplies per tile and (ci, co) instead of 16; the rows 0, 1, 3 of G g G^T are sums of phase taps.
+ * Mathematically varhip_upconv_phase_f32 and varhip_conv3x3_nhwc_f32 (up2 1); the rounding differs.  gn_part (may be NULL): H*W/128 blocks
+ * per sample, as many as varhip_upconv_phase_gn_f32 writes, but block 2 t + h is the 8-row half h of the t-th 16 x 16 output patch.
+ * Needs H % 16 == 0, W % 16 == 0, Cin % 32 == 0, Cout % 32 == 0, 16-byte aligned pointers; else VARHIP_EINVAL.  Results do not depend on
+ * B or on the image's position in the batch.  varhip_upconv_phase_f32 / varhip_upconv_phase_gn_f32 run this kernel for such shapes while
+ * the exported int vh_g_upconv_wino is non-zero (0 by default; var_amd.hip.upconv_winograd, set by the fp32 decoder around its launches). */
+/* pinned against float64 and the phase form (tests/test_winograd_up_gpu.py) */
+int varhip_conv3x3_wino_up_nhwc_f32(const float* in, const float* w_phase, const float* bias, float* out, double* gn_part,
+                                    int B, int H, int W, int Cin, int Cout, varhip_stream_t stream);
 int varhip_conv3x3_s2_nhwc_f32(const float* in, const float* w, const float* bias, float* out,
                                int B, int H, int W, int Cin, int Cout, varhip_stream_t stream);
 /* The 16-bit Downsample2x of the encoder (basic_vae.py:31-37: F.pad(0, 1, 0, 1) + 3x3 conv of stride 2): the index rule of
@@ -1208,9 +1220,10 @@ int varhip_cast_bf16_to_f32(const void* in, float* out, int64_t n, varhip_stream
  * 13 conv16_small (every other fp16 conv kernel), 14 attn16; 15 conv_wino (k_conv3x3_wino, the fused Winograd F(2x2,3x3) conv; its FLOPs
  * are the executed multiplies, 16 per 2x2 tile, so it is not priced as a direct conv).  Families 0, 1, 10 and 12 each map to exactly
  * one kernel symbol and 15 to the instantiations of one template (k_conv3x3_wino<residual, partials, 0>), so their averages can be checked
- * against a rocprofv3 kernel trace.  16 attn_profile (k_attn_profile, varhip_attn_profile_f32: FLOPs = both QK^T passes).  Returns the number of
- * families. */
-#define VARHIP_NFAM 17
+ * against a rocprofv3 kernel trace.  16 attn_profile (k_attn_profile, varhip_attn_profile_f32: FLOPs = both QK^T passes).
+ * 17 conv_wino_up (k_conv3x3_wino_up, the Upsample2x convs as position-sparse Winograd; FLOPs = the executed multiplies, 9 per 2x2 tile;
+ * a family of its own so that conv_wino keeps counting the ResnetBlock convs alone).  Returns the number of families. */
+#define VARHIP_NFAM 18
 int varhip_timing_enable(int on);
 /* restrict the timing to the families whose bit is set (default: all).  Every timed launch costs two event records on the stream —
  * about 2 % of a sampling call when all ~3000 launches are timed; bench.py times only what its roofline object reports. */

@@ -122,6 +122,31 @@ def run_wino(iters, rounds=3):
             md = min(res[(H, Cin, Cout, 'd')])
             line += f'   direct {md:7.3f} ms  {2.0 * B * H * H * 9 * Cin * Cout / md / 1e9:6.1f} TF   speed-up {md / mw:4.2f}x'
         print(line, flush=True)
+    if not dbg and not pick: run_wino_up(iters, rounds)
+
+
+def run_wino_up(iters, rounds=3):
+    """the `up` rows: the fp32 decoder's four Upsample2x convs at B = 64 (output side, channels), GroupNorm partials on: the direct four-phase
+    kernel (up2 form, 16 multiplies per 2x2 output tile) against the position-sparse Winograd kernel (9); TF are the executed multiplies"""
+    dev, B = 'cuda', 64
+    shapes = [(32, 640), (64, 320), (128, 320), (256, 160)]
+    res = {}
+    for r in range(rounds):
+        for (H, C) in shapes:
+            x = torch.nn.functional.silu(torch.randn(B, H // 2, H // 2, C, device=dev)); w = (torch.rand(C, 3, 3, C, device=dev) * 2 - 1) / (9 * C) ** 0.5
+            b = torch.randn(C, device=dev) * 0.1; out = torch.empty(B, H, H, C, device=dev)
+            wp = torch.empty(4, C, 2, 2, C, device=dev); hip.call('upconv_pack_f32', w, wp, C, C)
+            pd = torch.zeros(B, hip.conv_gn_blocks(H, H, C, phase=True), C, 2, dtype=torch.float64, device=dev)
+            pw = torch.zeros(B, hip.conv_gn_blocks(H, H, C), C, 2, dtype=torch.float64, device=dev)
+            n = max(iters // 2, 2) if H >= 128 else iters * 2
+            res.setdefault((H, C, 'd'), []).append(timeit(lambda: hip.call('upconv_phase_gn_f32', x, wp, b, out, pd, B, H, H, C, C), n))
+            res.setdefault((H, C, 'w'), []).append(timeit(lambda: hip.call('conv3x3_wino_up_nhwc_f32', x, wp, b, out, pw, B, H, H, C, C), n))
+            del x, w, out, wp, pd, pw
+    for (H, C) in shapes:
+        mw, md = min(res[(H, C, 'w')]), min(res[(H, C, 'd')])
+        tw, td = 2.0 * B * H * H / 4 * 9 * C * C / mw / 1e9, 2.0 * B * H * H / 4 * 16 * C * C / md / 1e9
+        print(f'up   {H // 2:3d}^2 -> {H:3d}^2 {C:3d}->{C:3d}: Winograd-up {mw:7.3f} ms  {tw:6.1f} TF executed ({tw / PEAK * 100:4.1f}%)'
+              f'   direct {md:7.3f} ms  {td:6.1f} TF   speed-up {md / mw:4.2f}x', flush=True)
 
 
 def run_attn(iters):

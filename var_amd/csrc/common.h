@@ -61,6 +61,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define VH_FAM_ATTN16 14
 // the fused Winograd F(2x2,3x3) convolution (winograd.hip): FLOPs counted as executed (16 multiplies per 2x2 tile), not as a direct conv
 #define VH_FAM_CONV_WINO 15
+// the Upsample2x convs as position-sparse Winograd (winograd.hip, k_conv3x3_wino_up): 9 executed multiplies per 2x2 tile
+#define VH_FAM_CONV_WINO_UP 17
 // the attention profile (attnprofile.hip): its own family, so that its time can be read next to k_attn_cached's ("attn")
 #define VH_FAM_ATTN_PROFILE 16
 
@@ -84,6 +86,11 @@ __device__ __forceinline__ void vh_dma16_buf(__amdgpu_buffer_rsrc_t rsrc, uint32
     asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
                  : : "v"(voff), "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(soff)), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory", "m0");
 }
+
+// winograd.hip: Upsample2x as position-sparse Winograd where the switch vh_g_upconv_wino is on and the shape qualifies; 1: not taken (the
+// caller runs the four-phase kernel), else the launch's status
+int vh_upconv_wino_try(const float* in, const float* w_phase, const float* bias, float* out, double* gn_part,
+                       int B, int H, int W, int Cin, int Cout, hipStream_t stream);
 
 // quant.hip: Phi (3x3 residual mix) + f_hat accumulation of one quantizer step on a gathered `up` map (also behind edit.hip's fused steps)
 void vh_quant_phi_accum(const float* up, const float* phi_w, const float* phi_b, float ratio, float* f_hat, int B, int P, int Cv, hipStream_t s);

@@ -784,6 +784,10 @@ static int upconv_phase_impl(const float* in, const float* w_phase, const float*
     if (B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || Cin <= 0 || Cout <= 0 || (Cin & 31) || !bias) return VARHIP_EINVAL;
     if (gn_part && !varhip_conv_gn_blocks(H, W, Cout, 1)) return VARHIP_EINVAL;
     if ((int64_t)B * H * W >= (1ll << 31)) return VARHIP_EINVAL;
+    {   // the fp32 decoder's switch (winograd.hip): the same result from 9 multiplies per 2x2 output tile instead of 16, same partial-block count
+        const int rc = vh_upconv_wino_try(in, w_phase, bias, out, gn_part, B, H, W, Cin, Cout, (hipStream_t)stream);
+        if (rc != 1) return rc;
+    }
     GemmP p{};
     p.A = in; p.W = w_phase; p.bias = bias; p.out = out; p.resid = nullptr; p.gamma = nullptr;
     p.ldw = 4ll * Cin; p.ldo = Cout; p.ldr = Cout; p.sW = (int64_t)Cout * 4 * Cin;

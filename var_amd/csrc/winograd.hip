@@ -263,7 +263,217 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_wino(WinoP p) {
     }
 }
 
+// ---- Upsample2x (nearest 2x, then conv3x3) on the LOW-resolution map: position-sparse F(2x2,3x3) ----------------------
+// The 4x4 window of the 2x2 output tile at (2i, 2j) takes its rows from low-res rows (i-1, i, i, i+1) = (a, b, b, c), so B^T d has rows
+// (a - b, 2b, 0, b - c): transform row 2 and, likewise, column 2 vanish.  9 of the 16 positions are left: 9 multiplies per tile and (ci, co).
+// The filter side needs no table of its own: with G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]] the rows 0, 1, 3 of G g are g's row 0, half the
+// sum of its rows, and its row 2 — and the pre-summed 2x2 phase kernels the direct form already uses (varhip_upconv_pack_f32: w_phase) hold
+// exactly those row and column sums.  The halves of G cancel the doublings of B^T d exactly, so neither is applied: the K loop multiplies
+// (sums of) phase weights by (a - b | b | b - c) in rows and columns.  Per lane and K tile the nine positions are 9 loads and 6 additions.
+//
+// Workgroup = 16 x 16 output pixels (64 tiles, one per low-res pixel of an 8 x 8 block) x 32 output channels; 4 waves, wave w owns ALL nine
+// positions of tile half th = w & 1 (32 tiles: one 8-row half of the output patch) and channel half ch = w >> 1 (16 channels): 72
+// accumulators, the nine filter quads of its channel half (36 registers; each weight byte is loaded by two waves, 36 KB per workgroup and
+// K tile against the 32 KB of k_conv3x3_wino), and the whole A^T (.) A of a tile in one lane: no LDS exchange.  Every wave runs the same 72 MFMAs
+// per K tile.  Per K tile the 10 x 10 low-res patch (rows of 12 pixel slots, 8 LDS-DMA requests) lands in LDS; padding = requests past the
+// descriptor's range, as above.  Chunk c of a pixel in patch row r sits in slot c ^ 2 (r & 1): every 16-lane group of a ds_read_b128 (two tile
+// rows x 8 tiles x the lanes' channel quads) then touches each 16-B bank slot once.
+// K order as in k_conv3x3_wino: K tile, step, channel 16 kt + 4 kq + s.  Schedule: per tile block the MFMAs run transform row by transform
+// row (3 positions in rotation, 4 steps), so the 3 filter quads of a row are dead after its 12 MFMAs of the last tile block and the next K tile's
+// go into the same registers there (9 loads per K tile: the counted wait is vmcnt(9)); the next patch's DMA goes out after tile block 0.
+constexpr int WU_PS = 12;                         // pixel slots per patch row (10 used: two tile rows = 24 slots keep the swizzle, so tb is an immediate)
+constexpr int WU_NDMA = 8;                        // ceil(10 * 12 / 16)
+constexpr int WU_STAGE = WU_NDMA * 16 * 64;
+constexpr int WU_LDS = 2 * WU_STAGE;
+
+__device__ __forceinline__ void wu_wait_dma_barrier() { asm volatile("s_waitcnt vmcnt(9)\n\ts_barrier" ::: "memory"); }
+
+template <bool GN>
+__global__ void __launch_bounds__(256, 2) k_conv3x3_wino_up(WinoP p) {         // p.H, p.W: the OUTPUT map; the input is [H/2][W/2][Cin]
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r16 = lane & 15, kq = lane >> 4, th = wave & 1, ch = wave >> 1;
+    int lin;
+    {
+        const int nwg = gridDim.x, bid = blockIdx.x, q = nwg >> 3, rem = nwg & 7, xcd = bid & 7, loc = bid >> 3;
+        lin = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + loc;
+    }
+    const int cg = lin % p.ncg, pidx = lin / p.ncg, b = pidx / p.ppi, pi = pidx - b * p.ppi, py = pi / p.pw, px = pi - py * p.pw;
+    const int y0 = py * 16, x0 = px * 16, c0 = cg * 32 + ch * 16;  // c0: this wave's 16 channels
+    const int H = p.H, W = p.W, Hi = H >> 1, Wi = W >> 1, Cin = p.Cin, Cout = p.Cout, nk = Cin >> 4;
+
+    // ---- DMA roles: request i of wave w is piece qd = w + 4 i (slots 16 qd .. 16 qd + 15 of the 10 x 12 patch, origin (y0 / 2 - 1, x0 / 2 - 1))
+    const int64_t img = (int64_t)Hi * Wi * Cin;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.in + (int64_t)b * img), 0, (int)(img * 4), 0x00020000);
+    uint32_t doff[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int pix = (wave + 4 * i) * 16 + (lane >> 2), c = lane & 3;
+        const int pr = pix / WU_PS, pc = pix - pr * WU_PS;
+        const int yy = (y0 >> 1) - 1 + pr, xx = (x0 >> 1) - 1 + pc;
+        const bool ok = pr < 10 && pc < 10 && (unsigned)yy < (unsigned)Hi && (unsigned)xx < (unsigned)Wi;
+        doff[i] = ok ? (uint32_t)((((int64_t)yy * Wi + xx) * Cin + ((c ^ ((pr & 1) << 1)) << 2)) * 4) : 0x80000000u;
+    }
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
+    auto dma = [&](int kt, int st) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) vh_dma16_buf(rsrc, doff[i], (uint32_t)kt * 64u, lds0 + st * WU_STAGE + (wave + 4 * i) * 1024);
+    };
+
+    // ---- filter fragments of position j = 3 r + c (transform row (0, 1, 3)[r], column (0, 1, 3)[c]) from w_phase [phase 2 py + px][Cout][a][b][Cin];
+    // channel c0 + r16, the 4 input channels 4 kq .. 4 kq + 3.  With P = phase 0, Q = phase 1, S = phase 2, T = phase 3 and tap index 2 a + b the
+    // registers are loaded with  P0 P1 Q1 | P2 P3 Q3 | S2 S3 T3  and become, row by row before their first MFMA of a K tile,
+    //   P0, P0 + P1, Q1 | P0 + P2, (P0 + P1) + (P2 + P3), Q1 + Q3 | S2, S2 + S3, T3     (sums over the kernel rows / columns a phase tap stands for)
+    const __amdgpu_buffer_rsrc_t ursrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.u, 0, (int)(64u * Cin * Cout), 0x00020000);
+    const uint32_t uoff = (uint32_t)((c0 + r16) * 4 * Cin + 4 * kq) * 4u;
+    f32x4 u[9];
+    auto load_u = [&](int kt, int r) __attribute__((always_inline)) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            u[3 * r + c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                ursrc, uoff, __builtin_amdgcn_readfirstlane((uint32_t)((((r == 2 ? 2 : 0) + (c == 2 ? 1 : 0)) * Cout * 4 + (r == 0 ? 0 : 2) + (c == 0 ? 0 : 1)) * Cin + 16 * kt) * 4u), 0));
+    };
+    dma(0, 0);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { load_u(0, r); __builtin_amdgcn_sched_barrier(0); }
+
+    // ---- patch reads: tile t = 32 th + 16 tb + r16 is low-res pixel (4 th + 2 tb + (r16 >> 3), r16 & 7) of the 8 x 8 block = patch pixel
+    // (+1, +1); its window is patch rows +0 .. +2 (a, b, c) and columns +0 .. +2.  The slot swizzle depends on the patch row's parity alone:
+    // one base for window rows 0 and 2, one for row 1; window column, window row, tile block are immediates
+    const int prow = 4 * th + (r16 >> 3), pbase = (prow * WU_PS + (r16 & 7)) * 64;
+    const uint32_t roff_e = (uint32_t)(pbase + ((kq ^ ((prow & 1) << 1)) << 4)), roff_o = (uint32_t)(pbase + ((kq ^ (((prow + 1) & 1) << 1)) << 4));
+
+    f32x4 acc[9][2];                                               // [j][tb]: D[co = c0 + 4 kq + e][tile = 32 th + 16 tb + r16]
+#pragma unroll
+    for (int j = 0; j < 9; ++j)
+#pragma unroll
+        for (int tb = 0; tb < 2; ++tb) acc[j][tb] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    f32x4 b4;
+    auto compute = [&](int st, int kt_dma, int kt_u, auto last) __attribute__((always_inline)) {
+        const char* sb = (const char*)smem + st * WU_STAGE;
+#pragma unroll
+        for (int tb = 0; tb < 2; ++tb) {
+            f32x4 d[3][3];                                         // [window row][window column], steps s = 0..3
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) d[r][c] = *(const f32x4*)(sb + (r == 1 ? roff_o : roff_e) + (r * WU_PS + c + tb * 2 * WU_PS) * 64);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                if (tb == 0) {                                     // this row's filter fragments from the phase taps (the order above)
+                    if (r == 0) u[1] = u[0] + u[1];
+                    if (r == 1) { u[4] = u[1] + (u[3] + u[4]); u[3] = u[0] + u[3]; u[5] = u[2] + u[5]; }
+                    if (r == 2) u[7] = u[6] + u[7];
+                }
+                f32x4 e[3];                                        // row r of B^T d without its doubling: a - b | b | b - c
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e[c] = r == 0 ? d[0][c] - d[1][c] : (r == 1 ? d[1][c] : d[1][c] - d[2][c]);
+                const f32x4 v[3] = {e[0] - e[1], e[1], e[1] - e[2]};
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc[3 * r + c][tb] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[3 * r + c][s], v[c][s], acc[3 * r + c][tb], 0, 0, 0);
+                if (tb == 1) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (decltype(last)::value) { if (r == 0) b4 = *(const f32x4*)(p.bias + c0 + 4 * kq); } else load_u(kt_u, r);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (tb == 0 && !decltype(last)::value) dma(kt_dma, st ^ 1);
+        }
+    };
+    // per wave and K tile the vector-memory order is: DMA of the next patch (after tile block 0), the 9 weight loads (tile block 1), the counted wait
+    wu_wait_dma_barrier();
+    int kt = 0;
+    for (; kt + 2 < nk; kt += 2) {
+        compute(0, kt + 1, kt + 1, std::false_type{});
+        wu_wait_dma_barrier();
+        compute(1, kt + 2, kt + 2, std::false_type{});
+        wu_wait_dma_barrier();
+    }
+    compute(0, kt + 1, kt + 1, std::false_type{});
+    wu_wait_dma_barrier();
+    compute(1, 0, 0, std::true_type{});
+
+    // ---- epilogue, all in this lane: with m2 = 0, (M A)[r] = (m[r][0] + m[r][1], m[r][1] - m[r][3]), and A^T over the rows the same way:
+    // y[0] = z[0] + z[1], y[1] = z[1] - z[3] — the association of k_conv3x3_wino with the zero terms dropped
+    const int nblk = (H * W) >> 7;
+    double gs[4] = {0.0, 0.0, 0.0, 0.0}, gq[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int tb = 0; tb < 2; ++tb) {
+        const int ty = 4 * th + 2 * tb + (r16 >> 3), tx = r16 & 7;
+        const int64_t obase = (((int64_t)b * H + y0 + 2 * ty) * W + x0 + 2 * tx) * Cout + c0 + 4 * kq;
+        f32x4 z[3][2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            z[r][0] = acc[3 * r][tb] + acc[3 * r + 1][tb]; z[r][1] = acc[3 * r + 1][tb] - acc[3 * r + 2][tb];
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+                const f32x4 v = (a == 0 ? z[0][bb] + z[1][bb] : z[1][bb] - z[2][bb]) + b4;
+                *(f32x4*)(p.out + obase + ((int64_t)a * W + bb) * Cout) = v;
+                if constexpr (GN) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { const double dd = (double)v[e]; gs[e] += dd; gq[e] += dd * dd; }
+                }
+            }
+    }
+    if constexpr (GN) {
+        // this wave's 32 tiles are the 8-row half th of the output patch: block 2 pi + th of k_conv3x3_wino's partial layout.  The 16 lanes of a
+        // channel quad sum by the fixed xor butterfly 8, 4, 2, 1; the first three levels also halve the quantities a lane carries (8 -> 4 -> 2 -> 1)
+        const double t8[8] = {gs[0], gq[0], gs[1], gq[1], gs[2], gq[2], gs[3], gq[3]};        // the order of the partial's 8 doubles
+        const bool h3 = lane & 8, h2 = lane & 4, h1 = lane & 2;
+        double r4[4], r2[2], r1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r4[k] = (h3 ? t8[4 + k] : t8[k]) + __shfl_xor(h3 ? t8[k] : t8[4 + k], 8, 64);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) r2[k] = (h2 ? r4[2 + k] : r4[k]) + __shfl_xor(h2 ? r4[k] : r4[2 + k], 4, 64);
+        r1 = (h1 ? r2[1] : r2[0]) + __shfl_xor(h1 ? r2[0] : r2[1], 2, 64);
+        r1 += __shfl_xor(r1, 1, 64);
+        if ((lane & 1) == 0)                                       // lane bits 3, 2, 1 name the quantity this lane ended up with
+            p.gn_part[(((int64_t)b * nblk + 2 * pi + th) * Cout + c0 + 4 * kq) * 2 + ((lane >> 1) & 7)] = r1;
+    }
+}
+
 }  // namespace
+
+// 0 when the shape is one k_conv3x3_wino_up takes
+static bool wino_up_ok(const float* in, const float* w_phase, const float* bias, float* out, int B, int H, int W, int Cin, int Cout) {
+    if (!in || !w_phase || !bias || !out || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return false;
+    if ((H & 15) || (W & 15) || (Cin & 31) || (Cout & 31)) return false;
+    if ((((uintptr_t)in | (uintptr_t)w_phase | (uintptr_t)bias | (uintptr_t)out) & 15)) return false;
+    if ((int64_t)(H / 2) * (W / 2) * Cin * 4 >= (1ll << 31) || 64ll * Cin * Cout >= (1ll << 31) || (int64_t)B * H * W >= (1ll << 31))
+        return false;                                              // descriptor windows (one low-res image, w_phase), pixel count
+    return (int64_t)B * (H / 16) * (W / 16) * (Cout / 32) < (1ll << 31);
+}
+
+extern "C" int varhip_conv3x3_wino_up_nhwc_f32(const float* in, const float* w_phase, const float* bias, float* out, double* gn_part,
+                                               int B, int H, int W, int Cin, int Cout, varhip_stream_t stream) {
+    if (!wino_up_ok(in, w_phase, bias, out, B, H, W, Cin, Cout)) return VARHIP_EINVAL;
+    const int ppi = (H / 16) * (W / 16), ncg = Cout / 32;
+    const int64_t nwg = (int64_t)B * ppi * ncg;
+    WinoP p{};
+    p.in = in; p.u = w_phase; p.bias = bias; p.resid = nullptr; p.out = out; p.gn_part = gn_part;
+    p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.ncg = ncg; p.pw = W / 16; p.ppi = ppi;
+    const double npix = (double)B * H * W;
+    // executed multiplies: 9 per 2x2 tile and (ci, co)
+    VhScope scope(VH_FAM_CONV_WINO_UP, (hipStream_t)stream, 2.0 * (npix / 4.0) * 9.0 * Cin * Cout,
+                  4.0 * (npix / 4.0 * Cin + npix * Cout + 16.0 * Cin * Cout));
+    hipLaunchKernelGGL(gn_part ? k_conv3x3_wino_up<true> : k_conv3x3_wino_up<false>, dim3((unsigned)nwg), dim3(256), WU_LDS, (hipStream_t)stream, p);
+    return vh_launch_status();
+}
+
+// The switch of varhip_upconv_phase[_gn]_f32 (gemm.hip): non-zero, a launch whose shape k_conv3x3_wino_up takes runs there.  A plain exported
+// int, 0 by default: every direct caller gets the four-phase kernel; DecoderEngine.upsample sets it around its own launch (var_amd/hip.py).
+extern "C" { int vh_g_upconv_wino = 0; }
+int vh_upconv_wino_try(const float* in, const float* w_phase, const float* bias, float* out, double* gn_part,
+                       int B, int H, int W, int Cin, int Cout, hipStream_t stream) {
+    if (!vh_g_upconv_wino || !wino_up_ok(in, w_phase, bias, out, B, H, W, Cin, Cout)) return 1;        // 1: not taken
+    return varhip_conv3x3_wino_up_nhwc_f32(in, w_phase, bias, out, gn_part, B, H, W, Cin, Cout, (varhip_stream_t)stream);
+}
 
 extern "C" int varhip_conv3x3_wino_nhwc_f32(const float* in, const float* u, const float* bias, const float* resid, float* out, double* gn_part,
                                             int B, int H, int W, int Cin, int Cout, varhip_stream_t stream) {

@@ -684,8 +684,8 @@ class DecoderEngine(_VaeOps):
     # sharing one VQVAE, or a VAR in the 16-bit mode next to direct VQVAE calls, never fight over a mode flag.
     precision = 'f32'
     unfused_tail = False         # tests: run norm_out / conv_out of the decoder as two launches
-    # The ResnetBlock convolutions (stride 1, 3x3) as fused Winograd F(2x2,3x3) (winograd.hip) where wino_ok() holds; False (tests, A/B runs):
-    # every conv on the direct implicit-GEMM kernel.  VARHIP_WINOGRAD=0 sets the default for a whole process.
+    # The ResnetBlock convolutions (stride 1, 3x3) as fused Winograd F(2x2,3x3) where wino_ok() holds, and the Upsample2x convolutions as its
+    # position-sparse form where the library's shape rule holds (winograd.hip); False (tests, A/B runs): every conv on the direct implicit-GEMM kernel.  VARHIP_WINOGRAD=0 sets the default for a whole process.
     winograd = os.environ.get('VARHIP_WINOGRAD', '1') != '0'
     WINO_MIN_HW = 16 * 16        # smallest map that takes it (1.63-1.72x faster than the direct kernel at every decoder level)
     # the precision flops_per_image_executed counts when not given one: that of the last decode_nhwc, or the one the owning SamplingEngine was
@@ -716,15 +716,21 @@ class DecoderEngine(_VaeOps):
         return self.w.get(key + '.wino') if self.winograd and self.wino_ok(Hh, Ww, Cin, Cout) else None
 
     def upsample(self, h, key, B, Hh, Ww):
-        """Upsample2x onto an Hh x Ww map: nearest 2x + conv3x3, as 4 phase convs on the low-res map.  Its result is normalised by the next
-        level's first ResnetBlock: the partials where the shape has them"""
+        """Upsample2x onto an Hh x Ww map: nearest 2x + conv3x3, from the pre-summed phase weights on the low-res map.  With `winograd` on, the
+        library runs the launch as position-sparse Winograd (9 multiplies per 2x2 output tile instead of the 16 of the four phase convs;
+        DESIGN.md §13.2) where the output tiles into 16 x 16 patches and the channels are multiples of 32 — the same entry points, the same
+        arguments.  Its result is normalised by the next level's first ResnetBlock: the partials where the shape has them"""
         wp = self.w[key + '.phase']
         up = torch.empty((B, Hh, Ww, wp.shape[1]), dtype=torch.float32, device=h.device)
         part = self._leave_partials(up, B, hip.conv_gn_blocks(Hh, Ww, wp.shape[1], phase=True))
-        if part is not None:
-            hip.call('upconv_phase_gn_f32', h, wp, self.w[key + '.bias'], up, part, B, Hh, Ww, wp.shape[4], wp.shape[1])
-        else:
-            hip.call('upconv_phase_f32', h, wp, self.w[key + '.bias'], up, B, Hh, Ww, wp.shape[4], wp.shape[1])
+        hip.upconv_winograd(self.winograd)
+        try:
+            if part is not None:
+                hip.call('upconv_phase_gn_f32', h, wp, self.w[key + '.bias'], up, part, B, Hh, Ww, wp.shape[4], wp.shape[1])
+            else:
+                hip.call('upconv_phase_f32', h, wp, self.w[key + '.bias'], up, B, Hh, Ww, wp.shape[4], wp.shape[1])
+        finally:
+            hip.upconv_winograd(False)
         return up
 
     def tail(self, h, key, B, Hh, Ww, denorm, clamp=True):
@@ -774,7 +780,9 @@ class DecoderEngine(_VaeOps):
     def flops_per_image_executed(self, P: int, precision: Optional[str] = None) -> float:
         """FLOPs the kernels execute for one decode in `precision` (None: `flops_precision`): as flops_per_image_reference, with the Upsample2x
         convolutions in their folded four-phase form (4 taps per output pixel instead of 9) and, in an f32 decode, the ResnetBlock convolutions
-        that take the Winograd path at 16 multiplies per 2x2 output tile (4 per output pixel instead of 9; the 16-bit decode has no such path)"""
+        that take the Winograd path at 16 multiplies per 2x2 output tile (4 per output pixel instead of 9; the 16-bit decode has no such path).
+        The Upsample2x convolutions are counted in the four-phase form in every precision, also where the f32 decode runs them at 9 multiplies
+        per tile (tests/test_winograd_cpu.py pins this count)"""
         return self._flops(P, precision or self.flops_precision or self.precision)
 
     def decode_nhwc(self, f_hat: torch.Tensor, denorm: bool = True, precision: Optional[str] = None, clamp: bool = True) -> torch.Tensor:

@@ -81,6 +81,12 @@ def conv_gn_blocks(H, W, Cout, phase=False) -> int:
     return int(lib().fn['conv_gn_blocks'](H, W, Cout, 1 if phase else 0))
 
 
+def upconv_winograd(on: bool):
+    """the library's switch for varhip_upconv_phase[_gn]_f32 (vh_g_upconv_wino, winograd.hip; off by default): on, a launch whose output tiles
+    into 16 x 16 patches with channels in multiples of 32 runs as position-sparse Winograd.  DecoderEngine.upsample sets it around its launch."""
+    ctypes.c_int.in_dll(lib().so, 'vh_g_upconv_wino').value = 1 if on else 0
+
+
 def conv16_gn_fusable(B, H, W, Cin, Cout) -> bool:
     """can the 16-bit conv apply the GroupNorm + SiLU in front of it to its own input patch (varhip_gnconv3x3_nhwc_*)?"""
     return bool(lib().fn['conv16_gn_fusable'](B, H, W, Cin, Cout))
