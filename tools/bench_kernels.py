@@ -97,13 +97,18 @@ def run_wino(iters, rounds=3):
     """the fp32 decoder's ResnetBlock convs at B = 64 (the six shapes of tests/test_winograd_gpu.py::SHAPES): the direct kernel against the
     fused Winograd kernel, residual and GroupNorm partials on as in conv2 of a block; executed TF = 16 multiplies per 2x2 tile and (ci, co).
     A/B of two builds: run once per library (VARHIP_LIB=...).  VARHIP_WINO_DBG=<bits> times the kernel's knock-outs (1 no epilogue,
-    2 no GroupNorm partials, 4 no residual, 8 no B^T d B; results are wrong, only the time means anything); WINO_SHAPES=0,5 picks shapes."""
+    2 no GroupNorm partials, 4 no residual, 8 no B^T d B; results are wrong, only the time means anything); WINO_SHAPES=0,5 picks shapes.
+    A library with the workgroup-shape hook is timed on both shapes at every level whose Cout is a multiple of 80: `Winograd`
+    is shape 0 (64 tiles x 32 channels), `wide` shape 1 (32 tiles x 80 channels); `auto` names the shape the library's own rule picks.  Of the
+    knock-outs the wide shape has 8 alone."""
     from var_amd.engine import wino_filter
     dev, B = 'cuda', 64
     shapes = [(256, 160, 160), (128, 160, 160), (64, 160, 320), (64, 320, 320), (32, 320, 320), (16, 640, 640)]
     pick = os.environ.get('WINO_SHAPES')
     if pick: shapes = [shapes[int(i)] for i in pick.split(',')]
     dbg = int(os.environ.get('VARHIP_WINO_DBG', '0'))
+    hooked = hasattr(hip.lib().so, 'varhip_wino_force_shape')       # a parent build (VARHIP_LIB=...) has one shape
+    wide = lambda Cout: hooked and Cout % 80 == 0 and dbg in (0, 8)
     res = {}
     for r in range(rounds):
         for (H, Cin, Cout) in shapes:
@@ -113,11 +118,21 @@ def run_wino(iters, rounds=3):
             u = wino_filter(w)
             n = max(iters // 2, 2) if H >= 128 else iters * 2
             if not dbg: res.setdefault((H, Cin, Cout, 'd'), []).append(timeit(lambda: hip.call('conv3x3_nhwc_f32', x, w, b, rs, out, B, H, H, Cin, Cout, 0, 0), n))
-            res.setdefault((H, Cin, Cout, 'w'), []).append(timeit(lambda: hip.call('conv3x3_wino_nhwc_f32', x, u, b, rs, out, part, B, H, H, Cin, Cout), n))
+            try:
+                if hooked: hip.wino_force_shape(0)
+                res.setdefault((H, Cin, Cout, 'w'), []).append(timeit(lambda: hip.call('conv3x3_wino_nhwc_f32', x, u, b, rs, out, part, B, H, H, Cin, Cout), n))
+                if wide(Cout):
+                    hip.wino_force_shape(1)
+                    res.setdefault((H, Cin, Cout, 'w1'), []).append(timeit(lambda: hip.call('conv3x3_wino_nhwc_f32', x, u, b, rs, out, part, B, H, H, Cin, Cout), n))
+            finally:
+                if hooked: hip.wino_force_shape(-1)
             del x, w, rs, out, part, u
     for (H, Cin, Cout) in shapes:
         mw = min(res[(H, Cin, Cout, 'w')]); tf = 2.0 * B * H * H / 4 * 16 * Cin * Cout / mw / 1e9
         line = f'wino dbg={dbg} {H:3d}^2 {Cin:3d}->{Cout:3d}: Winograd {mw:7.3f} ms  {tf:6.1f} TF executed ({tf / PEAK * 100:4.1f}%)'
+        if wide(Cout):
+            m1 = min(res[(H, Cin, Cout, 'w1')]); t1 = tf * mw / m1
+            line += f'   wide {m1:7.3f} ms  {t1:6.1f} TF ({t1 / PEAK * 100:4.1f}%)  wide/Winograd {m1 / mw:5.3f}  auto {hip.wino_auto_shape(H, H, Cin, Cout)}'
         if not dbg:
             md = min(res[(H, Cin, Cout, 'd')])
             line += f'   direct {md:7.3f} ms  {2.0 * B * H * H * 9 * Cin * Cout / md / 1e9:6.1f} TF   speed-up {md / mw:4.2f}x'

@@ -87,6 +87,29 @@ def upconv_winograd(on: bool):
     ctypes.c_int.in_dll(lib().so, 'vh_g_upconv_wino').value = 1 if on else 0
 
 
+def _wino_hook(name, nargs):
+    """the workgroup-shape hooks of varhip_conv3x3_wino_nhwc_f32 (winograd.hip): exported beside the header's entry points, ints in and out"""
+    fn = getattr(lib().so, 'varhip_wino_' + name)
+    fn.argtypes, fn.restype = [ctypes.c_int] * nargs, ctypes.c_int
+    return fn
+
+
+def wino_force_shape(shape: int):
+    """-1: the library's own rule; 0: 64 tiles x 32 channels per workgroup; 1: the wide shape, 32 tiles x 80 channels, where Cout % 80 == 0
+    (elsewhere shape 0 still runs).  Both shapes give the same bits.  Tests and experiments: reset to -1 in a `finally`."""
+    _wino_hook('force_shape', 1)(int(shape))
+
+
+def wino_last_shape() -> int:
+    """the shape the latest accepted varhip_conv3x3_wino_nhwc_f32 launch took (-1 before the first)"""
+    return int(_wino_hook('last_shape', 0)())
+
+
+def wino_auto_shape(H, W, Cin, Cout) -> int:
+    """the shape the library's own rule gives this level (host arithmetic: no GPU, no launch)"""
+    return int(_wino_hook('auto_shape', 4)(H, W, Cin, Cout))
+
+
 def conv16_gn_fusable(B, H, W, Cin, Cout) -> bool:
     """can the 16-bit conv apply the GroupNorm + SiLU in front of it to its own input patch (varhip_gnconv3x3_nhwc_*)?"""
     return bool(lib().fn['conv16_gn_fusable'](B, H, W, Cin, Cout))
